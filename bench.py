@@ -14,6 +14,13 @@ step), so exactly K steps are timed.  Inputs (token ids, decoded uint8 frames - 
 src/utils/vision_process.py:467-472) are resident in HBM before the timed region.
 Weights are random-init of the exact architecture; data is synthetic (no checkpoints / videos exist offline).
 Prints ONE JSON line on rank 0.
+
+A plain run does only what the headline figure needs: set up, warm up, time the K steps, print the line.  `--full` adds the secondary
+measurements after the timed region, each of which can still be left out with its own --no-* flag: the on-box peak probe (before the
+workload is built), the bare-engine-loop cross-check, the instrumented roofline window (and the sampling-policy drift) and the CPU baseline.
+`--dump-outputs DIR` writes what the timed path computed in its last step as DIR/<name>.npy (float32 / float64): seeded inputs, so two
+builds run with the same arguments can be compared output for output (every reduction of the step sums in a fixed order, so one build
+writes the same bits on every run).
 """
 import argparse
 import json
@@ -98,6 +105,9 @@ class Workload:
         self._feed = self._batches()
         self.P = None
         self.micro = 0
+        self.last = None
+        if args.dump_outputs:
+            self._capture_last_step()
 
     def _batches(self):
         """Endless stream of batches through the trainer's own data path: rank-sharded sampler -> prefetch thread (host half of the
@@ -195,6 +205,49 @@ class Workload:
                 self._finish(st, si == n - 1, n)
         self.opt.step()
         self.micro += n
+
+    # ------------------------------------------------------------------------------------------------------------ --dump-outputs
+    def _capture_last_step(self):
+        """Keep references (no copies, no waits) to what the latest micro-step's loss / backward and the latest optimizer step produced;
+        installed on the engine objects, so the trainer path and the bare engine loop are captured alike."""
+        core, opt = self.core, self.opt
+        self.last = {}
+        orig_lb, orig_step = core.loss_backward, opt.step
+
+        def loss_backward(st, completion_mask, advantages, *a, **k):
+            r = orig_lb(st, completion_mask, advantages, *a, **k)
+            self.last.update(completion_ids=st.completion_ids, completion_mask=completion_mask, advantages=advantages, logp=st.logp,
+                             ref_logp=st.ref_logp, loss_terms=r[0] if isinstance(r, tuple) else None)
+            return r
+
+        def step(*a, **k):
+            gnorm = orig_step(*a, **k)
+            self.last["grad_norm"] = gnorm
+            return gnorm
+        core.loss_backward, opt.step = loss_backward, step
+
+    def dump_outputs(self, out_dir, n_sample=1 << 21):
+        """Write the last timed step's outputs as DIR/<name>.npy: its completion tokens (float64) and mask, advantages, policy and reference
+        log-probs, loss terms (loss, KL, ...), the window's gradient norm (float64), and the same fixed, seeded sample of n_sample elements of the
+        updated weights - the bf16 working copy, and the fp32 master copy where this rank holds it whole.  About 32 MB for the default sample."""
+        os.makedirs(out_dir, exist_ok=True)
+        arrs = {}
+        for k, v in self.last.items():
+            if v is None:
+                continue
+            t = torch.as_tensor(v).detach().cpu().double()
+            t = t.reshape(1) if t.dim() == 0 else t
+            arrs[k] = t.numpy() if k in ("completion_ids", "grad_norm") else t.float().numpy()
+        arena = self.params.train
+        n = arena.w16.numel()
+        idx = torch.randint(0, n, (min(n_sample, n),), generator=torch.Generator().manual_seed(0)).sort().values.to(arena.w16.device)
+        arrs["weights_bf16_sample"] = arena.w16[idx].float().cpu().numpy()
+        if arena.master is not None and arena.shard is None:
+            arrs["weights_master_sample"] = arena.master[idx].cpu().numpy()
+        arrs["weights_sample_index"] = idx.cpu().double().numpy()
+        for k, a in arrs.items():
+            np.save(os.path.join(out_dir, k + ".npy"), a)
+        return sorted(arrs)
 
 
 def measure_peaks(ops, device):
@@ -453,6 +506,10 @@ def parse_args(argv=None):
                     "shard of master/m/v, all-gather bf16 weights; reference scripts/zero3.json) has been the DEFAULT for N in {2, 4, 8} since round 3; "
                     "--replicated-optimizer opts out")
     ap.add_argument("--replicated-optimizer", action="store_true", help="N > 1: keep master / m / v whole on every rank and all-reduce the gradient")
+    ap.add_argument("--full", action="store_true", help="also run the secondary measurements: peak probe, bare-engine-loop cross-check, roofline window, "
+                    "CPU baseline (each still subject to its --no-* flag); off by default")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the timed path computed in its last step "
+                    "as DIR/<name>.npy (float32 / float64, a fixed seeded sample of the weights; < 64 MB in all)")
     args = ap.parse_args(argv)
     if args.gpus < 1 or args.steps < 1 or args.warmup < 0 or args.ga < 1:
         ap.error("--gpus/--steps/--ga must be >= 1 and --warmup >= 0")
@@ -500,7 +557,7 @@ def main(argv=None):
     from time_r1_amd.ops import HipOps
     ops = HipOps(device)
     ops.use_priority_stream()            # main chain ahead of the weight-gradient side stream in the dispatcher (same call as the trainer)
-    peaks = measure_peaks(ops, device) if (rank == 0 and not args.no_peak_probe) else None
+    peaks = measure_peaks(ops, device) if (rank == 0 and args.full and not args.no_peak_probe) else None
     from time_r1_amd.dist import dist_diagnostics, exposed_ms
     diag = dist_diagnostics(device)          # collectives: every rank; N = 1: a local stub.  A hang here ends in the process-group timeout.
     wl = Workload(args, ops, device, rank)
@@ -536,10 +593,12 @@ def main(argv=None):
     else:
         gen_tokens = int(tr.generated_tokens - tok0)              # gathered completion lengths of the timed micro-steps, all ranks
         phases = {k: (v - ph0.get(k, 0.0)) / args.steps for k, v in tr.phase_ms_total.items()}   # per micro-step (rollout / vision are per window / ga)
+    if args.dump_outputs and rank == 0:
+        wl.dump_outputs(args.dump_outputs)          # what the last timed step computed, before anything after the timed region runs
 
     # cross-check: the same engine objects driven by a bare loop without the trainer class (a few windows, after the timed region)
     engine_leg = None
-    if not args.engine_path and not args.no_engine_leg:
+    if args.full and not args.engine_path and not args.no_engine_leg:
         n_leg = max(args.ga, min(args.steps, 4 * args.ga) // args.ga * args.ga)
         wl.engine_window()
         torch.cuda.synchronize(); dp.barrier(); torch.cuda.synchronize()
@@ -595,7 +654,8 @@ def main(argv=None):
                        "optimizer": "zero-sharded (reduce-scatter / local AdamW / all-gather)" if wl.shard else "replicated AdamW + gradient all-reduce"},
         }
     # ---- roofline of the dominant kernel, measured live with HIP events in one extra (untimed) step
-    if not args.no_roofline:
+    roofline = args.full and not args.no_roofline
+    if roofline:
         # every rank runs the extra window (it contains the gradient all-reduce); only rank 0 records events
         rec, orig = instrument_gemms(ops) if rank == 0 else ([], None)
         # the timed windows drive decode through ONE native call per step (csrc/decode.hip).  That driver records a pair of HIP events around
@@ -628,7 +688,7 @@ def main(argv=None):
         wl.eng.overlap_wgrad = overlap0
         if rank == 0:
             ops.gemm_nt, ops.norm_gemm, ops.gemm_skinny_fixup, ops.norm_gemm_qkv = orig
-    if rank == 0 and not args.no_roofline:
+    if rank == 0 and roofline:
         nstep = float(args.ga)
         big_ms = sum(e0.elapsed_time(e1) for s, M, N, K, e0, e1 in rec if not s)
         big_fl = sum(2.0 * M * N * K for s, M, N, K, e0, e1 in rec if not s)
@@ -706,7 +766,7 @@ def main(argv=None):
         out["roofline_secondary"] = other
     if rank == 0 and peaks:
         out["peak_probe"] = peaks
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         try:
             out["cpu_baseline"] = cpu_baseline(args)
         except Exception as e:  # the GPU numbers above stay valid; say why the baseline is missing

@@ -88,7 +88,7 @@ int64_t tr1_gemm_skinny_fixup_workspace_floats(int64_t M, int64_t N, int64_t K);
 int tr1_transpose_bf16(const void* in, int64_t ld_in, void* out, int64_t ld_out, int64_t R, int64_t C, void* stream);
 /* The same transpose with colsum_f32[c] += sum_r in[r, c]: the bias gradient of a Linear (reference: autograd of F.linear, q/k/v_proj bias TF:501-504) taken
  * from the pass that builds dY^T for its weight gradient. */
-int tr1_transpose_colsum_bf16(const void* in, int64_t ld_in, void* out, int64_t ld_out, int64_t R, int64_t C, void* colsum_f32, void* stream);
+int tr1_transpose_colsum_bf16(const void* in, int64_t ld_in, void* out, int64_t ld_out, int64_t R, int64_t C, void* colsum_f32, void* ws_f32, int64_t ws_floats, void* stream);
 
 /* ---- normalisation ------------------------------------------------------------------------------------------------- */
 /* ref: Qwen2RMSNorm TF:96-110 (fp32 math, cast to bf16 BEFORE the weight multiply).  If residual != NULL the kernel first forms
@@ -101,7 +101,7 @@ int tr1_rmsnorm_bwd(const void* dy, const void* x, const void* w, const void* rs
 int64_t tr1_rmsnorm_bwd_workspace_floats(int64_t rows, int64_t cols);
 /* ref: nn.LayerNorm(eps=1e-6) in VisionBlock TF:425-449 and PatchMerger.ln_q TF:277-290 */
 int tr1_layernorm_fwd(const void* x, const void* w, const void* b, void* y, void* mean, void* rstd, int64_t rows, int64_t cols, float eps, void* stream);
-int tr1_layernorm_bwd(const void* dy, const void* x, const void* w, const void* mean, const void* rstd, void* dx, void* dw_f32, void* db_f32, int64_t rows, int64_t cols, void* stream);
+int tr1_layernorm_bwd(const void* dy, const void* x, const void* w, const void* mean, const void* rstd, void* dx, void* dw_f32, void* db_f32, void* ws_f32, int64_t ws_floats, int64_t rows, int64_t cols, void* stream);
 
 /* ---- activations / elementwise ---------------------------------------------------------------------------------------- */
 /* ref: Qwen2MLP TF:459-466: out = silu(gate) * up with gu = [gate | up] along the feature axis */
@@ -114,7 +114,8 @@ int tr1_quickgelu_fwd(const void* x, void* y, int64_t n, void* stream);
 int tr1_add_bf16(const void* a, const void* b, void* y, int64_t n, void* stream);
 int tr1_cast_f32_to_bf16(const void* x, void* y, int64_t n, void* stream);
 int tr1_cast_bf16_to_f32(const void* x, void* y, int64_t n, void* stream);
-int tr1_colsum_accum(const void* dy, void* dbias_f32, int64_t rows, int64_t cols, void* stream);
+int tr1_colsum_accum(const void* dy, void* dbias_f32, int64_t rows, int64_t cols, void* ws_f32, int64_t ws_floats, void* stream);
+int64_t tr1_colsum_workspace_floats(int64_t rows, int64_t cols);
 
 /* ---- rotary embeddings ------------------------------------------------------------------------------------------------ */
 /* ref: Qwen2VLRotaryEmbedding TF:117-169 + apply_multimodal_rotary_pos_emb TF:180-222.  pos3: int32 [3, T] (t,h,w) from
@@ -254,7 +255,7 @@ int64_t tr1_sample_workspace_words(int64_t rows);
 
 /* ---- optimizer -------------------------------------------------------------------------------------------------------- */
 /* ref: DeepSpeed FusedAdam / DeepSpeedCPUAdam selected by scripts/zero3.json:13-21 and zero3_offload.json:24-31 (AdamW, clip 1.0) */
-int tr1_sumsq_accum(const void* g, int64_t n, void* out_scalar, void* stream);
+int tr1_sumsq_accum(const void* g, int64_t n, void* out_scalar, void* ws_f32, int64_t ws_floats, void* stream);
 int tr1_adamw_step(void* p_f32, void* m_f32, void* v_f32, void* g_f32, void* p_bf16, int64_t n, float lr, float beta1, float beta2, float eps, float weight_decay, int64_t step, const void* sumsq_scalar, float max_norm, float grad_mult, int zero_grad, void* stream);
 /* Data-parallel forms: the all-reduced gradient is consumed from its bf16 wire buffer (no copy back into the fp32 accumulator, which is only
  * zeroed).  ref: DeepSpeed's bf16 gradient all-reduce + FusedAdam (scripts/zero3.json:13-33). */
@@ -266,12 +267,12 @@ int tr1_adamw_step_g16(void* p_f32, void* m_f32, void* v_f32, void* g_f32, const
  * per-layer tensors (same range description as tr1_zero_ranges_periodic).  wire_bf16 (optional, [M, N] bf16, leading dimension ld_wire): the stored value rounded to bf16 as well - the data-parallel gradient exchange's wire copy (dist.GradSync / ShardSync) without its staging pass. */
 int tr1_wgrad_f32_sumsq(const void* A, const void* B, void* C_f32, int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldb, int64_t ldc, int accumulate, int b_kmajor, int64_t b_rows, void* sumsq_partials, int64_t partials_capacity, int64_t* n_partials, void* wire_bf16, int64_t ld_wire, void* stream);
 int tr1_sumsq_partials_accum(const void* partials_f32, int64_t n, void* out_scalar, void* stream);
-int tr1_sumsq_ranges_periodic(const void* g_f32, int64_t base, int64_t stride, int64_t count, const int64_t* rel_ranges, int64_t n_ranges, void* out_scalar, void* stream);
+int tr1_sumsq_ranges_periodic(const void* g_f32, int64_t base, int64_t stride, int64_t count, const int64_t* rel_ranges, int64_t n_ranges, void* out_scalar, void* ws_f32, int64_t ws_floats, void* stream);
 /* g[base + l*stride + r] = 0 for l < count, r in the <= 8 half-open ranges (rel_ranges = HOST array of 2*n_ranges offsets inside one period): clears the small
  * per-layer gradient tensors when the optimizer leaves the large matrices un-zeroed (their weight-gradient GEMMs overwrite them on the first micro-step of the
  * next accumulation window).  ref: optimizer.zero_grad() in HF Trainer.training_step / DeepSpeed engine.step (scripts/zero3.json). */
 int tr1_zero_ranges_periodic(void* g_f32, int64_t base, int64_t stride, int64_t count, const int64_t* rel_ranges, int64_t n_ranges, void* stream);
-int tr1_sumsq_accum_bf16(const void* g_bf16, int64_t n, void* out_scalar, void* stream);
+int tr1_sumsq_accum_bf16(const void* g_bf16, int64_t n, void* out_scalar, void* ws_f32, int64_t ws_floats, void* stream);
 
 /* ---- Collectives (rccl_{init, allreduce, reduce_scatter, allgather}) ------------------------------------------------------------------
  * There is ONE exchange path: time-r1_amd/dist.py drives RCCL through torch.distributed's "nccl" backend (which IS librccl on ROCm): per-segment

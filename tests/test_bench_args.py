@@ -15,6 +15,9 @@ def test_driver_command_line_is_accepted():
     assert bench.window_plan(a.warmup, a.ga) == [2, 2, 1] and sum(bench.window_plan(a.warmup, a.ga)) == 5
     assert bench.window_plan(a.steps, a.ga) == [2] * 10
     assert bench.resolve_launch(a, {}, 1) == ("run", None)
+    assert not a.full and a.dump_outputs is None          # a plain run: no secondary measurements, no output files
+    f = bench.parse_args(["--gpus", "1", "--steps", "20", "--warmup", "5", "--full", "--dump-outputs", "out"])
+    assert f.full and f.dump_outputs == "out" and (f.steps, f.warmup) == (20, 5)
 
 
 @pytest.mark.parametrize("k,ga", [(1, 2), (7, 2), (20, 3), (4, 1), (0, 2)])

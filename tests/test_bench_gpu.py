@@ -26,7 +26,7 @@ def _run(extra, env=None, timeout=600):
 
 
 def test_driver_argument_shape_runs_and_reports_contract_fields():
-    out = _run(["--gpus", "1", "--steps", "5", "--warmup", "3"])
+    out = _run(["--gpus", "1", "--steps", "5", "--warmup", "3", "--full"])
     assert out["metric"] == "grpo_samples_per_sec" and out["unit"] == "samples/s" and out["n_gpus"] == 1
     assert out["steps"] == 5 and out["warmup"] == 3 and out["optimizer_steps"] == 3 and out["windows"] == "2 x 2 + 1 x 1"
     assert out["value"] > 0 and abs(out["value"] - 1000.0 / out["ms_per_step"]) < 1e-6 * out["value"]
@@ -39,6 +39,32 @@ def test_driver_argument_shape_runs_and_reports_contract_fields():
         assert out[k]["frac_of_measured"] is None or out[k]["frac_of_measured"] <= 1.0 + 1e-9, out[k]
         assert "traffic_guard" in out[k]
     assert {"samples_per_sec", "rollout_tokens_per_sec", "perf/decode_hbm_frac", "perf/train_mfma_frac"} <= set(out["trainer_log_last"])
+
+
+def test_plain_run_is_lean_and_dumps_the_same_outputs_every_time(tmp_path):
+    """Without --full the run only times its steps (no peak probe, engine-loop leg, roofline window or CPU baseline); --dump-outputs writes the
+    last timed step's arrays as float32 / float64 .npy files under 64 MB, and a second run with the same arguments writes the same arrays.  A run
+    with one more timed step writes other arrays (the dump is the LAST step's, not the first's) from the same seeded weight-sample index."""
+    import numpy as np
+    outs, dumps = [], []
+    for i, steps in enumerate((3, 3, 4)):
+        d = tmp_path / ("run%d" % i)
+        outs.append(_run(["--gpus", "1", "--steps", str(steps), "--warmup", "1", "--dump-outputs", str(d)]))
+        dumps.append({f[:-4]: np.load(d / f) for f in sorted(os.listdir(d))})
+        assert outs[-1]["steps"] == steps
+    for out in outs:
+        assert out["ms_per_step"] > 0 and abs(out["value"] - 1000.0 / out["ms_per_step"]) < 1e-6 * out["value"]
+        assert not {"roofline", "roofline_secondary", "peak_probe", "cpu_baseline", "rollout_logp_drift"} & set(out) and out["engine_path"] is None
+    a, b, c = dumps
+    assert set(c) == set(a) and np.array_equal(c["weights_sample_index"], a["weights_sample_index"])
+    for k in ("logp", "weights_master_sample"):          # (lr 1e-6 rarely moves a bf16 weight: the working copy may not differ)
+        assert not np.array_equal(c[k], a[k]), k                                # the fourth step's outputs, not the third's
+    assert {"completion_ids", "completion_mask", "advantages", "logp", "loss_terms", "grad_norm", "weights_bf16_sample", "weights_master_sample"} <= set(a)
+    assert set(a) == set(b) and sum(x.nbytes for x in a.values()) <= 64 << 20
+    assert a["completion_ids"].shape == (4, 8) and a["logp"].shape == (4, 8)
+    for k in a:
+        assert a[k].dtype in (np.float32, np.float64) and a[k].shape == b[k].shape and np.isfinite(a[k]).all(), k
+        assert np.array_equal(a[k], b[k]), (k, np.abs(a[k] - b[k]).max())          # every reduction of the step runs in a fixed order
 
 
 def test_ragged_eos_run_counts_only_tokens_up_to_the_injected_eos():

@@ -9,7 +9,7 @@ import time_r1_amd  # noqa: F401
 from time_r1_amd import data as D
 from time_r1_amd import evaluate as E
 
-REF_JSON = "/root/reference/dataset/timer1/annotations/train_2k5.json"
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
 
 def test_tg_rows_schema(tmp_path):
@@ -25,9 +25,13 @@ def test_tg_rows_schema(tmp_path):
     assert len(D.load_json_dataset_tg(str(p), require_files=False)) == 2
 
 
-@pytest.mark.skipif(not os.path.exists(REF_JSON), reason="reference annotations only exist in the build container")
-def test_reads_the_reference_annotation_file():
-    ds = D.load_json_dataset_tg(REF_JSON, is_curriculum_learning=True, require_files=False)
+def test_reads_the_reference_annotation_file(tmp_path):
+    """The reference's dataset/timer1/annotations/train_2k5.json, stored gzip-compressed under tests/golden/."""
+    import gzip
+    path = tmp_path / "train_2k5.json"
+    with gzip.open(os.path.join(GOLDEN, "train_2k5.json.gz"), "rb") as f:
+        path.write_bytes(f.read())
+    ds = D.load_json_dataset_tg(str(path), is_curriculum_learning=True, require_files=False)
     assert len(ds) == 2500 and set(ds[0]) == {"task_type", "problem", "choices", "solution", "video_path", "durations", "video_start", "video_end", "preprocessed_path"}
 
 

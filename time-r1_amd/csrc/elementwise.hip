@@ -191,19 +191,27 @@ __global__ void scatter_rows_kernel(const bf16_t* __restrict__ src, const int* _
         reinterpret_cast<u32x4_t*>(dst + (int64_t)idx[t] * cols)[c] = reinterpret_cast<const u32x4_t*>(src + t * cols)[c];
     }
 }
-// dtable[ids[t], :] += dout[t, :]  (fp32 atomics; rows with ids[t] < 0 are skipped)
-__global__ void embed_bwd_kernel(const bf16_t* __restrict__ dout, const int* __restrict__ ids, float* __restrict__ dtable, int64_t T,
-                                 int cols) {
-    const int64_t total = T * cols;
-    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
-        const int64_t t = i / cols; const int c = (int)(i - t * cols);
-        const int id = ids[t];
-        if (id >= 0) atomicAdd(&dtable[(int64_t)id * cols + c], bf2f(dout[i]));
+// dtable[ids[t], :] += dout[t, :]  (rows with ids[t] < 0 are skipped).  No atomics: thread (column c, bucket blockIdx.y) owns the entries
+// dtable[id, c] with id % gridDim.y == blockIdx.y and adds their rows in ascending t, so repeated ids sum in the same order on every run.
+// A wave reads 64 ids at a time, ballots the rows of its bucket and visits only those, lowest row first (uniform loop; video rows, id < 0, cost nothing).
+__global__ __launch_bounds__(256) void embed_bwd_kernel(const bf16_t* __restrict__ dout, const int* __restrict__ ids, float* __restrict__ dtable,
+                                                        int64_t T, int cols) {
+    const int c = blockIdx.x * blockDim.x + threadIdx.x;
+    const int nb = gridDim.y, b = blockIdx.y, lane = threadIdx.x & 63;
+    for (int64_t t0 = 0; t0 < T; t0 += 64) {
+        const int idl = t0 + lane < T ? ids[t0 + lane] : -1;
+        unsigned long long m = __ballot(idl >= 0 && idl % nb == b);
+        while (m) {
+            const int j = __ffsll((long long)m) - 1;
+            m &= m - 1;
+            const int id = __shfl(idl, j);
+            if (c < cols) dtable[(int64_t)id * cols + c] += bf2f(dout[(t0 + j) * cols + c]);
+        }
     }
 }
 
-// dbias[c] += sum_r dy[r, c]
-__global__ __launch_bounds__(256) void colsum_kernel(const bf16_t* __restrict__ dy, float* __restrict__ dbias, int64_t rows, int cols,
+// part[blockIdx.y, c] = sum of dy[r, c] over the block's rows; norm_dw_reduce_kernel then adds the partial rows to dbias in a fixed order
+__global__ __launch_bounds__(256) void colsum_kernel(const bf16_t* __restrict__ dy, float* __restrict__ part, int64_t rows, int cols,
                                                      int rows_per_block) {
     const int64_t r0 = (int64_t)blockIdx.y * rows_per_block;
     int64_t r1 = r0 + rows_per_block; if (r1 > rows) r1 = rows;
@@ -214,15 +222,15 @@ __global__ __launch_bounds__(256) void colsum_kernel(const bf16_t* __restrict__ 
         const unsigned p = *reinterpret_cast<const unsigned*>(dy + r * cols + c);
         a0 += bflo(p); a1 += bfhi(p);
     }
-    atomicAdd(&dbias[c], a0); atomicAdd(&dbias[c + 1], a1);
+    part[(int64_t)blockIdx.y * cols + c] = a0; part[(int64_t)blockIdx.y * cols + c + 1] = a1;
 }
 
 // ---------------------------------------------------------------- transpose (with zero padding)
 // out[c, r] = in[r, c] for r < R, c < C; out has leading dimension ld_out >= R and columns [R, ld_out) are zero-filled.
 // 64 x 64 tile through LDS with 16-byte global accesses on both sides: rows are read 8 elements per lane, the transposed tile is written
 // 8 elements per lane (the 2-byte-per-lane form this replaces ran at ~1 TB/s and was 4.6 % of the 7B step's kernel time).
-// COLSUM: the tile's column sums are added to colsum[c] (fp32 atomics, one per column and block) - the bias gradient of a Linear taken from the pass that
-// builds dY^T for its weight gradient instead of a second read of dY (tr1_colsum_accum).
+// COLSUM: the tile's column sums go to row blockIdx.y of the partials colsum[ceil(R / 64), C] (norm_dw_reduce_kernel adds them up in a fixed order) - the
+// bias gradient of a Linear taken from the pass that builds dY^T for its weight gradient instead of a second read of dY (tr1_colsum_accum).
 template <bool COLSUM>
 __global__ __launch_bounds__(256) void transpose_kernel(const bf16_t* __restrict__ in, int64_t ld_in, bf16_t* __restrict__ out,
                                                         int64_t ld_out, int64_t R, int64_t C, float* __restrict__ colsum) {
@@ -283,7 +291,7 @@ __global__ __launch_bounds__(256) void transpose_kernel(const bf16_t* __restrict
             float a = 0.f;
 #pragma unroll
             for (int j = 0; j < 8; ++j) a += csum[j][threadIdx.x];
-            atomicAdd(&colsum[c0 + threadIdx.x], a);
+            colsum[(int64_t)blockIdx.y * C + c0 + threadIdx.x] = a;
         }
     }
 }
@@ -383,16 +391,21 @@ extern "C" int tr1_scatter_rows(const void* src, const void* idx, void* dst, int
 }
 extern "C" int tr1_embed_bwd(const void* dout, const void* ids, void* dtable_f32, int64_t T, int64_t cols, void* stream) {
     if (T == 0) return 0;
-    hipLaunchKernelGGL(embed_bwd_kernel, dim3(EW_GRID(T * cols)), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)dout, (const int*)ids,
+    hipLaunchKernelGGL(embed_bwd_kernel, dim3((unsigned)((cols + 255) / 256), 64), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)dout, (const int*)ids,
                        (float*)dtable_f32, T, (int)cols);
     TR1_LAUNCH_CHECK();
 }
-extern "C" int tr1_colsum_accum(const void* dy, void* dbias_f32, int64_t rows, int64_t cols, void* stream) {
+// ws_f32: tr1_colsum_workspace_floats(rows, cols) floats of per-block partial rows
+extern "C" int64_t tr1_colsum_workspace_floats(int64_t rows, int64_t cols) { return (rows + 127) / 128 * cols; }
+extern "C" int tr1_colsum_accum(const void* dy, void* dbias_f32, int64_t rows, int64_t cols, void* ws_f32, int64_t ws_floats, void* stream) {
     TR1_CHECK_ARG(cols % 2 == 0, "colsum: cols must be even");
     if (rows == 0) return 0;
     const int rpb = 128;
+    TR1_CHECK_ARG(ws_f32 && ws_floats >= tr1_colsum_workspace_floats(rows, cols), "colsum: workspace too small (tr1_colsum_workspace_floats)");
     dim3 grid((unsigned)((cols / 2 + 255) / 256), (unsigned)((rows + rpb - 1) / rpb));
-    hipLaunchKernelGGL(colsum_kernel, grid, dim3(256), 0, (hipStream_t)stream, (const bf16_t*)dy, (float*)dbias_f32, rows, (int)cols, rpb);
+    hipLaunchKernelGGL(colsum_kernel, grid, dim3(256), 0, (hipStream_t)stream, (const bf16_t*)dy, (float*)ws_f32, rows, (int)cols, rpb);
+    hipLaunchKernelGGL(norm_dw_reduce_kernel, dim3((unsigned)((cols + 63) / 64)), dim3(1024), 0, (hipStream_t)stream, (const float*)ws_f32,
+                       (float*)dbias_f32, (int)grid.y, (int)cols);
     TR1_LAUNCH_CHECK();
 }
 extern "C" int tr1_transpose_bf16(const void* in, int64_t ld_in, void* out, int64_t ld_out, int64_t R, int64_t C, void* stream) {
@@ -403,11 +416,16 @@ extern "C" int tr1_transpose_bf16(const void* in, int64_t ld_in, void* out, int6
     TR1_LAUNCH_CHECK();
 }
 // The same transpose, and colsum_f32[c] += sum_r in[r, c] (the bias gradient rides on the pass that builds dY^T)
-extern "C" int tr1_transpose_colsum_bf16(const void* in, int64_t ld_in, void* out, int64_t ld_out, int64_t R, int64_t C, void* colsum_f32, void* stream) {
+// ws_f32: ceil(R / 64) * C floats of per-tile-row column sums
+extern "C" int tr1_transpose_colsum_bf16(const void* in, int64_t ld_in, void* out, int64_t ld_out, int64_t R, int64_t C, void* colsum_f32, void* ws_f32,
+                                         int64_t ws_floats, void* stream) {
     TR1_CHECK_ARG(ld_out >= R && ld_in >= C && colsum_f32, "transpose_colsum: bad leading dimensions / missing colsum");
     if (R == 0 || C == 0) return 0;
+    TR1_CHECK_ARG(ws_f32 && ws_floats >= (R + 63) / 64 * C, "transpose_colsum: workspace too small (ceil(R / 64) * C floats)");
     dim3 grid((unsigned)((C + 63) / 64), (unsigned)((ld_out + 63) / 64));
-    hipLaunchKernelGGL(transpose_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, (const bf16_t*)in, ld_in, (bf16_t*)out, ld_out, R, C, (float*)colsum_f32);
+    hipLaunchKernelGGL(transpose_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, (const bf16_t*)in, ld_in, (bf16_t*)out, ld_out, R, C, (float*)ws_f32);
+    hipLaunchKernelGGL(norm_dw_reduce_kernel, dim3((unsigned)((C + 63) / 64)), dim3(1024), 0, (hipStream_t)stream, (const float*)ws_f32,
+                       (float*)colsum_f32, (int)((R + 63) / 64), (int)C);
     TR1_LAUNCH_CHECK();
 }
 

@@ -80,7 +80,7 @@ __global__ __launch_bounds__(256) void rmsnorm_fwd_kernel(const bf16_t* __restri
     }
 }
 
-// dx = rstd * (dy*w - xhat * mean(dy*w*xhat)) (+ dres) ; dw[c] += sum_r dy*xhat  (fp32 atomics, one per block per column)
+// dx = rstd * (dy*w - xhat * mean(dy*w*xhat)) (+ dres) ; dw[c] += sum_r dy*xhat  (per-block partial rows, added by norm_dw_reduce_kernel)
 __global__ __launch_bounds__(256) void rmsnorm_bwd_kernel(const bf16_t* __restrict__ dy, const bf16_t* __restrict__ x,
                                                           const bf16_t* __restrict__ w, const float* __restrict__ rstd_in,
                                                           const bf16_t* __restrict__ dres, bf16_t* __restrict__ dx,
@@ -154,26 +154,6 @@ __global__ __launch_bounds__(256) void rmsnorm_bwd_kernel(const bf16_t* __restri
     }
 }
 
-// dw[c] += sum_b part[b][c], b in ascending order inside each of 16 row groups, groups combined in a fixed order.  64 columns per block.
-__global__ __launch_bounds__(1024) void norm_dw_reduce_kernel(const float* __restrict__ part, float* __restrict__ dw, int nblk, int cols) {
-    __shared__ float red[16][64];
-    const int cl = threadIdx.x & 63, rg = threadIdx.x >> 6;
-    const int c = blockIdx.x * 64 + cl;
-    const int per = (nblk + 15) / 16, b0 = rg * per, b1 = min(nblk, b0 + per);
-    float s = 0.f;
-    if (c < cols) {
-#pragma unroll 8
-        for (int b = b0; b < b1; ++b) s += part[(size_t)b * cols + c];
-    }
-    red[rg][cl] = s;
-    __syncthreads();
-    if (rg == 0 && c < cols) {
-        float t = 0.f;
-#pragma unroll
-        for (int i = 0; i < 16; ++i) t += red[i][cl];
-        dw[c] += t;
-    }
-}
 
 __global__ __launch_bounds__(256) void layernorm_fwd_kernel(const bf16_t* __restrict__ x, const bf16_t* __restrict__ w,
                                                             const bf16_t* __restrict__ b, bf16_t* __restrict__ y,
@@ -236,14 +216,12 @@ __global__ __launch_bounds__(256) void layernorm_fwd_kernel(const bf16_t* __rest
 __global__ __launch_bounds__(256) void layernorm_bwd_kernel(const bf16_t* __restrict__ dy, const bf16_t* __restrict__ x,
                                                             const bf16_t* __restrict__ w, const float* __restrict__ mean_in,
                                                             const float* __restrict__ rstd_in, bf16_t* __restrict__ dx,
-                                                            float* __restrict__ dw, float* __restrict__ db, int rows, int cols) {
-    extern __shared__ __attribute__((aligned(16))) float lds_acc[];  // [2*cols]
+                                                            float* __restrict__ dw_part, float* __restrict__ db_part, int rows, int cols) {
+    extern __shared__ __attribute__((aligned(16))) float lds_acc[];  // [4 waves][cols]
     const int lane = threadIdx.x & 63;
     const int wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
     const int nwaves = (gridDim.x * blockDim.x) >> 6;
     const int nch = cols >> 3;
-    for (int c = threadIdx.x; c < 2 * cols; c += blockDim.x) lds_acc[c] = 0.f;
-    __syncthreads();
     float dwa[NORM_MAXC][8], dba[NORM_MAXC][8];
 #pragma unroll
     for (int i = 0; i < NORM_MAXC; ++i)
@@ -291,16 +269,23 @@ __global__ __launch_bounds__(256) void layernorm_bwd_kernel(const bf16_t* __rest
             }
         }
     }
+    // per-block partial rows of dgamma and dbeta, the four waves combined in a fixed order (no atomics: the gradients are reproducible)
+    float* mine = lds_acc + (threadIdx.x >> 6) * cols;
+    auto partial_row = [&](const float (&acc)[NORM_MAXC][8], float* __restrict__ part) {
 #pragma unroll
-    for (int i = 0; i < NORM_MAXC; ++i) {
-        const int c = lane + i * 64;
-        if (c < nch) {
+        for (int i = 0; i < NORM_MAXC; ++i) {
+            const int c = lane + i * 64;
+            if (c < nch)
 #pragma unroll
-            for (int j = 0; j < 8; ++j) { atomicAdd(&lds_acc[c * 8 + j], dwa[i][j]); atomicAdd(&lds_acc[cols + c * 8 + j], dba[i][j]); }
+                for (int j = 0; j < 8; ++j) mine[c * 8 + j] = acc[i][j];
         }
-    }
+        __syncthreads();
+        for (int c = threadIdx.x; c < cols; c += blockDim.x)
+            part[(size_t)blockIdx.x * cols + c] = (lds_acc[c] + lds_acc[cols + c]) + (lds_acc[2 * cols + c] + lds_acc[3 * cols + c]);
+    };
+    partial_row(dwa, dw_part);
     __syncthreads();
-    for (int c = threadIdx.x; c < cols; c += blockDim.x) { atomicAdd(&dw[c], lds_acc[c]); atomicAdd(&db[c], lds_acc[cols + c]); }
+    partial_row(dba, db_part);
 }
 
 static inline int norm_grid(int rows) { int g = (rows + 3) / 4; if (g > 2048) g = 2048; if (g < 1) g = 1; return g; }
@@ -350,14 +335,21 @@ extern "C" int tr1_layernorm_fwd(const void* x, const void* w, const void* b, vo
     TR1_LAUNCH_CHECK();
 }
 
+// ws_f32: 2 * tr1_rmsnorm_bwd_workspace_floats(rows, cols) floats (per-block partial rows of dgamma, then of dbeta)
 extern "C" int tr1_layernorm_bwd(const void* dy, const void* x, const void* w, const void* mean, const void* rstd, void* dx,
-                                 void* dw_f32, void* db_f32, int64_t rows, int64_t cols, void* stream) {
+                                 void* dw_f32, void* db_f32, void* ws_f32, int64_t ws_floats, int64_t rows, int64_t cols, void* stream) {
     TR1_CHECK_ARG(cols % 8 == 0 && cols <= 64 * 8 * NORM_MAXC, "layernorm_bwd: cols must be a multiple of 8 and <= 4096");
     TR1_CHECK_ARG(dw_f32 && db_f32, "layernorm_bwd: dw/db required");
     if (rows == 0) return 0;
-    int g = (int)((rows + 3) / 4); if (g > 512) g = 512;
-    hipLaunchKernelGGL(layernorm_bwd_kernel, dim3(g), dim3(256), 2 * cols * sizeof(float), (hipStream_t)stream, (const bf16_t*)dy,
-                       (const bf16_t*)x, (const bf16_t*)w, (const float*)mean, (const float*)rstd, (bf16_t*)dx, (float*)dw_f32,
-                       (float*)db_f32, (int)rows, (int)cols);
+    const int g = norm_bwd_blocks(rows);
+    TR1_CHECK_ARG(ws_f32 && ws_floats >= 2 * (int64_t)g * cols, "layernorm_bwd: workspace too small (2 x tr1_rmsnorm_bwd_workspace_floats)");
+    float* dw_part = (float*)ws_f32;
+    float* db_part = dw_part + (int64_t)g * cols;
+    hipLaunchKernelGGL(layernorm_bwd_kernel, dim3(g), dim3(256), 4 * cols * sizeof(float), (hipStream_t)stream, (const bf16_t*)dy,
+                       (const bf16_t*)x, (const bf16_t*)w, (const float*)mean, (const float*)rstd, (bf16_t*)dx, dw_part, db_part, (int)rows, (int)cols);
+    hipLaunchKernelGGL(norm_dw_reduce_kernel, dim3((unsigned)((cols + 63) / 64)), dim3(1024), 0, (hipStream_t)stream, (const float*)dw_part,
+                       (float*)dw_f32, g, (int)cols);
+    hipLaunchKernelGGL(norm_dw_reduce_kernel, dim3((unsigned)((cols + 63) / 64)), dim3(1024), 0, (hipStream_t)stream, (const float*)db_part,
+                       (float*)db_f32, g, (int)cols);
     TR1_LAUNCH_CHECK();
 }

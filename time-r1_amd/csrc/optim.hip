@@ -16,7 +16,7 @@
 #define OPT_ST(val, ptr) (*(ptr) = (val))
 #endif
 
-__global__ __launch_bounds__(256) void sumsq_kernel(const float* __restrict__ g, int64_t n, float* __restrict__ out) {
+__global__ __launch_bounds__(256) void sumsq_kernel(const float* __restrict__ g, int64_t n, float* __restrict__ part) {
     __shared__ float red[16];
     float s = 0.f;
     const int64_t n4 = n >> 2;
@@ -26,11 +26,11 @@ __global__ __launch_bounds__(256) void sumsq_kernel(const float* __restrict__ g,
     }
     if (blockIdx.x == 0) for (int64_t i = n4 * 4 + threadIdx.x; i < n; i += blockDim.x) s += g[i] * g[i];
     s = block_sum(s, red);
-    if (threadIdx.x == 0) atomicAdd(out, s);
+    if (threadIdx.x == 0) part[blockIdx.x] = s;        // per-block partial: partials_sum_kernel adds them in a fixed order (reproducible norm)
 }
 
 // the same sum over a bf16 array (data-parallel runs: the all-reduced gradient stays in its bf16 wire buffer and is consumed from there)
-__global__ __launch_bounds__(256) void sumsq_bf16_kernel(const bf16_t* __restrict__ g, int64_t n, float* __restrict__ out) {
+__global__ __launch_bounds__(256) void sumsq_bf16_kernel(const bf16_t* __restrict__ g, int64_t n, float* __restrict__ part) {
     __shared__ float red[16];
     float s = 0.f;
     const int64_t n8 = n >> 3;
@@ -41,7 +41,7 @@ __global__ __launch_bounds__(256) void sumsq_bf16_kernel(const bf16_t* __restric
     }
     if (blockIdx.x == 0) for (int64_t i = n8 * 8 + threadIdx.x; i < n; i += blockDim.x) { const float a = bf2f(g[i]); s += a * a; }
     s = block_sum(s, red);
-    if (threadIdx.x == 0) atomicAdd(out, s);
+    if (threadIdx.x == 0) part[blockIdx.x] = s;
 }
 
 // sumsq: device scalar with sum of squared grads (already multiplied by nothing); clip coefficient derived in-kernel so the
@@ -89,9 +89,13 @@ __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, float
     }
 }
 
-extern "C" int tr1_sumsq_accum(const void* g, int64_t n, void* out_scalar, void* stream) {
+// ws_f32: >= 2048 floats of scratch for the per-block partials (no float atomics: the same gradient gives the same norm on every run)
+extern "C" int tr1_sumsq_accum(const void* g, int64_t n, void* out_scalar, void* ws_f32, int64_t ws_floats, void* stream) {
     if (n == 0) return 0;
-    hipLaunchKernelGGL(sumsq_kernel, dim3(tr1_grid_1d(n / 4 + 1, 256, 2048)), dim3(256), 0, (hipStream_t)stream, (const float*)g, n, (float*)out_scalar);
+    const int nb = tr1_grid_1d(n / 4 + 1, 256, 2048);
+    TR1_CHECK_ARG(ws_f32 && ws_floats >= nb, "sumsq_accum: workspace too small");
+    hipLaunchKernelGGL(sumsq_kernel, dim3(nb), dim3(256), 0, (hipStream_t)stream, (const float*)g, n, (float*)ws_f32);
+    hipLaunchKernelGGL(partials_sum_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, (const float*)ws_f32, (int64_t)nb, (float*)out_scalar);
     TR1_LAUNCH_CHECK();
 }
 
@@ -123,9 +127,12 @@ extern "C" int tr1_adamw_step_g16(void* p_f32, void* m_f32, void* v_f32, void* g
     TR1_LAUNCH_CHECK();
 }
 
-extern "C" int tr1_sumsq_accum_bf16(const void* g_bf16, int64_t n, void* out_scalar, void* stream) {
+extern "C" int tr1_sumsq_accum_bf16(const void* g_bf16, int64_t n, void* out_scalar, void* ws_f32, int64_t ws_floats, void* stream) {
     if (n == 0) return 0;
-    hipLaunchKernelGGL(sumsq_bf16_kernel, dim3(tr1_grid_1d(n / 8 + 1, 256, 2048)), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)g_bf16, n, (float*)out_scalar);
+    const int nb = tr1_grid_1d(n / 8 + 1, 256, 2048);
+    TR1_CHECK_ARG(ws_f32 && ws_floats >= nb, "sumsq_accum_bf16: workspace too small");
+    hipLaunchKernelGGL(sumsq_bf16_kernel, dim3(nb), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)g_bf16, n, (float*)ws_f32);
+    hipLaunchKernelGGL(partials_sum_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, (const float*)ws_f32, (int64_t)nb, (float*)out_scalar);
     TR1_LAUNCH_CHECK();
 }
 
@@ -183,17 +190,17 @@ extern "C" int tr1_sumsq_partials_accum(const void* partials_f32, int64_t n, voi
 
 // out += sum of g[base + l * stride + r]^2 over l < count and r in the (<= 8) half-open ranges: the SMALL per-layer gradient tensors next to the large matrices
 // whose squared norm came out of the weight-gradient epilogues
-__global__ __launch_bounds__(256) void sumsq_periodic_kernel(const float* __restrict__ g, int64_t base, int64_t stride, ZeroRanges zr, float* __restrict__ out) {
+__global__ __launch_bounds__(256) void sumsq_periodic_kernel(const float* __restrict__ g, int64_t base, int64_t stride, ZeroRanges zr, float* __restrict__ part) {
     __shared__ float red[16];
     const float* gl = g + base + (int64_t)blockIdx.y * stride;
     float s = 0.f;
     for (int r = 0; r < zr.n; ++r)
         for (int64_t i = zr.a[r] + blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < zr.b[r]; i += (int64_t)gridDim.x * blockDim.x) { const float v = gl[i]; s += v * v; }
     s = block_sum(s, red);
-    if (threadIdx.x == 0) atomicAdd(out, s);
+    if (threadIdx.x == 0) part[(int64_t)blockIdx.y * gridDim.x + blockIdx.x] = s;
 }
 extern "C" int tr1_sumsq_ranges_periodic(const void* g_f32, int64_t base, int64_t stride, int64_t count, const int64_t* rel_ranges, int64_t n_ranges, void* out_scalar,
-                                         void* stream) {
+                                         void* ws_f32, int64_t ws_floats, void* stream) {
     TR1_CHECK_ARG(n_ranges >= 0 && n_ranges <= 8 && (n_ranges == 0 || rel_ranges) && out_scalar, "sumsq_ranges_periodic: at most 8 ranges");
     if (count <= 0 || n_ranges == 0) return 0;
     ZeroRanges zr; zr.n = (int)n_ranges;
@@ -204,6 +211,8 @@ extern "C" int tr1_sumsq_ranges_periodic(const void* g_f32, int64_t base, int64_
         if (zr.b[i] - zr.a[i] > longest) longest = zr.b[i] - zr.a[i];
     }
     const unsigned gx = (unsigned)((longest + 255) / 256 < 64 ? (longest + 255) / 256 : 64);
-    hipLaunchKernelGGL(sumsq_periodic_kernel, dim3(gx, (unsigned)count), dim3(256), 0, (hipStream_t)stream, (const float*)g_f32, base, stride, zr, (float*)out_scalar);
+    TR1_CHECK_ARG(ws_f32 && ws_floats >= (int64_t)gx * count, "sumsq_ranges_periodic: workspace too small (64 floats per period)");
+    hipLaunchKernelGGL(sumsq_periodic_kernel, dim3(gx, (unsigned)count), dim3(256), 0, (hipStream_t)stream, (const float*)g_f32, base, stride, zr, (float*)ws_f32);
+    hipLaunchKernelGGL(partials_sum_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, (const float*)ws_f32, (int64_t)gx * count, (float*)out_scalar);
     TR1_LAUNCH_CHECK();
 }

@@ -94,6 +94,37 @@ extern "C" void tr1_set_error_(const char* msg);
         return 0;                                                 \
     } while (0)
 
+// dw[c] += sum_b part[b][c] (the fixed-order second level of every per-block column reduction: norm weights, bias gradients), b in ascending order inside each of 16 row groups, groups combined in a fixed order.  64 columns per block.
+static __global__ __launch_bounds__(1024) void norm_dw_reduce_kernel(const float* __restrict__ part, float* __restrict__ dw, int nblk, int cols) {
+    __shared__ float red[16][64];
+    const int cl = threadIdx.x & 63, rg = threadIdx.x >> 6;
+    const int c = blockIdx.x * 64 + cl;
+    const int per = (nblk + 15) / 16, b0 = rg * per, b1 = min(nblk, b0 + per);
+    float s = 0.f;
+    if (c < cols) {
+#pragma unroll 8
+        for (int b = b0; b < b1; ++b) s += part[(size_t)b * cols + c];
+    }
+    red[rg][cl] = s;
+    __syncthreads();
+    if (rg == 0 && c < cols) {
+        float t = 0.f;
+#pragma unroll
+        for (int i = 0; i < 16; ++i) t += red[i][cl];
+        dw[c] += t;
+    }
+}
+
+// out[0] += sum of part[0 .. n) in a fixed order (one block of 256: thread t adds part[t], part[t + 256], ...; then the block tree) - the second level
+// of the per-block squared-norm partials
+static __global__ __launch_bounds__(256) void partials_sum_kernel(const float* __restrict__ part, int64_t n, float* __restrict__ out) {
+    __shared__ float red[16];
+    float s = 0.f;
+    for (int64_t i = threadIdx.x; i < n; i += 256) s += part[i];
+    s = block_sum(s, red);
+    if (threadIdx.x == 0) out[0] += s;
+}
+
 static inline int tr1_grid_1d(int64_t work_items, int per_block, int cap = 8192) {
     int64_t g = (work_items + per_block - 1) / per_block;
     if (g < 1) g = 1;

@@ -387,7 +387,9 @@ class HipOps:
         assert out.shape[0] == C and out.shape[1] >= R
         if colsum is not None:
             assert colsum.dtype == F32 and colsum.numel() == C and colsum.is_contiguous()
-            self.L.call("tr1_transpose_colsum_bf16", _p(x), _ld(x), _p(out), _ld(out), R, C, _p(colsum), self._s())
+            nws = (R + 63) // 64 * C
+            ws = self._workspace("transpose_colsum", nws, F32)
+            self.L.call("tr1_transpose_colsum_bf16", _p(x), _ld(x), _p(out), _ld(out), R, C, _p(colsum), _p(ws), nws, self._s())
             return out
         self.L.call("tr1_transpose_bf16", _p(x), _ld(x), _p(out), _ld(out), R, C, self._s())
         return out
@@ -433,7 +435,9 @@ class HipOps:
         rows, cols = x.shape
         assert dy.is_contiguous() and x.is_contiguous() and dw.dtype == F32 and db.dtype == F32
         dx = self.empty(rows, cols) if need_dx else None
-        self.L.call("tr1_layernorm_bwd", _p(dy), _p(x), _p(w), _p(mean), _p(rstd), _p(dx), _p(dw), _p(db), rows, cols, self._s())
+        nws = 2 * int(self.L.raw("tr1_rmsnorm_bwd_workspace_floats")(rows, cols))
+        ws = self._workspace("layernorm_bwd", nws, F32)
+        self.L.call("tr1_layernorm_bwd", _p(dy), _p(x), _p(w), _p(mean), _p(rstd), _p(dx), _p(dw), _p(db), _p(ws), nws, rows, cols, self._s())
         return dx
 
     # ---- activations ----------------------------------------------------------------------------------------------
@@ -486,7 +490,9 @@ class HipOps:
     def colsum_accum(self, dy, dbias):
         self._chk(dy)
         assert dy.is_contiguous() and dbias.dtype == F32 and dbias.numel() == dy.shape[1]
-        self.L.call("tr1_colsum_accum", _p(dy), _p(dbias), dy.shape[0], dy.shape[1], self._s())
+        nws = int(self.L.raw("tr1_colsum_workspace_floats")(dy.shape[0], dy.shape[1]))
+        ws = self._workspace("colsum", nws, F32)
+        self.L.call("tr1_colsum_accum", _p(dy), _p(dbias), dy.shape[0], dy.shape[1], _p(ws), nws, self._s())
 
     def cast_to_act(self, x_f32):
         assert x_f32.dtype == F32 and x_f32.is_contiguous()
@@ -748,7 +754,8 @@ class HipOps:
     # ---- optimizer ------------------------------------------------------------------------------------------------
     def sumsq_accum(self, g, out_scalar):
         assert g.dtype in (F32, BF16) and out_scalar.dtype == F32
-        self.L.call("tr1_sumsq_accum" if g.dtype == F32 else "tr1_sumsq_accum_bf16", _p(g), g.numel(), _p(out_scalar), self._s())
+        ws = self._workspace("sumsq", 2048, F32)              # per-block partials (at most 2048 blocks), summed in a fixed order
+        self.L.call("tr1_sumsq_accum" if g.dtype == F32 else "tr1_sumsq_accum_bf16", _p(g), g.numel(), _p(out_scalar), _p(ws), 2048, self._s())
 
     def wgrad_sumsq(self, a, b, gw, accumulate, partials, offset, b_kmajor=False, b_rows=0, wire=None):
         """gw[N, K] fp32 (+)= a[N, Mp] @ b^T (b = X^T [K, Mp]) or a @ b (b_kmajor: b = X [>= b_rows, K] as stored), and partials[offset : offset + n] receives
@@ -782,7 +789,9 @@ class HipOps:
         assert g.dtype == F32 and g.is_contiguous() and base + stride * count <= g.numel() and len(rel_ranges) <= 8
         flat = [int(x) for ab in rel_ranges for x in ab]
         arr = (ctypes.c_int64 * max(1, len(flat)))(*flat)
-        self.L.call("tr1_sumsq_ranges_periodic", _p(g), int(base), int(stride), int(count), arr, len(rel_ranges), _p(out_scalar), self._s())
+        nws = 64 * max(1, int(count))                       # at most 64 blocks per period
+        ws = self._workspace("sumsq_periodic", nws, F32)
+        self.L.call("tr1_sumsq_ranges_periodic", _p(g), int(base), int(stride), int(count), arr, len(rel_ranges), _p(out_scalar), _p(ws), nws, self._s())
 
     def zero_ranges_periodic(self, g, base, stride, count, rel_ranges):
         """g[base + l*stride + r] = 0 for l < count and r in the half-open `rel_ranges` [(a, b), ...] (<= 8) of one period."""

@@ -2,7 +2,7 @@
 # Round-3 evidence for BASELINE configs 2, 4, 5 on one box: bench JSON + kernel table each.  outputs under gpurun_out/evc_*
 cd "$GRAFT_REPO_ROOT"
 O=gpurun_out
-X="--no-cpu-baseline"
+X="--full --no-cpu-baseline"
 T="--no-cpu-baseline --no-roofline --no-peak-probe --no-engine-leg"
 timeout 600 python bench.py --rollout-fp8 --steps 8 --warmup 2 $X > $O/evc_cfg5.json 2> $O/evc_cfg5.err </dev/null
 bash tools/trace_bench.sh evc_cfg5 --rollout-fp8 --steps 4 --warmup 2 $T > /dev/null 2>&1 </dev/null

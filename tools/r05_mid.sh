@@ -2,7 +2,7 @@
 # round 5 mid-round check: full GPU suite, headline bench, configs 4 / 2 / 5
 cd "$GRAFT_REPO_ROOT"; O=gpurun_out; 
 timeout 1500 python -m pytest tests -m gpu -x -q 2>&1 | tail -6 > $O/r05_mid_gputest.txt
-timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 > $O/r05_mid_bench7b.json 2> $O/r05_mid_bench7b.err
+timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 --full > $O/r05_mid_bench7b.json 2> $O/r05_mid_bench7b.err
 X="--no-cpu-baseline --no-roofline --no-peak-probe --no-engine-leg"
 timeout 900 python bench.py --model qwen2.5-vl-7b --frames 64 --G 16 --C 1024 --beta 0 --clip-loss --steps 2 --warmup 2 $X > $O/r05_mid_cfg4.json 2> $O/r05_mid_cfg4.err
 timeout 600 python bench.py --model qwen2-vl-2b --frames 16 --steps 8 --warmup 2 $X > $O/r05_mid_cfg2.json 2> $O/r05_mid_cfg2.err

@@ -17,7 +17,7 @@ if [ -n "$db" ]; then
   rm -rf $O/ev_${tag}_fetch
 else echo "no fetch db"; tail -3 $O/ev_${tag}_fetch.err; fi
 # 2. the driver's command
-timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 > $O/ev_${tag}_bench.json 2> $O/ev_${tag}_bench.err </dev/null
+timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 --full > $O/ev_${tag}_bench.json 2> $O/ev_${tag}_bench.err </dev/null
 python - <<PY
 import json
 d = json.loads(open("$O/ev_${tag}_bench.json").read().strip().splitlines()[-1])

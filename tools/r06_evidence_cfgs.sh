@@ -2,7 +2,7 @@
 # Round-6 evidence for BASELINE configs 2, 4, 5 on one box: bench JSON + kernel table each.  outputs under gpurun_out/evc_*
 cd "$GRAFT_REPO_ROOT"
 O=gpurun_out
-X="--no-cpu-baseline"
+X="--full --no-cpu-baseline"
 T="--no-cpu-baseline --no-roofline --no-peak-probe --no-engine-leg"
 # config 5 first: HBM read traffic per launch of the fp8 decode kernels (own pass), so that the bench line below can attach roofline.traffic
 cd /tmp && export TMPDIR=/tmp; cd "$GRAFT_REPO_ROOT"
