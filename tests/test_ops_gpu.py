@@ -1048,3 +1048,36 @@ def test_weight_gradient_epilogue_also_writes_the_bf16_wire_copy(hip_ops, kmajor
         assert torch.equal(wire, gw_b.to(BF16)), "the wire copy must be the bf16 rounding of the stored gradient"
         want = (gw0.double() if acc else 0.0) + dy.double().t() @ x.double()
         close(gw_b.cpu(), want.float().cpu(), 0.02, rtol=0.02, what="wgrad with wire copy")
+
+
+def test_large_lds_launches_on_a_second_device(hip_ops, monkeypatch):
+    """Kernels above 64 KiB of dynamic LDS get their limit raised once per DEVICE (Tr1PerDevice in csrc/tr1_common.h), not once per process: the same
+    launches first on cuda:0, then on cuda:1 in the same process, give bit-identical results.  The 64-row attention forward (>= 3 072 key slots), the
+    phased 8-wave NT GEMM and the <= 16-row LDS-streamed gate/up + SwiGLU (norm_glu_lds_kernel)."""
+    if torch.cuda.device_count() < 2:
+        pytest.skip("needs two HIP devices")
+    from time_r1_amd.ops import HipOps
+    monkeypatch.delenv("TR1_FWD64", raising=False)
+    nh, nkv, hd = 4, 2, 128
+    pre, lo, hi = masks_prefix_shared(2900, 2, 100)
+    S = pre.numel()
+    attn_in = [rnd(S, nh * hd, seed=51), rnd(S, nkv * hd, seed=52), rnd(S, nkv * hd, seed=53), pre, lo, hi]
+    gemm_in = [rnd(4096, 256, seed=54), rnd(4096, 256, seed=55, scale=0.1)]
+    H, I = 1536, 2048
+    glu_in = [rnd(16, H, seed=56), (1.0 + 0.1 * rnd(H, seed=57).float()).to(BF16), rnd(2 * I, H, seed=58, scale=1.0 / math.sqrt(H))]
+
+    def run(ops, dev):
+        q, k, v, pr, l, h = [t.to(dev) for t in attn_in]
+        o, lse = ops.attn_fwd(q, k, None, pr, l, h, nh, nkv, S, hd, hd ** -0.5, v_rows=v)
+        c = ops.gemm_nt(*[t.to(dev) for t in gemm_in])
+        x, lnw, wgu = [t.to(dev) for t in glu_in]
+        a = ops.norm_gemm(x, lnw, 1e-6, wgu, glu=True)
+        torch.cuda.synchronize(dev)
+        return [t.cpu() for t in (o, lse, c, a)]
+
+    first = run(hip_ops, "cuda:0")
+    with torch.cuda.device(1):
+        second = run(HipOps("cuda:1"), "cuda:1")
+    for what, a, b in zip(("attention O", "attention LSE", "NT GEMM", "gate/up SwiGLU"), first, second):
+        assert torch.isfinite(a.float()).all(), what + ": non-finite values on cuda:0"
+        assert torch.equal(a, b), what + ": cuda:1 differs from cuda:0"

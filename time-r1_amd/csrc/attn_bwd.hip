@@ -11,7 +11,6 @@
 // gridDim.z blocks (the prefix key blocks see ~all query tiles, the suffix blocks only a few): partial dK/dV go to an fp32
 // workspace and a small reduce kernel sums and rounds them.
 #include "attn_common.h"
-#include <stdlib.h>
 
 #define DKDV32_MAXT 512     // query tiles per block of the 32x32x16 kernel (its LDS budget is spent on the tile ring + P exchange)
 #define ATT_QMETA 8         // ints per 64-row query tile in the mask summary written by attn_delta_kernel
@@ -1535,16 +1534,15 @@ static int launch_bwd(const AttnParams& p, hipStream_t s, float* ws, int64_t ws_
     constexpr int KB = NW * 16;
     const size_t dyn_dq = 2 * (2 * ATT_KV * KSTR) + 64;
     const size_t dyn_kv = 2 * (2 * 64 * KSTR + (NW == 8 ? 0 : 2 * D * 144) + 64 * 5 * 4 + 16) + (DKDV_MAXT + 1) * 4;
-    static bool attr_set = false;
-    if (!attr_set) {
+    static Tr1PerDevice lds;
+    if (lds.first()) {
         hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_bwd_dq_kernel<D>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn_dq);
         hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_bwd_dkdv_kernel<D, NW>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn_kv);
-        attr_set = true;
     }
     // head dim 128: the 32x32x16-MFMA dQ kernel (round 3)
     const size_t dyn_dq32 = 4 * (2 * 64 * 256) + 256;
-    static bool dq32_attr = false;
-    if (D == 128 && !dq32_attr) { hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_bwd_dq32_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn_dq32); dq32_attr = true; }
+    static Tr1PerDevice dq32_lds;
+    if (D == 128 && dq32_lds.first()) hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_bwd_dq32_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn_dq32);
     const bool use_dq32 = D == 128 && p.d_real == 128 && lse2 != nullptr &&
                           (uint64_t)p.n_slots * (uint64_t)(p.k_ld > p.v_ld ? p.k_ld : p.v_ld) * 2ull < 0xffffffffull;      // 32-bit DMA byte offsets
     if (use_dq32) hipLaunchKernelGGL(attn_bwd_dq32_kernel, dim3((unsigned)((nR + 255) / 256), p.n_kv), dim3(512), dyn_dq32, s, p, lse2);
@@ -1552,20 +1550,16 @@ static int launch_bwd(const AttnParams& p, hipStream_t s, float* ws, int64_t ws_
     // head dim 128 beyond the 32-bit DMA offsets of the 32x32x16 kernel: the LDS-DMA staged 16x16x32 form, 8 waves x 16 keys
     constexpr int DMA_NB = 4;
     const size_t dyn_dma = DMA_NB * (2 * 64 * 256 + 64 * 5 * 4) + (2 * DKDV_MAXT + 2) * 4;
-    static bool dma_attr = false;
-    if (D == 128 && !dma_attr) {
+    static Tr1PerDevice dma_lds;
+    if (D == 128 && dma_lds.first())
         hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_bwd_dkdv_dma_kernel<8, 1, DMA_NB>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn_dma);
-        dma_attr = true;
-    }
     // the 32x32x16-MFMA role-split kernel (round 3) for head dim 128
     constexpr int V32_NB = 3;
     const int v32_np = dkdv32_pairs();
     const size_t dyn_v32 = V32_NB * (2 * 64 * 256 + 64 * 5 * 4) + 2 * v32_np * (64 * 32 * 2) + (2 * DKDV32_MAXT + 2) * 4;
-    static bool v32_attr = false;
-    if (D == 128 && !v32_attr) {
+    static Tr1PerDevice v32_lds;
+    if (D == 128 && v32_lds.first())
         hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_bwd_dkdv32_kernel<V32_NB, 6>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        v32_attr = true;
-    }
     const bool use_v32 = D == 128 && p.d_real == 128 && lse2 != nullptr &&
                          (uint64_t)p.T * (uint64_t)(p.q_ld > p.do_ld ? p.q_ld : p.do_ld) * 2ull < 0xffffffffull;      // 32-bit DMA byte offsets
     const bool use_dma = D == 128 && p.d_real == 128 && lse2 != nullptr;
@@ -1647,9 +1641,7 @@ static int attn_bwd_impl(const void* Q, int64_t q_ld, const void* K, int64_t k_l
     const int n_qtiles = (int)((T * p.group + 63) / 64);
     float* lse2 = (float*)delta + T * n_heads;                                   // second half of the delta scratch: log2-scaled LSE
     const unsigned delta_blocks = (unsigned)((T * n_heads + 15) / 16);          // >= 4 * n_qtiles (n_heads >= group)
-    static int fuse_delta = -1;                                                  // TR1_BWD_FUSE_DELTA=0: the separate attn_delta_kernel launch (A/B measurements)
-    if (fuse_delta < 0) { const char* e = getenv("TR1_BWD_FUSE_DELTA"); fuse_delta = e ? atoi(e) : 1; }
-    if (fuse_delta && d_pad == 128 && bwd32_both(p)) {
+    if (d_pad == 128 && bwd32_both(p)) {
         p.O = (bf16_t*)const_cast<void*>(O); p.o_ld = o_ld; p.lse2_out = lse2; p.qmeta_out = (int*)qmeta_ws;      // delta, lse2 and qmeta come out of the dQ kernel's prologue
     } else
     hipLaunchKernelGGL(attn_delta_kernel, dim3(delta_blocks > (unsigned)n_qtiles ? delta_blocks : (unsigned)n_qtiles), dim3(256), 0, s,

@@ -644,8 +644,8 @@ int tr1_launch_attn_dec32(AttnParams& p, dim3 grid, hipStream_t s) {
     const uint64_t kbytes = (uint64_t)p.kv_batch_slots * (uint64_t)p.k_ld * 2ull, vbytes = (uint64_t)128 * (uint64_t)p.vt_ld * 2ull;
     if (kbytes >= 0xffffffffull || vbytes >= 0xffffffffull || (uint64_t)p.n_slots * (uint64_t)p.k_ld * 2ull >= 0xffffffffull) return 0;
     const size_t dyn = 4 * (64 * 256 + 128 * 128) + 64 * 256 + 768 + 64;
-    static bool attr = false;
-    if (!attr) { hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_dec32_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn); attr = true; }
+    static Tr1PerDevice lds;
+    if (lds.first()) hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_dec32_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn);
     hipLaunchKernelGGL(attn_dec32_kernel, grid, dim3(512), dyn, s, p);
     return 1;
 }
@@ -676,11 +676,10 @@ static int attn_fwd_rows_impl(const void* Q, int64_t q_ld, const void* K, int64_
         blocks = (unsigned)p.xcd_pad;
     }
     const size_t dyn = 4 * (2 * 64 * 256) + 128 + FWD_PROBE_LDS;
-    static bool attr = false;
-    if (!attr) {
+    static Tr1PerDevice lds;
+    if (lds.first()) {
         hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_fwd32_kernel<8>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn);
         hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_fwd32_kernel<6>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn);
-        attr = true;
     }
     // head dim 128, all 128 features live, long key ranges: the 64-rows-per-wave kernel (attn_fwd64.hip, bit-identical results).  Its software pipeline pays one
     // extra body per block for fill / drain, so it wins from ~30 key tiles per block on (tools/sweep_fwd64.py, profiles/r06_sweep_fwd64.txt: -8 % at 3 072 prompt

@@ -83,9 +83,7 @@ static int decode_step_impl(int w8, const void* layer_ptrs, const int64_t* dims,
     const bool down_fixup = !(qm & QM_DOWN) && R >= 16 && inter >= 8192;
     const bool down_fixup8 = w8 == 2 && (qm & QM_DOWN) && R <= 16 && inter >= 8192 && inter % 512 == 0 && hid % 64 == 0;      // fp8 MFMA: LDS-streamed split-K form
     // round 6 (2B shapes): down projection with its whole weight slice in flight (csrc/oproj.hip long-K form) on the fragment-major SwiGLU output of the gate/up launch
-    static int down_frag_on = -1;
-    if (down_frag_on < 0) { const char* e = getenv("TR1_DOWN_FRAG"); down_frag_on = e ? atoi(e) : 1; }
-    const bool down_frag = down_frag_on && !(qm & (QM_DOWN | QM_GU)) && R <= 16 && inter > 3584 && tr1_gemm_oproj_frag_ok(R, hid, inter) &&
+    const bool down_frag = !(qm & (QM_DOWN | QM_GU)) && R <= 16 && inter > 3584 && tr1_gemm_oproj_frag_ok(R, hid, inter) &&
                            tr1_norm_gemm_glu_frag_ok(R, inter, hid);
     TR1_CHECK_ARG(c.ok, "decode_step: workspace too small (tr1_decode_step_workspace_bytes)");
     const void* const* lp = (const void* const*)layer_ptrs;

@@ -341,96 +341,9 @@ TR1_DEV void store_acc256_lds(const f32x4_t (&acc)[RT][4], char* __restrict__ wa
 
 TR1_DEV float epi_silu(float x) { return x / (1.f + __expf(-x)); }
 
-template <bool IS_B, int ROWS>
-TR1_DEV void stage_tile2(const bf16_t* __restrict__ g, int64_t ld, int64_t row0, int64_t rows_valid, int64_t k0, char* lds_tile,
-                         int wave, int lane) {
-    constexpr int NINST = ROWS / 8;                    // instructions of 8 rows (1 KiB) each
-    constexpr int PER_WAVE = (NINST + 7) / 8;
-#pragma unroll
-    for (int i = 0; i < PER_WAVE; ++i) {
-        const int inst = wave * PER_WAVE + i;
-        if (inst < NINST) {                            // wave-uniform
-            const int row = inst * 8 + (lane >> 3);
-            const int phys = lane & 7;
-            const int logical = phys ^ (IS_B ? keyB(row) : keyA(row));
-            int64_t grow = row0 + row;
-            if (grow >= rows_valid) grow = rows_valid - 1;
-            const bf16_t* src = g + grow * ld + k0 + logical * 8;
-            __builtin_amdgcn_global_load_lds((gptr_t)src, (lptr_t)(lds_tile + inst * 1024), 16, 0, 0);
-        }
-    }
-}
-
-template <bool OUT_F32, bool ACCUM, int RT>
-__global__ __launch_bounds__(512) void gemm_nt256_kernel(const bf16_t* __restrict__ A, const bf16_t* __restrict__ B, void* __restrict__ Cv,
-                                                         const bf16_t* __restrict__ bias, const bf16_t* __restrict__ residual,
-                                                         int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldb, int64_t ldc,
-                                                         int64_t ldr, int tiles_m, int tiles_n) {
-    constexpr int BMX = RT * 32;                       // 2 waves along M
-    constexpr int A_BYTES = BMX * BK * 2, BUF_BYTES = A_BYTES + TILE2_BYTES;
-    extern __shared__ __attribute__((aligned(16))) char smem2[];  // [buf][A | B]
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int wm = wave >> 2, wn = wave & 3;
-    const int nwg = tiles_m * tiles_n;
-    int wgid;
-    {
-        const int b = blockIdx.x, xcd = b & 7, q = nwg >> 3, r = nwg & 7;
-        wgid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (b >> 3);
-    }
-    const int GROUP_M = 4;
-    const int group = wgid / (GROUP_M * tiles_n);
-    const int first_m = group * GROUP_M;
-    const int gsz = min(tiles_m - first_m, GROUP_M);
-    const int in_group = wgid - group * GROUP_M * tiles_n;
-    const int tm = first_m + in_group % gsz;
-    const int tn = in_group / gsz;
-    const int64_t m0 = (int64_t)tm * BMX, n0 = (int64_t)tn * BN2;
-
-    f32x4_t acc[RT][4];
-#pragma unroll
-    for (int i = 0; i < RT; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) acc[i][j] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
-
-    const int nk = (int)(K / BK);
-    stage_tile2<false, BMX>(A, lda, m0, M, 0, smem2, wave, lane);
-    stage_tile2<true, BN2>(B, ldb, n0, N, 0, smem2 + A_BYTES, wave, lane);
-    const int u = lane & 15, g = lane >> 4;
-    for (int kt = 0; kt < nk; ++kt) {
-        __syncthreads();
-        char* curA = smem2 + (kt & 1) * BUF_BYTES;
-        char* curB = curA + A_BYTES;
-        if (kt + 1 < nk) {
-            char* nxtA = smem2 + ((kt + 1) & 1) * BUF_BYTES;
-            stage_tile2<false, BMX>(A, lda, m0, M, (int64_t)(kt + 1) * BK, nxtA, wave, lane);
-            stage_tile2<true, BN2>(B, ldb, n0, N, (int64_t)(kt + 1) * BK, nxtA + A_BYTES, wave, lane);
-        }
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks) {
-            bf16x8_t xa[RT], wb[4];
-            const int chunk = ks * 4 + g;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const int row = wn * 64 + (u >> 2) * 16 + j * 4 + (u & 3);
-                wb[j] = *reinterpret_cast<const bf16x8_t*>(curB + row * 128 + ((chunk ^ keyB(row)) << 4));
-            }
-#pragma unroll
-            for (int i = 0; i < RT; ++i) {
-                const int row = wm * (RT * 16) + i * 16 + u;
-                xa[i] = *reinterpret_cast<const bf16x8_t*>(curA + row * 128 + ((chunk ^ keyA(row)) << 4));
-            }
-#pragma unroll
-            for (int i = 0; i < RT; ++i)
-#pragma unroll
-                for (int j = 0; j < 4; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wb[j], xa[i], acc[i][j], 0, 0, 0);
-        }
-    }
-    store_acc256<OUT_F32, ACCUM, RT>(acc, Cv, bias, residual, M, N, ldc, ldr, m0 + wm * (RT * 16), n0 + wn * 64, u, g);
-}
-
 // ------------------------------------------------------------------------------------------------------------------
-// Phased ("ping-pong") form of the 8-wave kernel.  Same block tile, LDS image, swizzle, fragment mapping and epilogue as
-// gemm_nt256_kernel, but the K loop is cut into 4 phases per 64-wide K-tile and the two wave groups (wm = 0 / 1: the two waves
+// Phased ("ping-pong") form of the 8-wave kernel (the 256-column tiles described above).  The K loop is cut into 4 phases per 64-wide
+// K-tile and the two wave groups (wm = 0 / 1: the two waves
 // that share a SIMD) run one barrier apart, so while one wave of a SIMD issues its MFMAs the other one reads its next fragments
 // from LDS and issues the HBM->LDS DMA for the tiles ahead - the matrix pipe never waits for LDS.
 //   phase q of tile t:  [ds_read the A fragments of M-quarter q (phase 0: also all B fragments);  issue this phase's DMA rounds;
@@ -1612,10 +1525,6 @@ __global__ __launch_bounds__(512) void norm_glu_lds_kernel(const bf16_t* __restr
 #undef GLU_NEXT_PAIR
 }
 
-// TR1_NG32_CFG: A/B hook for the 17..32-row rmsnorm + projection kernels (plain and fused-QKV take the SAME form so they stay bit-identical).
-// Default 1 = 8 waves x UNROLL 2 (fused QKV at 32 rows: 19.7 -> 18.4 us; 144 blocks for 256 CUs, so the extra waves are what adds loads in flight)
-static int ng32_cfg() { static int c = -1; if (c < 0) { c = 1; } return c; }
-
 // 1 when tr1_norm_gemm_skinny(..., glu = 2) can write the SwiGLU output fragment-major (the LDS-streamed <= 16-row form; N % 32: whole 32-column fragments)
 extern "C" int tr1_norm_gemm_glu_frag_ok(int64_t M, int64_t N, int64_t K) {
     const int64_t nst = K / 512;
@@ -1635,47 +1544,37 @@ extern "C" int tr1_norm_gemm_skinny(const void* x, const void* lnw, const void* 
                        dim3(WV * 64), 0, s, (const bf16_t*)x, (const bf16_t*)lnw, (const bf16_t*)W, (bf16_t*)out, (const bf16_t*)bias, \
                        (int)M, N, K, ldx, ldw, ldc, eps, N)
     // gate/up + SwiGLU at <= 16 rows: UNROLL 2 keeps the kernel at 128 VGPRs = 4 blocks per CU (1024 slots for 1184 blocks); measured 59.2 vs 60.9 us
-    static int glu_lds = -1;                         // TR1_GLU_LDS=0 selects the register-fragment form (A/B measurements)
-    if (glu_lds < 0) { glu_lds = 1; }
     const int64_t nst = K / 512;                     // 64-wide stages per wave (8 waves split K)
-    static int head_lds = -1;                        // TR1_HEAD_LDS=0: the lm_head stays on the register-fragment kernel (A/B measurements)
-    if (head_lds < 0) { head_lds = 1; }
-    if (!glu && M > 16 && M <= 32 && head_lds && glu_lds && N >= 65536 && N % 32 == 0 && K % 512 == 0 && (nst == 7 || nst == 4 || nst == 3)) {
+    if (!glu && M > 16 && M <= 32 && N >= 65536 && N % 32 == 0 && K % 512 == 0 && (nst == 7 || nst == 4 || nst == 3)) {
         // 17 .. 32 rows (config 4): two row groups per wave against the same LDS stage, single reduction buffer
         constexpr int RING = 3;
         const size_t dyn = 8 * RING * 4096 + (1 * 8 * 2 * 2 * 16 * 17 + 8 * 2 * 16) * sizeof(float) + 8192;
-        static int n_cu_h2 = 0;
-        if (!n_cu_h2) {
-            hipDeviceProp_t prop; int dev = 0;
-            hipGetDevice(&dev); hipGetDeviceProperties(&prop, dev);
-            n_cu_h2 = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
+        static Tr1PerDevice lds;
+        if (lds.first()) {
 #define HL2_ATTR(NSTV) hipFuncSetAttribute(reinterpret_cast<const void*>(&norm_glu_lds_kernel<NSTV, RING, 1, 2, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn)
             HL2_ATTR(7); HL2_ATTR(4); HL2_ATTR(3);
 #undef HL2_ATTR
         }
-        const int64_t NPh = N / 32;
-        const unsigned gridh = (unsigned)(NPh < n_cu_h2 ? NPh : n_cu_h2);
+        const int64_t NPh = N / 32, n_cu = tr1_cu_count();
+        const unsigned gridh = (unsigned)(NPh < n_cu ? NPh : n_cu);
 #define HL2_LAUNCH(NSTV) hipLaunchKernelGGL((norm_glu_lds_kernel<NSTV, RING, 1, 2, 2>), dim3(gridh), dim3(512), dyn, s, (const bf16_t*)x, (const bf16_t*)lnw, (const bf16_t*)W, \
                                             (bf16_t*)out, (int)M, N, K, ldx, ldw, ldc, eps, N / 2, (const bf16_t*)bias, QkvEpi{})
         if (nst == 7) HL2_LAUNCH(7); else if (nst == 4) HL2_LAUNCH(4); else HL2_LAUNCH(3);
 #undef HL2_LAUNCH
         TR1_LAUNCH_CHECK();
     }
-    if (!glu && M <= 16 && head_lds && glu_lds && N >= 65536 && N % 32 == 0 && K % 512 == 0 && (nst == 7 || nst == 4 || nst == 3)) {
+    if (!glu && M <= 16 && N >= 65536 && N % 32 == 0 && K % 512 == 0 && (nst == 7 || nst == 4 || nst == 3)) {
         // wide plain projection (the lm_head) through the LDS stream: 256 persistent blocks x 8 waves, column pairs (n, n + N/2)
         constexpr int RING = 3;
         const size_t dyn = 8 * RING * 4096 + (2 * 8 * 2 * 16 * 17 + 8 * 16) * sizeof(float) + 8192 + 16384;
-        static int n_cu_h = 0;
-        if (!n_cu_h) {
-            hipDeviceProp_t prop; int dev = 0;
-            hipGetDevice(&dev); hipGetDeviceProperties(&prop, dev);
-            n_cu_h = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
+        static Tr1PerDevice lds;
+        if (lds.first()) {
 #define HL_ATTR(NSTV) hipFuncSetAttribute(reinterpret_cast<const void*>(&norm_glu_lds_kernel<NSTV, RING, 2, 1, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn)
             HL_ATTR(7); HL_ATTR(4); HL_ATTR(3);
 #undef HL_ATTR
         }
-        const int64_t NPh = N / 32;
-        const unsigned gridh = (unsigned)(NPh < n_cu_h ? NPh : n_cu_h);
+        const int64_t NPh = N / 32, n_cu = tr1_cu_count();
+        const unsigned gridh = (unsigned)(NPh < n_cu ? NPh : n_cu);
 #define HL_LAUNCH(NSTV) hipLaunchKernelGGL((norm_glu_lds_kernel<NSTV, RING, 2, 1, 2>), dim3(gridh), dim3(512), dyn, s, (const bf16_t*)x, (const bf16_t*)lnw, (const bf16_t*)W, \
                                            (bf16_t*)out, (int)M, N, K, ldx, ldw, ldc, eps, N / 2, (const bf16_t*)bias, QkvEpi{})
         if (nst == 7) HL_LAUNCH(7); else if (nst == 4) HL_LAUNCH(4); else HL_LAUNCH(3);
@@ -1683,25 +1582,22 @@ extern "C" int tr1_norm_gemm_skinny(const void* x, const void* lnw, const void* 
         TR1_LAUNCH_CHECK();
     }
     TR1_CHECK_ARG(glu != 2 || tr1_norm_gemm_glu_frag_ok(M, N, K), "norm_gemm_skinny: glu = 2 (fragment-major SwiGLU output) needs M <= 16 and the LDS-streamed form (tr1_norm_gemm_glu_frag_ok)");
-    if (glu && M <= 32 && glu_lds && K % 512 == 0 && (nst == 7 || nst == 4 || nst == 3) && N % 16 == 0) {   // hidden 3584 / 2048 / 1536
+    if (glu && M <= 32 && K % 512 == 0 && (nst == 7 || nst == 4 || nst == 3) && N % 16 == 0) {   // hidden 3584 / 2048 / 1536
         // <= 16 rows: ring of 3 + double reduction buffer (a ring of 4 with a single buffer and a second barrier per pair measured the same).
         // 17..32 rows (config 4 decodes 2 x 16 rollouts): two row groups per wave against the SAME LDS stage, ring of 3, single reduction
         // buffer (132 KB of LDS): 77.4 -> 52.8 us at 32 x 18944 x 3584 (5.1 TB/s of weights) over the register-fragment form.
         constexpr int RING = 3;
         const size_t dyn1 = 8 * RING * 4096 + (2 * 8 * 2 * 16 * 17 + 8 * 16) * sizeof(float) + 8192 + 16384;      // + the waves' norm-weight KiB + one x stage each
         const size_t dyn2 = 8 * RING * 4096 + (1 * 8 * 2 * 2 * 16 * 17 + 8 * 2 * 16) * sizeof(float) + 8192;
-        static int n_cu = 0;
-        if (!n_cu) {
-            hipDeviceProp_t prop; int dev = 0;
-            hipGetDevice(&dev); hipGetDeviceProperties(&prop, dev);
-            n_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
+        static Tr1PerDevice lds;
+        if (lds.first()) {
 #define GLU_ATTR(NSTV)                                                                                                                          \
     hipFuncSetAttribute(reinterpret_cast<const void*>(&norm_glu_lds_kernel<NSTV, RING, 2, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn1); \
     hipFuncSetAttribute(reinterpret_cast<const void*>(&norm_glu_lds_kernel<NSTV, RING, 1, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn2)
             GLU_ATTR(7); GLU_ATTR(4); GLU_ATTR(3);
 #undef GLU_ATTR
         }
-        const int64_t NP = N / 16;
+        const int64_t NP = N / 16, n_cu = tr1_cu_count();
         const unsigned grid = (unsigned)(NP < n_cu ? NP : n_cu);
 #define GLU_LAUNCH(NSTV)                                                                                                                        \
     do {                                                                                                                                        \
@@ -1721,7 +1617,7 @@ extern "C" int tr1_norm_gemm_skinny(const void* x, const void* lnw, const void* 
         if (M <= 16) NG4(2, 1); else NG4(2, 2);
 #undef NG4
     }
-    else     { if (M <= 16) NG(8, 2, 1, false); else if (M <= 32) { const int c = ng32_cfg(); if (c == 1) NG(8, 2, 2, false); else if (c == 2) NG(8, 1, 2, false); else if (c == 3) NG(4, 1, 2, false); else NG(4, 2, 2, false); } else NG(4, 2, 4, false); }   // 8 waves: see tr1_norm_gemm_qkv
+    else     { if (M <= 16) NG(8, 2, 1, false); else if (M <= 32) NG(8, 2, 2, false); else NG(4, 2, 4, false); }   // 8 waves: see tr1_norm_gemm_qkv
 #undef NG
     TR1_LAUNCH_CHECK();
 }
@@ -1738,25 +1634,23 @@ extern "C" int tr1_norm_gemm_qkv(const void* x, const void* lnw, const void* Wqk
     hipStream_t s = (hipStream_t)stream;
     const dim3 grid((unsigned)(heads * (head_dim / 32)));
     // M <= 16: only heads * hd/32 = 144 blocks (7B) for 256 CUs, so 8 waves per block split K and double the loads in flight per CU
-    // (tools/microbench.py fused, TR1_NG_CFG: 15.8 -> 13.5 us)
+    // (tools/microbench.py fused: 15.8 -> 13.5 us); 17 .. 32 rows likewise 8 waves x UNROLL 2, the same form as tr1_norm_gemm_skinny so the two stay
+    // bit-identical (fused QKV at 32 rows: 19.7 -> 18.4 us)
 #define NGQ(WV, UN, MGR)                                                                                                              \
     hipLaunchKernelGGL((norm_gemm_skinny_kernel<WV, UN, MGR, false, 2, true>), grid, dim3(WV * 64), 0, s, (const bf16_t*)x, (const bf16_t*)lnw, \
                        (const bf16_t*)Wqkv, (bf16_t*)nullptr, (const bf16_t*)bias, (int)M, N, K, ldx, ldw, (int64_t)0, eps, (int64_t)0, qe)
-    // TR1_QKV_LDS (default 1): weights by DMA through per-wave LDS rings (norm_glu_lds_kernel, QKV mode; bit-identical).  Before the x slice was staged
-    // by DMA as well the decode step measured 3 547 us with it against 3 472 us for the register-fragment form with x in LDS; with the staged x it is
-    // 3 277 against 3 325 us.  0 selects the register-fragment kernel (x through LDS unless TR1_QKV_XLDS=0).
-    static int qlds = -1;
-    if (qlds < 0) { qlds = 1; }
+    // Weights by DMA through per-wave LDS rings (norm_glu_lds_kernel, QKV mode; bit-identical).  Before the x slice was staged by DMA as well the
+    // decode step measured 3 547 us with it against 3 472 us for the register-fragment form with x in LDS; with the staged x it is 3 277 against
+    // 3 325 us.  Other shapes take the register-fragment kernel (x through LDS where it fits).
     const int64_t nst = K / 512;
-    if (M > 16 && M <= 32 && qlds && K % 512 == 0 && (nst == 7 || nst == 4 || nst == 3)) {      // 17 .. 32 rows (config 4): two row groups per wave, ring of 3
+    if (M > 16 && M <= 32 && K % 512 == 0 && (nst == 7 || nst == 4 || nst == 3)) {      // 17 .. 32 rows (config 4): two row groups per wave, ring of 3
         constexpr int RING2 = 3;
         const size_t dyn = 8 * RING2 * 4096 + (1 * 8 * 2 * 2 * 16 * 17 + 8 * 2 * 16) * sizeof(float) + 8192;
-        static bool attr_q2 = false;
-        if (!attr_q2) {
+        static Tr1PerDevice lds;
+        if (lds.first()) {
 #define QL2_ATTR(NSTV) hipFuncSetAttribute(reinterpret_cast<const void*>(&norm_glu_lds_kernel<NSTV, RING2, 1, 2, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn)
             QL2_ATTR(7); QL2_ATTR(4); QL2_ATTR(3);
 #undef QL2_ATTR
-            attr_q2 = true;
         }
 #define QL2_LAUNCH(NSTV) hipLaunchKernelGGL((norm_glu_lds_kernel<NSTV, RING2, 1, 2, 1>), grid, dim3(512), dyn, s, (const bf16_t*)x, (const bf16_t*)lnw, (const bf16_t*)Wqkv, \
                                             (bf16_t*)nullptr, (int)M, N, K, ldx, ldw, (int64_t)0, eps, (int64_t)(head_dim / 2), (const bf16_t*)bias, qe)
@@ -1764,15 +1658,14 @@ extern "C" int tr1_norm_gemm_qkv(const void* x, const void* lnw, const void* Wqk
 #undef QL2_LAUNCH
         TR1_LAUNCH_CHECK();
     }
-    if (M <= 16 && qlds && K % 512 == 0 && (nst == 7 || nst == 4 || nst == 3)) {
+    if (M <= 16 && K % 512 == 0 && (nst == 7 || nst == 4 || nst == 3)) {
         constexpr int RING = 4;
         const size_t dyn = 8 * RING * 4096 + (1 * 8 * 2 * 16 * 17 + 8 * 16) * sizeof(float) + 8192;      // (ring of 4: the x staging fits without the extra stage area... see XSLOT0)
-        static bool attr_q = false;
-        if (!attr_q) {
+        static Tr1PerDevice lds;
+        if (lds.first()) {
 #define QL_ATTR(NSTV) hipFuncSetAttribute(reinterpret_cast<const void*>(&norm_glu_lds_kernel<NSTV, RING, 1, 1, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn)
             QL_ATTR(7); QL_ATTR(4); QL_ATTR(3);
 #undef QL_ATTR
-            attr_q = true;
         }
 #define QL_LAUNCH(NSTV) hipLaunchKernelGGL((norm_glu_lds_kernel<NSTV, RING, 1, 1, 1>), grid, dim3(512), dyn, s, (const bf16_t*)x, (const bf16_t*)lnw, (const bf16_t*)Wqkv, \
                                            (bf16_t*)nullptr, (int)M, N, K, ldx, ldw, (int64_t)0, eps, (int64_t)(head_dim / 2), (const bf16_t*)bias, qe)
@@ -1780,15 +1673,13 @@ extern "C" int tr1_norm_gemm_qkv(const void* x, const void* lnw, const void* Wqk
 #undef QL_LAUNCH
         TR1_LAUNCH_CHECK();
     }
-    static int xlds = -1;                            // TR1_QKV_XLDS=0: activation rows through the vector-memory path as well (A/B measurements)
-    if (xlds < 0) { xlds = 1; }
-    if (M <= 16 && xlds && K / 64 / 8 >= 2 && K * 32 <= 120 * 1024 && (int64_t)M * ldx * 2 < 0x7fffffffLL) {
-        static bool attr_x = false;
-        if (!attr_x) { hipFuncSetAttribute(reinterpret_cast<const void*>(&norm_gemm_skinny_kernel<8, 2, 1, false, 2, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 120 * 1024); attr_x = true; }
+    if (M <= 16 && K / 64 / 8 >= 2 && K * 32 <= 120 * 1024 && (int64_t)M * ldx * 2 < 0x7fffffffLL) {
+        static Tr1PerDevice lds;
+        if (lds.first()) hipFuncSetAttribute(reinterpret_cast<const void*>(&norm_gemm_skinny_kernel<8, 2, 1, false, 2, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 120 * 1024);
         hipLaunchKernelGGL((norm_gemm_skinny_kernel<8, 2, 1, false, 2, true, true>), grid, dim3(512), (size_t)(K * 32), s, (const bf16_t*)x, (const bf16_t*)lnw,
                            (const bf16_t*)Wqkv, (bf16_t*)nullptr, (const bf16_t*)bias, (int)M, N, K, ldx, ldw, (int64_t)0, eps, (int64_t)0, qe);
     }
-    else if (M <= 16) NGQ(8, 2, 1); else if (M <= 32) { const int c = ng32_cfg(); if (c == 1) NGQ(8, 2, 2); else if (c == 2) NGQ(8, 1, 2); else if (c == 3) NGQ(4, 1, 2); else NGQ(4, 2, 2); } else NGQ(4, 2, 4);
+    else if (M <= 16) NGQ(8, 2, 1); else if (M <= 32) NGQ(8, 2, 2); else NGQ(4, 2, 4);
 #undef NGQ
     TR1_LAUNCH_CHECK();
 }
@@ -1796,8 +1687,6 @@ extern "C" int tr1_norm_gemm_qkv(const void* x, const void* lnw, const void* Wqk
 // Launch of the decode-regime kernel (single pass over K; the split-K + fixup form is launched by tr1_gemm_skinny_fixup).
 static void launch_skinny(const void* A, const void* B, void* C, const void* bias, const void* residual, int64_t M, int64_t N, int64_t K,
                           int64_t lda, int64_t ldb, int64_t ldc, int64_t ldr, int out_f32, int ksplit, hipStream_t s) {
-    static int force_ncol = -1;
-    if (force_ncol < 0) { force_ncol = 0; }
 #define SK(WV, UN, NC, MGR)                                                                                                          \
     hipLaunchKernelGGL((gemm_skinny_kernel<WV, UN, NC, MGR>), dim3((unsigned)((N + 16 * NC - 1) / (16 * NC)), (unsigned)ksplit),    \
                        dim3(WV * 64), 0, s, (const bf16_t*)A, (const bf16_t*)B, out_f32 ? nullptr : (bf16_t*)C,                     \
@@ -1806,18 +1695,16 @@ static void launch_skinny(const void* A, const void* B, void* C, const void* bia
     // choices measured on MI355X with tools/microbench.py skinny (non-temporal loads hurt; 8-way in-block split-K pays for long K)
     // (A/B on MI355X, M = 16: gate_up 37888x3584 67.6 -> 56.8 us with NCOL 2; lm_head 152064x3584 247 -> 188 us with NCOL 4;
     //  the 3584x18944 down projection has too few column groups for NCOL > 1 and wants split-K instead)
-    const int ncol = force_ncol > 0 ? force_ncol : (N >= 100000 ? 4 : (N >= 4096 && ksplit == 1 ? 2 : 1));
+    const int ncol = N >= 100000 ? 4 : (N >= 4096 && ksplit == 1 ? 2 : 1);
     const bool longk = K / ksplit >= 8192;
     if (M <= 16) {
         if (longk) { if (ncol >= 2 && N >= 16384) SK(8, 2, 2, 1); else SK(8, 4, 1, 1); }
         else if (ncol == 4) SK(4, 2, 4, 1);
         else if (ncol == 2) SK(4, 4, 2, 1);
         else {
-            static int xlds = -1;                    // TR1_SKINNY_XLDS=0: activation rows through the vector-memory path (A/B measurements)
-            if (xlds < 0) { xlds = 1; }
-            if (xlds && ksplit == 1 && K / 64 / 4 >= 4 && K * 32 <= 120 * 1024 && (int64_t)M * lda * 2 < 0x7fffffffLL) {
-                static bool attr_x = false;
-                if (!attr_x) { hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_skinny_kernel<4, 4, 1, 1, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 120 * 1024); attr_x = true; }
+            if (ksplit == 1 && K / 64 / 4 >= 4 && K * 32 <= 120 * 1024 && (int64_t)M * lda * 2 < 0x7fffffffLL) {
+                static Tr1PerDevice lds;
+                if (lds.first()) hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_skinny_kernel<4, 4, 1, 1, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 120 * 1024);
                 hipLaunchKernelGGL((gemm_skinny_kernel<4, 4, 1, 1, true>), dim3((unsigned)((N + 15) / 16), 1u), dim3(256), (size_t)(K * 32), s, (const bf16_t*)A,
                                    (const bf16_t*)B, out_f32 ? nullptr : (bf16_t*)C, out_f32 ? (float*)C : nullptr, (const bf16_t*)bias, (const bf16_t*)residual,
                                    (int)M, N, K, lda, ldb, ldc, ldr, (float*)nullptr, (int*)nullptr);
@@ -1851,20 +1738,17 @@ extern "C" int tr1_gemm_nt_bf16(const void* A, const void* B, void* C, const voi
     }
     {   // tile choice: CU-rounds x block area / relative efficiency of the structure (tile-count quantisation).
         // 128x128 runs 2 blocks per CU (512 slots), the phased 8-wave forms 1 block per CU at ~1.25x the MFMA rate per CU.
-        static int force = -1;
-        if (force < 0) { force = 0; }
         auto blocks = [&](int64_t bm, int64_t bn) { return ((M + bm - 1) / bm) * ((N + bn - 1) / bn); };
         auto cost = [&](int64_t bm, int64_t bn, int64_t slots, double eff) {
             const int64_t t = blocks(bm, bn);
             return (double)((t + slots - 1) / slots) * (double)slots * (double)(bm * bn) / eff;
         };
         int rt = 0;
-        if (force == 224) rt = 7; else if (force == 256) rt = 8; else if (force == 288) rt = 9; else if (force == 320) rt = 10; else if (force == 128) rt = 0;
-        else if (M >= 512 && N >= 256) {
+        if (M >= 512 && N >= 256) {
             double best = cost(BM, BN, 512, 0.80);
             // intrinsic efficiency of the phased 8-wave forms relative to 256 x 256 (more A-fragment reuse per B fragment with taller tiles),
             // measured on M = 37888, N = 3584, K = 5120 and 8192^3 after removing tile-count quantisation: 224: 0.94, 288: 1.025, 320: 1.03;
-            // the 128 x 128 form reaches 0.80 of the 256 x 256 rate per CU (tools/microbench.py gemm with TR1_GEMM_TILE forced)
+            // the 128 x 128 form reaches 0.80 of the 256 x 256 rate per CU (tools/microbench.py gemm, tile forced)
             static const double eff[4] = {0.94, 1.0, 1.025, 1.03};
             for (int r = 7; r <= 10; ++r) {
                 const double c = cost(r * 32, BN2, 256, eff[r - 7]);
@@ -1874,26 +1758,20 @@ extern "C" int tr1_gemm_nt_bf16(const void* A, const void* B, void* C, const voi
         if (rt) {
             const int bmx = rt * 32;
             const int64_t t2m = (M + bmx - 1) / bmx, t2n = (N + BN2 - 1) / BN2;
-            static int phased = -1;                    // TR1_GEMM_PHASED=0 selects the single-barrier form (A/B measurements)
-            if (phased < 0) { phased = 1; }
-            const size_t dyn = 2 * ((size_t)bmx * BK * 2 + TILE2_BYTES) + (phased ? 4096 : 0);
-            static bool attr_set = false;
-            if (!attr_set) {
+            const size_t dyn = 2 * ((size_t)bmx * BK * 2 + TILE2_BYTES) + 4096;
+            static Tr1PerDevice lds;
+            if (lds.first()) {
                 const int mx = (int)(2 * (320 * BK * 2 + TILE2_BYTES)) + 4096;
-#define SETA(OF, AC, R) do { hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_nt256_kernel<OF, AC, R>), hipFuncAttributeMaxDynamicSharedMemorySize, mx); \
-                             hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_nt8p_kernel<OF, AC, R>), hipFuncAttributeMaxDynamicSharedMemorySize, mx); } while (0)
+#define SETA(OF, AC, R) hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_nt8p_kernel<OF, AC, R>), hipFuncAttributeMaxDynamicSharedMemorySize, mx)
 #define SETR(R) do { SETA(false, false, R); SETA(true, false, R); SETA(true, true, R); } while (0)
                 SETR(7); SETR(8); SETR(9); SETR(10);
 #undef SETR
 #undef SETA
-                attr_set = true;
             }
             dim3 grid2((unsigned)(t2m * t2n));
 #define LAUNCH2(OF, AC, R)                                                                                                            \
-    do { if (phased) hipLaunchKernelGGL((gemm_nt8p_kernel<OF, AC, R>), grid2, dim3(512), dyn, s, (const bf16_t*)A, (const bf16_t*)B, C, (const bf16_t*)bias, \
-                       (const bf16_t*)residual, M, N, K, lda, ldb, ldc, ldr, (int)t2m, (int)t2n, GemmEpi{});                          \
-    else hipLaunchKernelGGL((gemm_nt256_kernel<OF, AC, R>), grid2, dim3(512), dyn, s, (const bf16_t*)A, (const bf16_t*)B, C, (const bf16_t*)bias, \
-                       (const bf16_t*)residual, M, N, K, lda, ldb, ldc, ldr, (int)t2m, (int)t2n); } while (0)
+    hipLaunchKernelGGL((gemm_nt8p_kernel<OF, AC, R>), grid2, dim3(512), dyn, s, (const bf16_t*)A, (const bf16_t*)B, C, (const bf16_t*)bias, \
+                       (const bf16_t*)residual, M, N, K, lda, ldb, ldc, ldr, (int)t2m, (int)t2n, GemmEpi{})
 #define LAUNCH2R(R) do { if (out_f32) { if (accumulate) LAUNCH2(true, true, R); else LAUNCH2(true, false, R); } else LAUNCH2(false, false, R); } while (0)
             if (rt == 7) LAUNCH2R(7); else if (rt == 9) LAUNCH2R(9); else if (rt == 10) LAUNCH2R(10); else LAUNCH2R(8);
 #undef LAUNCH2R
@@ -1930,14 +1808,13 @@ extern "C" int tr1_gemm_nn_bf16(const void* A, const void* B, void* C, int64_t M
     const int bmx = rt * 32;
     const int64_t t2m = (M + bmx - 1) / bmx, t2n = (N + BN2 - 1) / BN2;
     const size_t dyn = 2 * ((size_t)bmx * BK * 2 + TILE2_BYTES) + 4096;
-    static bool attr_set = false;
-    if (!attr_set) {
+    static Tr1PerDevice lds;
+    if (lds.first()) {
         const int mx = (int)(2 * (320 * BK * 2 + TILE2_BYTES)) + 4096;
         hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_nt8p_kernel<false, false, 7, true>), hipFuncAttributeMaxDynamicSharedMemorySize, mx);
         hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_nt8p_kernel<false, false, 8, true>), hipFuncAttributeMaxDynamicSharedMemorySize, mx);
         hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_nt8p_kernel<false, false, 9, true>), hipFuncAttributeMaxDynamicSharedMemorySize, mx);
         hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_nt8p_kernel<false, false, 10, true>), hipFuncAttributeMaxDynamicSharedMemorySize, mx);
-        attr_set = true;
     }
     dim3 grid2((unsigned)(t2m * t2n));
 #define LAUNCHNN(R) hipLaunchKernelGGL((gemm_nt8p_kernel<false, false, R, true>), grid2, dim3(512), dyn, s, (const bf16_t*)A, (const bf16_t*)B, C, \
@@ -1967,13 +1844,12 @@ extern "C" int tr1_gemm_nn_acc_f32(const void* A, const void* B, void* C, int64_
     const int bmx = rt * 32;
     const int64_t t2m = (M + bmx - 1) / bmx, t2n = (N + BN2 - 1) / BN2;
     const size_t dyn = 2 * ((size_t)bmx * BK * 2 + TILE2_BYTES) + 4096;
-    static bool attr_set = false;
-    if (!attr_set) {
+    static Tr1PerDevice lds;
+    if (lds.first()) {
         const int mx = (int)(2 * (320 * BK * 2 + TILE2_BYTES)) + 4096;
 #define SETN(AC, R) hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_nt8p_kernel<true, AC, R, true>), hipFuncAttributeMaxDynamicSharedMemorySize, mx)
         SETN(false, 7); SETN(false, 8); SETN(false, 9); SETN(false, 10); SETN(true, 7); SETN(true, 8); SETN(true, 9); SETN(true, 10);
 #undef SETN
-        attr_set = true;
     }
     dim3 grid2((unsigned)(t2m * t2n));
 #define LAUNCHNA(AC, R) hipLaunchKernelGGL((gemm_nt8p_kernel<true, AC, R, true>), grid2, dim3(512), dyn, s, (const bf16_t*)A, (const bf16_t*)B, C, \
@@ -2017,15 +1893,14 @@ extern "C" int tr1_wgrad_f32_sumsq(const void* A, const void* B, void* C, int64_
     TR1_CHECK_ARG(blocks * 8 <= partials_capacity, "wgrad_f32_sumsq: partials buffer too small (8 floats per 256-column tile block)");
     const size_t dyn = 2 * ((size_t)bmx * BK * 2 + TILE2_BYTES) + 4096;
     {
-        static bool set_ = false;
-        if (!set_) {
+        static Tr1PerDevice lds;
+        if (lds.first()) {
             const int mx = (int)(2 * (320 * BK * 2 + TILE2_BYTES)) + 4096;
 #define SETW(AC, R, KM) hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_nt8p_kernel<true, AC, R, KM>), hipFuncAttributeMaxDynamicSharedMemorySize, mx)
 #define SETWR(R) do { SETW(false, R, false); SETW(true, R, false); SETW(false, R, true); SETW(true, R, true); } while (0)
             SETWR(7); SETWR(8); SETWR(9); SETWR(10);
 #undef SETWR
 #undef SETW
-            set_ = true;
         }
     }
     TR1_CHECK_ARG(!wire_bf16 || ld_wire % 4 == 0, "wgrad_f32_sumsq: ld_wire % 4 required");
@@ -2057,12 +1932,12 @@ static int epi_pick_rt(int64_t M, int64_t Ntiles) {
          else if (RTV == 10) { hipLaunchKernelGGL((gemm_nt8p_kernel<KERN_ARGS(10)>), __VA_ARGS__); }                                      \
          else { hipLaunchKernelGGL((gemm_nt8p_kernel<KERN_ARGS(8)>), __VA_ARGS__); } } while (0)
 #define EPI_SETATTR(KERN_ARGS)                                                                                                             \
-    do { static bool set_ = false; if (!set_) { const int mx = (int)(2 * (320 * BK * 2 + TILE2_BYTES)) + 4096;                             \
+    do { static Tr1PerDevice lds_; if (lds_.first()) { const int mx = (int)(2 * (320 * BK * 2 + TILE2_BYTES)) + 4096;                     \
         hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_nt8p_kernel<KERN_ARGS(7)>), hipFuncAttributeMaxDynamicSharedMemorySize, mx);  \
         hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_nt8p_kernel<KERN_ARGS(8)>), hipFuncAttributeMaxDynamicSharedMemorySize, mx);  \
         hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_nt8p_kernel<KERN_ARGS(9)>), hipFuncAttributeMaxDynamicSharedMemorySize, mx);  \
         hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_nt8p_kernel<KERN_ARGS(10)>), hipFuncAttributeMaxDynamicSharedMemorySize, mx); \
-        set_ = true; } } while (0)
+        } } while (0)
 
 // a[M, I] = silu(x Wg^T) * (x Wu^T) with Wgu = [2I, K] (gate rows, then up rows); gu_out (optional) receives the projection itself [M, 2I] for the backward.
 // Bit-identical to tr1_gemm_nt_bf16 + tr1_swiglu_fwd.
@@ -2305,13 +2180,12 @@ extern "C" int tr1_lmhead_lse_fwd(const void* hn, const void* W, const void* tar
     const int bmx = rt * 32;
     const int64_t t2m = (M + bmx - 1) / bmx, t2n = (N + BN2 - 1) / BN2;
     const size_t dyn = 2 * ((size_t)bmx * BK * 2 + TILE2_BYTES) + 4096;
-    static bool attr_set = false;
-    if (!attr_set) {
+    static Tr1PerDevice lds;
+    if (lds.first()) {
         const int mx = (int)(2 * (320 * BK * 2 + TILE2_BYTES)) + 4096;
 #define SETL(R) hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_nt8p_kernel<false, false, R, false, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, mx)
         SETL(7); SETL(8); SETL(9); SETL(10);
 #undef SETL
-        attr_set = true;
     }
     dim3 grid2((unsigned)(t2m * t2n));
 #define LAUNCHL(R) hipLaunchKernelGGL((gemm_nt8p_kernel<false, false, R, false, 1>), grid2, dim3(512), dyn, s, (const bf16_t*)hn, (const bf16_t*)W, part_ws, \
@@ -2480,22 +2354,18 @@ static int skinny_fix_cfg(int64_t M, int64_t N, int64_t K, int* ncol, int* mg) {
     *ncol = (K >= 8192 && *mg <= 2) ? 4 : 2;
     int ks = K >= 2048 ? 4 : 1;
     // Few column groups (a narrow output over a long K - the Qwen2-VL-2B down projection: 1536 / 64 = 24 groups x 4 slabs = 96 blocks on 256 CUs, 2.1 TB/s): as
-    // many K slabs (<= 16, whole 64-k stages each) as still give at most one block per CU - 24 x 10 = 240 blocks there.  TR1_DOWN_KS=4 keeps the four slabs.
-    static int ks_max = -1;
-    if (ks_max < 0) { ks_max = 16; }
+    // many K slabs (<= 16, whole 64-k stages each) as still give at most one block per CU - 24 x 10 = 240 blocks there.
     const int64_t groups = (N + 16 * *ncol - 1) / (16 * *ncol);
     if (ks == 4 && *mg == 1 && groups * 4 < 192)
-        for (int cand = 5; cand <= ks_max && cand <= 16; ++cand)
+        for (int cand = 5; cand <= 16; ++cand)
             if (K % ((int64_t)cand * 64) == 0 && groups * cand <= 256) ks = cand;
     return ks;
 }
 
 // 56-column blocks for the LDS-streamed <= 16-row form when that is what fills the chip: N % 56 == 0 and N/56 x ks <= 256 < more blocks than N/64 x ks
-// (7B down projection: 64 x 4 = 256 blocks instead of 56 x 4 = 224).  TR1_DOWN_COLS=64 keeps the 64-column blocks (A/B measurements).
+// (7B down projection: 64 x 4 = 256 blocks instead of 56 x 4 = 224).
 static bool skinny_fix_cols56(int64_t N, int ks, int ncol, int mg) {
-    static int cols = -1;
-    if (cols < 0) { cols = 56; }
-    return cols == 56 && mg <= 2 && ncol == 4 && ks > 1 && N % 56 == 0 && (N / 56) * ks <= 256 && (N / 56) > (N + 63) / 64;
+    return mg <= 2 && ncol == 4 && ks > 1 && N % 56 == 0 && (N / 56) * ks <= 256 && (N / 56) > (N + 63) / 64;
 }
 
 extern "C" int64_t tr1_gemm_skinny_fixup_workspace_floats(int64_t M, int64_t N, int64_t K) {
@@ -2515,9 +2385,7 @@ extern "C" int tr1_gemm_skinny_fixup(const void* A, const void* B, void* C, cons
     TR1_CHECK_ARG(N % 8 == 0 && lda % 8 == 0 && ldb % 8 == 0 && ldc % 8 == 0 && (!residual || ldr % 8 == 0), "gemm_skinny_fixup: N%8, ld%8 required");
     int ncol, mg;
     const int ks = skinny_fix_cfg(M, N, K, &ncol, &mg);
-    static int down_lds = -1;                        // TR1_DOWN_LDS=0 selects the register-fragment form (A/B measurements); 6 / 7 = waves per block
-    if (down_lds < 0) { down_lds = 7; }
-    const bool c56 = down_lds && (K / ks) % 64 == 0 && skinny_fix_cols56(N, ks, ncol, mg);
+    const bool c56 = (K / ks) % 64 == 0 && skinny_fix_cols56(N, ks, ncol, mg);
     const int64_t groups = c56 ? N / 56 : (N + 16 * ncol - 1) / (16 * ncol);
     TR1_CHECK_ARG(ws_f32 && ws_floats >= ks * groups * ncol * mg * 256 + groups, "gemm_skinny_fixup: workspace too small");
     float* tiles = (float*)ws_f32;
@@ -2528,38 +2396,30 @@ extern "C" int tr1_gemm_skinny_fixup(const void* A, const void* B, void* C, cons
                        (const bf16_t*)A, (const bf16_t*)B, (bf16_t*)C, (float*)nullptr, (const bf16_t*)bias, (const bf16_t*)residual, \
                        (int)M, N, K, lda, ldb, ldc, ldr, tiles, ks > 1 ? cnt : (int*)nullptr)
     if (c56 && mg == 2) {       // round 5, 17 .. 32 rows: 56-column blocks as well (256 blocks), whose 11 KiB stages leave room for a seventh wave
-        static bool attr562 = false;
+        static Tr1PerDevice lds;
         constexpr int DYN = 7 * 2 * (7 * 1024 + 2 * 2048) + 16;
-        if (!attr562) { hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_skinny_lds_fix_kernel<7, 2, 7>), hipFuncAttributeMaxDynamicSharedMemorySize, DYN); attr562 = true; }
+        if (lds.first()) hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_skinny_lds_fix_kernel<7, 2, 7>), hipFuncAttributeMaxDynamicSharedMemorySize, DYN);
         hipLaunchKernelGGL((gemm_skinny_lds_fix_kernel<7, 2, 7>), dim3((unsigned)groups, (unsigned)ks), dim3(448), DYN, s, (const bf16_t*)A, (const bf16_t*)B,
                            (bf16_t*)C, (const bf16_t*)bias, (const bf16_t*)residual, (int)M, N, K, lda, ldb, ldc, ldr, tiles, cnt);
     }
-    else if (mg == 2 && ncol == 4 && ks > 1 && down_lds && (K / ks) % 64 == 0 && N % 64 == 0) {       // 17 .. 32 rows: 12 KiB stages, 6 waves
-        static bool attr2 = false;
-        if (!attr2) { hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_skinny_lds_fix_kernel<6, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, 6 * 2 * 12288 + 16); attr2 = true; }
+    else if (mg == 2 && ncol == 4 && ks > 1 && (K / ks) % 64 == 0 && N % 64 == 0) {       // 17 .. 32 rows: 12 KiB stages, 6 waves
+        static Tr1PerDevice lds;
+        if (lds.first()) hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_skinny_lds_fix_kernel<6, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, 6 * 2 * 12288 + 16);
         hipLaunchKernelGGL((gemm_skinny_lds_fix_kernel<6, 2>), dim3((unsigned)groups, (unsigned)ks), dim3(384), 6 * 2 * 12288 + 16, s, (const bf16_t*)A, (const bf16_t*)B,
                            (bf16_t*)C, (const bf16_t*)bias, (const bf16_t*)residual, (int)M, N, K, lda, ldb, ldc, ldr, tiles, cnt);
     }
     else if (c56) {
-        static bool attr56 = false;
+        static Tr1PerDevice lds;
         constexpr int DYN = 7 * 2 * (7 * 1024 + 2048) + 16;
-        if (!attr56) { hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_skinny_lds_fix_kernel<7, 1, 7>), hipFuncAttributeMaxDynamicSharedMemorySize, DYN); attr56 = true; }
+        if (lds.first()) hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_skinny_lds_fix_kernel<7, 1, 7>), hipFuncAttributeMaxDynamicSharedMemorySize, DYN);
         hipLaunchKernelGGL((gemm_skinny_lds_fix_kernel<7, 1, 7>), dim3((unsigned)groups, (unsigned)ks), dim3(448), DYN, s, (const bf16_t*)A, (const bf16_t*)B,
                            (bf16_t*)C, (const bf16_t*)bias, (const bf16_t*)residual, (int)M, N, K, lda, ldb, ldc, ldr, tiles, cnt);
     }
-    else if (mg == 1 && ncol == 4 && ks > 1 && down_lds && (K / ks) % 64 == 0 && N % 64 == 0) {
-        static bool attr_set = false;
-        if (!attr_set) {
-            hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_skinny_lds_fix_kernel<6>), hipFuncAttributeMaxDynamicSharedMemorySize, 6 * 2 * 10240 + 16);
-            hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_skinny_lds_fix_kernel<7>), hipFuncAttributeMaxDynamicSharedMemorySize, 7 * 2 * 10240 + 16);
-            attr_set = true;
-        }
-        if (down_lds == 6)
-            hipLaunchKernelGGL((gemm_skinny_lds_fix_kernel<6>), dim3((unsigned)groups, (unsigned)ks), dim3(384), 6 * 2 * 10240 + 16, s, (const bf16_t*)A, (const bf16_t*)B,
-                               (bf16_t*)C, (const bf16_t*)bias, (const bf16_t*)residual, (int)M, N, K, lda, ldb, ldc, ldr, tiles, cnt);
-        else
-            hipLaunchKernelGGL((gemm_skinny_lds_fix_kernel<7>), dim3((unsigned)groups, (unsigned)ks), dim3(448), 7 * 2 * 10240 + 16, s, (const bf16_t*)A, (const bf16_t*)B,
-                               (bf16_t*)C, (const bf16_t*)bias, (const bf16_t*)residual, (int)M, N, K, lda, ldb, ldc, ldr, tiles, cnt);
+    else if (mg == 1 && ncol == 4 && ks > 1 && (K / ks) % 64 == 0 && N % 64 == 0) {       // <= 16 rows: 10 KiB stages, 7 waves
+        static Tr1PerDevice lds;
+        if (lds.first()) hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_skinny_lds_fix_kernel<7>), hipFuncAttributeMaxDynamicSharedMemorySize, 7 * 2 * 10240 + 16);
+        hipLaunchKernelGGL((gemm_skinny_lds_fix_kernel<7>), dim3((unsigned)groups, (unsigned)ks), dim3(448), 7 * 2 * 10240 + 16, s, (const bf16_t*)A, (const bf16_t*)B,
+                           (bf16_t*)C, (const bf16_t*)bias, (const bf16_t*)residual, (int)M, N, K, lda, ldb, ldc, ldr, tiles, cnt);
     }
     else if (mg == 1) { if (ncol == 4) SKF(4, 2, 4, 1); else SKF(4, 4, 2, 1); }
     else if (mg == 2) { if (ncol == 4) SKF(4, 2, 4, 2); else SKF(4, 2, 2, 2); }

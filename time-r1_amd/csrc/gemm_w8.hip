@@ -787,27 +787,6 @@ extern "C" int tr1_gemm_skinny_w8(const void* x, const void* lnw, const void* W_
                        (bf16_t*)out, (const bf16_t*)bias, (const bf16_t*)residual, (int)M, N, K, ldx, ldw, ldc, ldr, eps, N)
 #define W8_MG(WV, UN, NC, NRM, GL)                                                         \
     do { if (mg == 1) W8(WV, UN, NC, 1, NRM, GL); else if (mg == 2) W8(WV, UN, NC, 2, NRM, GL); else W8(WV, 1, NC, 4, NRM, GL); } while (0)
-    {   // tuning hook for tools/microbench.py w8: TR1_W8_CFG=<waves><unroll><ncol> (M <= 16 only)
-        static int cfg = -1;
-        if (cfg < 0) { cfg = 0; }
-        if (cfg && !glu && M <= 16) {
-            const bool nrm = lnw != nullptr;
-#define W8C(WV, UN, NC) do { if (nrm) W8(WV, UN, NC, 1, true, false); else W8(WV, UN, NC, 1, false, false); TR1_LAUNCH_CHECK(); } while (0)
-            switch (cfg) {
-                case 442: W8C(4, 4, 2);
-                case 424: W8C(4, 2, 4);
-                case 444: W8C(4, 4, 4);
-                case 822: W8C(8, 2, 2);
-                case 824: W8C(8, 2, 4);
-                case 814: W8C(8, 1, 4);
-                case 842: W8C(8, 4, 2);
-                case 441: W8C(4, 4, 1);
-                case 841: W8C(8, 4, 1);
-                default: break;
-            }
-#undef W8C
-        }
-    }
     // column groups per block: the activations are re-read from L2 by every block, and with fp8 weights they are as many bytes as a
     // 2-group weight slab - 4 groups halve that traffic (measured, M = 16: lm_head 168 -> 140 us)
     if (glu) { if (mg == 1) W8(4, 2, 4, 1, true, true); else if (mg == 2) W8(4, 2, 4, 2, true, true); else W8(4, 1, 2, 4, true, true); }
@@ -836,47 +815,19 @@ extern "C" int tr1_gemm_skinny_w8a8(const void* x, const void* lnw, const void* 
                        (bf16_t*)out, (const bf16_t*)bias, (const bf16_t*)residual, (int)M, N, K, ldx, ldw, ldc, ldr, eps, N)
 #define W8_MG(WV, UN, NC, NRM, GL)                                                         \
     do { if (mg == 1) W8(WV, UN, NC, 1, NRM, GL); else if (mg == 2) W8(WV, UN, NC, 2, NRM, GL); else W8(WV, 1, NC, 4, NRM, GL); } while (0)
-    {   // tuning hook for tools/microbench.py w8: TR1_W8A8_CFG=<waves><unroll><ncol> (M <= 16 only)
-        static int cfg = -1;
-        if (cfg < 0) { cfg = 0; }
-        if (cfg && !glu && M <= 16) {
-            const bool nrm = lnw != nullptr;
-#define W8C(WV, UN, NC) do { if (nrm) W8(WV, UN, NC, 1, true, false); else W8(WV, UN, NC, 1, false, false); TR1_LAUNCH_CHECK(); } while (0)
-            switch (cfg) {
-                case 442: W8C(4, 4, 2);
-                case 424: W8C(4, 2, 4);
-                case 444: W8C(4, 4, 4);
-                case 822: W8C(8, 2, 2);
-                case 824: W8C(8, 2, 4);
-                case 814: W8C(8, 1, 4);
-                case 842: W8C(8, 4, 2);
-                case 441: W8C(4, 4, 1);
-                case 841: W8C(8, 4, 1);
-                default: break;
-            }
-#undef W8C
-        }
-    }
-    // column groups per block: the activations are re-read from L2 by every block, and with fp8 weights they are as many bytes as a
-    // 2-group weight slab - 4 groups halve that traffic (measured, M = 16: lm_head 168 -> 140 us)
-    {   // gate/up at <= 16 rows, hidden 3584 / 2048 / 1536: the LDS-streamed form (TR1_W8_GLU_LDS=0: register-fragment form, A/B runs)
-        static int glu_lds = -1;
-        if (glu_lds < 0) { glu_lds = 1; }
+    {   // gate/up at <= 16 rows, hidden 3584 / 2048 / 1536: the LDS-streamed form
         const int64_t nw = K / 512;
-        if (glu && M <= 16 && glu_lds && K % 512 == 0 && (nw == 7 || nw == 4 || nw == 3) && N % 16 == 0) {
+        if (glu && M <= 16 && K % 512 == 0 && (nw == 7 || nw == 4 || nw == 3) && N % 16 == 0) {
             constexpr int RING = 3;
-            static int n_cu = 0;
             const size_t dyn = (size_t)nw * RING * 4096 + (2 * nw * 2 * 16 * 17 + nw * 16) * sizeof(float) + (size_t)nw * (4096 + 1024);      // + one x stage and the norm-weight KiB per wave
-            if (!n_cu) {
-                hipDeviceProp_t prop; int dev = 0;
-                hipGetDevice(&dev); hipGetDeviceProperties(&prop, dev);
-                n_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
+            static Tr1PerDevice lds;
+            if (lds.first()) {
                 const int mx = 7 * RING * 4096 + (2 * 7 * 2 * 16 * 17 + 7 * 16) * (int)sizeof(float) + 7 * (4096 + 1024);
                 hipFuncSetAttribute(reinterpret_cast<const void*>(&norm_glu_lds_f8_kernel<7, RING>), hipFuncAttributeMaxDynamicSharedMemorySize, mx);
                 hipFuncSetAttribute(reinterpret_cast<const void*>(&norm_glu_lds_f8_kernel<4, RING>), hipFuncAttributeMaxDynamicSharedMemorySize, mx);
                 hipFuncSetAttribute(reinterpret_cast<const void*>(&norm_glu_lds_f8_kernel<3, RING>), hipFuncAttributeMaxDynamicSharedMemorySize, mx);
             }
-            const int64_t NP = N / 16;
+            const int64_t NP = N / 16, n_cu = tr1_cu_count();
             const unsigned grid = (unsigned)(NP < n_cu ? NP : n_cu);
 #define G8L(NWV) hipLaunchKernelGGL((norm_glu_lds_f8_kernel<NWV, RING>), dim3(grid), dim3(NWV * 64), dyn, s, (const bf16_t*)x, (const bf16_t*)lnw, \
                                     (const unsigned char*)W_fp8, (const float*)wscale, (bf16_t*)out, (int)M, N, K, ldx, ldw, ldc, eps, N)
@@ -885,17 +836,17 @@ extern "C" int tr1_gemm_skinny_w8a8(const void* x, const void* lnw, const void* 
             TR1_LAUNCH_CHECK();
         }
     }
+    // column groups per block: the activations are re-read from L2 by every block, and with fp8 weights they are as many bytes as a
+    // 2-group weight slab - 4 groups halve that traffic (measured, M = 16: lm_head 168 -> 140 us)
     if (glu) { if (mg == 1) W8(4, 2, 4, 1, true, true); else if (mg == 2) W8(4, 2, 4, 2, true, true); else W8(4, 1, 2, 4, true, true); }
     else if (lnw && N >= 100000) { if (mg == 1) W8(4, 2, 4, 1, true, false); else if (mg == 2) W8(4, 2, 4, 2, true, false); else W8(4, 1, 2, 4, true, false); }
     else {
 // x image (32 bytes per k: 16 rows of bf16) + the norm weight, which arrives in whole 1 KiB DMA instructions (the last one may run past K * 2 bytes)
 #define W8X_LDS(K_) ((int64_t)(K_) * 32 + (((int64_t)(K_) * 2 + 1023) / 1024) * 1024)
-        static int xlds = -1;                        // TR1_W8A8_XLDS=0: activation rows / norm weight through the vector-memory path (A/B measurements)
-        if (xlds < 0) { xlds = 1; }
-        const bool x_ok = xlds && mg == 1 && K < 8192 && K % 128 == 0 && W8X_LDS(K) <= 128 * 1024 && (int64_t)M * ldx * 2 < 0x7fffffffLL;
+        const bool x_ok = mg == 1 && K < 8192 && K % 128 == 0 && W8X_LDS(K) <= 128 * 1024 && (int64_t)M * ldx * 2 < 0x7fffffffLL;
 #define W8X(NC, NRM) do {                                                                                                                        \
-            static bool attr_ = false;                                                                                                           \
-            if (!attr_) { hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_skinny_w8a8_kernel<4, 2, NC, 1, NRM, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024); attr_ = true; } \
+            static Tr1PerDevice lds_;                                                                                                            \
+            if (lds_.first()) hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_skinny_w8a8_kernel<4, 2, NC, 1, NRM, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024); \
             hipLaunchKernelGGL((gemm_skinny_w8a8_kernel<4, 2, NC, 1, NRM, false, true>), dim3((unsigned)((N + 16 * NC - 1) / (16 * NC))), dim3(256), (size_t)W8X_LDS(K), s, \
                                (const bf16_t*)x, (const bf16_t*)lnw, (const unsigned char*)W_fp8, (const float*)wscale, (bf16_t*)out, (const bf16_t*)bias,  \
                                (const bf16_t*)residual, (int)M, N, K, ldx, ldw, ldc, ldr, eps, N);                                              \
@@ -927,8 +878,8 @@ extern "C" int tr1_gemm_skinny_fixup_w8a8(const void* x, const void* W_fp8, cons
         float* tiles56 = (float*)ws_f32;
         int* cnt56 = (int*)(tiles56 + KS * g56 * 4 * 256);
         const size_t dyn56 = WV7 * 2 * (7 * 1024 + 4096) + 16;
-        static bool attr56 = false;
-        if (!attr56) { hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_skinny_lds_fix_f8_kernel<WV7, 7>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn56); attr56 = true; }
+        static Tr1PerDevice lds;
+        if (lds.first()) hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_skinny_lds_fix_f8_kernel<WV7, 7>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn56);
         hipLaunchKernelGGL((gemm_skinny_lds_fix_f8_kernel<WV7, 7>), dim3((unsigned)g56, KS), dim3(WV7 * 64), dyn56, (hipStream_t)stream, (const bf16_t*)x,
                            (const unsigned char*)W_fp8, (const float*)wscale, (bf16_t*)out, (const bf16_t*)bias, (const bf16_t*)residual, (int)M, N, K, ldx,
                            ldw, ldc, ldr, tiles56, cnt56);
@@ -939,8 +890,8 @@ extern "C" int tr1_gemm_skinny_fixup_w8a8(const void* x, const void* W_fp8, cons
     float* tiles = (float*)ws_f32;
     int* cnt = (int*)(tiles + KS * groups * 4 * 256);
     const size_t dyn = WV * 2 * 12288 + 16;
-    static bool attr_set = false;
-    if (!attr_set) { hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_skinny_lds_fix_f8_kernel<WV>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn); attr_set = true; }
+    static Tr1PerDevice lds;
+    if (lds.first()) hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_skinny_lds_fix_f8_kernel<WV>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn);
     hipLaunchKernelGGL((gemm_skinny_lds_fix_f8_kernel<WV>), dim3((unsigned)groups, KS), dim3(WV * 64), dyn, (hipStream_t)stream, (const bf16_t*)x,
                        (const unsigned char*)W_fp8, (const float*)wscale, (bf16_t*)out, (const bf16_t*)bias, (const bf16_t*)residual, (int)M, N, K, ldx,
                        ldw, ldc, ldr, tiles, cnt);

@@ -105,18 +105,8 @@ __global__ __launch_bounds__(OPJ_WAVES * 64) void oproj_frag_kernel(const bf16_t
     }
 }
 
-// per-device caches (a process normally drives ONE GPU, but tools / tests may touch more: the CU count and the raised dynamic-LDS limit belong to a device)
-static int opj_dev() { int dev = 0; return (hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < 16) ? dev : 0; }
 static int opj_cols(int64_t N) {
-    static int cus_of[16] = {0};
-    const int dev = opj_dev();
-    int cus = cus_of[dev];
-    if (!cus) {
-        hipDeviceProp_t pr;
-        cus = (hipGetDeviceProperties(&pr, dev) == hipSuccess) ? pr.multiProcessorCount : 256;
-        if (cus <= 0) cus = 256;
-        cus_of[dev] = cus;
-    }
+    const int cus = tr1_cu_count();
     for (int c = (int)((N + cus - 1) / cus); c <= 16; ++c)
         if (c >= 1 && N % c == 0) return c;
     return 0;
@@ -132,9 +122,7 @@ static bool opj_long_ok(int64_t M, int64_t N, int64_t K) {
 // 1 when tr1_gemm_oproj_frag covers the shape: the decode driver then asks the split-KV merge (o projection) / the gate-up epilogue (down projection) for the
 // fragment-major activation (tr1_attn_fwd_planned_frag, tr1_norm_gemm_skinny glu = 2)
 extern "C" int tr1_gemm_oproj_frag_ok(int64_t M, int64_t N, int64_t K) {
-    static int on = -1;
-    if (on < 0) { const char* e = getenv("TR1_O_FRAG"); on = e ? atoi(e) : 1; }
-    if (!(on && M >= 1 && M <= 32 && K % 64 == 0 && K >= 512 && N % 2 == 0 && opj_cols(N) > 0)) return 0;
+    if (!(M >= 1 && M <= 32 && K % 64 == 0 && K >= 512 && N % 2 == 0 && opj_cols(N) > 0)) return 0;
     return K <= OPJ_WAVES * OPJ_MAXS * 64 || opj_long_ok(M, N, K);
 }
 
@@ -149,16 +137,16 @@ extern "C" int tr1_gemm_oproj_frag(const void* Xfrag, const void* W, const void*
     const size_t dyn = (size_t)(K / 64) * (lng ? 1024 : 2048) + (size_t)OPJ_WAVES * mg * 16 * 17 * 4 + 16;
     hipStream_t s = (hipStream_t)stream;
     const dim3 grid((unsigned)(N / cols));
-#define OPJ_LAUNCH(KERNEL, SLOT)                                                                                                                      \
+#define OPJ_LAUNCH(KERNEL)                                                                                                                            \
     do {                                                                                                                                              \
-        static bool attr_[3][16] = {{false}};                                                                                                         \
-        if (!attr_[SLOT][opj_dev()]) { hipFuncSetAttribute(reinterpret_cast<const void*>(&KERNEL), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 512); attr_[SLOT][opj_dev()] = true; } \
+        static Tr1PerDevice lds_;                                                                                                                     \
+        if (lds_.first()) hipFuncSetAttribute(reinterpret_cast<const void*>(&KERNEL), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 512);   \
         hipLaunchKernelGGL((KERNEL), grid, dim3(OPJ_WAVES * 64), dyn, s, (const bf16_t*)Xfrag, (const bf16_t*)W, (const bf16_t*)residual, (bf16_t*)C, (int)M, N, K, \
                            ldw, ldr, ldc, cols);                                                                                                      \
     } while (0)
-    if (lng) OPJ_LAUNCH((oproj_frag_kernel<1, OPJ_MAXS_LONG, 1>), 2);
-    else if (mg == 1) OPJ_LAUNCH((oproj_frag_kernel<1, OPJ_MAXS, 2>), 0);
-    else OPJ_LAUNCH((oproj_frag_kernel<2, OPJ_MAXS, 2>), 1);
+    if (lng) OPJ_LAUNCH((oproj_frag_kernel<1, OPJ_MAXS_LONG, 1>));
+    else if (mg == 1) OPJ_LAUNCH((oproj_frag_kernel<1, OPJ_MAXS, 2>));
+    else OPJ_LAUNCH((oproj_frag_kernel<2, OPJ_MAXS, 2>));
 #undef OPJ_LAUNCH
     TR1_LAUNCH_CHECK();
 }

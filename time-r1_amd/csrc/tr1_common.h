@@ -94,6 +94,26 @@ extern "C" void tr1_set_error_(const char* msg);
         return 0;                                                 \
     } while (0)
 
+// ---- per-device host state.  A process normally drives ONE GPU, but tools and tests may touch more: the CU count and a kernel's raised
+// dynamic-LDS limit belong to a device, so both are kept per device (ordinals 0..15).
+inline int tr1_device() { int dev = 0; return (hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < 16) ? dev : 0; }
+inline int tr1_cu_count() {
+    static int cached[16] = {0};
+    const int dev = tr1_device();
+    if (!cached[dev]) {
+        hipDeviceProp_t pr;
+        const int cus = (hipGetDeviceProperties(&pr, dev) == hipSuccess) ? pr.multiProcessorCount : 0;
+        cached[dev] = cus > 0 ? cus : 256;
+    }
+    return cached[dev];
+}
+// once per device and call site - the launchers raise their kernels' dynamic-LDS limits behind it:
+//     static Tr1PerDevice lds; if (lds.first()) hipFuncSetAttribute(..., hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+struct Tr1PerDevice {
+    bool done[16] = {};
+    bool first() { const int d = tr1_device(); if (done[d]) return false; return done[d] = true; }
+};
+
 // dw[c] += sum_b part[b][c] (the fixed-order second level of every per-block column reduction: norm weights, bias gradients), b in ascending order inside each of 16 row groups, groups combined in a fixed order.  64 columns per block.
 static __global__ __launch_bounds__(1024) void norm_dw_reduce_kernel(const float* __restrict__ part, float* __restrict__ dw, int nblk, int cols) {
     __shared__ float red[16][64];
