@@ -111,6 +111,9 @@ int tr1_swiglu_bwd(const void* dout, const void* gu, void* dgu, int64_t rows, in
 int tr1_gelu_fwd(const void* x, void* y, int64_t n, void* stream);
 int tr1_gelu_bwd(const void* x, const void* dy, void* dx, int64_t n, void* stream);
 int tr1_quickgelu_fwd(const void* x, void* y, int64_t n, void* stream);
+/* ref: VisionMlp quick_gelu TF:293-301 backward (fix_vit=False trains the blocks, timer1_trainer.py:267-288): dx = dy (s + 1.702 x s (1 - s)),
+ * s = sigmoid(1.702 x), fp32 math on bf16 inputs, rounded once */
+int tr1_quickgelu_bwd(const void* x, const void* dy, void* dx, int64_t n, void* stream);
 int tr1_add_bf16(const void* a, const void* b, void* y, int64_t n, void* stream);
 int tr1_cast_f32_to_bf16(const void* x, void* y, int64_t n, void* stream);
 int tr1_cast_bf16_to_f32(const void* x, void* y, int64_t n, void* stream);
@@ -125,6 +128,11 @@ int tr1_mrope_table(const void* pos3, void* cosb, void* sinb, int64_t T, int64_t
 int tr1_vision_rope_table(const void* hw, void* cosb, void* sinb, int64_t N, int64_t head_dim, float theta, void* stream);
 /* rotate-half RoPE on n_heads heads stored inside rows of `in` (row stride ld_in); backward != 0 applies the adjoint rotation */
 int tr1_rope_apply(const void* in, int64_t ld_in, void* out, int64_t ld_out, const void* cosb, const void* sinb, int64_t T, int64_t n_heads, int64_t head_dim, int backward, void* stream);
+/* ref: VisionAttention TF:379-396 (q / k / v split of the fused qkv, apply_rotary_pos_emb_vision TF:225-248), backward of the tower's 128-wide padded
+ * heads (fix_vit=False, timer1_trainer.py:267-288): [T, n_heads*128] with feature d < half at h*128 + d and its partner at h*128 + hoff + d ->
+ * [T, n_heads*2*half] (row stride ld_out, may be a column view); rotate != 0 applies the adjoint rotation (cos / sin fp32 [T, half]).
+ * Bit-identical to compacting + tr1_rope_apply(backward=1). */
+int tr1_vit_heads_unpad(const void* in, int64_t ld_in, void* out, int64_t ld_out, const void* cosb, const void* sinb, int64_t T, int64_t n_heads, int64_t half, int64_t hoff, int rotate, void* stream);
 
 /* ---- embedding / scatter ---------------------------------------------------------------------------------------------- */
 /* ref: embed_tokens TF:1160 and the masked_scatter of video embeddings TF:1170-1176 */

@@ -59,13 +59,13 @@ __global__ void swiglu_bwd_kernel(const bf16_t* __restrict__ dout, const bf16_t*
     }
 }
 
-// mode 0: gelu(erf) fwd, 1: quick_gelu fwd, 2: gelu(erf) bwd (needs dy), 3: silu fwd? (unused)
+// mode 0: gelu(erf) fwd, 1: quick_gelu fwd, 2: gelu(erf) bwd (needs dy), 3: quick_gelu bwd (needs dy)
 template <int MODE>
 __global__ void act_kernel(const bf16_t* __restrict__ x, const bf16_t* __restrict__ dy, bf16_t* __restrict__ y, int64_t nchunks) {
     for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < nchunks; i += (int64_t)gridDim.x * blockDim.x) {
         const u32x4_t p = reinterpret_cast<const u32x4_t*>(x)[i];
         u32x4_t d = {0, 0, 0, 0};
-        if (MODE == 2) d = reinterpret_cast<const u32x4_t*>(dy)[i];
+        if (MODE >= 2) d = reinterpret_cast<const u32x4_t*>(dy)[i];
         u32x4_t o;
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
@@ -74,7 +74,10 @@ __global__ void act_kernel(const bf16_t* __restrict__ x, const bf16_t* __restric
             for (int k = 0; k < 2; ++k) {
                 if (MODE == 0) r[k] = 0.5f * v[k] * (1.f + erff(v[k] * 0.70710678118654752f));
                 else if (MODE == 1) r[k] = v[k] / (1.f + __expf(-1.702f * v[k]));
-                else {
+                else if (MODE == 3) {      // d/dx x s(1.702 x) = s + 1.702 x s (1 - s); s -> 0 / 1 at large |x| (expf saturates), never NaN
+                    const float s = 1.f / (1.f + __expf(-1.702f * v[k]));
+                    r[k] = g[k] * (s + 1.702f * v[k] * s * (1.f - s));
+                } else {
                     float cdf = 0.5f * (1.f + erff(v[k] * 0.70710678118654752f));
                     float pdf = 0.3989422804014327f * __expf(-0.5f * v[k] * v[k]);
                     r[k] = g[k] * (cdf + v[k] * pdf);
@@ -155,6 +158,45 @@ __global__ void rope_apply_kernel(const bf16_t* __restrict__ in, int64_t ld_in, 
         bf16_t* dst = out + t * ld_out + (int64_t)h * head_dim + c * 8;
         const u32x4_t a = *reinterpret_cast<const u32x4_t*>(src);
         const u32x4_t b = *reinterpret_cast<const u32x4_t*>(src + half);
+        const float* cp = cosb + t * half + c * 8;
+        const float* sp = sinb + t * half + c * 8;
+        u32x4_t oa, ob;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const float c0 = cp[2 * j], c1 = cp[2 * j + 1], s0 = sp[2 * j] * sgn, s1 = sp[2 * j + 1] * sgn;
+            const float a0 = bflo(a[j]), a1 = bfhi(a[j]), b0 = bflo(b[j]), b1 = bfhi(b[j]);
+            oa[j] = pack2bf(a0 * c0 - b0 * s0, a1 * c1 - b1 * s1);
+            ob[j] = pack2bf(b0 * c0 + a0 * s0, b1 * c1 + a1 * s1);
+        }
+        *reinterpret_cast<u32x4_t*>(dst) = oa;
+        *reinterpret_cast<u32x4_t*>(dst + half) = ob;
+    }
+}
+
+// Vision tower heads back from the 128-wide padded layout (Engine._vit_pad128, csrc/gemm.hip EPI 7) to the checkpoint's head_dim = 2*half
+// layout: feature d < half of head h sits at column h*128 + d, its rotary partner at h*128 + hoff + d.  rotate != 0 also applies the adjoint
+// (backward) rotation with the same arithmetic as rope_apply_kernel (sgn = -1), so the result is bit-identical to compacting and then running
+// tr1_rope_apply(backward=1).  One lane per 16-byte chunk of a half.
+__global__ void vit_heads_unpad_kernel(const bf16_t* __restrict__ in, int64_t ld_in, bf16_t* __restrict__ out, int64_t ld_out,
+                                       const float* __restrict__ cosb, const float* __restrict__ sinb, int64_t T, int n_heads, int half, int hoff,
+                                       int rotate) {
+    const int hc = half >> 3;
+    const int64_t total = T * n_heads * hc;
+    const float sgn = -1.f;
+    for (int64_t idx = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; idx < total; idx += (int64_t)gridDim.x * blockDim.x) {
+        const int c = (int)(idx % hc);
+        const int64_t th = idx / hc;
+        const int h = (int)(th % n_heads);
+        const int64_t t = th / n_heads;
+        const bf16_t* src = in + t * ld_in + (int64_t)h * 128 + c * 8;
+        bf16_t* dst = out + t * ld_out + (int64_t)h * 2 * half + c * 8;
+        const u32x4_t a = *reinterpret_cast<const u32x4_t*>(src);
+        const u32x4_t b = *reinterpret_cast<const u32x4_t*>(src + hoff);
+        if (!rotate) {
+            *reinterpret_cast<u32x4_t*>(dst) = a;
+            *reinterpret_cast<u32x4_t*>(dst + half) = b;
+            continue;
+        }
         const float* cp = cosb + t * half + c * 8;
         const float* sp = sinb + t * half + c * 8;
         u32x4_t oa, ob;
@@ -334,6 +376,13 @@ extern "C" int tr1_gelu_bwd(const void* x, const void* dy, void* dx, int64_t n, 
                        (bf16_t*)dx, n / 8);
     TR1_LAUNCH_CHECK();
 }
+extern "C" int tr1_quickgelu_bwd(const void* x, const void* dy, void* dx, int64_t n, void* stream) {
+    TR1_CHECK_ARG(n % 8 == 0, "quickgelu_bwd: n must be a multiple of 8");
+    if (n == 0) return 0;
+    hipLaunchKernelGGL(act_kernel<3>, dim3(EW_GRID(n / 8)), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)x, (const bf16_t*)dy,
+                       (bf16_t*)dx, n / 8);
+    TR1_LAUNCH_CHECK();
+}
 extern "C" int tr1_add_bf16(const void* a, const void* b, void* y, int64_t n, void* stream) {
     TR1_CHECK_ARG(n % 8 == 0, "add: n must be a multiple of 8");
     if (n == 0) return 0;
@@ -373,6 +422,16 @@ extern "C" int tr1_rope_apply(const void* in, int64_t ld_in, void* out, int64_t 
     hipLaunchKernelGGL(rope_apply_kernel, dim3(EW_GRID(T * n_heads * head_dim / 16)), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)in,
                        ld_in, (bf16_t*)out, ld_out, (const float*)cosb, (const float*)sinb, (int)T, (int)n_heads, (int)head_dim,
                        backward ? -1.f : 1.f);
+    TR1_LAUNCH_CHECK();
+}
+extern "C" int tr1_vit_heads_unpad(const void* in, int64_t ld_in, void* out, int64_t ld_out, const void* cosb, const void* sinb, int64_t T,
+                                   int64_t n_heads, int64_t half, int64_t hoff, int rotate, void* stream) {
+    TR1_CHECK_ARG(half > 0 && half % 8 == 0 && hoff % 8 == 0 && hoff >= half && hoff + half <= 128 && ld_in % 8 == 0 && ld_out % 8 == 0
+                  && ld_in >= n_heads * 128 && ld_out >= n_heads * 2 * half, "vit_heads_unpad: half%8, hoff%8, half <= hoff <= 128-half, ld%8 and ld >= row width required");
+    TR1_CHECK_ARG(!rotate || (cosb && sinb), "vit_heads_unpad: rotate needs cos / sin");
+    if (T == 0) return 0;
+    hipLaunchKernelGGL(vit_heads_unpad_kernel, dim3(EW_GRID(T * n_heads * half / 8)), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)in, ld_in,
+                       (bf16_t*)out, ld_out, (const float*)cosb, (const float*)sinb, T, (int)n_heads, (int)half, (int)hoff, rotate);
     TR1_LAUNCH_CHECK();
 }
 extern "C" int tr1_gather_rows(const void* table, const void* ids, void* out, int64_t T, int64_t cols, void* stream) {

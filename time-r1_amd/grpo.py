@@ -107,6 +107,7 @@ class GRPOCore:
             pp = ops.zeros(pix.shape[0], v.patch_dim_padded)
             pp[:, : v.patch_dim] = pix.to(pp.device).to(pp.dtype)
         st.feats, st.vis_perm = eng.vit_features(pp, grid)        # frozen blocks: once per prompt (reference: 3 x G times)
+        st.pixels = pp if eng.params.train_vit else None          # fix_vit=False: the reference tower and the backward's recompute read them again
         st.vid_embeds, st.merger_ctx = eng.merger_fwd(eng.params.train, st.feats, save=True, perm=st.vis_perm)
         return st
 
@@ -194,7 +195,9 @@ class GRPOCore:
         st.ref_logp = None
         if self.beta != 0.0:
             ra = self.ref_arena
-            ref_vid, _ = eng.merger_fwd(ra, st.feats, save=False, perm=st.vis_perm)
+            # fix_vit=False: the reference policy's features come from the INITIAL tower (its copy in the reference arena, reference :295-307)
+            ref_feats = eng.vit_features(st.pixels, st.grid, arena=ra)[0] if eng.params.train_vit else st.feats
+            ref_vid, _ = eng.merger_fwd(ra, ref_feats, save=False, perm=st.vis_perm)
             h0r = eng.embed(ra, st.ids_packed, ref_vid, st.vid_rows)
             hLr, _ = eng.llm_fwd(ra, h0r, st.cos, st.sin, st.masks, save=False, tail_from=eng.tail_rows_from(st.P, st.layout.M))
             rlogp, _, _ = eng.head_fwd(ra, hLr, st.pred_rows, st.targets, save=False)
@@ -231,8 +234,14 @@ class GRPOCore:
         ids_g = st.ids_packed.clone()
         ids_g[st.vid_rows.long()] = -1
         dvid = eng.embed_bwd(dh0, ids_g, st.vid_rows)
-        eng.merger_bwd(st.merger_ctx, dvid)
+        dfeats = eng.merger_bwd(st.merger_ctx, dvid)
         st.llm_ctx = st.head_ctx = st.merger_ctx = None
+        if dfeats is not None:
+            # fix_vit=False: the tower's activations are recomputed here, one prompt at a time (prepare() keeps none), then its backward runs.
+            # Its gradient ranges are handed to the exchange by grad_sync.finish() (GradSync / ShardSync cover every range nobody announced).
+            _, _, vctx = eng.vit_features(st.pixels, st.grid, save=True)
+            eng.vit_bwd(vctx, dfeats)
+            st.pixels = None
         return out3, row_len
 
 

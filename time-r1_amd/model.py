@@ -139,14 +139,25 @@ class Engine:
         return self.ops.gemm_nn(dy, w)
 
     # ============================================================================================================ ViT
-    def vit_features(self, pixels, grid_thw):
-        """Frozen vision blocks. pixels: [N_v, patch_dim_padded] act dtype; grid_thw: list of (t,h,w).
+    def vit_features(self, pixels, grid_thw, arena=None, save=False):
+        """Vision blocks. pixels: [N_v, patch_dim_padded] act dtype; grid_thw: list of (t,h,w).  arena: the weights (default: the arena that
+        holds the tower, ModelParams.vit; the reference policy's arena for its log-probs when the tower trains).
         Returns (feats [N_v, embed], perm): perm is None for Qwen2-VL; for Qwen2.5-VL the rows of feats are in WINDOW order and perm is
-        the int32 device tensor (window_index) merger_fwd/bwd use to restore the natural order of the merged tokens."""
+        the int32 device tensor (window_index) merger_fwd/bwd use to restore the natural order of the merged tokens.
+        save=True (fix_vit=False, the tower's backward): returns (feats, perm, ctx) with the activations vit_bwd reads; the features are
+        bit-identical to save=False (fc1 + bias, then the QuickGELU kernel: gemm.hip documents EPI 5 as bit-identical to that pair)."""
+        a = arena if arena is not None else self.params.vit
+        ctx = dict(pixels=pixels, grid=grid_thw, arena=a, blocks=[]) if save else None
         if self.cfg.vision.variant == "qwen2_5_vl":
-            return self._vit_features_25(pixels, grid_thw)
-        ops, v, fz = self.ops, self.cfg.vision, self.params.frozen
+            feats, perm = self._vit_features_25(pixels, grid_thw, a, ctx)
+        else:
+            feats, perm = self._vit_features_2(pixels, grid_thw, a, ctx)
+        return (feats, perm, ctx) if save else (feats, perm)
+
+    def _vit_features_2(self, pixels, grid_thw, fz, ctx):
+        ops, v = self.ops, self.cfg.vision
         E, H, hd = v.embed_dim, v.num_heads, v.head_dim
+        save = ctx is not None
         hw = ops.tensor(vision_hw_ids(grid_thw, v.spatial_merge_size), I32)
         pre, lo, hi = [ops.tensor(a, I32) for a in vision_segments(grid_thw)]
         N = pixels.shape[0]
@@ -154,32 +165,44 @@ class Engine:
         cos, sin = ops.vision_rope_table(hw, hd)
         x = ops.gemm_nt(pixels, fz.w("patch.w"))
         scale = hd ** -0.5
-        pad = self._vit_pad128(N)
+        pad = self._vit_pad128(N, fz)
+        if save:
+            ctx.update(cos=cos, sin=sin, pad=pad, scale=scale)
         for i in range(v.depth):
             p = "v%d." % i
-            y, _, _ = ops.layernorm_fwd(x, fz.w(p + "n1.w"), fz.w(p + "n1.b"), v.ln_eps, need_stats=False)
-            x = self._vit_attention(i, y, x, cos, sin, pre, lo, hi, N, scale, pad)
-            y, _, _ = ops.layernorm_fwd(x, fz.w(p + "n2.w"), fz.w(p + "n2.b"), v.ln_eps, need_stats=False)
-            z = ops.gemm_quickgelu(y, fz.w(p + "fc1.w"), fz.w(p + "fc1.b"))          # fc1 + bias + QuickGELU in the GEMM epilogue
+            B = dict(x=x, masks=(pre, lo, hi)) if save else None
+            y, mean1, rstd1 = ops.layernorm_fwd(x, fz.w(p + "n1.w"), fz.w(p + "n1.b"), v.ln_eps, need_stats=save)
+            x = self._vit_attention(i, y, x, cos, sin, pre, lo, hi, N, scale, pad, fz, B)
+            y2, mean2, rstd2 = ops.layernorm_fwd(x, fz.w(p + "n2.w"), fz.w(p + "n2.b"), v.ln_eps, need_stats=save)
+            if save:
+                zp = ops.gemm_nt(y2, fz.w(p + "fc1.w"), bias=fz.w(p + "fc1.b"))          # pre-activation kept for the QuickGELU backward
+                z = ops.quickgelu_fwd(zp)
+                B.update(y=y, mean1=mean1, rstd1=rstd1, xm=x, y2=y2, mean2=mean2, rstd2=rstd2, zp=zp, z=z)
+                ctx["blocks"].append(B)
+            else:
+                z = ops.gemm_quickgelu(y2, fz.w(p + "fc1.w"), fz.w(p + "fc1.b"))          # fc1 + bias + QuickGELU in the GEMM epilogue
             x = ops.gemm_nt(z, fz.w(p + "fc2.w"), bias=fz.w(p + "fc2.b"), residual=x)
         return x, None
 
     # ---- vision attention sub-block (both towers): x + proj(attention(rope(q), rope(k), v))
-    def _vit_pad128(self, N):
+    def _vit_pad128(self, N, fz=None):
         """Head dim 80 on 128-wide zero-padded heads: feature d < 40 at column d, d + 40 at 48 + d (round 6; 64 + d before: the live features now end at 96 and
         the attention launch skips the last quarter of its MFMAs, ops.attn_fwd(live96=True)), so that (a) the q|k|v GEMM's epilogue adds the bias and
         applies the 2-D rotary embedding and (b) the head-dim-128 attention kernel (32x32x16 MFMA,
         K and V row-major: no V^T copy) runs the tower - 236 -> ~140 us per block at config 3 against the 96-wide 16x16 kernel, and the two rope launches
         and the V^T pack disappear.  Returns None when the shapes / backend do not allow it.  The padded output-projection weights (zero columns at the pad
-        positions) are derived ONCE per version of the frozen arena."""
-        ops, v, fz = self.ops, self.cfg.vision, self.params.frozen
+        positions) are derived ONCE per version of the arena that holds them (fz: default ModelParams.vit): keyed on Arena.version, which the optimizer
+        bumps when its HIP kernels rewrite the weights (torch never sees those writes), and on torch's in-place counter for writes through torch."""
+        ops, v = self.ops, self.cfg.vision
+        fz = fz if fz is not None else self.params.vit
         ok = getattr(ops, "vit_pad128_ok", None)
         if ok is None or not ok(v.num_heads, v.head_dim):
             return None
         H, hd, E, half = v.num_heads, v.head_dim, v.embed_dim, v.head_dim // 2
         hoff = 48 if half <= 48 else 64              # where the second rotary half starts inside a 128-wide head (csrc/gemm.hip EPI 7)
-        cache = self.__dict__.setdefault("_vit_pad_cache", {})
-        ver = (fz.w16.data_ptr(), fz.w16._version)         # torch's in-place version counter: any write to the frozen arena (loaders, tests) rebuilds
+        caches = self.__dict__.setdefault("_vit_pad_cache", {})
+        cache = caches.setdefault(fz.w16.data_ptr(), {})      # one entry per arena (policy tower, reference tower)
+        ver = (fz.w16.data_ptr(), fz.w16._version, getattr(fz, "version", 0))
         if cache.get("ver") != ver:
             proj = []
             for i in range(v.depth):
@@ -188,34 +211,42 @@ class Engine:
                 wp[:, :, :half] = w[:, :, :half]
                 wp[:, :, hoff:hoff + half] = w[:, :, half:]
                 proj.append(wp.view(E, H * 128))
-            cache.update(ver=ver, proj=proj, bufs=None)
-        if cache.get("bufs") is None or cache["bufs"][0].shape[0] != N:
-            cache["bufs"] = [ops.zeros(N, H * 128) for _ in range(4)]      # q, k, v, o: pad columns stay zero (the live-96 attention launch never writes o's columns 96..127)
-        return dict(proj=cache["proj"], bufs=cache["bufs"], live96=hoff == 48)
+            cache.update(ver=ver, proj=proj)
+        shared = caches.setdefault("bufs", [None])
+        if shared[0] is None or shared[0][0].shape[0] != N:
+            shared[0] = [ops.zeros(N, H * 128) for _ in range(4)]      # q, k, v, o: pad columns stay zero (the live-96 attention launch never writes o's columns 96..127)
+        return dict(proj=cache["proj"], bufs=shared[0], live96=hoff == 48, hoff=hoff)
 
-    def _vit_attention(self, i, y, x, cos, sin, pre, lo, hi, N, scale, pad):
-        ops, v, fz = self.ops, self.cfg.vision, self.params.frozen
+    def _vit_attention(self, i, y, x, cos, sin, pre, lo, hi, N, scale, pad, fz, B=None):
+        """B (save mode): receives q / k / v / o / lse of this block (padded: fresh zero-padded buffers per block instead of the shared ones)."""
+        ops, v = self.ops, self.cfg.vision
         E, H, hd = v.embed_dim, v.num_heads, v.head_dim
         p = "v%d." % i
+        save = B is not None
         if pad is not None:
-            q, k, vv, o = pad["bufs"]
+            q, k, vv, o = [ops.zeros(N, H * 128) for _ in range(4)] if save else pad["bufs"]
             ops.gemm_qkv_rope_vit(y, fz.w(p + "qkv.w"), fz.w(p + "qkv.b"), cos, sin, H, hd // 2, q, k, vv)
-            ops.attn_fwd(q, k, None, pre, lo, hi, H, H, N, 128, scale, need_lse=False, v_rows=vv, out=o, live96=pad["live96"])
+            _, lse = ops.attn_fwd(q, k, None, pre, lo, hi, H, H, N, 128, scale, need_lse=save, v_rows=vv, out=o, live96=pad["live96"])
+            if save:
+                B.update(q=q, k=k, v=vv, o=o, lse=lse)
             return ops.gemm_nt(o, pad["proj"][i], bias=fz.w(p + "proj.b"), residual=x)
         qkv = ops.gemm_nt(y, fz.w(p + "qkv.w"), bias=fz.w(p + "qkv.b"))
         q = ops.rope_apply(qkv[:, :E], H, hd, cos, sin)
         k = ops.rope_apply(qkv[:, E:2 * E], H, hd, cos, sin)
         vt = ops.pack_transpose(qkv[:, 2 * E:], H, H, hd)
-        o, _ = ops.attn_fwd(q, k, vt, pre, lo, hi, H, H, N, hd, scale, need_lse=False)
+        o, lse = ops.attn_fwd(q, k, vt, pre, lo, hi, H, H, N, hd, scale, need_lse=save)
+        if save:
+            B.update(q=q, k=k, v=qkv[:, 2 * E:], o=o, lse=lse)
         return ops.gemm_nt(o, fz.w(p + "proj.w"), bias=fz.w(p + "proj.b"), residual=x)
 
-    def _vit_features_25(self, pixels, grid_thw):
+    def _vit_features_25(self, pixels, grid_thw, fz, ctx):
         """Qwen2.5-VL tower (transformers/models/qwen2_5_vl/modeling_qwen2_5_vl.py:408-470 forward, :294-325 block, :85-96 MLP):
         merged tokens are permuted once into window-major order, so BOTH attention flavours are contiguous segments of the same
         two-interval mask kernel - windows for most blocks, whole temporal patches for `fullatt_block_indexes` (a frame's windows
         stay contiguous after the permutation).  RMSNorm + biased SwiGLU MLP (width zero-padded to a multiple of 64)."""
-        ops, v, fz = self.ops, self.cfg.vision, self.params.frozen
+        ops, v = self.ops, self.cfg.vision
         E, H, hd, U = v.embed_dim, v.num_heads, v.head_dim, v.merge_unit
+        save = ctx is not None
         N = pixels.shape[0]
         widx, cu_win = vision_window_index(grid_thw, v.spatial_merge_size, v.window_size, v.patch_size)
         hw = vision_hw_ids(grid_thw, v.spatial_merge_size)
@@ -228,16 +259,81 @@ class Engine:
         x = ops.gemm_nt(pixels, fz.w("patch.w"))
         x = ops.gather_rows(x.view(N // U, U * E), perm).view(N, E)
         scale = hd ** -0.5
-        pad = self._vit_pad128(N)
+        pad = self._vit_pad128(N, fz)
+        if save:
+            ctx.update(cos=cos, sin=sin, pad=pad, scale=scale, perm=perm)
         for i in range(v.depth):
             p = "v%d." % i
             pre, lo, hi = seg_full if i in v.fullatt_block_indexes else seg_win
-            y, _, _ = ops.rmsnorm_fwd(x, fz.w(p + "n1.w"), v.ln_eps, need_rstd=False)
-            x = self._vit_attention(i, y, x, cos, sin, pre, lo, hi, N, scale, pad)
-            y, _, _ = ops.rmsnorm_fwd(x, fz.w(p + "n2.w"), v.ln_eps, need_rstd=False)
-            a, _ = ops.gemm_glu(y, fz.w(p + "gu.w"), save_gu=False, bias=fz.w(p + "gu.b"))      # gate/up + bias + SwiGLU in the GEMM epilogue
+            B = dict(x=x, masks=(pre, lo, hi)) if save else None
+            y, rstd1, _ = ops.rmsnorm_fwd(x, fz.w(p + "n1.w"), v.ln_eps, need_rstd=save)
+            x = self._vit_attention(i, y, x, cos, sin, pre, lo, hi, N, scale, pad, fz, B)
+            y2, rstd2, _ = ops.rmsnorm_fwd(x, fz.w(p + "n2.w"), v.ln_eps, need_rstd=save)
+            a, gu = ops.gemm_glu(y2, fz.w(p + "gu.w"), save_gu=save, bias=fz.w(p + "gu.b"))      # gate/up + bias + SwiGLU in the GEMM epilogue
+            if save:
+                B.update(y=y, rstd1=rstd1, xm=x, y2=y2, rstd2=rstd2, gu=gu, a=a)
+                ctx["blocks"].append(B)
             x = ops.gemm_nt(a, fz.w(p + "down.w"), bias=fz.w(p + "down.b"), residual=x)
         return x, perm
+
+    def vit_bwd(self, ctx, dfeats):
+        """Backward of the vision tower (fix_vit=False, reference timer1_trainer.py:267-288) from vit_features(save=True)'s ctx.  dfeats: gradient
+        wrt the features [N_v, E] (merger_bwd); accumulates the tower's weight gradients into the trainable arena, blocks in reverse.  Weight
+        gradients accumulate (the optimizer zeroes the tower's ranges: they are outside Engine.lazy_zero_plan)."""
+        ops, v, tr = self.ops, self.cfg.vision, self.params.train
+        assert self.params.train_vit, "vit_bwd needs the tower in the trainable arena (ModelParams(train_vit=True))"
+        q25 = v.variant == "qwen2_5_vl"
+        E, H, hd = v.embed_dim, v.num_heads, v.head_dim
+        half, pad, cos, sin, scale = hd // 2, ctx["pad"], ctx["cos"], ctx["sin"], ctx["scale"]
+        N = dfeats.shape[0]
+        dx = dfeats
+        for i in reversed(range(v.depth)):
+            p = "v%d." % i
+            B = ctx["blocks"][i]
+            # ---- MLP: x_out = mlp(norm2(xm)) + xm
+            if q25:
+                self._wgrad(dx, B["a"], tr.g(p + "down.w"))
+                ops.colsum_accum(dx, tr.g(p + "down.b"))
+                dgu = ops.dgrad_glu_bwd(dx, tr.w(p + "down.w"), B["gu"])              # SwiGLU backward in the dgrad's epilogue (EPI 3)
+                self._wgrad(dgu, B["y2"], tr.g(p + "gu.w"), bias_g=tr.g(p + "gu.b"))
+                dy2 = self._dgrad(dgu, tr.w(p + "gu.w"))
+                dxm = ops.rmsnorm_bwd(dy2, B["xm"], tr.w(p + "n2.w"), B["rstd2"], dres=dx, dw=tr.g(p + "n2.w"))
+            else:
+                self._wgrad(dx, B["z"], tr.g(p + "fc2.w"), bias_g=tr.g(p + "fc2.b"))
+                dz = ops.quickgelu_bwd(B["zp"], self._dgrad(dx, tr.w(p + "fc2.w")))
+                self._wgrad(dz, B["y2"], tr.g(p + "fc1.w"), bias_g=tr.g(p + "fc1.b"))
+                dy2 = self._dgrad(dz, tr.w(p + "fc1.w"))
+                dxm = ops.add(dx, ops.layernorm_bwd(dy2, B["xm"], tr.w(p + "n2.w"), B["mean2"], B["rstd2"], tr.g(p + "n2.w"), tr.g(p + "n2.b"), need_dx=True))
+            # ---- attention: xm = proj(attn(rope(q), rope(k), v)) + x
+            pre, lo, hi = B["masks"]
+            dqkv = ops.empty(N, 3 * E)
+            if pad is not None:
+                hoff = pad["hoff"]
+                oc = ops.vit_heads_unpad(B["o"], H, half, hoff, ops.empty(N, E))          # compact o for the proj weight gradient
+                self._wgrad(dxm, oc, tr.g(p + "proj.w"), bias_g=tr.g(p + "proj.b"))
+                do = self._dgrad(dxm, pad["proj"][i])          # through the padded proj weight: do's pad columns are zero
+                dq, dk, dv = ops.attn_bwd(B["q"], B["k"], B["v"], B["o"], do, B["lse"], pre, lo, hi, H, H, N, 128, scale)
+                ops.vit_heads_unpad(dq, H, half, hoff, dqkv[:, :E], cos, sin)
+                ops.vit_heads_unpad(dk, H, half, hoff, dqkv[:, E:2 * E], cos, sin)
+                ops.vit_heads_unpad(dv, H, half, hoff, dqkv[:, 2 * E:])
+            else:
+                self._wgrad(dxm, B["o"], tr.g(p + "proj.w"), bias_g=tr.g(p + "proj.b"))
+                do = self._dgrad(dxm, tr.w(p + "proj.w"))
+                ops.attn_bwd(B["q"], B["k"], B["v"], B["o"], do, B["lse"], pre, lo, hi, H, H, N, hd, scale,
+                             dq_out=dqkv[:, :E], dk_out=dqkv[:, E:2 * E], dv_out=dqkv[:, 2 * E:], rope=(cos, sin))
+            self._wgrad(dqkv, B["y"], tr.g(p + "qkv.w"), bias_g=tr.g(p + "qkv.b"))
+            dy = self._dgrad(dqkv, tr.w(p + "qkv.w"))
+            if q25:
+                dx = ops.rmsnorm_bwd(dy, B["x"], tr.w(p + "n1.w"), B["rstd1"], dres=dxm, dw=tr.g(p + "n1.w"))
+            else:
+                dx = ops.add(dxm, ops.layernorm_bwd(dy, B["x"], tr.w(p + "n1.w"), B["mean1"], B["rstd1"], tr.g(p + "n1.w"), tr.g(p + "n1.b"), need_dx=True))
+            ctx["blocks"][i] = None             # release this block's activations
+        if q25:          # the window permutation: x_win[j] = x_nat[perm[j]] over merge units -> scatter the rows back
+            U = v.merge_unit
+            dnat = ops.empty(N, E)
+            ops.scatter_rows(dx.view(N // U, U * E).contiguous(), ctx["perm"], dnat.view(N // U, U * E))
+            dx = dnat
+        self._wgrad(dx, ctx["pixels"], tr.g("patch.w"))       # pad columns of the pixels are zero: so is the gradient of patch.w's pad columns
 
     def merger_fwd(self, arena: Arena, feats, save, perm=None):
         """PatchMerger (trainable even with fix_vit, reference timer1_trainer.py:277-280). feats [N_v, E] -> [N_v/4, out_hidden].
@@ -262,7 +358,9 @@ class Engine:
         return out, ctx
 
     def merger_bwd(self, ctx, dout):
+        """Returns the gradient wrt the tower's features when the tower trains (ModelParams.train_vit), else None."""
         ops, tr = self.ops, self.params.train
+        need_dx = self.params.train_vit
         if ctx["perm"] is not None:
             dout = ops.gather_rows(dout, ctx["perm"])
         self._wgrad(dout, ctx["g1"], tr.g("merger.fc2.w"))
@@ -274,10 +372,11 @@ class Engine:
         dxv = self._dgrad(dz1, tr.w("merger.fc1.w"))
         dxn = dxv.view(ctx["feats"].shape)
         if self.cfg.vision.variant == "qwen2_5_vl":
-            ops.rmsnorm_bwd(dxn, ctx["feats"], tr.w("merger.ln.w"), ctx["rstd"], dw=tr.g("merger.ln.w"))
+            dfeats = ops.rmsnorm_bwd(dxn, ctx["feats"], tr.w("merger.ln.w"), ctx["rstd"], dw=tr.g("merger.ln.w"))
         else:
-            ops.layernorm_bwd(dxn, ctx["feats"], tr.w("merger.ln.w"), ctx["mean"], ctx["rstd"], tr.g("merger.ln.w"), tr.g("merger.ln.b"),
-                              need_dx=False)  # the blocks below are frozen: no dx
+            dfeats = ops.layernorm_bwd(dxn, ctx["feats"], tr.w("merger.ln.w"), ctx["mean"], ctx["rstd"], tr.g("merger.ln.w"), tr.g("merger.ln.b"),
+                                       need_dx=need_dx)  # frozen blocks below (fix_vit): no dx
+        return dfeats if need_dx else None
 
     # ============================================================================================================ LLM
     def embed(self, arena: Arena, ids, vid_embeds=None, vid_rows=None):

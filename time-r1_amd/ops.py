@@ -480,6 +480,14 @@ class HipOps:
         self.L.call("tr1_quickgelu_fwd", _p(x), _p(y), x.numel(), self._s())
         return y
 
+    def quickgelu_bwd(self, x, dy):
+        """dx = dy * d quick_gelu(x) / dx (the Qwen2-VL vision MLP's activation, trained with fix_vit=False)."""
+        self._chk(x, dy)
+        assert x.is_contiguous() and dy.is_contiguous() and x.shape == dy.shape
+        dx = torch.empty_like(x)
+        self.L.call("tr1_quickgelu_bwd", _p(x), _p(dy), _p(dx), x.numel(), self._s())
+        return dx
+
     def add(self, a, b):
         self._chk(a, b)
         assert a.is_contiguous() and b.is_contiguous() and a.shape == b.shape
@@ -533,6 +541,18 @@ class HipOps:
         if out is None:
             out = self.empty(T, n_heads * head_dim)
         self.L.call("tr1_rope_apply", _p(x), _ld(x), _p(out), _ld(out), _p(cos), _p(sin), T, n_heads, head_dim, int(backward), self._s())
+        return out
+
+    def vit_heads_unpad(self, x128, n_heads, half, hoff, out, cos=None, sin=None):
+        """Vision heads from the 128-wide padded layout (Engine._vit_pad128: feature d < half at d, its partner at hoff + d) back to
+        [T, n_heads * 2 * half] in `out` (may be a column view); with cos / sin the adjoint rotary rotation is applied on the way
+        (bit-identical to compacting + rope_apply(backward=True))."""
+        self._chk(x128, out)
+        T = x128.shape[0]
+        assert x128.shape[1] >= n_heads * 128 and out.shape == (T, n_heads * 2 * half)
+        if cos is not None:
+            assert cos.dtype == F32 and sin.dtype == F32 and cos.is_contiguous() and sin.is_contiguous() and cos.shape == (T, half) == sin.shape
+        self.L.call("tr1_vit_heads_unpad", _p(x128), _ld(x128), _p(out), _ld(out), _p(cos), _p(sin), T, n_heads, half, hoff, int(cos is not None), self._s())
         return out
 
     # ---- gathers --------------------------------------------------------------------------------------------------

@@ -3,6 +3,8 @@ reference-model snapshot are single large operations (MI355X: few, large HBM/xGM
 
   trainable arena : bf16 working weights + fp32 master / m / v / grad   (LLM + patch-merger; reference timer1_trainer.py:272-280)
   frozen arena    : bf16 only (ViT patch-embed + blocks when fix_vit=True)
+With train_vit (fix_vit=False, reference timer1_trainer.py:267-288) the ViT specs are appended to the trainable arena after the merger and
+the frozen arena is empty; `ModelParams.vit` names whichever arena holds the tower.
 """
 import math
 import re
@@ -166,16 +168,45 @@ class Arena:
         return a
 
 
-class ModelParams:
-    """Qwen2-VL parameters: `train` arena (LLM + merger) and `frozen` arena (ViT)."""
+def arena_specs(cfg: ModelConfig, train_vit=False):
+    """(trainable specs, frozen specs) of the two arenas: the ViT goes after the merger when it trains, so every LLM / merger offset is
+    the same in both layouts and init_random draws the same weights by name."""
+    if train_vit:
+        return _specs_llm(cfg) + _specs_merger(cfg) + _specs_vit(cfg), []
+    return _specs_llm(cfg) + _specs_merger(cfg), _specs_vit(cfg)
 
-    def __init__(self, cfg: ModelConfig, ops, seed=0, init="random", optimizer_state=True):
+
+class ModelParams:
+    """Qwen2-VL parameters: `train` arena (LLM + merger, + ViT with train_vit) and `frozen` arena (ViT, empty with train_vit)."""
+
+    def __init__(self, cfg: ModelConfig, ops, seed=0, init="random", optimizer_state=True, train_vit=False):
         self.cfg = cfg
         self.ops = ops
-        self.train = Arena(ops, _specs_llm(cfg) + _specs_merger(cfg), with_optimizer_state=optimizer_state, with_grad=True)
-        self.frozen = Arena(ops, _specs_vit(cfg), with_optimizer_state=False)
+        self.train_vit = bool(train_vit)
+        trs, fzs = arena_specs(cfg, self.train_vit)
+        self.train = Arena(ops, trs, with_optimizer_state=optimizer_state, with_grad=True)
+        self.frozen = Arena(ops, fzs, with_optimizer_state=False)
         if init == "random":
             self.init_random(seed)
+
+    @property
+    def vit(self):
+        """The arena that holds the vision tower (patch embedding + blocks): `frozen`, or `train` with train_vit."""
+        return self.train if self.train_vit else self.frozen
+
+    def relayout(self, train_vit):
+        """This model's weights in the arena layout of `train_vit` (self when it already matches): a fresh ModelParams with the bf16 weights
+        copied by name; the optimizer state starts fresh (fp32 master = the bf16 weights).  Both models exist until the caller drops this one (at
+        7B two copies do not fit one card: build the layout you need directly)."""
+        if bool(train_vit) == self.train_vit:
+            return self
+        out = ModelParams(self.cfg, self.ops, init="none", optimizer_state=self.train.master is not None, train_vit=train_vit)
+        for src in (self.train, self.frozen):
+            for name in src.names():
+                dst = out.train if name in out.train.offsets else out.frozen
+                dst.w(name).copy_(src.w(name))
+        out.train.sync_master_from_w16()
+        return out
 
     # lm_head is tied to the embedding for the 2B model (shared storage -> shared gradient view)
     def lm_head_w(self, arena=None):
@@ -214,7 +245,7 @@ class ModelParams:
             for name, shape in arena.specs:
                 if name.endswith("ln1") or name.endswith("ln2") or name == "norm" or name.endswith("ln.w") or name.endswith("n1.w") or name.endswith("n2.w"):
                     arena.w(name).fill_(1.0)
-        self.frozen.w("patch.w")[:, self.cfg.vision.patch_dim:].zero_()
+        self.vit.w("patch.w")[:, self.cfg.vision.patch_dim:].zero_()
         self._zero_vision_mlp_padding()
         self.train.sync_master_from_w16()
 
@@ -225,7 +256,7 @@ class ModelParams:
         i0, ip = v.mlp_dim, v.mlp_dim_padded
         for i in range(v.depth):
             p = "v%d." % i
-            gu, gb, dw = self.frozen.w(p + "gu.w"), self.frozen.w(p + "gu.b"), self.frozen.w(p + "down.w")
+            gu, gb, dw = self.vit.w(p + "gu.w"), self.vit.w(p + "gu.b"), self.vit.w(p + "down.w")
             gu[i0:ip].zero_(); gu[ip + i0:].zero_(); gb[i0:ip].zero_(); gb[ip + i0:].zero_(); dw[:, i0:].zero_()
 
     # ---- HF checkpoint <-> arena ----------------------------------------------------------------------------------
@@ -241,7 +272,7 @@ class ModelParams:
                         return sd[k]
             raise KeyError(cands)
 
-        tr, fz = self.train, self.frozen
+        tr, fz = self.train, self.vit
 
         def put(arena, name, t):
             dst = arena.w(name)
@@ -301,7 +332,7 @@ class ModelParams:
 
     def export_hf_state_dict(self):
         """Trainable + frozen weights under transformers-5.x key names (16-bit, like `stage3_gather_16bit_weights_on_model_save`)."""
-        cfg, tr, fz = self.cfg, self.train, self.frozen
+        cfg, tr, fz = self.cfg, self.train, self.vit
         t = cfg.text
         sd = {"model.language_model.embed_tokens.weight": tr.w("embed")}
         for i in range(t.n_layers):

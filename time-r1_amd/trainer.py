@@ -244,25 +244,25 @@ def config_from_hf(hc, name="model"):
     return cfg
 
 
-def load_model_dir(path, ops):
-    """HF checkpoint directory (config.json + *.safetensors) -> (ModelConfig, ModelParams)."""
+def load_model_dir(path, ops, train_vit=False):
+    """HF checkpoint directory (config.json + *.safetensors) -> (ModelConfig, ModelParams); train_vit: the tower in the trainable arena."""
     from safetensors.torch import load_file
     cfg = config_from_hf(json.load(open(os.path.join(path, "config.json"))), name=os.path.basename(os.path.normpath(path)))
     sd = {}
     for f in sorted(os.listdir(path)):
         if f.endswith(".safetensors"):
             sd.update(load_file(os.path.join(path, f)))
-    params = ModelParams(cfg, ops, init="none")
+    params = ModelParams(cfg, ops, init="none", train_vit=train_vit)
     params.load_hf_state_dict(sd)
     return cfg, params
 
 
-def load_hf_module(model, ops):
+def load_hf_module(model, ops, train_vit=False):
     """A loaded transformers model (reference timer1_trainer.py:184-206, :244-262 accepts a `PreTrainedModel` instance as well as a path) ->
     (ModelConfig, ModelParams): its config and state dict are copied into the engine's arenas; the module itself is not kept."""
     hc = model.config.to_dict()
     cfg = config_from_hf(hc, name=str(getattr(model.config, "_name_or_path", "") or type(model).__name__).rstrip("/").split("/")[-1])
-    params = ModelParams(cfg, ops, init="none")
+    params = ModelParams(cfg, ops, init="none", train_vit=train_vit)
     params.load_hf_state_dict({k: v.detach() for k, v in model.state_dict().items()})
     return cfg, params
 
@@ -281,8 +281,6 @@ class TimeR1_Trainer:
         self.args = args
         if peft_config is not None:
             raise NotImplementedError("LoRA/peft is not part of the MI355X engine (the reference scripts train full parameters)")
-        if not getattr(args, "fix_vit", True):
-            raise NotImplementedError("fix_vit=False (training the ViT blocks) is not implemented; every reference script sets fix_vit true")
         mik = getattr(args, "model_init_kwargs", None) or {}
         td = mik.get("torch_dtype")
         if isinstance(td, str) and td not in ("auto", "bfloat16", "float16", "float32"):   # reference :221-235
@@ -292,19 +290,25 @@ class TimeR1_Trainer:
             ops = HipOps("cuda:%d" % int(os.environ.get("LOCAL_RANK", "0")))
             ops.use_priority_stream()
         self.ops = ops
-        # ---- model
+        # ---- model.  fix_vit=False (the reference's default, main.py:44-49; GRPOConfig keeps True): the patch embedding, the vision blocks and the
+        # merger all train (reference :267-288) - the tower's weights live in the trainable arena (ModelParams(train_vit=True)), so AdamW, the clipping
+        # norm, the data-parallel exchange, the reference snapshot and the checkpoints cover them with the rest of the arena
+        train_vit = not getattr(args, "fix_vit", True)
         if isinstance(model, str):
             if model in PRESETS:
                 self.cfg = PRESETS[model]()
-                self.params = ModelParams(self.cfg, ops, seed=args.seed)
+                self.params = ModelParams(self.cfg, ops, seed=args.seed, train_vit=train_vit)
             else:
-                self.cfg, self.params = load_model_dir(model, ops)
+                self.cfg, self.params = load_model_dir(model, ops, train_vit=train_vit)
         elif isinstance(model, ModelParams):
-            self.cfg, self.params = model.cfg, model
+            # a ModelParams of the other layout is copied by name into a new one (optimizer state included) while the caller's stays alive: two copies
+            # of the model at once, which a 7B model does not fit on one card - there, pass a preset / checkpoint directory / ModelConfig, or build
+            # ModelParams(train_vit=not fix_vit) yourself (no copy)
+            self.cfg, self.params = model.cfg, model.relayout(train_vit)
         elif isinstance(model, ModelConfig):
-            self.cfg, self.params = model, ModelParams(model, ops, seed=args.seed)
+            self.cfg, self.params = model, ModelParams(model, ops, seed=args.seed, train_vit=train_vit)
         elif hasattr(model, "state_dict") and hasattr(model, "config"):
-            self.cfg, self.params = load_hf_module(model, ops)      # a loaded transformers model, like the reference accepts
+            self.cfg, self.params = load_hf_module(model, ops, train_vit=train_vit)      # a loaded transformers model, like the reference accepts
         else:
             raise TypeError("model must be a checkpoint path, a preset name, a ModelConfig, a ModelParams or a loaded transformers model")
         self.model = self.params
