@@ -260,6 +260,12 @@ int tr1_sample_tokens(const void* logits, int64_t ld, int64_t rows, int64_t V, f
  * kernel re-zeroes it), so neither a copy kernel nor a memset runs between two decode steps. */
 int tr1_sample_tokens_step(const void* logits, int64_t ld, int64_t rows, int64_t V, float temperature, int64_t top_k, uint64_t seed, int64_t group_rows, uint64_t seed_stride, const void* step_ptr, void* tokens, int64_t tok_ld, void* finished, int64_t eos_id, int64_t pad_id, int stop_at_eos, void* u_out, void* ws_u32, int64_t ws_words, void* next_ids, int ws_zeroed, void* stream);
 int64_t tr1_sample_workspace_words(int64_t rows);
+/* ref: the greedy SamplingParams(temperature=0) of the evaluation / filtering decoder, src/vllm_inference/vllm_infer.py:80-113.  bf16 logits [rows, V], row
+ * stride ld >= V, any V >= 1, any 2-byte-aligned pointer.  Row r with finished[r] != 0: pad_id goes to tokens[r*tok_ld + *step_ptr] and next_ids[r], no logit
+ * is read.  Otherwise the token is the LOWEST index among the entries equal to the row maximum (compared as floats); it goes to tokens and next_ids, and when it
+ * equals eos_id, finished[r] = 1 and *done_count += 1 (int32 on the device, zeroed by the caller once per generate call).  next_ids and done_count may be null.
+ * One launch, no workspace, no memset. */
+int tr1_greedy_tokens_step(const void* logits, int64_t ld, int64_t rows, int64_t V, const void* step_ptr, void* tokens, int64_t tok_ld, void* finished, int64_t eos_id, int64_t pad_id, void* next_ids, void* done_count, void* stream);
 
 /* ---- optimizer -------------------------------------------------------------------------------------------------------- */
 /* ref: DeepSpeed FusedAdam / DeepSpeedCPUAdam selected by scripts/zero3.json:13-21 and zero3_offload.json:24-31 (AdamW, clip 1.0) */

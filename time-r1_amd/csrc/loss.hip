@@ -443,6 +443,70 @@ __global__ __launch_bounds__(1024) void samp_sum_pick_kernel(SampleArgs a) {
     if (a.finished && tok == a.eos_id) a.finished[r] = 1;
 }
 
+// ---- greedy decoding: token = lowest index among the row's maxima, ONE launch per decode step (no workspace, no memset) ------------------------
+// One 1024-thread block per row.  The row is split into a scalar head (up to the first 16-byte boundary), a body of 8-logit chunks read with
+// 16-byte loads (thread t takes chunks t, t + 1024, ..., GREEDY_UNROLL loads in flight) and a scalar tail, so any V >= 1,
+// any ld >= V and any 2-byte-aligned pointer work.  The step's logits were just written by the lm_head launch: this is an L2 / MALL read.
+#define GREEDY_UNROLL 4
+struct GreedyArgs {
+    const bf16_t* logits; int64_t ld; int V; const int* step_ptr; int* tokens; int64_t tok_ld; int* finished; int eos_id, pad_id; int* next_ids; int* done_count;
+};
+__global__ __launch_bounds__(1024) void greedy_tokens_kernel(GreedyArgs a) {
+    __shared__ float sv[16];
+    __shared__ int si[16];
+    const int r = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int step = a.step_ptr ? *a.step_ptr : 0;
+    int* tok_out = a.tokens + (int64_t)r * a.tok_ld + step;
+    if (a.finished[r]) { if (tid == 0) { *tok_out = a.pad_id; if (a.next_ids) a.next_ids[r] = a.pad_id; } return; }      // block-uniform: finished[r] is only written after the barrier below
+    const bf16_t* row = a.logits + (int64_t)r * a.ld;
+    const int head = min(a.V, (int)(((16u - (unsigned)(reinterpret_cast<uintptr_t>(row) & 15u)) & 15u) >> 1));
+    const int nch = (a.V - head) >> 3, tail0 = head + nch * 8;
+    float v = -INFINITY; int idx = 0x7fffffff;
+    if (tid < head) tr1_argmax_pick(v, idx, bf2f(row[tid]), tid);
+    if (nch > 0) {
+        const u32x4_t* body = reinterpret_cast<const u32x4_t*>(row + head);
+        for (int c0 = tid; c0 < nch; c0 += 1024 * GREEDY_UNROLL) {
+            u32x4_t w[GREEDY_UNROLL];
+#pragma unroll
+            for (int u = 0; u < GREEDY_UNROLL; ++u) w[u] = body[min(c0 + u * 1024, nch - 1)];      // clamped: a repeated chunk only offers real (value, index) pairs again
+#pragma unroll
+            for (int u = 0; u < GREEDY_UNROLL; ++u) {
+                const int base = head + min(c0 + u * 1024, nch - 1) * 8;
+#pragma unroll
+                for (int e = 0; e < 8; ++e) {
+                    const float x = (e & 1) ? bfhi(w[u][e >> 1]) : bflo(w[u][e >> 1]);
+                    tr1_argmax_pick(v, idx, x, base + e);
+                }
+            }
+        }
+    }
+    if (tid < a.V - tail0) tr1_argmax_pick(v, idx, bf2f(row[tail0 + tid]), tail0 + tid);
+    wave_argmax(v, idx);
+    if (lane == 0) { sv[wave] = v; si[wave] = idx; }
+    __syncthreads();
+    if (wave != 0) return;
+    v = lane < 16 ? sv[lane] : -INFINITY; idx = lane < 16 ? si[lane] : 0x7fffffff;
+    wave_argmax(v, idx);
+    if (lane != 0) return;
+    const int tok = (idx >= 0 && idx < a.V) ? idx : 0;      // (a row of NaNs compares false everywhere: stay inside the vocabulary)
+    *tok_out = tok;
+    if (a.next_ids) a.next_ids[r] = tok;
+    if (tok == a.eos_id) { a.finished[r] = 1; if (a.done_count) atomicAdd(a.done_count, 1); }
+}
+
+extern "C" int tr1_greedy_tokens_step(const void* logits, int64_t ld, int64_t rows, int64_t V, const void* step_ptr, void* tokens, int64_t tok_ld,
+                                      void* finished, int64_t eos_id, int64_t pad_id, void* next_ids, void* done_count, void* stream) {
+    TR1_CHECK_ARG(logits && tokens && finished, "greedy: logits, tokens and finished must not be null");
+    TR1_CHECK_ARG(V >= 1 && V < (1ll << 31) - 8 && ld >= V && rows >= 0 && tok_ld >= 1, "greedy: need 1 <= V < 2^31 - 8, ld >= V, tok_ld >= 1");
+    TR1_CHECK_ARG((reinterpret_cast<uintptr_t>(logits) & 1) == 0, "greedy: logits must be 2-byte aligned");
+    if (rows == 0) return 0;
+    GreedyArgs a;
+    a.logits = (const bf16_t*)logits; a.ld = ld; a.V = (int)V; a.step_ptr = (const int*)step_ptr; a.tokens = (int*)tokens; a.tok_ld = tok_ld;
+    a.finished = (int*)finished; a.eos_id = (int)eos_id; a.pad_id = (int)pad_id; a.next_ids = (int*)next_ids; a.done_count = (int*)done_count;
+    hipLaunchKernelGGL(greedy_tokens_kernel, dim3((unsigned)rows), dim3(1024), 0, (hipStream_t)stream, a);
+    TR1_LAUNCH_CHECK();
+}
+
 extern "C" int tr1_logp_entropy_fwd(const void* logits, int64_t ld, const void* targets, void* logp, void* entropy, void* lse, int64_t R,
                                     int64_t V, void* stream) {
     TR1_CHECK_ARG(ld % 8 == 0, "logp_entropy: ld must be a multiple of 8");

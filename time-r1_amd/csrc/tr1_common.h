@@ -50,6 +50,18 @@ TR1_DEV float wave_max(float v) {
     v = fmaxf(v, tr1_row_ror<8>(v)); v = fmaxf(v, tr1_row_ror<4>(v)); v = fmaxf(v, tr1_row_ror<2>(v)); v = fmaxf(v, tr1_row_ror<1>(v));
     return v;
 }
+// (value, index) pairs through the same exchanges: the larger value wins, equal values keep the LOWER index (torch.argmax made deterministic).  The index
+// travels as raw bits (the swaps and rotations move registers, no float arithmetic touches it).  Every lane ends with the wave's pair.
+TR1_DEV void tr1_argmax_pick(float& v, int& i, float pv, int pi) { if (pv > v || (pv == v && pi < i)) { v = pv; i = pi; } }
+TR1_DEV void wave_argmax(float& v, int& i) {
+    float a, b, ia, ib;
+    tr1_halves32(v, a, b); tr1_halves32(__int_as_float(i), ia, ib); v = a; i = __float_as_int(ia); tr1_argmax_pick(v, i, b, __float_as_int(ib));
+    tr1_halves16(v, a, b); tr1_halves16(__int_as_float(i), ia, ib); v = a; i = __float_as_int(ia); tr1_argmax_pick(v, i, b, __float_as_int(ib));
+    tr1_argmax_pick(v, i, tr1_row_ror<8>(v), __float_as_int(tr1_row_ror<8>(__int_as_float(i))));
+    tr1_argmax_pick(v, i, tr1_row_ror<4>(v), __float_as_int(tr1_row_ror<4>(__int_as_float(i))));
+    tr1_argmax_pick(v, i, tr1_row_ror<2>(v), __float_as_int(tr1_row_ror<2>(__int_as_float(i))));
+    tr1_argmax_pick(v, i, tr1_row_ror<1>(v), __float_as_int(tr1_row_ror<1>(__int_as_float(i))));
+}
 
 // block-wide sum for blockDim.x <= 1024 (multiple of 64); red must hold >= 16 floats
 TR1_DEV float block_sum(float v, float* red) {

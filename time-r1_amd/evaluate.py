@@ -39,25 +39,70 @@ def grounding_metrics(ious, thresholds=(0.3, 0.5, 0.7)):
     return out
 
 
-def evaluate_grounding(trainer, dataset, max_new_tokens=None, limit=None):
-    """Greedy-decodes one completion per row with the trainer's engine and scores it. Returns (metrics, per-row records)."""
+def _prepare_row(trainer, core, row):
+    video_inputs, fps_inputs = trainer._video_inputs(row)
+    conv = trainer.make_conversation_video(row)
+    text = trainer.processing_class.apply_chat_template(conv, tokenize=False, add_generation_prompt=True)
+    pi = trainer.processing_class(text=[text], images=None, videos=[video_inputs[0]], fps=[fps_inputs[0]], padding=True, return_tensors="pt",
+                                  padding_side="left", add_special_tokens=False)
+    return core.prepare(np.asarray(pi["input_ids"]).reshape(-1), pi["pixel_values_videos"], np.asarray(pi["video_grid_thw"]))
+
+
+def _score_row(trainer, row, toks):
+    completion = trainer.processing_class.batch_decode(toks, skip_special_tokens=True)[0]
+    iou = compute_iou(extract_answer_span(completion), row["solution"])
+    return {"problem": row["problem"], "solution": list(row["solution"]), "completion": completion, "iou": iou}
+
+
+def evaluate_grounding(trainer, dataset, max_new_tokens=None, limit=None, batch_size=None, rank=0, world=1):
+    """Greedy-decodes one completion per row with the trainer's engine and scores it. Returns (metrics, per-row records).
+
+    batch_size=None: one row at a time through the top_k = 1 sampler, every decode step enqueued.
+    batch_size in [1, 64]: rows rank, rank + world, ... of the first `limit` rows (the reference's --curr_idx / --total_idx sharding, evaluate.py:44-45),
+    `batch_size` prompts decoded together (one row each, the last batch may be short) on a greedy core: argmax tokens from one launch per step, and the decode
+    loop ends soon after every row of the batch has produced EOS (rollout.Rollout).  Records stay in dataset order and also carry "index" (the dataset
+    index).  world > 1: returns (None, this rank's records); gather_evaluation() completes them on every rank."""
     from .grpo import GRPOCore
     a = trainer.args
-    core = GRPOCore(trainer.engine, None, 1, max_new_tokens or trainer.max_completion_length, beta=0.0, temperature=1.0, top_k=1, seed=0,
-                    rope_index_mode=a.rope_index_mode, stop_at_eos=True, reuse_prefill=False)
-    records, ious = [], []
     n = len(dataset) if limit is None else min(limit, len(dataset))
+    C = max_new_tokens or trainer.max_completion_length
+    if batch_size is not None:
+        if isinstance(batch_size, bool) or int(batch_size) != batch_size or not 1 <= int(batch_size) <= 64:
+            raise ValueError("batch_size must be None or an integer in [1, 64] (the decode step holds at most 64 rows), got %r" % (batch_size,))
+        if not 0 <= int(rank) < int(world):
+            raise ValueError("need 0 <= rank < world, got rank %r, world %r" % (rank, world))
+        core = GRPOCore(trainer.engine, None, 1, C, beta=0.0, temperature=1.0, top_k=1, seed=0, rope_index_mode=a.rope_index_mode, stop_at_eos=True,
+                        reuse_prefill=False, greedy=True)
+        mine = list(range(int(rank), n, int(world)))
+        records = []
+        for k in range(0, len(mine), int(batch_size)):
+            idx = mine[k:k + int(batch_size)]
+            rows = [dataset[i] for i in idx]
+            toks = core.rollout_many([_prepare_row(trainer, core, row) for row in rows])
+            for i, row, t in zip(idx, rows, toks):
+                rec = _score_row(trainer, row, t.cpu())
+                rec["index"] = i
+                records.append(rec)
+        if int(world) > 1:
+            return None, records
+        return grounding_metrics([r["iou"] for r in records]), records
+    core = GRPOCore(trainer.engine, None, 1, C, beta=0.0, temperature=1.0, top_k=1, seed=0,
+                    rope_index_mode=a.rope_index_mode, stop_at_eos=True, reuse_prefill=False)
+    records = []
     for i in range(n):
         row = dataset[i]
-        video_inputs, fps_inputs = trainer._video_inputs(row)
-        conv = trainer.make_conversation_video(row)
-        text = trainer.processing_class.apply_chat_template(conv, tokenize=False, add_generation_prompt=True)
-        pi = trainer.processing_class(text=[text], images=None, videos=[video_inputs[0]], fps=[fps_inputs[0]], padding=True, return_tensors="pt",
-                                      padding_side="left", add_special_tokens=False)
-        st = core.prepare(np.asarray(pi["input_ids"]).reshape(-1), pi["pixel_values_videos"], np.asarray(pi["video_grid_thw"]))
-        toks = core.rollout(st).cpu()
-        completion = trainer.processing_class.batch_decode(toks, skip_special_tokens=True)[0]
-        iou = compute_iou(extract_answer_span(completion), row["solution"])
-        ious.append(iou)
-        records.append({"problem": row["problem"], "solution": list(row["solution"]), "completion": completion, "iou": iou})
-    return grounding_metrics(ious), records
+        toks = core.rollout(_prepare_row(trainer, core, row)).cpu()
+        records.append(_score_row(trainer, row, toks))
+    return grounding_metrics([r["iou"] for r in records]), records
+
+
+def gather_evaluation(records):
+    """This rank's records of evaluate_grounding(..., rank, world) -> (metrics, all records sorted by "index") on EVERY rank
+    (torch.distributed.all_gather_object; a single process gets its own records back)."""
+    import torch.distributed as dist
+    if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+        parts = [None] * dist.get_world_size()
+        dist.all_gather_object(parts, records)
+        records = [r for p in parts for r in p]
+    records = sorted(records, key=lambda r: r["index"])
+    return grounding_metrics([r["iou"] for r in records]), records

@@ -771,6 +771,21 @@ class HipOps:
                     int(group_rows), int(seed_stride) & (2**64 - 1), _p(step_dev), _p(tokens), tokens.stride(0), _p(finished), int(eos_id), int(pad_id), int(bool(stop_at_eos)), _p(u_out),
                     _p(ws), nws, self._s())
 
+    def greedy_tokens(self, logits, step_dev, tokens, finished, eos_id, pad_id, next_ids=None, done_count=None):
+        """tokens[r, *step_dev] = lowest index among the maxima of logits[r] (pad_id for rows already finished); a row that selects eos_id is marked
+        finished and counted in done_count (int32 [1], zeroed by the caller once per generate call).  One launch, no workspace."""
+        self._chk(logits)
+        assert logits.dim() == 2 and logits.stride(1) == 1, "greedy_tokens: [rows, V] with unit column stride"
+        rows, V = logits.shape
+        assert rows <= 1 or logits.stride(0) >= V, "greedy_tokens: rows must not overlap"      # (stride 0 = one row shown to several: use it with rows == 1 only)
+        assert tokens.dtype == I32 and tokens.dim() == 2 and tokens.stride(1) == 1 and tokens.shape[0] == rows
+        assert finished.dtype == I32 and finished.numel() == rows and finished.is_contiguous()
+        assert step_dev is None or step_dev.dtype == I32
+        assert next_ids is None or (next_ids.dtype == I32 and next_ids.numel() == rows and next_ids.is_contiguous())
+        assert done_count is None or (done_count.dtype == I32 and done_count.numel() == 1)
+        self.L.call("tr1_greedy_tokens_step", _p(logits), max(int(logits.stride(0)), V), rows, V, _p(step_dev), _p(tokens), tokens.stride(0), _p(finished),
+                    int(eos_id), int(pad_id), _p(next_ids), _p(done_count), self._s())
+
     # ---- optimizer ------------------------------------------------------------------------------------------------
     def sumsq_accum(self, g, out_scalar):
         assert g.dtype in (F32, BF16) and out_scalar.dtype == F32

@@ -32,10 +32,22 @@ class KVCache:
 
 
 class Rollout:
-    def __init__(self, engine, num_generations, max_completion_length, temperature=1.0, top_k=50, seed=1234, stop_at_eos=False):
+    """greedy=True (evaluation / sample filtering, the reference's SamplingParams(temperature=0) at src/vllm_inference/vllm_infer.py:80-113): every token is
+    the lowest index among its row's maxima (ops.greedy_tokens, one launch per step; a backend without that op keeps the top_k = 1 sampler), rows stop at
+    EOS and the decode loop stops early: every `poll_every` steps the count of finished rows is copied to pinned host memory behind an event, and before a
+    step is enqueued the host reads only a copy recorded at least `poll_every` steps earlier - it never waits on the step it has just enqueued, the queue
+    never drains, and no per-step .item() / synchronize() exists.  Up to 2 * poll_every padding-only steps may therefore run after the last row has
+    finished; the result equals running all C - 1 steps, because finished rows only ever receive pad_token_id (tokens start as pad_token_id in this mode).
+    poll_every=0 switches the early stop off.  last_steps_run = decode steps enqueued by the last call.  greedy=False: nothing of this is executed."""
+
+    def __init__(self, engine, num_generations, max_completion_length, temperature=1.0, top_k=50, seed=1234, stop_at_eos=False, greedy=False, poll_every=8):
         self.eng = engine
         self.G, self.C = int(num_generations), int(max_completion_length)
         self.temperature, self.top_k, self.seed, self.stop_at_eos = float(temperature), int(top_k or 0), int(seed), bool(stop_at_eos)
+        self.greedy, self.poll_every = bool(greedy), int(poll_every or 0)
+        if self.greedy:
+            self.top_k, self.stop_at_eos = 1, True
+        self.last_steps_run = 0
         self._cache = None
         self.calls = 0
         self.force_nsplit = 0         # > 0: fixed split count of the decode attention (A/B runs)
@@ -53,6 +65,10 @@ class Rollout:
     def _kv(self, B, s_cap):
         t = self.eng.cfg.text
         c = self._cache
+        if self.greedy:      # evaluation: every batch has other prompt lengths - round the capacity up and keep a cache that is large enough
+            s_cap = (s_cap + 511) // 512 * 512
+            if c is not None and c.B == B and c.s_cap >= s_cap:
+                return c
         if c is None or c.s_cap != s_cap or c.B != B:
             self._cache = None      # release before re-allocating
             c = self._cache = KVCache(self.eng.ops, t.n_layers, t.kv_dim, s_cap, B)
@@ -114,8 +130,11 @@ class Rollout:
         scale = hd ** -0.5
         w_lm = eng.params.lm_head_w(arena)
         steps = ops.tensor(np.arange(C, dtype=np.int32), I32)
-        tokens_all = ops.zeros(B * G, C, dtype=I32)
+        greedy = self.greedy
+        greedy_op = greedy and hasattr(ops, "greedy_tokens")      # (a backend without the op: the top_k = 1 sampler, as before)
+        tokens_all = torch.full((B * G, C), int(cfg.pad_token_id), dtype=I32, device=steps.device) if greedy else ops.zeros(B * G, C, dtype=I32)
         finished_all = ops.zeros(B * G, dtype=I32)
+        done_count = ops.zeros(1, dtype=I32) if greedy_op else None      # rows that selected EOS; zeroed here, once per call
         slogp_all = ops.zeros(B * G, C, dtype=torch.float32) if self.track_logp else None
         per = []
         cos_rows, sin_rows = [], []
@@ -142,8 +161,12 @@ class Rollout:
             logits = ops.gemm_nt(hn, w_lm)  # [1, V]
             tokens = tokens_all[b * G:(b + 1) * G]
             finished = finished_all[b * G:(b + 1) * G]
-            ops.sample_tokens(logits.expand(G, logits.shape[1]), self.temperature, self.top_k, seed, steps[0:1], tokens, finished,
-                              cfg.eos_token_id, cfg.pad_token_id, self.stop_at_eos)
+            if greedy_op:
+                ops.greedy_tokens(logits if G == 1 else logits.expand(G, logits.shape[1]).contiguous(), steps[0:1], tokens, finished, cfg.eos_token_id,
+                                  cfg.pad_token_id, done_count=done_count)
+            else:
+                ops.sample_tokens(logits.expand(G, logits.shape[1]), self.temperature, self.top_k, seed, steps[0:1], tokens, finished,
+                                  cfg.eos_token_id, cfg.pad_token_id, self.stop_at_eos)
             if slogp_all is not None:      # (the first token is drawn from the bf16 prefill's logits in every mode)
                 slogp_all[b * G:(b + 1) * G, 0] = ops.logp_entropy_fwd(logits.expand(G, logits.shape[1]).contiguous(), tokens[:, 0].contiguous())[0]
             # ---- per-step tables (positions, slots, masks) built once
@@ -203,15 +226,40 @@ class Rollout:
             ev0 = torch.cuda.Event(enable_timing=True)
             ev0.record()
         host_plan = ops.attn_plan(G, t.n_heads, t.n_kv_heads, B) if (not native and fused and hasattr(ops, "attn_plan")) else None
+        pe = self.poll_every if greedy else 0
+        polls = []          # (decode steps enqueued when the copy was recorded, slot in host_counts, event or None)
+        if pe > 0:
+            on_dev = steps.device.type == "cuda"
+            host_counts = torch.zeros((C - 1) // pe + 1, dtype=I32, pin_memory=on_dev)
+        self.last_steps_run = 0
         for s in range(C - 1):
+            if pe > 0:
+                if polls and s - polls[0][0] >= pe:          # a copy recorded >= poll_every steps ago: waiting for it leaves >= poll_every steps queued
+                    _, slot, ev = polls.pop(0)
+                    if ev is not None:
+                        ev.synchronize()
+                    if int(host_counts[slot]) >= R:
+                        break
+                if s > 0 and s % pe == 0:
+                    slot = s // pe
+                    host_counts[slot:slot + 1].copy_(done_count if greedy_op else finished_all.sum(dtype=I32).reshape(1), non_blocking=True)
+                    ev = None
+                    if on_dev:
+                        ev = torch.cuda.Event()
+                        ev.record()
+                    polls.append((s, slot, ev))
+            self.last_steps_run = s + 1
             if native:
                 if s == 0:
                     ids_buf.copy_(tokens_all[:, 0])          # later steps: the sampler wrote the drawn tokens into ids_buf itself (next_ids)
                 logits = ops.decode_step(plan, embed_p, norm_p, lm_p, ids_p, cos_p + s * R * half * 4, sin_p + s * R * half * 4, slot_p + s * R * 4,
                                          pre_p, lo_p, hi_p + s * R * 4, t.rms_eps, scale)
-                # all prompts of the window in ONE sampler launch set; every prompt keeps its own Philox stream (seed_b = seed_0 + 7919 b)
-                ops.sample_tokens(logits, self.temperature, self.top_k, per[0]["seed"], steps[s + 1:s + 2], tokens_all, finished_all, cfg.eos_token_id,
-                                  cfg.pad_token_id, self.stop_at_eos, group_rows=G, seed_stride=7919, next_ids=ids_buf)
+                if greedy_op:
+                    ops.greedy_tokens(logits, steps[s + 1:s + 2], tokens_all, finished_all, cfg.eos_token_id, cfg.pad_token_id, next_ids=ids_buf, done_count=done_count)
+                else:
+                    # all prompts of the window in ONE sampler launch set; every prompt keeps its own Philox stream (seed_b = seed_0 + 7919 b)
+                    ops.sample_tokens(logits, self.temperature, self.top_k, per[0]["seed"], steps[s + 1:s + 2], tokens_all, finished_all, cfg.eos_token_id,
+                                      cfg.pad_token_id, self.stop_at_eos, group_rows=G, seed_stride=7919, next_ids=ids_buf)
                 if slogp_all is not None:
                     slogp_all[:, s + 1] = ops.logp_entropy_fwd(logits, tokens_all[:, s + 1].contiguous())[0]
                 continue
@@ -264,7 +312,9 @@ class Rollout:
             else:
                 hn, _, _ = ops.rmsnorm_fwd(h, arena.w("norm"), t.rms_eps, need_rstd=False)
                 logits = ops.gemm_nt(hn, w_lm)
-            for b, st in enumerate(per):
+            if greedy_op:
+                ops.greedy_tokens(logits, steps[s + 1:s + 2], tokens_all, finished_all, cfg.eos_token_id, cfg.pad_token_id, done_count=done_count)
+            for b, st in enumerate(() if greedy_op else per):
                 ops.sample_tokens(logits[b * G:(b + 1) * G], self.temperature, self.top_k, st["seed"], steps[s + 1:s + 2], st["tokens"],
                                   st["finished"], cfg.eos_token_id, cfg.pad_token_id, self.stop_at_eos)
             if slogp_all is not None:

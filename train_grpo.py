@@ -70,6 +70,8 @@ def main():
     ap.add_argument("--filter_task", default="0070_all", choices=["0070_all", "gaussian_03", "random_sample"])
     ap.add_argument("--filter_k", type=int, default=2500)
     ap.add_argument("--filter_max_new_tokens", type=int, default=1024)
+    ap.add_argument("--filter_batch_size", type=int, default=16, help="prompts decoded together by the filter stage, 1..64 (batched greedy decoding with "
+                    "early stop, the queries sharded over all ranks); 0 = one row at a time through the top_k=1 sampler on rank 0")
     ns, _unknown = ap.parse_known_args()      # unknown reference flags (--fp16 ...) are ignored on purpose
     init_from_env("cuda")
     set_global_seed(42)
@@ -94,17 +96,23 @@ def main():
     else:
         trainer.train()
     trainer.save_model(args.output_dir)
-    if ns.filter_split and trainer.state.is_world_process_zero:
+    bs = int(ns.filter_batch_size)
+    if ns.filter_split and (bs > 0 or trainer.state.is_world_process_zero):
         from time_r1_amd import filtering
-        from time_r1_amd.evaluate import evaluate_grounding
+        from time_r1_amd.evaluate import evaluate_grounding, gather_evaluation
         from time_r1_amd.data import _clean_sentence
         items = filtering.load_filter_split(ns.filter_split)
         rows = [{"task_type": "tg", "problem": _clean_sentence(it["sentence"]), "choices": "", "solution": (float(it["timestamp"][0]), float(it["timestamp"][1])),
                  "video_path": it["video"], "durations": it["duration"], "video_start": it["video_start"], "video_end": it["video_end"],
                  "preprocessed_path": ""} for it in items]
-        _, records = evaluate_grounding(trainer, rows, max_new_tokens=ns.filter_max_new_tokens)
-        shares, path = filtering.filter_epoch(items, records, ns.filter_output_dir or os.path.join(args.output_dir, "filtering"), ns.filter_task, ns.filter_k)
-        print("filtering: share of samples with tIoU > 0.3 / 0.5 / 0.7 = %s; next training set: %s" % (shares, path))
+        if bs > 0:      # every rank answers its stride of the queries (reference: --curr_idx i --total_idx num_gpus), then all ranks hold all records
+            _, records = evaluate_grounding(trainer, rows, max_new_tokens=ns.filter_max_new_tokens, batch_size=bs, rank=trainer.dp.rank, world=trainer.dp.world)
+            _, records = gather_evaluation(records)
+        else:
+            _, records = evaluate_grounding(trainer, rows, max_new_tokens=ns.filter_max_new_tokens)
+        if trainer.state.is_world_process_zero:
+            shares, path = filtering.filter_epoch(items, records, ns.filter_output_dir or os.path.join(args.output_dir, "filtering"), ns.filter_task, ns.filter_k)
+            print("filtering: share of samples with tIoU > 0.3 / 0.5 / 0.7 = %s; next training set: %s" % (shares, path))
 
 
 if __name__ == "__main__":
