@@ -144,6 +144,8 @@ TR1_DEV void philox4x32_10(unsigned c[4], unsigned k0, unsigned k1) {
 }
 // 16-bit order-preserving key of a bf16 logit (temperature > 0 does not change the order, so top-k is selected on raw logits)
 TR1_DEV unsigned bfkey(bf16_t b) { return (b & 0x8000u) ? ((~(unsigned)b) & 0xffffu) : ((unsigned)b | 0x8000u); }
+// +0.0 and -0.0 compare equal as floats, so a k-th value of +0.0 ties with every -0.0 (HF's warper keeps both); -0.0 holds the next lower key
+TR1_DEV unsigned samp_zero_tie(unsigned thr) { return thr == 0x8000u ? 0x7fffu : thr; }
 TR1_DEV float key_logit(unsigned k) { const unsigned b = (k & 0x8000u) ? (k & 0x7fffu) : ((~k) & 0xffffu); return bf2f((bf16_t)b); }
 
 // Multi-block sampler.  The vocabulary row (152k bf16 logits, L2 resident) is cut into SAMP_S slices, one 256-thread block each:
@@ -241,7 +243,7 @@ TR1_DEV unsigned samp_threshold(const SampleArgs& a, const unsigned* ws) {   // 
     int bin, rem, lo, rem2;
     samp_find_bin(ws, a.top_k, bin, rem);
     samp_find_bin(ws + 256, rem, lo, rem2);
-    return ((unsigned)bin << 8) | (unsigned)lo;
+    return samp_zero_tie(((unsigned)bin << 8) | (unsigned)lo);
 }
 
 __global__ __launch_bounds__(256) void samp_slice_sum_kernel(SampleArgs a) {
@@ -341,7 +343,7 @@ __global__ __launch_bounds__(1024) void samp_sum_pick_kernel(SampleArgs a) {
     else {
         samp_find_bin_par(shist, a.top_k, scr, &sbin, &srem);
         samp_find_bin_par(shist + 256, srem, scr, &slo, &srem2);
-        if (tid == 0) sthr = ((unsigned)sbin << 8) | (unsigned)slo;
+        if (tid == 0) sthr = samp_zero_tie(((unsigned)sbin << 8) | (unsigned)slo);
         __syncthreads();
     }
     const unsigned thr = sthr;
