@@ -57,7 +57,7 @@ class GRPOCore:
         G, C = self.G, self.C
         kv = sum(sum(P + G * s for s in range(1, C)) for P in states) * t.kv_dim * 2 * 2.0 * t.n_layers   # prefix once per prompt + every group's suffix
         self.work["decode_bytes"] += (C - 1) * w_bytes + kv
-        for e0, e1 in getattr(self.roll, "decode_events", []):
+        for e0, e1 in self.roll.decode_events:
             e1.synchronize()
             self.work["decode_ms_events"] += e0.elapsed_time(e1)
         self.roll.decode_events = []

@@ -9,7 +9,6 @@ Reference call sites restated here (transformers/models/qwen2_vl/modeling_qwen2_
   decoder layer  :559-624; attention :501-556; MLP :459-466; final norm :839; lm_head :1323; video scatter :1170-1176
 and the logprob stage of src/time_r1/rl/timer1_trainer.py:449-481.
 """
-import os
 
 import numpy as np
 import torch
@@ -26,16 +25,9 @@ class Engine:
     def __init__(self, cfg: ModelConfig, ops, params: ModelParams):
         self.cfg, self.ops, self.params = cfg, ops, params
         self.overlap_wgrad = True      # weight gradients on a second HIP stream (attribute for A/B runs; measured equal in rounds 4-5: the backward is a serial sum)
-        # weight gradients that stay on the MAIN stream (d = down, g = gate/up, o, q = qkv); the rest runs on the side stream beside the dgrad
-        # chain.  With the dgrad reading the weights as stored (NN form) the main stream has slack: keeping the down projection's weight
-        # gradient there balanced the two streams best on MI355X (backward 175 ms against 180 with everything on the side stream; with the main
-        # chain on a high-priority stream: "d" 161, "" 164, "dq" 161, "o" / "dg" 174 ms).  TR1_WGRAD_MAIN overrides for A/B runs.
-        self.wgrad_on_main = os.environ.get("TR1_WGRAD_MAIN", "d")
         self.wgrad_overwrite_first = True    # see _wgrad: relies on the optimizer zeroing the gradient arena and bumping arena.version (AdamWFlat.step)
         self._gw_ver = {}
         self.lazy_zero_active = False        # set by the owner of the optimizer when AdamWFlat.lazy_zero is in force (see _wgrad)
-        self.fused_head = True    # lm_head -> logp / entropy in the GEMM epilogue where the logits are not kept
-        self.wgrad_nn = True      # weight gradients read the saved activation as stored (attribute for A/B runs)
         self._side = None
         # set (by the owner of the optimizer) for the backward of a window's LAST micro-step: the weight-gradient epilogues of the decoder layers' large
         # matrices then also leave the squared norm of the final gradient (AdamWFlat.norm_sink_begin / step)
@@ -64,7 +56,7 @@ class Engine:
         sink = self.norm_sink
         if sink is not None and key is not None and key.split(".", 1)[-1] in self.OVERWRITTEN and hasattr(ops, "wgrad_sumsq"):
             # last micro-step of the window: same GEMM, and its epilogue also leaves the sum of squares of the FINAL gradient values it stores
-            kmaj = self.wgrad_nn and x.shape[1] >= 2 * dy.shape[1]
+            kmaj = x.shape[1] >= 2 * dy.shape[1]
             sync = sink.get("sync")
             off = self.params.train.offsets[key][0]
             wire = sync.wire_view(off, gw.shape) if sync is not None else None      # data-parallel: the exchange's bf16 copy comes out of this epilogue too
@@ -80,7 +72,7 @@ class Engine:
         # shape), so it only pays where the saved transpose is the larger piece: x at least twice as wide as dy (the down projection,
         # x = the 18944-column SwiGLU output: 735 -> 650 us per layer; gate/up, o, qkv and the lm_head stay on the transposed copy).
         nn = getattr(ops, "wgrad_nn", None)
-        if nn is not None and self.wgrad_nn and x.shape[1] >= 2 * dy.shape[1] and nn(dyt, x, gw, acc):
+        if nn is not None and x.shape[1] >= 2 * dy.shape[1] and nn(dyt, x, gw, acc):
             return
         ops.gemm_nt(dyt, ops.transpose(x), out_f32=True, out=gw, accumulate=acc)
 
@@ -589,18 +581,20 @@ class Engine:
                 L = dict(L)
                 for key in ("a", "gu", "xn2", "h2", "rstd2", "o"):
                     L[key] = Lf[key][t0:]
-            # h_out = a @ Wd^T + h2
-            _sync = self.wgrad_on_main
+            # h_out = a @ Wd^T + h2.  The down projection's weight gradient stays on the MAIN stream, the other three run on the side stream beside the
+            # dgrad chain: with the dgrad reading the weights as stored (NN form) the main stream has slack, and this placement balanced the two streams
+            # best on MI355X (backward 175 ms against 180 with everything on the side stream; with the main chain on a high-priority stream: down 161,
+            # none 164, down + qkv 161, o or down + gate/up 174 ms).  With a_shared it has to be there: its operand is rebuilt on the main stream
             if a_shared:                  # one SwiGLU-output buffer for all layers (alloc_ctx_bufs): rebuild this layer's rows from its gate/up tensor, main stream
                 ops.swiglu_fwd(L["gu"], out=L["a"])
-            self._wgrad_async(dh, L["a"], tr.g(p + "down.w"), None if ("d" in _sync or a_shared) else side, key=p + "down.w")
+            self._wgrad_async(dh, L["a"], tr.g(p + "down.w"), None, key=p + "down.w")
             # down-projection dgrad with the SwiGLU backward in its epilogue, which also leaves dgu^T (the gate/up weight gradient's operand) from its LDS staging
             dgu, dgut = ops.dgrad_glu_bwd(dh, tr.w(p + "down.w"), L["gu"], want_t=True)
-            self._wgrad_async(dgu, L["xn2"], tr.g(p + "gu.w"), None if "g" in _sync else side, key=p + "gu.w", dyt=dgut)
+            self._wgrad_async(dgu, L["xn2"], tr.g(p + "gu.w"), side, key=p + "gu.w", dyt=dgut)
             dxn2 = self._dgrad(dgu, tr.w(p + "gu.w"), key=p + "gu.w")
             dh2 = ops.rmsnorm_bwd(dxn2, L["h2"], tr.w(p + "ln2"), L["rstd2"], dres=dh, dw=tr.g(p + "ln2"))
             # h2 = o @ Wo^T + h
-            self._wgrad_async(dh2, L["o"], tr.g(p + "o.w"), None if "o" in _sync else side, key=p + "o.w")
+            self._wgrad_async(dh2, L["o"], tr.g(p + "o.w"), side, key=p + "o.w")
             do = self._dgrad(dh2, tr.w(p + "o.w"), key=p + "o.w")
             if tail:                                  # back to all rows for the attention backward (every row's K / V took part): zero gradient above the tail
                 L = Lf
@@ -611,7 +605,7 @@ class Engine:
             # kernels' epilogues); the bias gradient is summed by the transpose that feeds the weight gradient
             ops.attn_bwd(L["q"], L["k"], L["v"], L["o"], do, L["lse"], pre, lo, hi, t.n_heads, t.n_kv_heads, M, hd, scale,
                          dq_out=dqkv[:, :qd], dk_out=dqkv[:, qd:qd + kvd], dv_out=dqkv[:, qd + kvd:], rope=(cos, sin))
-            self._wgrad_async(dqkv, L["xn"], tr.g(p + "qkv.w"), None if "q" in _sync else side, key=p + "qkv.w", bias_g=tr.g(p + "qkv.b"))
+            self._wgrad_async(dqkv, L["xn"], tr.g(p + "qkv.w"), side, key=p + "qkv.w", bias_g=tr.g(p + "qkv.b"))
             dxn = self._dgrad(dqkv, tr.w(p + "qkv.w"), key=p + "qkv.w")
             dh = ops.rmsnorm_bwd(dxn, L["h"], tr.w(p + "ln1"), L["rstd1"], dres=dh2, dw=tr.g(p + "ln1"))
             ctx["layers"][i] = None  # release this layer's activations
@@ -655,7 +649,7 @@ class Engine:
         w = self.params.lm_head_w(arena)
         R, ch = hp.shape[0], self.HEAD_CHUNK_ROWS
         fused = None
-        if (not save or R > ch) and self.fused_head and hasattr(ops, "lmhead_lse"):
+        if (not save or R > ch) and hasattr(ops, "lmhead_lse"):
             # nobody reads these logits again (reference-policy forward; the large-R policy forward recomputes them chunk by chunk in the
             # backward): lm_head with the log-softmax statistics reduced in the GEMM epilogue - no [R, V] tensor in HBM at all
             fused = ops.lmhead_lse(hn, w, targets)

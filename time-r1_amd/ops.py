@@ -218,7 +218,7 @@ class HipOps:
     def vit_pad128_ok(self, n_heads, head_dim):
         """The vision tower can run on 128-wide zero-padded heads (fused q|k|v + rotary epilogue -> head-dim-128 attention kernel)."""
         half = head_dim // 2
-        return bool(self.FUSE_EPI and self.FWD32 and head_dim < 128 and head_dim % 16 == 0 and half <= 64 and (n_heads * half) % 128 == 0)
+        return bool(self.FUSE_EPI and head_dim < 128 and head_dim % 16 == 0 and half <= 64 and (n_heads * half) % 128 == 0)
 
     def gemm_qkv_rope_vit(self, x, w_qkv, bias, cos, sin, n_heads, half, q128, k128, v128):
         """Vision q|k|v projection + bias + rotary into 128-wide padded heads (pad columns of q128 / k128 / v128 must already be zero)."""
@@ -229,8 +229,6 @@ class HipOps:
         self.L.call("tr1_gemm_qkv_rope_vit_bf16", _p(x), _p(w_qkv), _p(bias), _p(cos), _p(sin), _p(q128), _ld(q128), _p(k128), _ld(k128), _p(v128), _ld(v128),
                     M, n_heads, half, K, _ld(x), _ld(w_qkv), self._s())
 
-    DGU_T = True        # dgu^T from the fused dgrad's epilogue instead of a transpose pass (class attribute for A/B runs)
-
     def dgrad_glu_bwd(self, dh, w_down, gu, want_t=False):
         """dgu[M, 2I] = swiglu_bwd(dh @ w_down, gu) with w_down [H, I] as stored (K-major operand).  want_t: -> (dgu, dgu^T or None); the fused kernel can
         write dgu^T [2I, Mp] (Mp = M rounded up to 64, padding zero: what transpose(dgu) returns) from its epilogue staging."""
@@ -240,7 +238,7 @@ class HipOps:
         if (self.FUSE_EPI and M >= 512 and I >= 256 and H % 64 == 0 and I % 8 == 0 and dh.stride(1) == 1 and w_down.stride(1) == 1 and gu.stride(1) == 1
                 and ((M + 255) // 256) * ((I + 255) // 256) >= 192):
             dgu = self.empty(M, 2 * I)
-            dgt = self.empty(2 * I, (M + 63) // 64 * 64) if (want_t and self.DGU_T) else None
+            dgt = self.empty(2 * I, (M + 63) // 64 * 64) if want_t else None
             self.L.call("tr1_gemm_nn_glubwd_bf16", _p(dh), _p(w_down), _p(gu), _p(dgu), M, I, H, _ld(dh), _ld(w_down), _ld(gu), _ld(dgu),
                         _p(dgt), _ld(dgt) if dgt is not None else 0, self._s())
             return (dgu, dgt) if want_t else dgu
@@ -296,7 +294,7 @@ class HipOps:
         N = q.shape[0] // 2 if glu else q.shape[0]
         assert q.dtype == torch.uint8 and q.shape[1] == K and x.stride(1) == 1 and q.stride(1) == 1 and scale.dtype == F32
         out = self.empty(M, N)
-        if a8 and lnw is None and not glu and M <= 16 and K >= 8192 and K % 512 == 0 and N % 64 == 0:     # same choice as csrc/decode.hip (bitwise-equal paths)
+        if a8 and lnw is None and not glu and M <= 16 and K >= 8192 and K % 512 == 0 and N % 64 == 0:
             n = int(self.L.raw("tr1_gemm_skinny_fixup_workspace_floats")(M, N, K))
             key = "skinny_fix8_%d_%d_%d" % (M, N, K)
             ws = self._ws.get(key)
@@ -605,8 +603,6 @@ class HipOps:
         """int32 buffer for attn_fwd(plan=..., plan_mode=1|2): the relevant-tile lists of one decode step, shared by its layers."""
         return self.zeros(self.L.raw("tr1_attn_plan_ints")(T, n_heads, n_kv, n_batch), dtype=I32)
 
-    FWD32 = True      # head dim 128, nsplit 1: the 32x32x16-MFMA forward over row-major K / V (class attribute: tests / tools may clear it)
-
     def attn_fwd(self, q, k, vt, pre, lo, hi, n_heads, n_kv, n_slots, head_dim, scale, nsplit=1, need_lse=True, out=None, n_batch=1,
                  kv_batch_slots=0, plan=None, plan_mode=0, v_rows=None, live96=False):
         """n_batch > 1: q/out/masks hold n_batch problems of T = rows/n_batch tokens each; problem b reads cache slots from b*kv_batch_slots.
@@ -647,7 +643,7 @@ class HipOps:
     def attn_fwd_rows_ok(self, head_dim, nsplit=1, n_batch=1, n_slots=0, ld=0):
         """True when attn_fwd(v_rows=...) would take the row-major K / V kernel (callers can then skip building V^T).  The kernel addresses
         K / V with 32-bit DMA offsets: operands of n_slots rows x ld elements must stay below 4 GiB (csrc/attn_fwd32.hip, tr1_attn_fwd_rows)."""
-        return self.FWD32 and head_dim == 128 and nsplit == 1 and n_batch == 1 and n_slots * ld * 2 < 0xffffffff
+        return head_dim == 128 and nsplit == 1 and n_batch == 1 and n_slots * ld * 2 < 0xffffffff
 
     def attn_bwd(self, q, k, v, o, do, lse, pre, lo, hi, n_heads, n_kv, n_slots, head_dim, scale, dv_out=None, dq_out=None, dk_out=None, rope=None):
         """-> dq [T, n_heads*hd], dk, dv [n_slots, n_kv*hd]. Builds the transposed operand copies it needs.
