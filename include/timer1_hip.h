@@ -260,6 +260,26 @@ int tr1_sample_tokens(const void* logits, int64_t ld, int64_t rows, int64_t V, f
  * kernel re-zeroes it), so neither a copy kernel nor a memset runs between two decode steps. */
 int tr1_sample_tokens_step(const void* logits, int64_t ld, int64_t rows, int64_t V, float temperature, int64_t top_k, uint64_t seed, int64_t group_rows, uint64_t seed_stride, const void* step_ptr, void* tokens, int64_t tok_ld, void* finished, int64_t eos_id, int64_t pad_id, int stop_at_eos, void* u_out, void* ws_u32, int64_t ws_words, void* next_ids, int ws_zeroed, void* stream);
 int64_t tr1_sample_workspace_words(int64_t rows);
+/* TF: TopPLogitsWarper and MinPLogitsWarper behind TemperatureLogitsWarper and TopKLogitsWarper (transformers generation/logits_process.py; the order of
+ * GenerationMixin._get_logits_processor), and SamplingParams(top_p=...) of ref: src/vllm_inference/vllm_infer.py:106-111.  The arguments of tr1_sample_tokens /
+ * tr1_sample_tokens_step plus 0 < top_p <= 1 (1 = off) and 0 <= min_p <= 1 (0 = off); workspace: tr1_sample_filtered_workspace_words(rows) words, 8-byte aligned.
+ * top-p keeps a logit value iff the softmax(x/T) mass (over the top-k set) of the strictly larger logits is < top_p: equal logits stand or fall together
+ * (deterministic where the warper's unstable sort is not; identical on rows without ties), the maximum always stays.  min-p keeps x iff
+ * exp((x - max)/T) >= min_p.  The kept set is the intersection of the three; the draw is the inverse CDF of tr1_sample_tokens with the same Philox stream.
+ * With top_p = 1 and min_p = 0 the launches and the tokens are those of tr1_sample_tokens / tr1_sample_tokens_step. */
+int tr1_sample_tokens_filtered(const void* logits, int64_t ld, int64_t rows, int64_t V, float temperature, int64_t top_k, float top_p, float min_p, uint64_t seed, int64_t group_rows, uint64_t seed_stride, const void* step_ptr, void* tokens, int64_t tok_ld, void* finished, int64_t eos_id, int64_t pad_id, int stop_at_eos, void* u_out, void* ws_u32, int64_t ws_words, void* stream);
+int tr1_sample_tokens_filtered_step(const void* logits, int64_t ld, int64_t rows, int64_t V, float temperature, int64_t top_k, float top_p, float min_p, uint64_t seed, int64_t group_rows, uint64_t seed_stride, const void* step_ptr, void* tokens, int64_t tok_ld, void* finished, int64_t eos_id, int64_t pad_id, int stop_at_eos, void* u_out, void* ws_u32, int64_t ws_words, void* next_ids, int ws_zeroed, void* stream);
+int64_t tr1_sample_filtered_workspace_words(int64_t rows);
+/* TF: RepetitionPenaltyLogitsProcessor (transformers generation/logits_process.py), SamplingParams(repetition_penalty=...) of ref:
+ * src/vllm_inference/vllm_infer.py:106-111.  out[r, v] = logits[r, v] where bit v of seen[r] is clear, else x * penalty (x < 0) or x / penalty, computed in
+ * fp32 with an IEEE division and rounded ONCE to nearest-even bf16 (the warper keeps fp32; the sampler's domain here is bf16).  seen: uint32 [rows, seen_ld],
+ * bit (v & 31) of word v >> 5.  ld may be 0 (one row shown to all).  out must not alias logits. */
+int tr1_penalize_logits(const void* logits, int64_t ld, void* out, int64_t out_ld, const void* seen, int64_t seen_ld, int64_t rows, int64_t V, float penalty, void* stream);
+/* The seen sets of the penalty (TF: RepetitionPenaltyLogitsProcessor gathers over input_ids = prompt + generated tokens): ids[n] (a prompt) into each of `rows`
+ * bitmap rows; and the token every row has just drawn, tokens[r*tok_ld + *step_ptr] (step_ptr null: offset 0), except rows with finished[r] != 0 (finished may
+ * be null), whose token is padding.  Ids outside [0, V) are ignored.  Marking twice changes nothing. */
+int tr1_mark_seen_ids(const void* ids, int64_t n, void* seen, int64_t seen_ld, int64_t rows, int64_t V, void* stream);
+int tr1_mark_seen_drawn(const void* tokens, int64_t tok_ld, const void* step_ptr, const void* finished, void* seen, int64_t seen_ld, int64_t rows, int64_t V, void* stream);
 /* ref: the greedy SamplingParams(temperature=0) of the evaluation / filtering decoder, src/vllm_inference/vllm_infer.py:80-113.  bf16 logits [rows, V], row
  * stride ld >= V, any V >= 1, any 2-byte-aligned pointer.  Row r with finished[r] != 0: pad_id goes to tokens[r*tok_ld + *step_ptr] and next_ids[r], no logit
  * is read.  Otherwise the token is the LOWEST index among the entries equal to the row maximum (compared as floats); it goes to tokens and next_ids, and when it

@@ -1,9 +1,9 @@
 // Vocabulary-side kernels of the GRPO step for gfx950: per-token log-prob + entropy over the lm_head logits (forward and
-// backward), the GRPO loss/gradient on [G, C] token grids, and the rollout sampler (temperature + top-k + inverse CDF, Philox).
+// backward), the GRPO loss/gradient on [G, C] token grids, and the rollout sampler (repetition penalty, temperature + top-k + top-p + min-p, inverse CDF, Philox).
 //
 // Reference semantics:
 //   logp / entropy : src/time_r1/rl/timer1_trainer.py:458-481  (log_softmax, gather, H = -sum p log p)
-//   KL (k3)        : :635-639        loss (both branches): :713-737       sampling: HF generate(do_sample, temperature, top_k)
+//   KL (k3)        : :635-639        loss (both branches): :713-737       sampling: HF generate(do_sample, temperature, top_k, top_p, min_p, repetition_penalty)
 #include "tr1_common.h"
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -156,12 +156,19 @@ TR1_DEV float key_logit(unsigned k) { const unsigned b = (k & 0x8000u) ? (k & 0x
 // Workspace per row (uint32 words): hist_hi[256] | hist_lo[256] | misc[8] (0: max key) | slice sums[SAMP_S] (float)
 #define SAMP_S 32
 #define SAMP_WS_WORDS (256 + 256 + 8 + SAMP_S)
+// top-p / min-p extension per row: mass_hi[256] | mass_lo[256] (64-bit fixed point, 2 words each) | misc[8] (0: final threshold key)
+#define SAMP_EXT_WORDS (512 + 512 + 8)
 
 struct SampleArgs {
     const bf16_t* logits; int64_t ld; int V; float inv_temp; int top_k; unsigned long long seed; int group_rows; unsigned long long seed_stride; const int* step_ptr; int* tokens; int64_t tok_ld;
     int* finished; int eos_id, pad_id, stop_at_eos; float* u_out; unsigned* ws;
     int* next_ids;      // optional [rows]: the drawn token once more, where the next decode step's embedding gather reads it (no copy kernel in between)
     int ws_clean;       // the caller zero-filled ws once: the fused pick kernel re-zeroes what the histogram kernels dirtied (no memset per call)
+};
+// The launches of the top-p / min-p path carry three more arguments; without those filters the kernels receive SampleArgs and run the code they always ran.
+struct SampleArgsF : SampleArgs {
+    unsigned* ext;      // SAMP_EXT_WORDS per row behind the rows' SAMP_WS_WORDS blocks; word 1024 = the final threshold key
+    float top_p, min_p;
 };
 
 TR1_DEV bool samp_row_done(const SampleArgs& a, int r) { return a.finished && a.stop_at_eos && a.finished[r]; }
@@ -238,7 +245,9 @@ __global__ __launch_bounds__(256) void samp_hist_lo_kernel(SampleArgs a) {
     if (h[threadIdx.x]) atomicAdd(&ws[256 + threadIdx.x], h[threadIdx.x]);
 }
 
-TR1_DEV unsigned samp_threshold(const SampleArgs& a, const unsigned* ws) {   // 16-bit key of the k-th largest logit (0 = keep all)
+// EXT (top-p / min-p): samp_filter_thr_kernel has folded all three filters into one key, word 1024 of the row's extension block
+template <bool EXT> TR1_DEV unsigned samp_threshold(const SampleArgs& a, const unsigned* ws, const unsigned* ext, int r) {   // 16-bit key of the k-th largest logit (0 = keep all)
+    if (EXT) return ext[(int64_t)r * SAMP_EXT_WORDS + 1024];
     if (a.top_k <= 0 || a.top_k >= a.V) return 0u;
     int bin, rem, lo, rem2;
     samp_find_bin(ws, a.top_k, bin, rem);
@@ -246,13 +255,13 @@ TR1_DEV unsigned samp_threshold(const SampleArgs& a, const unsigned* ws) {   // 
     return samp_zero_tie(((unsigned)bin << 8) | (unsigned)lo);
 }
 
-__global__ __launch_bounds__(256) void samp_slice_sum_kernel(SampleArgs a) {
+template <bool EXT> TR1_DEV void samp_slice_sum_body(const SampleArgs& a, unsigned* ext) {
     __shared__ float red[16];
     __shared__ unsigned sthr;
     const int r = blockIdx.y;
     if (samp_row_done(a, r)) return;
     unsigned* ws = a.ws + (int64_t)r * SAMP_WS_WORDS;
-    if (threadIdx.x == 0) sthr = samp_threshold(a, ws);
+    if (threadIdx.x == 0) sthr = samp_threshold<EXT>(a, ws, ext, r);
     __syncthreads();
     const unsigned thr = sthr;
     const float mx = key_logit(ws[512]);
@@ -263,8 +272,10 @@ __global__ __launch_bounds__(256) void samp_slice_sum_kernel(SampleArgs a) {
     acc = block_sum(acc, red);
     if (threadIdx.x == 0) reinterpret_cast<float*>(ws + 520)[blockIdx.x] = acc;
 }
+__global__ __launch_bounds__(256) void samp_slice_sum_kernel(SampleArgs a) { samp_slice_sum_body<false>(a, nullptr); }
+__global__ __launch_bounds__(256) void samp_slice_sum_ext_kernel(SampleArgsF a) { samp_slice_sum_body<true>(a, a.ext); }
 
-__global__ __launch_bounds__(256) void samp_pick_kernel(SampleArgs a) {
+template <bool EXT> TR1_DEV void samp_pick_body(const SampleArgs& a, unsigned* ext) {
     __shared__ float part[256];
     __shared__ unsigned sthr; __shared__ int sslice; __shared__ float sbase, starget;
     const int r = blockIdx.x, tid = threadIdx.x;
@@ -274,7 +285,7 @@ __global__ __launch_bounds__(256) void samp_pick_kernel(SampleArgs a) {
     unsigned* ws = a.ws + (int64_t)r * SAMP_WS_WORDS;
     const float* sums = reinterpret_cast<const float*>(ws + 520);
     if (tid == 0) {
-        sthr = samp_threshold(a, ws);
+        sthr = samp_threshold<EXT>(a, ws, ext, r);
         float Z = 0.f;
         for (int i = 0; i < SAMP_S; ++i) Z += sums[i];
         // several prompts in one launch: rows [b*group_rows, (b+1)*group_rows) use seed + b*seed_stride and their row index inside the group,
@@ -319,6 +330,8 @@ __global__ __launch_bounds__(256) void samp_pick_kernel(SampleArgs a) {
         if (a.finished && tok == a.eos_id) a.finished[r] = 1;
     }
 }
+__global__ __launch_bounds__(256) void samp_pick_kernel(SampleArgs a) { samp_pick_body<false>(a, nullptr); }
+__global__ __launch_bounds__(256) void samp_pick_ext_kernel(SampleArgsF a) { samp_pick_body<true>(a, a.ext); }
 
 // slice_sum + pick in ONE launch, one 1024-thread block per row (the separate pair cost 15 + 33 us per decode step, most of it the serial
 // walks of thread 0).  The 16 waves own contiguous segments of the row; a wave reads its segment coalesced (64 lanes x 16 bytes per
@@ -326,7 +339,7 @@ __global__ __launch_bounds__(256) void samp_pick_kernel(SampleArgs a) {
 // iteration -> lane) with one lane finally walking 8 logits.  Needs V % 8 == 0, ld % 8 == 0 and V <= SAMP_FUSED_MAXV.
 #define SAMP_MAXIT 20
 #define SAMP_FUSED_MAXV (16 * 64 * SAMP_MAXIT * 8)
-__global__ __launch_bounds__(1024) void samp_sum_pick_kernel(SampleArgs a) {
+template <bool EXT> TR1_DEV void samp_sum_pick_body(const SampleArgs& a, unsigned* ext) {
     __shared__ float wsum[16];
     __shared__ unsigned sthr; __shared__ int sseg; __shared__ float sbase, starget;
     const int r = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -339,7 +352,8 @@ __global__ __launch_bounds__(1024) void samp_sum_pick_kernel(SampleArgs a) {
     __shared__ int sbin, srem, slo, srem2;
     if (tid < 512) shist[tid] = ws[tid];
     __syncthreads();
-    if (a.top_k <= 0 || a.top_k >= a.V) { if (tid == 0) sthr = 0u; __syncthreads(); }
+    if (EXT) { if (tid == 0) sthr = ext[(int64_t)r * SAMP_EXT_WORDS + 1024]; __syncthreads(); }
+    else if (a.top_k <= 0 || a.top_k >= a.V) { if (tid == 0) sthr = 0u; __syncthreads(); }
     else {
         samp_find_bin_par(shist, a.top_k, scr, &sbin, &srem);
         samp_find_bin_par(shist + 256, srem, scr, &slo, &srem2);
@@ -395,6 +409,7 @@ __global__ __launch_bounds__(1024) void samp_sum_pick_kernel(SampleArgs a) {
     if (lane == 0) wsum[wave] = wtot;
     __syncthreads();
     if (a.ws_clean && tid < SAMP_WS_WORDS) ws[tid] = 0u;        // every thread has read the histograms and the row max: leave the row's workspace zero for the next call
+    if (EXT && a.ws_clean && tid == 0) ext[(int64_t)r * SAMP_EXT_WORDS + 1024] = 0u;      // (the threshold key was read before the barrier above)
     if (tid == 0) {
         float Z = 0.f;
         for (int w = 0; w < 16; ++w) Z += wsum[w];
@@ -443,6 +458,199 @@ __global__ __launch_bounds__(1024) void samp_sum_pick_kernel(SampleArgs a) {
     *tok_out = tok;
     if (a.next_ids) a.next_ids[r] = tok;
     if (a.finished && tok == a.eos_id) a.finished[r] = 1;
+}
+__global__ __launch_bounds__(1024) void samp_sum_pick_kernel(SampleArgs a) { samp_sum_pick_body<false>(a, nullptr); }
+__global__ __launch_bounds__(1024) void samp_sum_pick_ext_kernel(SampleArgsF a) { samp_sum_pick_body<true>(a, a.ext); }
+
+// ---- top-p / min-p: two more filters, folded with top-k into ONE threshold key --------------------------------------------------------------------
+// Order of HF generate: temperature, top-k, top-p, min-p.  K = the set top-k keeps (ties with the k-th value included; everything when top-k is off).
+//   top-p : masses softmax(x/T) over K; a value class v (all tokens of one logit value) is kept iff the mass of the tokens of K with x > v is < top_p.
+//           Equal logits stand or fall together (the rule top-k uses), the row maximum always stays; on rows without ties this is TopPLogitsWarper.
+//   min-p : keep x iff exp((x - max)/T) >= min_p - a ratio to the maximum, independent of the normalisation, so it intersects with the other two.
+// Each filter is "key >= some 16-bit key", so the kept set is key >= max of the three keys and the inverse-CDF kernels above run unchanged.
+// The masses that decide the top-p boundary are 64-bit fixed point (exp(..) * 2^40, truncated, integer atomics): the sums do not depend on the order
+// of the atomics, so the same row gives the same key on every run.  Z >= 2^40 (the maximum has mass 2^40), Z < 2^58 for any V < 2^18, and the
+// truncation is below V * 2^-40 of the mass.  Two levels like the count histograms: mass per high byte of the key over K, then per low byte inside
+// the bin that holds the boundary.  The float expression of a mass is the one the sum passes use.
+#define SAMP_MASS_SCALE 1099511627776.0f      // 2^40
+typedef unsigned long long samp_u64;
+TR1_DEV samp_u64 samp_mass(bf16_t b, float mx, float inv_temp) { return (samp_u64)(__expf((bf2f(b) - mx) * inv_temp) * SAMP_MASS_SCALE); }
+
+// top-k threshold key by a 256-thread block (the search of samp_sum_pick_kernel): shist 512, scr 8, si 4 words of LDS.  Block-uniform result.
+TR1_DEV unsigned samp_topk_thr_par(const SampleArgs& a, const unsigned* ws, unsigned* shist, unsigned* scr, int* si) {
+    if (a.top_k <= 0 || a.top_k >= a.V) return 0u;
+    shist[threadIdx.x] = ws[threadIdx.x]; shist[256 + threadIdx.x] = ws[256 + threadIdx.x];
+    __syncthreads();
+    samp_find_bin_par(shist, a.top_k, scr, &si[0], &si[1]);
+    samp_find_bin_par(shist + 256, si[1], scr, &si[2], &si[3]);
+    return samp_zero_tie(((unsigned)si[0] << 8) | (unsigned)si[2]);
+}
+
+// Boundary search over a 256-bin mass histogram by a 256-thread block, bins taken from the top: the LOWEST bin b with
+// (base + mass in bins > b) < top_p * Z.  Z = Zin, or the histogram's total when Zin == 0.  The condition holds for the top bin (the caller's
+// base satisfies it) and, once false, stays false, so exactly one thread writes.  The chosen bin is never empty: an empty bin has the same mass
+// above it as the bin below.  The comparison is in fp64 on integers: deterministic.
+TR1_DEV void samp_mass_find_par(const samp_u64* hist, samp_u64 base, samp_u64 Zin, float top_p, samp_u64* scr, int* bin_out, samp_u64* above_out,
+                                samp_u64* tot_out) {
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const samp_u64 val = hist[255 - tid];
+    samp_u64 incl = val;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) { const samp_u64 t = __shfl_up(incl, d, 64); if (lane >= d) incl += t; }
+    if (lane == 63) scr[w] = incl;
+    if (tid == 0) { *bin_out = 255; *above_out = base; }      // (only a row of NaNs leaves it at that)
+    __syncthreads();
+    samp_u64 off = base;
+    for (int j = 0; j < w; ++j) off += scr[j];
+    incl += off;
+    const samp_u64 excl = incl - val, tot = base + scr[0] + scr[1] + scr[2] + scr[3];
+    const double lim = (double)top_p * (double)(Zin ? Zin : tot);
+    if ((double)excl < lim && (tid == 255 || !((double)incl < lim))) { *bin_out = 255 - tid; *above_out = excl; }
+    if (tid == 0) *tot_out = tot;
+    __syncthreads();
+}
+
+__global__ __launch_bounds__(256) void samp_mass_hi_kernel(SampleArgsF a) {
+    __shared__ samp_u64 h[256];
+    __shared__ unsigned shist[512], scr[8];
+    __shared__ int si[4];
+    const int r = blockIdx.y;
+    if (samp_row_done(a, r)) return;
+    const unsigned* ws = a.ws + (int64_t)r * SAMP_WS_WORDS;
+    h[threadIdx.x] = 0ull;
+    const unsigned thr = samp_topk_thr_par(a, ws, shist, scr, si);
+    __syncthreads();
+    const float mx = key_logit(ws[512]);
+    const bf16_t* row = a.logits + (int64_t)r * a.ld;
+    const int per = (a.V + SAMP_S - 1) / SAMP_S, i0 = blockIdx.x * per, i1 = min(a.V, i0 + per);
+    for (int i = i0 + threadIdx.x; i < i1; i += 256) {
+        const bf16_t b = row[i]; const unsigned k = bfkey(b);
+        if (k >= thr) { const samp_u64 m = samp_mass(b, mx, a.inv_temp); if (m) atomicAdd(&h[k >> 8], m); }
+    }
+    __syncthreads();
+    samp_u64* mh = reinterpret_cast<samp_u64*>(a.ext + (int64_t)r * SAMP_EXT_WORDS);
+    if (h[threadIdx.x]) atomicAdd(&mh[threadIdx.x], h[threadIdx.x]);
+}
+
+__global__ __launch_bounds__(256) void samp_mass_lo_kernel(SampleArgsF a) {
+    __shared__ samp_u64 h[256], smh[256], scr64[4], sabove, stot;
+    __shared__ unsigned shist[512], scr[8];
+    __shared__ int si[4], sbin;
+    const int r = blockIdx.y;
+    if (samp_row_done(a, r)) return;
+    const unsigned* ws = a.ws + (int64_t)r * SAMP_WS_WORDS;
+    samp_u64* mh = reinterpret_cast<samp_u64*>(a.ext + (int64_t)r * SAMP_EXT_WORDS);
+    h[threadIdx.x] = 0ull;
+    smh[threadIdx.x] = mh[threadIdx.x];
+    const unsigned thr = samp_topk_thr_par(a, ws, shist, scr, si);
+    __syncthreads();
+    samp_mass_find_par(smh, 0ull, 0ull, a.top_p, scr64, &sbin, &sabove, &stot);
+    const unsigned bin = (unsigned)sbin;
+    const float mx = key_logit(ws[512]);
+    const bf16_t* row = a.logits + (int64_t)r * a.ld;
+    const int per = (a.V + SAMP_S - 1) / SAMP_S, i0 = blockIdx.x * per, i1 = min(a.V, i0 + per);
+    for (int i = i0 + threadIdx.x; i < i1; i += 256) {
+        const bf16_t b = row[i]; const unsigned k = bfkey(b);
+        if ((k >> 8) == bin && k >= thr) { const samp_u64 m = samp_mass(b, mx, a.inv_temp); if (m) atomicAdd(&h[k & 255u], m); }
+    }
+    __syncthreads();
+    if (h[threadIdx.x]) atomicAdd(&mh[256 + threadIdx.x], h[threadIdx.x]);
+}
+
+// One 256-thread block per row: the three keys and their maximum.  Leaves the mass histograms zero for the next call (the ws_zeroed contract).
+__global__ __launch_bounds__(256) void samp_filter_thr_kernel(SampleArgsF a) {
+    __shared__ samp_u64 smh[256], scr64[4], sabove, stot, sabove2, stot2;
+    __shared__ unsigned shist[512], scr[8], smin;
+    __shared__ int si[4], sbin, slo;
+    const int r = blockIdx.x, tid = threadIdx.x;
+    if (samp_row_done(a, r)) return;
+    const unsigned* ws = a.ws + (int64_t)r * SAMP_WS_WORDS;
+    unsigned* ext = a.ext + (int64_t)r * SAMP_EXT_WORDS;
+    samp_u64* mh = reinterpret_cast<samp_u64*>(ext);
+    const unsigned thr_k = samp_topk_thr_par(a, ws, shist, scr, si);
+    const unsigned maxkey = ws[512];
+    const float mx = key_logit(maxkey);
+    unsigned thr_p = 0u;
+    if (a.top_p < 1.f) {
+        smh[tid] = mh[tid];
+        __syncthreads();
+        samp_mass_find_par(smh, 0ull, 0ull, a.top_p, scr64, &sbin, &sabove, &stot);
+        smh[tid] = mh[256 + tid];
+        __syncthreads();
+        samp_mass_find_par(smh, sabove, stot, a.top_p, scr64, &slo, &sabove2, &stot2);
+        thr_p = ((unsigned)sbin << 8) | (unsigned)slo;
+        if (a.ws_clean) { mh[tid] = 0ull; mh[256 + tid] = 0ull; }
+    }
+    unsigned thr_m = 0u;
+    if (a.min_p > 0.f) {
+        // smallest key whose mass ratio to the maximum reaches min_p: the ratio grows with the key, so first the lowest high byte whose TOP key passes,
+        // then the lowest low byte inside it.  Keys above the row maximum do not occur in the row: they count as passing.
+        if (tid == 0) smin = 255u;
+        __syncthreads();
+        unsigned k = ((unsigned)tid << 8) | 255u;
+        if (k > maxkey || __expf((key_logit(k) - mx) * a.inv_temp) >= a.min_p) atomicMin(&smin, (unsigned)tid);
+        __syncthreads();
+        const unsigned hb = smin;
+        __syncthreads();
+        if (tid == 0) smin = 255u;
+        __syncthreads();
+        k = (hb << 8) | (unsigned)tid;
+        if (k > maxkey || __expf((key_logit(k) - mx) * a.inv_temp) >= a.min_p) atomicMin(&smin, (unsigned)tid);
+        __syncthreads();
+        thr_m = (hb << 8) | smin;
+    }
+    if (tid == 0) ext[1024] = samp_zero_tie(max(thr_k, max(thr_p, thr_m)));
+}
+
+// ---- repetition penalty (RepetitionPenaltyLogitsProcessor): a seen token's logit x becomes x * penalty if x < 0, else x / penalty -------------------
+// fp32 with an IEEE division, then ONE rounding to nearest-even bf16 (the sampler's domain stays bf16; HF keeps fp32 here).  seen: one bit per token,
+// [rows, seen_ld] words.  The result goes to a separate buffer: the raw logits are still read afterwards (Rollout.track_logp).  ld may be 0: one
+// prefill row shown to several rows.
+struct PenaltyArgs { const bf16_t* logits; int64_t ld; bf16_t* out; int64_t out_ld; const unsigned* seen; int64_t seen_ld; int V; float penalty; };
+TR1_DEV bf16_t samp_penalize(bf16_t b, float penalty) { const float x = bf2f(b); return f2bf(x < 0.f ? x * penalty : __fdiv_rn(x, penalty)); }
+
+// 8 logits per thread: one 16-byte load, one byte of the bitmap, one 16-byte store; chunks without a seen token are copied untouched
+__global__ __launch_bounds__(256) void penalize_vec_kernel(PenaltyArgs a) {
+    const int ch = blockIdx.x * 256 + threadIdx.x, r = blockIdx.y;
+    if (ch >= (a.V >> 3)) return;
+    u32x4_t v = *reinterpret_cast<const u32x4_t*>(a.logits + (int64_t)r * a.ld + (int64_t)ch * 8);
+    const unsigned bits = (a.seen[(int64_t)r * a.seen_ld + (ch >> 2)] >> ((ch & 3) * 8)) & 0xffu;
+    if (bits) {
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            if (bits & (1u << e)) {
+                const unsigned w = v[e >> 1];
+                v[e >> 1] = (e & 1) ? ((w & 0xffffu) | ((unsigned)samp_penalize((bf16_t)(w >> 16), a.penalty) << 16))
+                                    : ((w & 0xffff0000u) | (unsigned)samp_penalize((bf16_t)(w & 0xffffu), a.penalty));
+            }
+        }
+    }
+    *reinterpret_cast<u32x4_t*>(a.out + (int64_t)r * a.out_ld + (int64_t)ch * 8) = v;
+}
+__global__ __launch_bounds__(256) void penalize_scalar_kernel(PenaltyArgs a) {      // any V, any ld, any 2-byte-aligned pointer
+    const int i = blockIdx.x * 256 + threadIdx.x, r = blockIdx.y;
+    if (i >= a.V) return;
+    const bf16_t b = a.logits[(int64_t)r * a.ld + i];
+    const bool seen = (a.seen[(int64_t)r * a.seen_ld + (i >> 5)] >> (i & 31)) & 1u;
+    a.out[(int64_t)r * a.out_ld + i] = seen ? samp_penalize(b, a.penalty) : b;
+}
+
+// every id of a list (a prompt) into each of `rows` bitmap rows; ids outside [0, V) are ignored
+__global__ __launch_bounds__(256) void mark_ids_kernel(const int* __restrict__ ids, int64_t n, unsigned* seen, int64_t seen_ld, int rows, int V) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const int id = ids[i];
+    if (id < 0 || id >= V) return;
+    for (int r = 0; r < rows; ++r) atomicOr(&seen[(int64_t)r * seen_ld + (id >> 5)], 1u << (id & 31));
+}
+// the token each row has just drawn (toks[r * tok_ld + *step_ptr]); rows with finished[r] != 0 hold a pad token (or the EOS that ended them): skipped
+__global__ __launch_bounds__(256) void mark_drawn_kernel(const int* __restrict__ toks, int64_t tok_ld, const int* step_ptr, const int* finished,
+                                                         unsigned* seen, int64_t seen_ld, int rows, int V) {
+    const int r = blockIdx.x * 256 + threadIdx.x;
+    if (r >= rows || (finished && finished[r])) return;
+    const int id = toks[(int64_t)r * tok_ld + (step_ptr ? *step_ptr : 0)];
+    if (id < 0 || id >= V) return;
+    atomicOr(&seen[(int64_t)r * seen_ld + (id >> 5)], 1u << (id & 31));
 }
 
 // ---- greedy decoding: token = lowest index among the row's maxima, ONE launch per decode step (no workspace, no memset) ------------------------
@@ -536,31 +744,52 @@ extern "C" int tr1_grpo_loss(const void* logp, const void* ref_logp, const void*
 }
 extern "C" int64_t tr1_sample_workspace_words(int64_t rows) { return rows * SAMP_WS_WORDS; }
 
-static int sample_tokens_impl(const void* logits, int64_t ld, int64_t rows, int64_t V, float temperature, int64_t top_k,
+static int sample_tokens_impl(const void* logits, int64_t ld, int64_t rows, int64_t V, float temperature, int64_t top_k, float top_p, float min_p,
                                  uint64_t seed, int64_t group_rows, uint64_t seed_stride, const void* step_ptr, void* tokens, int64_t tok_ld,
                                  void* finished, int64_t eos_id, int64_t pad_id, int stop_at_eos, void* u_out, void* ws_u32, int64_t ws_words,
-                                 void* next_ids, int ws_zeroed, void* stream) {
+                                 void* next_ids, int ws_zeroed, bool filtered, void* stream) {
     TR1_CHECK_ARG(temperature > 0.f, "sample: temperature must be > 0");
-    TR1_CHECK_ARG(ws_u32 && ws_words >= rows * SAMP_WS_WORDS, "sample: workspace too small (tr1_sample_workspace_words)");
+    const int64_t row_words = filtered ? SAMP_WS_WORDS + SAMP_EXT_WORDS : SAMP_WS_WORDS;
+    TR1_CHECK_ARG(ws_u32 && ws_words >= rows * row_words, "sample: workspace too small (tr1_sample_workspace_words / tr1_sample_filtered_workspace_words)");
+    TR1_CHECK_ARG(!filtered || (top_p > 0.f && top_p <= 1.f && min_p >= 0.f && min_p <= 1.f), "sample: need 0 < top_p <= 1 and 0 <= min_p <= 1");
+    TR1_CHECK_ARG(!filtered || (reinterpret_cast<uintptr_t>(ws_u32) & 7) == 0, "sample: the filtered workspace must be 8-byte aligned");
+    TR1_CHECK_ARG(!filtered || (V >= 1 && V < (1ll << 31) - 8), "sample: need 1 <= V < 2^31 - 8");
     if (rows == 0) return 0;
     hipStream_t s = (hipStream_t)stream;
-    SampleArgs a;
+    SampleArgsF a;
     a.logits = (const bf16_t*)logits; a.ld = ld; a.V = (int)V; a.inv_temp = 1.0f / temperature; a.top_k = (int)top_k; a.seed = seed; a.group_rows = (int)group_rows; a.seed_stride = seed_stride;
     a.step_ptr = (const int*)step_ptr; a.tokens = (int*)tokens; a.tok_ld = tok_ld; a.finished = (int*)finished; a.eos_id = (int)eos_id;
     a.pad_id = (int)pad_id; a.stop_at_eos = stop_at_eos; a.u_out = (float*)u_out; a.ws = (unsigned*)ws_u32;
     a.next_ids = (int*)next_ids;
+    // top_p = 1 and min_p = 0 keep everything: exactly the launches of the unfiltered entry points
+    const bool use_p = filtered && top_p < 1.f, use_m = filtered && min_p > 0.f;
+    a.ext = (use_p || use_m) ? (unsigned*)ws_u32 + rows * SAMP_WS_WORDS : nullptr;
+    a.top_p = use_p ? top_p : 1.f; a.min_p = use_m ? min_p : 0.f;
     const bool fused = V % 8 == 0 && ld % 8 == 0 && V <= SAMP_FUSED_MAXV && (reinterpret_cast<uintptr_t>(logits) & 15) == 0;
     a.ws_clean = (ws_zeroed && fused) ? 1 : 0;
-    if (!a.ws_clean) hipMemsetAsync(ws_u32, 0, (size_t)rows * SAMP_WS_WORDS * 4, s);
+    const size_t ws_bytes = (size_t)rows * (a.ext ? SAMP_WS_WORDS + SAMP_EXT_WORDS : SAMP_WS_WORDS) * 4;
+    if (!a.ws_clean) hipMemsetAsync(ws_u32, 0, ws_bytes, s);
     dim3 grid(SAMP_S, (unsigned)rows);
-    hipLaunchKernelGGL(samp_hist_hi_kernel, grid, dim3(256), 0, s, a);     // also yields the row max (needed without top-k too)
-    if (top_k > 0 && top_k < V) hipLaunchKernelGGL(samp_hist_lo_kernel, grid, dim3(256), 0, s, a);
+    const SampleArgs& a0 = a;      // what the kernels shared with the unfiltered path receive
+    hipLaunchKernelGGL(samp_hist_hi_kernel, grid, dim3(256), 0, s, a0);     // also yields the row max (needed without top-k too)
+    if (top_k > 0 && top_k < V) hipLaunchKernelGGL(samp_hist_lo_kernel, grid, dim3(256), 0, s, a0);
+    if (use_p) {
+        hipLaunchKernelGGL(samp_mass_hi_kernel, grid, dim3(256), 0, s, a);
+        hipLaunchKernelGGL(samp_mass_lo_kernel, grid, dim3(256), 0, s, a);
+    }
+    if (a.ext) hipLaunchKernelGGL(samp_filter_thr_kernel, dim3((unsigned)rows), dim3(256), 0, s, a);
     if (fused) {
-        hipLaunchKernelGGL(samp_sum_pick_kernel, dim3((unsigned)rows), dim3(1024), 0, s, a);
+        if (a.ext) hipLaunchKernelGGL(samp_sum_pick_ext_kernel, dim3((unsigned)rows), dim3(1024), 0, s, a);
+        else hipLaunchKernelGGL(samp_sum_pick_kernel, dim3((unsigned)rows), dim3(1024), 0, s, a0);
     } else {
-        hipLaunchKernelGGL(samp_slice_sum_kernel, grid, dim3(256), 0, s, a);
-        hipLaunchKernelGGL(samp_pick_kernel, dim3((unsigned)rows), dim3(256), 0, s, a);
-        if (ws_zeroed) hipMemsetAsync(ws_u32, 0, (size_t)rows * SAMP_WS_WORDS * 4, s);      // keep the caller's "zero between calls" contract on this path too
+        if (a.ext) {
+            hipLaunchKernelGGL(samp_slice_sum_ext_kernel, grid, dim3(256), 0, s, a);
+            hipLaunchKernelGGL(samp_pick_ext_kernel, dim3((unsigned)rows), dim3(256), 0, s, a);
+        } else {
+            hipLaunchKernelGGL(samp_slice_sum_kernel, grid, dim3(256), 0, s, a0);
+            hipLaunchKernelGGL(samp_pick_kernel, dim3((unsigned)rows), dim3(256), 0, s, a0);
+        }
+        if (ws_zeroed) hipMemsetAsync(ws_u32, 0, ws_bytes, s);      // keep the caller's "zero between calls" contract on this path too
     }
     TR1_LAUNCH_CHECK();
 }
@@ -569,8 +798,8 @@ extern "C" int tr1_sample_tokens(const void* logits, int64_t ld, int64_t rows, i
                                  uint64_t seed, int64_t group_rows, uint64_t seed_stride, const void* step_ptr, void* tokens, int64_t tok_ld,
                                  void* finished, int64_t eos_id, int64_t pad_id, int stop_at_eos, void* u_out, void* ws_u32, int64_t ws_words,
                                  void* stream) {
-    return sample_tokens_impl(logits, ld, rows, V, temperature, top_k, seed, group_rows, seed_stride, step_ptr, tokens, tok_ld, finished, eos_id, pad_id,
-                              stop_at_eos, u_out, ws_u32, ws_words, nullptr, 0, stream);
+    return sample_tokens_impl(logits, ld, rows, V, temperature, top_k, 1.f, 0.f, seed, group_rows, seed_stride, step_ptr, tokens, tok_ld, finished, eos_id, pad_id,
+                              stop_at_eos, u_out, ws_u32, ws_words, nullptr, 0, false, stream);
 }
 
 // The decode loop's form: next_ids[row] (optional) receives the drawn token as well - the buffer the next step's embedding gather reads, so no copy
@@ -580,6 +809,62 @@ extern "C" int tr1_sample_tokens_step(const void* logits, int64_t ld, int64_t ro
                                       uint64_t seed, int64_t group_rows, uint64_t seed_stride, const void* step_ptr, void* tokens, int64_t tok_ld,
                                       void* finished, int64_t eos_id, int64_t pad_id, int stop_at_eos, void* u_out, void* ws_u32, int64_t ws_words,
                                       void* next_ids, int ws_zeroed, void* stream) {
-    return sample_tokens_impl(logits, ld, rows, V, temperature, top_k, seed, group_rows, seed_stride, step_ptr, tokens, tok_ld, finished, eos_id, pad_id,
-                              stop_at_eos, u_out, ws_u32, ws_words, next_ids, ws_zeroed, stream);
+    return sample_tokens_impl(logits, ld, rows, V, temperature, top_k, 1.f, 0.f, seed, group_rows, seed_stride, step_ptr, tokens, tok_ld, finished, eos_id, pad_id,
+                              stop_at_eos, u_out, ws_u32, ws_words, next_ids, ws_zeroed, false, stream);
+}
+
+// ---- sampler with top-p and min-p (HF TopPLogitsWarper / MinPLogitsWarper behind temperature and top-k; vLLM SamplingParams(top_p, min_p)) -----------
+// Same arguments as tr1_sample_tokens / tr1_sample_tokens_step plus the two filters, and a larger workspace (tr1_sample_filtered_workspace_words).
+// top_p = 1 and min_p = 0 run exactly the launches of the unfiltered entry points and give the same tokens.
+extern "C" int64_t tr1_sample_filtered_workspace_words(int64_t rows) { return rows * (SAMP_WS_WORDS + SAMP_EXT_WORDS); }
+
+extern "C" int tr1_sample_tokens_filtered(const void* logits, int64_t ld, int64_t rows, int64_t V, float temperature, int64_t top_k, float top_p, float min_p,
+                                          uint64_t seed, int64_t group_rows, uint64_t seed_stride, const void* step_ptr, void* tokens, int64_t tok_ld,
+                                          void* finished, int64_t eos_id, int64_t pad_id, int stop_at_eos, void* u_out, void* ws_u32, int64_t ws_words,
+                                          void* stream) {
+    return sample_tokens_impl(logits, ld, rows, V, temperature, top_k, top_p, min_p, seed, group_rows, seed_stride, step_ptr, tokens, tok_ld, finished, eos_id,
+                              pad_id, stop_at_eos, u_out, ws_u32, ws_words, nullptr, 0, true, stream);
+}
+
+extern "C" int tr1_sample_tokens_filtered_step(const void* logits, int64_t ld, int64_t rows, int64_t V, float temperature, int64_t top_k, float top_p,
+                                               float min_p, uint64_t seed, int64_t group_rows, uint64_t seed_stride, const void* step_ptr, void* tokens,
+                                               int64_t tok_ld, void* finished, int64_t eos_id, int64_t pad_id, int stop_at_eos, void* u_out, void* ws_u32,
+                                               int64_t ws_words, void* next_ids, int ws_zeroed, void* stream) {
+    return sample_tokens_impl(logits, ld, rows, V, temperature, top_k, top_p, min_p, seed, group_rows, seed_stride, step_ptr, tokens, tok_ld, finished, eos_id,
+                              pad_id, stop_at_eos, u_out, ws_u32, ws_words, next_ids, ws_zeroed, true, stream);
+}
+
+extern "C" int tr1_penalize_logits(const void* logits, int64_t ld, void* out, int64_t out_ld, const void* seen, int64_t seen_ld, int64_t rows, int64_t V,
+                                   float penalty, void* stream) {
+    TR1_CHECK_ARG(logits && out && seen && logits != out, "penalize: logits, out and seen must not be null, and out must not be logits");
+    TR1_CHECK_ARG(penalty > 0.f, "penalize: penalty must be > 0");
+    TR1_CHECK_ARG(V >= 1 && V < (1ll << 31) - 8 && rows >= 0 && rows < 65536 && (ld == 0 || ld >= V) && out_ld >= V && seen_ld >= (V + 31) / 32,
+                  "penalize: need 1 <= V < 2^31 - 8, rows < 65536, ld == 0 or ld >= V, out_ld >= V, seen_ld >= ceil(V / 32)");
+    if (rows == 0) return 0;
+    PenaltyArgs a;
+    a.logits = (const bf16_t*)logits; a.ld = ld; a.out = (bf16_t*)out; a.out_ld = out_ld; a.seen = (const unsigned*)seen; a.seen_ld = seen_ld; a.V = (int)V;
+    a.penalty = penalty;
+    const bool vec = V % 8 == 0 && ld % 8 == 0 && out_ld % 8 == 0 && ((reinterpret_cast<uintptr_t>(logits) | reinterpret_cast<uintptr_t>(out)) & 15) == 0;
+    if (vec) hipLaunchKernelGGL(penalize_vec_kernel, dim3((unsigned)((V / 8 + 255) / 256), (unsigned)rows), dim3(256), 0, (hipStream_t)stream, a);
+    else hipLaunchKernelGGL(penalize_scalar_kernel, dim3((unsigned)((V + 255) / 256), (unsigned)rows), dim3(256), 0, (hipStream_t)stream, a);
+    TR1_LAUNCH_CHECK();
+}
+
+extern "C" int tr1_mark_seen_ids(const void* ids, int64_t n, void* seen, int64_t seen_ld, int64_t rows, int64_t V, void* stream) {
+    TR1_CHECK_ARG(seen && (ids || n == 0) && n >= 0 && n < (1ll << 31), "mark_seen_ids: null pointer or bad count");
+    TR1_CHECK_ARG(V >= 1 && V < (1ll << 31) - 8 && rows >= 0 && seen_ld >= (V + 31) / 32, "mark_seen_ids: need V >= 1 and seen_ld >= ceil(V / 32)");
+    if (rows == 0 || n == 0) return 0;
+    hipLaunchKernelGGL(mark_ids_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (const int*)ids, n, (unsigned*)seen, seen_ld,
+                       (int)rows, (int)V);
+    TR1_LAUNCH_CHECK();
+}
+
+extern "C" int tr1_mark_seen_drawn(const void* tokens, int64_t tok_ld, const void* step_ptr, const void* finished, void* seen, int64_t seen_ld, int64_t rows,
+                                   int64_t V, void* stream) {
+    TR1_CHECK_ARG(seen && tokens && tok_ld >= 1, "mark_seen_drawn: null pointer or tok_ld < 1");
+    TR1_CHECK_ARG(V >= 1 && V < (1ll << 31) - 8 && rows >= 0 && rows < (1ll << 31) && seen_ld >= (V + 31) / 32, "mark_seen_drawn: need V >= 1 and seen_ld >= ceil(V / 32)");
+    if (rows == 0) return 0;
+    hipLaunchKernelGGL(mark_drawn_kernel, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (const int*)tokens, tok_ld,
+                       (const int*)step_ptr, (const int*)finished, (unsigned*)seen, seen_ld, (int)rows, (int)V);
+    TR1_LAUNCH_CHECK();
 }

@@ -54,8 +54,9 @@ def _score_row(trainer, row, toks):
     return {"problem": row["problem"], "solution": list(row["solution"]), "completion": completion, "iou": iou}
 
 
-def evaluate_grounding(trainer, dataset, max_new_tokens=None, limit=None, batch_size=None, rank=0, world=1):
+def evaluate_grounding(trainer, dataset, max_new_tokens=None, limit=None, batch_size=None, rank=0, world=1, repetition_penalty=1.0):
     """Greedy-decodes one completion per row with the trainer's engine and scores it. Returns (metrics, per-row records).
+    repetition_penalty != 1 (SamplingParams(repetition_penalty=...) of the reference's vllm_infer.py:106-111): the argmax is taken over the penalised logits.
 
     batch_size=None: one row at a time through the top_k = 1 sampler, every decode step enqueued.
     batch_size in [1, 64]: rows rank, rank + world, ... of the first `limit` rows (the reference's --curr_idx / --total_idx sharding, evaluate.py:44-45),
@@ -72,7 +73,7 @@ def evaluate_grounding(trainer, dataset, max_new_tokens=None, limit=None, batch_
         if not 0 <= int(rank) < int(world):
             raise ValueError("need 0 <= rank < world, got rank %r, world %r" % (rank, world))
         core = GRPOCore(trainer.engine, None, 1, C, beta=0.0, temperature=1.0, top_k=1, seed=0, rope_index_mode=a.rope_index_mode, stop_at_eos=True,
-                        reuse_prefill=False, greedy=True)
+                        reuse_prefill=False, greedy=True, repetition_penalty=repetition_penalty)
         mine = list(range(int(rank), n, int(world)))
         records = []
         for k in range(0, len(mine), int(batch_size)):
@@ -87,7 +88,7 @@ def evaluate_grounding(trainer, dataset, max_new_tokens=None, limit=None, batch_
             return None, records
         return grounding_metrics([r["iou"] for r in records]), records
     core = GRPOCore(trainer.engine, None, 1, C, beta=0.0, temperature=1.0, top_k=1, seed=0,
-                    rope_index_mode=a.rope_index_mode, stop_at_eos=True, reuse_prefill=False)
+                    rope_index_mode=a.rope_index_mode, stop_at_eos=True, reuse_prefill=False, repetition_penalty=repetition_penalty)
     records = []
     for i in range(n):
         row = dataset[i]

@@ -24,7 +24,8 @@ class StepState:
 
 class GRPOCore:
     def __init__(self, engine: Engine, ref_arena=None, num_generations=8, max_completion_length=200, beta=0.04, use_grpo=False,
-                 temperature=1.0, top_k=50, seed=1234, rope_index_mode="hf4", stop_at_eos=False, reuse_prefill=True, greedy=False):
+                 temperature=1.0, top_k=50, seed=1234, rope_index_mode="hf4", stop_at_eos=False, reuse_prefill=True, greedy=False,
+                 top_p=1.0, min_p=None, repetition_penalty=1.0):
         self.eng = engine
         self.ops = engine.ops
         self.cfg = engine.cfg
@@ -36,7 +37,8 @@ class GRPOCore:
         # The rollout's prefill IS the policy forward over the prompt rows (same weights inside an accumulation window): keep its
         # activations and run the update's policy forward over the G*C completion rows only.
         self.reuse_prefill = bool(reuse_prefill)
-        self.roll = Rollout(engine, self.G, self.C, temperature, top_k, seed, stop_at_eos, greedy=greedy)      # greedy: evaluation (argmax tokens, early stop)
+        self.roll = Rollout(engine, self.G, self.C, temperature, top_k, seed, stop_at_eos, greedy=greedy, top_p=top_p, min_p=min_p,
+                            repetition_penalty=repetition_penalty)      # greedy: evaluation (argmax tokens, early stop)
         if self.beta != 0.0 and ref_arena is None:
             raise ValueError("beta != 0 needs a reference-policy arena (reference timer1_trainer.py:295-307)")
         # algorithmic work of what was run since the trainer last read it (TimeR1_Trainer.log -> perf/* keys): bytes the decode steps must

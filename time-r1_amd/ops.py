@@ -746,26 +746,68 @@ class HipOps:
         return dlogp, out3, row_len, row_kl
 
     def sample_tokens(self, logits, temperature, top_k, seed, step_dev, tokens, finished, eos_id, pad_id, stop_at_eos, u_out=None, group_rows=0,
-                      seed_stride=0, next_ids=None):
-        """next_ids (int32 [rows], optional): also receives the drawn tokens (the next decode step's embedding gather reads it: no copy kernel)."""
+                      seed_stride=0, next_ids=None, top_p=1.0, min_p=0.0):
+        """next_ids (int32 [rows], optional): also receives the drawn tokens (the next decode step's embedding gather reads it: no copy kernel).
+        top_p / min_p: nucleus and min-p filters behind top-k (HF order); at the defaults (1.0, 0.0) the call is the unfiltered entry point's."""
         self._chk(logits)
         assert tokens.dtype == I32 and (step_dev is None or step_dev.dtype == I32)
         rows, V = logits.shape
-        nws = self.L.raw("tr1_sample_workspace_words")(rows)
+        top_p, min_p = 1.0 if top_p is None else float(top_p), 0.0 if min_p is None else float(min_p)
+        if not (0.0 < top_p <= 1.0 and 0.0 <= min_p <= 1.0):
+            raise ValueError("sample_tokens: need 0 < top_p <= 1 and 0 <= min_p <= 1 (got %r, %r)" % (top_p, min_p))
+        filt = top_p < 1.0 or min_p > 0.0
+        sfx, extra = ("_filtered", (top_p, min_p)) if filt else ("", ())
+        nws = self.L.raw("tr1_sample_filtered_workspace_words" if filt else "tr1_sample_workspace_words")(rows)
+        head = (_p(logits), _ld(logits), rows, V, float(temperature), int(top_k or 0)) + extra + (int(seed) & (2**64 - 1), int(group_rows),
+                int(seed_stride) & (2**64 - 1), _p(step_dev), _p(tokens), tokens.stride(0), _p(finished), int(eos_id), int(pad_id), int(bool(stop_at_eos)), _p(u_out))
         if next_ids is not None:
             assert next_ids.dtype == I32 and next_ids.numel() == rows and next_ids.is_contiguous()
-            key = ("sampler_step", rows)
+            key = ("sampler_step" + sfx, rows)
             ws = self._ws.get(key)
             if ws is None:
-                ws = self._ws[key] = torch.zeros(nws, dtype=I32, device=self.device)      # zero ONCE: the pick kernel leaves it zero after every call
-            self.L.call("tr1_sample_tokens_step", _p(logits), _ld(logits), rows, V, float(temperature), int(top_k or 0), int(seed) & (2**64 - 1),
-                        int(group_rows), int(seed_stride) & (2**64 - 1), _p(step_dev), _p(tokens), tokens.stride(0), _p(finished), int(eos_id), int(pad_id),
-                        int(bool(stop_at_eos)), _p(u_out), _p(ws), nws, _p(next_ids), 1, self._s())
+                ws = self._ws[key] = torch.zeros(nws, dtype=I32, device=self.device)      # zero ONCE: the kernels leave it zero after every call
+            self.L.call("tr1_sample_tokens%s_step" % sfx, *head, _p(ws), nws, _p(next_ids), 1, self._s())
             return
-        ws = self._workspace("sampler", nws, I32)
-        self.L.call("tr1_sample_tokens", _p(logits), _ld(logits), rows, V, float(temperature), int(top_k or 0), int(seed) & (2**64 - 1),
-                    int(group_rows), int(seed_stride) & (2**64 - 1), _p(step_dev), _p(tokens), tokens.stride(0), _p(finished), int(eos_id), int(pad_id), int(bool(stop_at_eos)), _p(u_out),
-                    _p(ws), nws, self._s())
+        ws = self._workspace("sampler" + sfx, nws, I32)
+        self.L.call("tr1_sample_tokens" + sfx, *head, _p(ws), nws, self._s())
+
+    @staticmethod
+    def seen_words(V):
+        """Words per row of the seen-token bitmap of a V-token vocabulary (int32 [rows, seen_words(V)], zero = nothing seen)."""
+        return (int(V) + 31) // 32
+
+    def penalize_logits(self, logits, seen, penalty, out=None):
+        """Repetition penalty on bf16 logits [rows, V] (row stride >= V, or 0: one row shown to all): tokens whose bit is set in seen (int32
+        [rows, >= seen_words(V)]) get x * penalty (x < 0) or x / penalty in fp32, rounded once to bf16.  Writes `out` (never the input) and returns it."""
+        self._chk(logits)
+        assert logits.dim() == 2 and logits.stride(1) == 1 and seen.dtype == I32 and seen.dim() == 2 and seen.stride(1) == 1
+        rows, V = logits.shape
+        assert seen.shape[0] == rows and seen.shape[1] >= self.seen_words(V) and seen.device == logits.device
+        if not float(penalty) > 0.0:
+            raise ValueError("penalize_logits: penalty must be > 0 (got %r)" % (penalty,))
+        if out is None:
+            out = torch.empty(rows, V, dtype=BF16, device=self.device)
+        self._chk(out)
+        assert out.shape == (rows, V) and out.stride(1) == 1 and out.data_ptr() != logits.data_ptr()
+        self.L.call("tr1_penalize_logits", _p(logits), int(logits.stride(0)), _p(out), int(out.stride(0)), _p(seen), int(seen.stride(0)), rows, V,
+                    float(penalty), self._s())
+        return out
+
+    def mark_seen(self, seen, V, ids=None, tokens=None, step_dev=None, finished=None):
+        """Sets bits of the seen bitmap (int32 [rows, >= seen_words(V)]).  ids (int32 [n]): every id into EVERY row (a prompt and its G rows).
+        tokens (int32 [rows] or [rows, C] with step_dev): row r's token tokens[r] / tokens[r, *step_dev] into row r, except rows with finished[r] != 0
+        (their token is padding).  Ids outside [0, V) are ignored; marking is idempotent."""
+        assert seen.dtype == I32 and seen.dim() == 2 and seen.stride(1) == 1 and seen.shape[1] >= self.seen_words(V) and seen.device.type == "cuda"
+        assert (ids is None) != (tokens is None), "mark_seen: either ids or tokens"
+        rows = seen.shape[0]
+        if ids is not None:
+            assert ids.dtype == I32 and ids.dim() == 1 and ids.is_contiguous()
+            self.L.call("tr1_mark_seen_ids", _p(ids), ids.numel(), _p(seen), int(seen.stride(0)), rows, int(V), self._s())
+            return
+        assert tokens.dtype == I32 and tokens.shape[0] == rows and (tokens.dim() == 1 or tokens.stride(1) == 1)
+        assert step_dev is None or step_dev.dtype == I32
+        assert finished is None or (finished.dtype == I32 and finished.numel() == rows and finished.is_contiguous())
+        self.L.call("tr1_mark_seen_drawn", _p(tokens), int(tokens.stride(0)), _p(step_dev), _p(finished), _p(seen), int(seen.stride(0)), rows, int(V), self._s())
 
     def greedy_tokens(self, logits, step_dev, tokens, finished, eos_id, pad_id, next_ids=None, done_count=None):
         """tokens[r, *step_dev] = lowest index among the maxima of logits[r] (pad_id for rows already finished); a row that selects eos_id is marked

@@ -7,6 +7,7 @@ each decode step is a batch of single-token rows whose GEMMs take the HBM-stream
 bound, so the prompts of one gradient-accumulation window (weights are constant inside it) are decoded TOGETHER: with GA = 2 and
 G = 8 every weight byte read from HBM serves 16 rows instead of 8.  Attention stays per prompt (own prefix, own KV cache).
 """
+import inspect
 from collections import namedtuple
 
 import numpy as np
@@ -38,10 +39,25 @@ class Rollout:
     step is enqueued the host reads only a copy recorded at least `poll_every` steps earlier - it never waits on the step it has just enqueued, the queue
     never drains, and no per-step .item() / synchronize() exists.  Up to 2 * poll_every padding-only steps may therefore run after the last row has
     finished; the result equals running all C - 1 steps, because finished rows only ever receive pad_token_id (tokens start as pad_token_id in this mode).
-    poll_every=0 switches the early stop off.  last_steps_run = decode steps enqueued by the last call.  greedy=False: nothing of this is executed."""
+    poll_every=0 switches the early stop off.  last_steps_run = decode steps enqueued by the last call.  greedy=False: nothing of this is executed.
 
-    def __init__(self, engine, num_generations, max_completion_length, temperature=1.0, top_k=50, seed=1234, stop_at_eos=False, greedy=False, poll_every=8):
+    top_p / min_p / repetition_penalty (HF generate's order: penalty, temperature, top-k, top-p, min-p; defaults 1 / 0 / 1 = off, and then no call differs
+    from a Rollout without them).  A token is seen by a row when it is in the row's prompt or was drawn for the row before (padding of finished rows
+    does not count); a seen token's logit x becomes x * penalty (x < 0) or x / penalty, rounded to bf16, in a buffer of its own - track_logp keeps
+    reading the raw logits, as it already ignores top-k.  Greedy mode honours the penalty and ignores top_p / min_p (the argmax survives both).  A
+    backend whose sample_tokens lacks top_p / min_p, or that has no penalize_logits / mark_seen, raises NotImplementedError when a non-default is asked."""
+
+    def __init__(self, engine, num_generations, max_completion_length, temperature=1.0, top_k=50, seed=1234, stop_at_eos=False, greedy=False, poll_every=8,
+                 top_p=1.0, min_p=0.0, repetition_penalty=1.0):
         self.eng = engine
+        self.top_p, self.min_p = 1.0 if top_p is None else float(top_p), 0.0 if min_p is None else float(min_p)
+        self.repetition_penalty = 1.0 if repetition_penalty is None else float(repetition_penalty)
+        if not 0.0 < self.top_p <= 1.0:
+            raise ValueError("top_p must be in (0, 1] (1 = off), got %r" % (top_p,))
+        if not 0.0 <= self.min_p <= 1.0:
+            raise ValueError("min_p must be in [0, 1] (0 = off), got %r" % (min_p,))
+        if not 0.0 < self.repetition_penalty < float("inf"):
+            raise ValueError("repetition_penalty must be a positive number (1 = off), got %r" % (repetition_penalty,))
         self.G, self.C = int(num_generations), int(max_completion_length)
         self.temperature, self.top_k, self.seed, self.stop_at_eos = float(temperature), int(top_k or 0), int(seed), bool(stop_at_eos)
         self.greedy, self.poll_every = bool(greedy), int(poll_every or 0)
@@ -114,8 +130,34 @@ class Rollout:
         """One prompt. prompt_ids: int32 device tensor [P]; prompt_pos3: numpy [3, P]; returns (tokens int32 [G, C] on device, layout)."""
         return self.generate_many(arena, [(prompt_ids, vid_embeds, vid_rows, prompt_pos3, delta)], save_prefill)[0]
 
-    def _buffers(self, items, greedy_op):
-        """What one call allocates: the per-row outputs, the packed layouts and the KV cache."""
+    def _filter_kwargs(self, ops):
+        """Extra keyword arguments of ops.sample_tokens: none at the defaults (and in greedy mode), so a backend without them keeps working."""
+        if self.greedy or (self.top_p == 1.0 and self.min_p == 0.0):
+            return {}
+        pars = inspect.signature(ops.sample_tokens).parameters
+        if not ({"top_p", "min_p"} <= set(pars) or any(p.kind == p.VAR_KEYWORD for p in pars.values())):
+            raise NotImplementedError("top_p = %g / min_p = %g: the %r backend's sample_tokens has no top_p / min_p arguments"
+                                      % (self.top_p, self.min_p, getattr(ops, "name", type(ops).__name__)))
+        return dict(top_p=self.top_p, min_p=self.min_p)
+
+    def _penalized(self, buf, logits, r0=0):
+        """The logits the selection reads: `logits` itself without a penalty, else their penalised copy in buf.pen[r0 : r0 + rows]."""
+        if buf.seen is None:
+            return logits
+        n = logits.shape[0]
+        return self.eng.ops.penalize_logits(logits, buf.seen[r0:r0 + n], self.repetition_penalty, out=buf.pen[r0:r0 + n])
+
+    def _mark_drawn(self, buf, col, r0=0, n=None):
+        """Column `col` of the tokens (just written) into the seen sets of rows [r0, r0 + n); finished rows hold padding there and are skipped."""
+        if buf.seen is None:
+            return
+        n = buf.tokens.shape[0] - r0 if n is None else n
+        self.eng.ops.mark_seen(buf.seen[r0:r0 + n], buf.seen_vocab, tokens=buf.tokens[r0:r0 + n], step_dev=buf.steps[col:col + 1],
+                               finished=buf.finished[r0:r0 + n] if self.stop_at_eos else None)
+
+    def _buffers(self, items, greedy_op, V=None):
+        """What one call allocates: the per-row outputs, the packed layouts and the KV cache; with a repetition penalty also the seen bitmap
+        (one bit per token of the V-token vocabulary and row) and the buffer of penalised logits."""
         ops, G, C, R = self.eng.ops, self.G, self.C, len(items) * self.G
         steps = ops.tensor(np.arange(C, dtype=np.int32), I32)
         tokens = torch.full((R, C), int(self.eng.cfg.pad_token_id), dtype=I32, device=steps.device) if self.greedy else ops.zeros(R, C, dtype=I32)
@@ -123,7 +165,14 @@ class Rollout:
         done_count = ops.zeros(1, dtype=I32) if greedy_op else None      # rows that selected EOS; zeroed here, once per call
         slogp = ops.zeros(R, C, dtype=torch.float32) if self.track_logp else None
         lays = [PackedLayout(int(it[0].shape[0]), G, C) for it in items]
-        return _Buffers(greedy_op, steps, tokens, finished, done_count, slogp, lays, self._kv(len(items), max(l.S_cap for l in lays)))
+        seen = pen = None
+        if self.repetition_penalty != 1.0:
+            if not (hasattr(ops, "penalize_logits") and hasattr(ops, "mark_seen")):
+                raise NotImplementedError("repetition_penalty = %g: the %r backend has no penalize_logits / mark_seen"
+                                          % (self.repetition_penalty, getattr(ops, "name", type(ops).__name__)))
+            V = int(self.eng.cfg.text.vocab_size if V is None else V)
+            seen, pen = ops.zeros(R, (V + 31) // 32, dtype=I32), ops.empty(R, V)
+        return _Buffers(greedy_op, steps, tokens, finished, done_count, slogp, lays, self._kv(len(items), max(l.S_cap for l in lays)), seen, pen, V)
 
     def _prefill(self, arena, w_lm, buf, b, item, save_prefill):
         """Prompt b: prefill into its cache slots, first token (and its log-prob), and this prompt's decode tables."""
@@ -147,12 +196,17 @@ class Rollout:
         hn, _, _ = ops.rmsnorm_fwd(hL[P - 1:P], arena.w("norm"), t.rms_eps, need_rstd=False)
         logits = ops.gemm_nt(hn, w_lm)  # [1, V]
         tokens, finished = buf.tokens[b * G:(b + 1) * G], buf.finished[b * G:(b + 1) * G]
+        sel = logits      # what the selection reads: with a penalty, the one prefill row penalised by the prompt's tokens (all G rows have seen just those)
+        if buf.seen is not None:
+            ops.mark_seen(buf.seen[b * G:(b + 1) * G], buf.seen_vocab, ids=prompt_ids.contiguous())
+            sel = self._penalized(buf, logits, b * G)
         if buf.greedy_op:
-            ops.greedy_tokens(logits if G == 1 else logits.expand(G, logits.shape[1]).contiguous(), buf.steps[0:1], tokens, finished, cfg.eos_token_id,
+            ops.greedy_tokens(sel if G == 1 else sel.expand(G, sel.shape[1]).contiguous(), buf.steps[0:1], tokens, finished, cfg.eos_token_id,
                               cfg.pad_token_id, done_count=buf.done_count)
         else:
-            ops.sample_tokens(logits.expand(G, logits.shape[1]), self.temperature, self.top_k, seed, buf.steps[0:1], tokens, finished,
-                              cfg.eos_token_id, cfg.pad_token_id, self.stop_at_eos)
+            ops.sample_tokens(sel.expand(G, sel.shape[1]), self.temperature, self.top_k, seed, buf.steps[0:1], tokens, finished,
+                              cfg.eos_token_id, cfg.pad_token_id, self.stop_at_eos, **self._filter_kwargs(ops))
+        self._mark_drawn(buf, 0, b * G, G)
         if buf.slogp is not None:      # (the first token is drawn from the bf16 prefill's logits in every mode)
             buf.slogp[b * G:(b + 1) * G, 0] = ops.logp_entropy_fwd(logits.expand(G, logits.shape[1]).contiguous(), tokens[:, 0].contiguous())[0]
         # ---- per-step tables (positions, slots, masks) built once
@@ -187,7 +241,8 @@ class Rollout:
         on_gpu = dev is not None and torch.device(dev).type == "cuda"
         greedy_op = self.greedy and hasattr(ops, "greedy_tokens")      # (a backend without the op: the top_k = 1 sampler, as before)
         w_lm = eng.params.lm_head_w(arena)
-        buf = self._buffers(items, greedy_op)
+        self._filter_kwargs(ops)      # (a backend that cannot honour top_p / min_p: refuse before anything is computed)
+        buf = self._buffers(items, greedy_op, int(w_lm.shape[0]))
         per = [self._prefill(arena, w_lm, buf, b, it, save_prefill) for b, it in enumerate(items)]
         tab = self._step_tables(per, buf.cache, int(torch.cuda.get_device_properties(dev).multi_processor_count) if on_gpu else 256)
         fused = B * G <= 64        # the fused decode kernels hold all rows of a step in one MFMA column block set
@@ -220,7 +275,8 @@ class Rollout:
 
 
 # One call's allocations: tokens / slogp [B*G, C], finished [B*G], done_count [1] (greedy_op only), steps = arange(C), one layout per prompt, the KV cache
-_Buffers = namedtuple("_Buffers", "greedy_op steps tokens finished done_count slogp lays cache")
+# seen int32 [B*G, ceil(seen_vocab / 32)] / pen [B*G, seen_vocab]: only with a repetition penalty (else None)
+_Buffers = namedtuple("_Buffers", "greedy_op steps tokens finished done_count slogp lays cache seen pen seen_vocab")
 # cos / sin [C, B*G, half]; slots [C, B*G] into the unified cache; hi [C, B*G]: hi of step s = the slot just appended (cache-local); pre / lo [B*G]
 _StepTables = namedtuple("_StepTables", "cos sin slots hi pre lo nsplit")
 
@@ -295,13 +351,15 @@ class _NativeStep(_Step):
 
     def select(self, s, logits):
         roll, ops, cfg, buf = self.roll, self.ops, self.cfg, self.buf
+        logits = roll._penalized(buf, logits)
         if buf.greedy_op:
             ops.greedy_tokens(logits, buf.steps[s + 1:s + 2], buf.tokens, buf.finished, cfg.eos_token_id, cfg.pad_token_id, next_ids=self.ids,
                               done_count=buf.done_count)
         else:
             # all prompts of the window in ONE sampler launch set; every prompt keeps its own Philox stream (seed_b = seed_0 + 7919 b)
             ops.sample_tokens(logits, roll.temperature, roll.top_k, self.per[0]["seed"], buf.steps[s + 1:s + 2], buf.tokens, buf.finished, cfg.eos_token_id,
-                              cfg.pad_token_id, roll.stop_at_eos, group_rows=roll.G, seed_stride=7919, next_ids=self.ids)
+                              cfg.pad_token_id, roll.stop_at_eos, group_rows=roll.G, seed_stride=7919, next_ids=self.ids, **roll._filter_kwargs(ops))
+        roll._mark_drawn(buf, s + 1)
 
 
 class _HostStep(_Step):
@@ -370,8 +428,10 @@ class _HostStep(_Step):
 
     def select(self, s, logits):
         roll, ops, cfg, buf, G = self.roll, self.ops, self.cfg, self.buf, self.roll.G
+        logits = roll._penalized(buf, logits)
         if buf.greedy_op:
             ops.greedy_tokens(logits, buf.steps[s + 1:s + 2], buf.tokens, buf.finished, cfg.eos_token_id, cfg.pad_token_id, done_count=buf.done_count)
         for b, st in enumerate(() if buf.greedy_op else self.per):      # every prompt with its own seed and row slices
             ops.sample_tokens(logits[b * G:(b + 1) * G], roll.temperature, roll.top_k, st["seed"], buf.steps[s + 1:s + 2], st["tokens"],
-                              st["finished"], cfg.eos_token_id, cfg.pad_token_id, roll.stop_at_eos)
+                              st["finished"], cfg.eos_token_id, cfg.pad_token_id, roll.stop_at_eos, **roll._filter_kwargs(ops))
+        roll._mark_drawn(buf, s + 1)

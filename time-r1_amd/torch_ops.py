@@ -359,6 +359,34 @@ def sample_tokens(logits: Tensor, temperature: float, top_k: int, seed: int, ste
     _ops(logits).sample_tokens(logits, temperature, top_k, seed, step, tokens, finished, eos_id, pad_id, stop_at_eos)
 
 
+@_op("sample_tokens_filtered", mutates_args=("tokens", "finished"))
+def sample_tokens_filtered(logits: Tensor, temperature: float, top_k: int, top_p: float, min_p: float, seed: int, step: Tensor, tokens: Tensor,
+                           finished: Tensor, eos_id: int, pad_id: int, stop_at_eos: bool) -> None:
+    """sample_tokens with the nucleus (top_p) and min-p filters behind top-k: TopPLogitsWarper / MinPLogitsWarper, equal logits kept or dropped together."""
+    _ops(logits).sample_tokens(logits, temperature, top_k, seed, step, tokens, finished, eos_id, pad_id, stop_at_eos, top_p=top_p, min_p=min_p)
+
+
+@_op("penalize_logits")
+def penalize_logits(logits: Tensor, seen: Tensor, penalty: float) -> Tensor:
+    """RepetitionPenaltyLogitsProcessor on bf16 logits [rows, V] with a seen bitmap int32 [rows, ceil(V / 32)]; fp32 arithmetic, one rounding to bf16."""
+    return _ops(logits).penalize_logits(logits, seen, penalty)
+
+
+@penalize_logits.register_fake
+def _(logits, seen, penalty):
+    return logits.new_empty(logits.shape)
+
+
+@_op("mark_seen_ids", mutates_args=("seen",))
+def mark_seen_ids(seen: Tensor, vocab_size: int, ids: Tensor) -> None:
+    _ops(seen).mark_seen(seen, vocab_size, ids=ids)
+
+
+@_op("mark_seen_drawn", mutates_args=("seen",))
+def mark_seen_drawn(seen: Tensor, vocab_size: int, tokens: Tensor, step: Optional[Tensor], finished: Optional[Tensor]) -> None:
+    _ops(seen).mark_seen(seen, vocab_size, tokens=tokens, step_dev=step, finished=finished)
+
+
 @_op("adamw_step", mutates_args=("p32", "m", "v", "g", "p16"))
 def adamw_step(p32: Tensor, m: Tensor, v: Tensor, g: Tensor, p16: Tensor, lr: float, beta1: float, beta2: float, eps: float, weight_decay: float, step: int,
                max_norm: float, grad_mult: float) -> Tensor:
@@ -388,7 +416,8 @@ def _(frames_u8, out_h, out_w, k_pad):
 
 
 OP_NAMES = ["rmsnorm_fwd", "rmsnorm_bwd", "swiglu_fwd", "swiglu_bwd", "linear_fwd", "linear_bwd", "rope_fwd", "mrope_table", "attn_fwd", "attn_bwd",
-            "logp_entropy_fwd", "logp_bwd", "lmhead_logp_entropy", "grpo_loss", "sample_tokens", "adamw_step", "video_preprocess"]
+            "logp_entropy_fwd", "logp_bwd", "lmhead_logp_entropy", "grpo_loss", "sample_tokens", "sample_tokens_filtered", "penalize_logits", "mark_seen_ids",
+            "mark_seen_drawn", "adamw_step", "video_preprocess"]
 
 
 # ================================================================================================ dropping the ops into an HF model

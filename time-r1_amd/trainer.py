@@ -61,6 +61,19 @@ start time to end time
 _TEMPLATES = {"v1": QUESTION_TEMPLATE_TG_v1, "v2": QUESTION_TEMPLATE_TG_v2, "v3": QUESTION_TEMPLATE_TG_v3}
 
 
+def generation_config_dict(cfg, args):
+    """What save_model writes as generation_config.json; top_p / min_p / repetition_penalty only when they are not the defaults."""
+    d = {"eos_token_id": cfg.eos_token_id, "pad_token_id": cfg.pad_token_id, "do_sample": True, "temperature": float(getattr(args, "temperature", 1.0))}
+    top_p, min_p, rep = getattr(args, "top_p", 1.0), getattr(args, "min_p", None), getattr(args, "repetition_penalty", 1.0)
+    if top_p is not None and float(top_p) != 1.0:
+        d["top_p"] = float(top_p)
+    if min_p is not None and float(min_p) != 0.0:
+        d["min_p"] = float(min_p)
+    if rep is not None and float(rep) != 1.0:
+        d["repetition_penalty"] = float(rep)
+    return d
+
+
 @dataclasses.dataclass
 class GRPOConfig:
     """The training arguments the reference reads (trl.GRPOConfig + main.py:44-70 MY_GRPOConfig), as a plain dataclass."""
@@ -71,6 +84,21 @@ class GRPOConfig:
     max_completion_length: int = 256
     temperature: float = 0.9
     top_k: Optional[int] = 50               # transformers 4.51 GenerationConfig default
+    top_p: float = 1.0                      # nucleus filter behind top-k (GenerationConfig.top_p / trl.GRPOConfig.top_p / vLLM SamplingParams.top_p); 1 = off
+    min_p: Optional[float] = None           # keep tokens with p >= min_p * p_max (GenerationConfig.min_p / trl.GRPOConfig.min_p); None or 0 = off
+    repetition_penalty: float = 1.0         # logits of tokens in the prompt or already drawn: x / penalty (x > 0), x * penalty (x < 0); 1 = off
+
+    def __post_init__(self):
+        self.top_p = 1.0 if self.top_p is None else float(self.top_p)
+        self.min_p = None if self.min_p is None else float(self.min_p)
+        self.repetition_penalty = 1.0 if self.repetition_penalty is None else float(self.repetition_penalty)
+        if not 0.0 < self.top_p <= 1.0:
+            raise ValueError("top_p must be in (0, 1], got %r" % (self.top_p,))
+        if self.min_p is not None and not 0.0 <= self.min_p <= 1.0:
+            raise ValueError("min_p must be None or in [0, 1], got %r" % (self.min_p,))
+        if not 0.0 < self.repetition_penalty < float("inf"):
+            raise ValueError("repetition_penalty must be a positive number, got %r" % (self.repetition_penalty,))
+
     beta: float = 0.04
     use_grpo: bool = False
     prompt_type: str = "v1"
@@ -352,7 +380,8 @@ class TimeR1_Trainer:
                                                  is_main_process=self.dp.rank == 0, unwrap_model=lambda m: m)
         self.core = GRPOCore(self.engine, self.ref_model, self.num_generations, self.max_completion_length, beta=self.beta,
                              use_grpo=self.use_grpo, temperature=args.temperature, top_k=args.top_k, seed=args.seed + 1000 * self.dp.rank,
-                             rope_index_mode=args.rope_index_mode, stop_at_eos=args.stop_at_eos)
+                             rope_index_mode=args.rope_index_mode, stop_at_eos=args.stop_at_eos, top_p=getattr(args, "top_p", 1.0),
+                             min_p=getattr(args, "min_p", None), repetition_penalty=getattr(args, "repetition_penalty", 1.0))
         self.core.roll.weight_dtype = getattr(args, "rollout_weight_dtype", "bf16")
         keep = getattr(args, "rollout_fp8_keep_bf16", None)
         if keep is None:
@@ -890,8 +919,7 @@ class TimeR1_Trainer:
         sp = getattr(self.processing_class, "save_pretrained", None)
         if sp is not None:
             sp(output_dir)
-        json.dump({"eos_token_id": self.cfg.eos_token_id, "pad_token_id": self.cfg.pad_token_id, "do_sample": True,
-                   "temperature": float(getattr(self.args, "temperature", 1.0))}, open(os.path.join(output_dir, "generation_config.json"), "w"), indent=1)
+        json.dump(generation_config_dict(self.cfg, self.args), open(os.path.join(output_dir, "generation_config.json"), "w"), indent=1)
 
     def _save_checkpoint(self):
         d = os.path.join(self.args.output_dir, "checkpoint-%d" % self.state.global_step)
