@@ -429,7 +429,7 @@ def periodic_arena(case, kind, tail=9):
 # ---- wgrad_sumsq
 def _replay(N, K, kmajor):
     """Replay of the integer cost model in tr1_wgrad_f32_sumsq (csrc/gemm.hip) for a gradient of N rows x K columns: tile height in rows.  The NT form
-    starts from 224 and takes a taller tile only when strictly cheaper (the NT GEMM dispatch's own choice); the K-major form is epi_pick_rt (start 256)."""
+    starts from 224 and takes a taller tile only when strictly cheaper (the NT GEMM dispatch's own choice); the K-major form starts from 256 (nt8p_pick_rt with first = 224 / 256)."""
     t2n = (K + 255) // 256
 
     def cost(bm, eff):

@@ -41,7 +41,10 @@ def both(hip_ops, ref_ops, fn, *tensors, **kw):
 @pytest.mark.parametrize("M,N,K", [(1, 128, 256), (8, 512, 3584), (16, 72, 320), (130, 200, 64), (257, 384, 192), (300, 1152, 512),
                                    (128, 128, 64), (513, 136, 1216),
                                    # decode regime with several 16-row groups (G = 16 / prompts batched over the accumulation window)
-                                   (17, 72, 320), (24, 512, 3584), (32, 4096, 3584), (33, 200, 8192), (48, 16400, 8192), (64, 1152, 512), (32, 100096, 256)])
+                                   (17, 72, 320), (24, 512, 3584), (32, 4096, 3584), (33, 200, 8192), (48, 16400, 8192), (64, 1152, 512), (32, 100096, 256),
+                                   # the phased 8-wave tiles at 224 / 256 / 288 / 320 rows: five column tiles, the last one ragged
+                                   # (tests/test_gemm_tile_heights.py replays the launcher's choice on the CPU)
+                                   (7169, 1032, 64), (11425, 1032, 64), (13057, 1032, 64), (14689, 1032, 64)])
 def test_gemm_nt(hip_ops, ref_ops, M, N, K):
     a, b, bias, res = rnd(M, K, seed=1), rnd(N, K, seed=2, scale=0.1), rnd(N, seed=3), rnd(M, N, seed=4)
     atol = 0.02 * math.sqrt(K) * 0.1 + 0.02
@@ -225,7 +228,8 @@ class _unfused:
         del self.ops.FUSE_EPI            # back to the class default
 
 
-@pytest.mark.parametrize("M,I,K,save", [(300, 640, 256, True), (1111, 1032, 512, True), (700, 200, 128, False), (5074, 2048, 256, True), (65, 8, 64, True)])
+@pytest.mark.parametrize("M,I,K,save", [(300, 640, 256, True), (1111, 1032, 512, True), (700, 200, 128, False), (5074, 2048, 256, True), (65, 8, 64, True),
+                                        (11425, 520, 64, True), (13057, 520, 64, False)])       # 256- and 288-row tiles (224 and 320 above)
 def test_gemm_glu_fused_epilogue(hip_ops, ref_ops, M, I, K, save):
     """gate/up GEMM with SwiGLU in the epilogue (csrc/gemm.hip EPI 2): bit-identical to GEMM + swiglu_fwd, close to the oracle; I % 128 != 0 and
     output views included."""
@@ -245,7 +249,8 @@ def test_gemm_glu_fused_epilogue(hip_ops, ref_ops, M, I, K, save):
     close(a, ar, 0.02 * math.sqrt(K) * 0.1 + 0.02, rtol=3e-2, what="glu a")
 
 
-@pytest.mark.parametrize("M,N,K", [(13376 // 8, 5120, 1280), (300, 200, 64), (1000, 264, 128)])
+@pytest.mark.parametrize("M,N,K", [(13376 // 8, 5120, 1280), (300, 200, 64), (1000, 264, 128),
+                                   (11425, 1032, 64), (13057, 1032, 64), (14689, 1032, 64)])       # 256-, 288- and 320-row tiles (224 above)
 def test_gemm_quickgelu_and_biased_glu_fused_epilogue(hip_ops, ref_ops, M, N, K):
     """Vision-tower MLPs: fc1 + bias + QuickGELU (Qwen2-VL) and gate/up + bias + SwiGLU (Qwen2.5-VL) in the GEMM epilogue, bit-identical to the
     separate kernels."""
@@ -262,7 +267,8 @@ def test_gemm_quickgelu_and_biased_glu_fused_epilogue(hip_ops, ref_ops, M, N, K)
     assert torch.equal(a, a0)
 
 
-@pytest.mark.parametrize("M,nh,nkv,K,row0", [(300, 4, 2, 256, 0), (1000, 28, 4, 512, 0), (333, 12, 2, 192, 77), (5074, 2, 2, 64, 0)])
+@pytest.mark.parametrize("M,nh,nkv,K,row0", [(300, 4, 2, 256, 0), (1000, 28, 4, 512, 0), (333, 12, 2, 192, 77), (5074, 2, 2, 64, 0),
+                                             (11425, 6, 2, 64, 0), (13057, 6, 2, 64, 5), (14689, 6, 2, 64, 0)])       # 256-, 288- and 320-row tiles (224 above)
 def test_gemm_qkv_rope_fused_epilogue(hip_ops, ref_ops, M, nh, nkv, K, row0):
     """q|k|v projection + bias + M-RoPE in the GEMM epilogue (EPI 4): q / k / v bit-identical to GEMM + rope_apply; k written into rows
     [row0, row0 + M) of a wider cache buffer, v into a column view."""
@@ -285,7 +291,7 @@ def test_gemm_qkv_rope_fused_epilogue(hip_ops, ref_ops, M, nh, nkv, K, row0):
     close(q, qr, atol, rtol=3e-2, what="q rope"); close(k, kr, atol, rtol=3e-2, what="k rope"); close(v, vr, atol, rtol=3e-2, what="v")
 
 
-@pytest.mark.parametrize("M,H,K", [(1000, 16, 1280), (300, 16, 128), (5074, 32, 64)])
+@pytest.mark.parametrize("M,H,K", [(1000, 16, 1280), (300, 16, 128), (5074, 32, 64), (3809, 16, 64), (4353, 16, 64)])       # the last two: 256- and 288-row tiles (224 and 320 before them)
 def test_gemm_qkv_rope_vit_padded_heads(hip_ops, ref_ops, M, H, K):
     """Vision q|k|v projection + bias + 2-D rotary embedding written as 128-wide zero-padded heads (csrc/gemm.hip EPI 7): d < 40 at column d, d + 40 at 48 + d (round 6: live features end at 96).
     Bit-identical to GEMM + rope_apply(head dim 80) scattered into that layout; pad columns untouched (zero)."""
@@ -310,7 +316,8 @@ def test_gemm_qkv_rope_vit_padded_heads(hip_ops, ref_ops, M, H, K):
     close(q128.view(M, H, 128)[:, :, :half], qr.view(M, H, hd)[:, :, :half], 0.02 * math.sqrt(K) * 0.1 + 0.03, rtol=3e-2, what="q vs oracle")
 
 
-@pytest.mark.parametrize("M,I,H", [(2048, 6400, 256), (1600, 8192, 128), (5074, 4096, 64), (1537, 8200, 64), (1440, 8192, 64), (1568, 8192, 64), (1824, 8192, 128), (2016, 8192, 64)])
+@pytest.mark.parametrize("M,I,H", [(2048, 6400, 256), (1600, 8192, 128), (5074, 4096, 64), (1537, 8200, 64), (1440, 8192, 64), (1568, 8192, 64), (1824, 8192, 128), (2016, 8192, 64),
+                                   (13057, 1032, 64)])       # 288-row tiles (224, 256 and 320 above)
 def test_dgrad_glu_bwd_fused_epilogue(hip_ops, ref_ops, M, I, H):
     """Down-projection dgrad (weight as stored) with the SwiGLU backward in its epilogue (EPI 3): bit-identical to gemm_nn + swiglu_bwd."""
     dh, w, gu = rnd(M, H, seed=1), rnd(H, I, seed=2, scale=0.1), rnd(M, 2 * I, seed=3)
@@ -1013,7 +1020,8 @@ def test_norm_gemm_qkv_fused(hip_ops, ref_ops, R, nh, nkv, hd, K):
     close(outs[0][2], vt, 0.05, what="fused qkv: V^T cache")
 
 
-@pytest.mark.parametrize("M,N,K", [(512, 256, 64), (1000, 520, 192), (5074, 3584, 4608), (1600, 3584, 18944), (700, 264, 1024), (2049, 1288, 320)])
+@pytest.mark.parametrize("M,N,K", [(512, 256, 64), (1000, 520, 192), (5074, 3584, 4608), (1600, 3584, 18944), (700, 264, 1024), (2049, 1288, 320),
+                                   (9729, 1032, 64), (11425, 1032, 64), (14689, 1032, 64)])       # 224-, 256- and 320-row tiles of the K-major form (288 above)
 def test_gemm_nn(hip_ops, M, N, K):
     """K-major B operand (dgrad dX = dY @ W reads the weight as stored): transposing LDS reads vs a float64 product, and bit-equal to the
     NT kernel fed with the transposed copy (same tiles, same k order inside every MFMA, same accumulation order)."""

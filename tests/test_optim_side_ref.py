@@ -186,16 +186,15 @@ def test_wgrad_tile_height_replay_matches_the_launcher_source():
     flat, src = oc.launcher_source("tr1_wgrad_f32_sumsq", os.path.join(CSRC, "gemm.hip"))
     flat = flat[:flat.index("*n_partials = blocks * 8;") + 30]
     assert "const int64_t t2n = (N + BN2 - 1) / BN2;" in flat
-    assert "if (b_kmajor) rt = epi_pick_rt(M, t2n);" in flat
-    assert "auto cost = [&](int64_t bm, double eff) { const int64_t t = ((M + bm - 1) / bm) * t2n; return (double)((t + 255) / 256) * 256.0 * (double)(bm * BN2) / eff; };" in flat
-    assert "rt = 7; double best = cost(224, eff[0]);" in flat
-    assert "for (int r = 8; r <= 10; ++r) { const double c = cost(r * 32, eff[r - 7]); if (c < best) { best = c; rt = r; } }" in flat
+    # K-major: start at 256 (256, 224, 288, 320); NT: start at 224 (224, 256, 288, 320) - the two branches of the replay
+    assert "nt8p_pick_rt(M, t2n, b_kmajor ? 256 : 224)" in flat and flat.count("nt8p_pick_rt(") == 1
     assert "*n_partials = blocks * 8;" in flat
     import re
-    pick = re.sub(r"\s+", " ", src[src.index("static int epi_pick_rt(int64_t M, int64_t Ntiles) {"):][:700])
-    assert "const int64_t t = ((M + bm - 1) / bm) * Ntiles;" in pick and "int rt = 8; double best = cost(256, 1.0);" in pick
-    assert "for (int r = 7; r <= 10; ++r) { const double c = cost(r * 32, eff[r - 7]); if (c < best) { best = c; rt = r; } }" in pick
-    assert flat.count("static const double eff[4] = {0.94, 1.0, 1.025, 1.03};") == 1 and "static const double eff[4] = {0.94, 1.0, 1.025, 1.03};" in pick
+    whole = re.sub(r"\s+", " ", src)
+    # the one table, the one cost and the one picker of the 8-wave tile height
+    assert whole.count("static const double NT8P_EFF[4] = {0.94, 1.0, 1.025, 1.03};") == 1 and whole.count("{0.94, 1.0, 1.025, 1.03}") == 1
+    assert "static double nt8p_cost(int64_t M, int64_t n_tiles, int64_t rows, double eff) { const int64_t t = ((M + rows - 1) / rows) * n_tiles; return (double)((t + 255) / 256) * 256.0 * (double)(rows * BN2) / eff; }" in whole
+    assert "static int nt8p_pick_rt(int64_t M, int64_t n_tiles, int first) { int rt = first / 32; double best = nt8p_cost(M, n_tiles, first, NT8P_EFF[rt - 7]); for (int r = 7; r <= 10; ++r) { const double c = nt8p_cost(M, n_tiles, r * 32, NT8P_EFF[r - 7]); if (c < best) { best = c; rt = r; } } return rt; }" in whole
     assert re.search(r"#define BN2 256\b", src)
 
 

@@ -78,13 +78,14 @@ def test_lmhead_tile_height_replay_matches_the_launcher_source():
     """The replay is only worth something while it is the launcher's rule: pin the constants it copies."""
     src = open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "time-r1_amd", "csrc", "gemm.hip")).read()
     body = src[src.index('extern "C" int tr1_lmhead_lse_fwd'):]
-    body = body[:body.index("LAUNCHL(7)")]
-    flat = re.sub(r"\s+", " ", body)
-    assert "const int64_t t = ((M + bm - 1) / bm) * ((N + BN2 - 1) / BN2);" in flat
-    assert "return (double)((t + 255) / 256) * 256.0 * (double)(bm * BN2) / eff;" in flat
-    assert "static const double eff[4] = {0.94, 1.0, 1.025, 1.03};" in flat
-    assert "int rt = 8; double best = cost(256, 1.0);" in flat
-    assert "for (int r = 7; r <= 10; ++r) { const double c = cost(r * 32, eff[r - 7]); if (c < best) { best = c; rt = r; } }" in flat
+    body = body[:body.index("lse_combine_kernel")]
+    flat, whole = re.sub(r"\s+", " ", body), re.sub(r"\s+", " ", src)
+    # the one table, the one cost and the one picker of the 8-wave tile height (first = 256: 256, 224, 288, 320 - the order of the replay)
+    assert whole.count("static const double NT8P_EFF[4] = {0.94, 1.0, 1.025, 1.03};") == 1 and whole.count("{0.94, 1.0, 1.025, 1.03}") == 1
+    assert "static double nt8p_cost(int64_t M, int64_t n_tiles, int64_t rows, double eff) { const int64_t t = ((M + rows - 1) / rows) * n_tiles; return (double)((t + 255) / 256) * 256.0 * (double)(rows * BN2) / eff; }" in whole
+    assert "static int nt8p_pick_rt(int64_t M, int64_t n_tiles, int first) { int rt = first / 32; double best = nt8p_cost(M, n_tiles, first, NT8P_EFF[rt - 7]); for (int r = 7; r <= 10; ++r) { const double c = nt8p_cost(M, n_tiles, r * 32, NT8P_EFF[r - 7]); if (c < best) { best = c; rt = r; } } return rt; }" in whole
+    # the lm_head's call: start at 256, whole and ragged 256-column tiles
+    assert "const int64_t t2n = (N + BN2 - 1) / BN2;" in flat and "nt8p_pick_rt(M, t2n, 256)" in flat and flat.count("nt8p_pick_rt(") == 1
     assert re.search(r"#define BN2 256\b", src)
 
 

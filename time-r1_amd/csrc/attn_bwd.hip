@@ -1534,32 +1534,19 @@ static int launch_bwd(const AttnParams& p, hipStream_t s, float* ws, int64_t ws_
     constexpr int KB = NW * 16;
     const size_t dyn_dq = 2 * (2 * ATT_KV * KSTR) + 64;
     const size_t dyn_kv = 2 * (2 * 64 * KSTR + (NW == 8 ? 0 : 2 * D * 144) + 64 * 5 * 4 + 16) + (DKDV_MAXT + 1) * 4;
-    static Tr1PerDevice lds;
-    if (lds.first()) {
-        hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_bwd_dq_kernel<D>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn_dq);
-        hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_bwd_dkdv_kernel<D, NW>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn_kv);
-    }
     // head dim 128: the 32x32x16-MFMA dQ kernel (round 3)
     const size_t dyn_dq32 = 4 * (2 * 64 * 256) + 256;
-    static Tr1PerDevice dq32_lds;
-    if (D == 128 && dq32_lds.first()) hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_bwd_dq32_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn_dq32);
     const bool use_dq32 = D == 128 && p.d_real == 128 && lse2 != nullptr &&
                           (uint64_t)p.n_slots * (uint64_t)(p.k_ld > p.v_ld ? p.k_ld : p.v_ld) * 2ull < 0xffffffffull;      // 32-bit DMA byte offsets
-    if (use_dq32) hipLaunchKernelGGL(attn_bwd_dq32_kernel, dim3((unsigned)((nR + 255) / 256), p.n_kv), dim3(512), dyn_dq32, s, p, lse2);
-    else hipLaunchKernelGGL(attn_bwd_dq_kernel<D>, dim3((unsigned)((nR + 127) / 128), p.n_kv), dim3(256), dyn_dq, s, p);
+    if (use_dq32) tr1_launch<attn_bwd_dq32_kernel>(dim3((unsigned)((nR + 255) / 256), p.n_kv), dim3(512), dyn_dq32, (int)dyn_dq32, s, p, lse2);
+    else tr1_launch<attn_bwd_dq_kernel<D>>(dim3((unsigned)((nR + 127) / 128), p.n_kv), dim3(256), dyn_dq, (int)dyn_dq, s, p);
     // head dim 128 beyond the 32-bit DMA offsets of the 32x32x16 kernel: the LDS-DMA staged 16x16x32 form, 8 waves x 16 keys
     constexpr int DMA_NB = 4;
     const size_t dyn_dma = DMA_NB * (2 * 64 * 256 + 64 * 5 * 4) + (2 * DKDV_MAXT + 2) * 4;
-    static Tr1PerDevice dma_lds;
-    if (D == 128 && dma_lds.first())
-        hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_bwd_dkdv_dma_kernel<8, 1, DMA_NB>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn_dma);
     // the 32x32x16-MFMA role-split kernel (round 3) for head dim 128
     constexpr int V32_NB = 3;
     const int v32_np = dkdv32_pairs();
     const size_t dyn_v32 = V32_NB * (2 * 64 * 256 + 64 * 5 * 4) + 2 * v32_np * (64 * 32 * 2) + (2 * DKDV32_MAXT + 2) * 4;
-    static Tr1PerDevice v32_lds;
-    if (D == 128 && v32_lds.first())
-        hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_bwd_dkdv32_kernel<V32_NB, 6>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     const bool use_v32 = D == 128 && p.d_real == 128 && lse2 != nullptr &&
                          (uint64_t)p.T * (uint64_t)(p.q_ld > p.do_ld ? p.q_ld : p.do_ld) * 2ull < 0xffffffffull;      // 32-bit DMA byte offsets
     const bool use_dma = D == 128 && p.d_real == 128 && lse2 != nullptr;
@@ -1571,9 +1558,9 @@ static int launch_bwd(const AttnParams& p, hipStream_t s, float* ws, int64_t ws_
         if (!ws || ws_floats < need) { tr1_set_error_("attention bwd: workspace too small"); return 1000; }
         pk = ws; pv = ws + (int64_t)QS * p.n_slots * kvd;
     }
-    if (use_v32) hipLaunchKernelGGL((attn_bwd_dkdv32_kernel<V32_NB, 6>), dim3((unsigned)(p.n_kv * QS), 1, (unsigned)((p.n_slots + 191) / 192)), dim3(768), dyn_v32, s, p, n_qtiles, lse2, pk, pv);
-    else if (use_dma) hipLaunchKernelGGL((attn_bwd_dkdv_dma_kernel<8, 1, DMA_NB>), dim3((unsigned)(p.n_kv * QS), 1, (unsigned)((p.n_slots + 127) / 128)), dim3(512), dyn_dma, s, p, n_qtiles, lse2, pk, pv);
-    else hipLaunchKernelGGL((attn_bwd_dkdv_kernel<D, NW>), dim3((unsigned)(p.n_kv * QS), 1, (unsigned)((p.n_slots + KB - 1) / KB)), dim3(NW * 64), dyn_kv, s, p, n_qtiles, pk, pv);
+    if (use_v32) tr1_launch<attn_bwd_dkdv32_kernel<V32_NB, 6>>(dim3((unsigned)(p.n_kv * QS), 1, (unsigned)((p.n_slots + 191) / 192)), dim3(768), dyn_v32, 160 * 1024, s, p, n_qtiles, lse2, pk, pv);
+    else if (use_dma) tr1_launch<attn_bwd_dkdv_dma_kernel<8, 1, DMA_NB>>(dim3((unsigned)(p.n_kv * QS), 1, (unsigned)((p.n_slots + 127) / 128)), dim3(512), dyn_dma, (int)dyn_dma, s, p, n_qtiles, lse2, pk, pv);
+    else tr1_launch<attn_bwd_dkdv_kernel<D, NW>>(dim3((unsigned)(p.n_kv * QS), 1, (unsigned)((p.n_slots + KB - 1) / KB)), dim3(NW * 64), dyn_kv, (int)dyn_kv, s, p, n_qtiles, pk, pv);
     const bool rope = p.rope_cos != nullptr;
     bool dk_rotated = false;
     if (QS > 1) {

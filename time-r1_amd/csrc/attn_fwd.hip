@@ -508,9 +508,7 @@ int tr1_launch_attn_dec32(AttnParams& p, dim3 grid, hipStream_t s);      // attn
 template <int D, int CB, int PF>
 static void launch_fwd(dim3 grid, hipStream_t s, const AttnParams& p) {
     const size_t dyn = 2 * (ATT_KV * (2 * D + 16) + D * 144) + 64 + (PF > 1 ? (ATT_LIST_CAP + 1) * 4 : 0);
-    static Tr1PerDevice lds;
-    if (lds.first()) hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_fwd_kernel<D, CB, PF>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn);
-    hipLaunchKernelGGL((attn_fwd_kernel<D, CB, PF>), grid, dim3(256), dyn, s, p);
+    tr1_launch<attn_fwd_kernel<D, CB, PF>>(grid, dim3(256), dyn, (int)dyn, s, p);
 }
 
 static int attn_check(const AttnParams& p, int d_pad) {

@@ -644,9 +644,7 @@ int tr1_launch_attn_dec32(AttnParams& p, dim3 grid, hipStream_t s) {
     const uint64_t kbytes = (uint64_t)p.kv_batch_slots * (uint64_t)p.k_ld * 2ull, vbytes = (uint64_t)128 * (uint64_t)p.vt_ld * 2ull;
     if (kbytes >= 0xffffffffull || vbytes >= 0xffffffffull || (uint64_t)p.n_slots * (uint64_t)p.k_ld * 2ull >= 0xffffffffull) return 0;
     const size_t dyn = 4 * (64 * 256 + 128 * 128) + 64 * 256 + 768 + 64;
-    static Tr1PerDevice lds;
-    if (lds.first()) hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_dec32_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn);
-    hipLaunchKernelGGL(attn_dec32_kernel, grid, dim3(512), dyn, s, p);
+    tr1_launch<attn_dec32_kernel>(grid, dim3(512), dyn, (int)dyn, s, p);
     return 1;
 }
 
@@ -676,11 +674,6 @@ static int attn_fwd_rows_impl(const void* Q, int64_t q_ld, const void* K, int64_
         blocks = (unsigned)p.xcd_pad;
     }
     const size_t dyn = 4 * (2 * 64 * 256) + 128 + FWD_PROBE_LDS;
-    static Tr1PerDevice lds;
-    if (lds.first()) {
-        hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_fwd32_kernel<8>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn);
-        hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_fwd32_kernel<6>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn);
-    }
     // head dim 128, all 128 features live, long key ranges: the 64-rows-per-wave kernel (attn_fwd64.hip, bit-identical results).  Its software pipeline pays one
     // extra body per block for fill / drain, so it wins from ~30 key tiles per block on (tools/sweep_fwd64.py, profiles/r06_sweep_fwd64.txt: -8 % at 3 072 prompt
     // tokens, -3 % at 2 048, +1 % at 1 536, +12 % at 256) and loses on the vision towers' 13-tile segments (live-96 form built and measured: 195 against 173 us).
@@ -688,8 +681,8 @@ static int attn_fwd_rows_impl(const void* Q, int64_t q_ld, const void* K, int64_
     const char* f64 = getenv("TR1_FWD64");
     const bool use64 = !live96 && (f64 ? f64[0] != '0' : n_slots >= 3072);
     if (use64) tr1_launch_attn_fwd64(p, blocks, (hipStream_t)stream);
-    else if (live96) hipLaunchKernelGGL(attn_fwd32_kernel<6>, dim3(blocks), dim3(512), dyn, (hipStream_t)stream, p);
-    else hipLaunchKernelGGL(attn_fwd32_kernel<8>, dim3(blocks), dim3(512), dyn, (hipStream_t)stream, p);
+    else if (live96) tr1_launch<attn_fwd32_kernel<6>>(dim3(blocks), dim3(512), dyn, (int)dyn, (hipStream_t)stream, p);
+    else tr1_launch<attn_fwd32_kernel<8>>(dim3(blocks), dim3(512), dyn, (int)dyn, (hipStream_t)stream, p);
     TR1_LAUNCH_CHECK();
 }
 

@@ -438,8 +438,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
 // launched by attn_fwd_rows_impl (attn_fwd32.hip) for head-dim-128 row-major launches; same grid as attn_fwd32_kernel (256 packed rows per block)
 int tr1_launch_attn_fwd64(AttnParams& p, unsigned blocks, hipStream_t s) {
     const size_t dyn = 8 * (64 * 256) + 128 + F64_PROBE_LDS;
-    static Tr1PerDevice lds;
-    if (lds.first()) hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_fwd64_kernel<8>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn);
-    hipLaunchKernelGGL(attn_fwd64_kernel<8>, dim3(blocks), dim3(256), dyn, s, p);
+    tr1_launch<attn_fwd64_kernel<8>>(dim3(blocks), dim3(256), dyn, (int)dyn, s, p);
     return 0;
 }

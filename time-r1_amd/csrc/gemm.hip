@@ -167,62 +167,12 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_kernel(const bf16_t* __restric
 // RT = 16-row MFMA tiles per wave along M: 7 / 8 / 9 / 10 -> 224 / 256 / 288 / 320 x 256 block.  The 288-row form exists for the M = 5074 (P + G*C)
 // GEMMs with N = 3584: 18 x 14 = 252 blocks fill the 256 CUs in ONE round at 98 % padding efficiency, where 256 x 256 needs two rounds
 // (280 blocks) and 128 x 128 three (1120 blocks on 512 slots).
-// Epilogue of the 8-wave forms: lane (u, g) owns output row mrow0 + i*16 + u, 16 contiguous columns from ncol0 + g*16.
-template <bool OUT_F32, bool ACCUM, int RT>
-TR1_DEV void store_acc256(const f32x4_t (&acc)[RT][4], void* __restrict__ Cv, const bf16_t* __restrict__ bias, const bf16_t* __restrict__ residual,
-                          int64_t M, int64_t N, int64_t ldc, int64_t ldr, int64_t mrow0, int64_t ncol0, int u, int g) {
-    const int64_t nbase = ncol0 + g * 16;
-#pragma unroll
-    for (int i = 0; i < RT; ++i) {
-        const int64_t m = mrow0 + i * 16 + u;
-        if (m >= M) continue;
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-            const int64_t n = nbase + h * 8;
-            if (n + 8 > N) continue;
-            float v[8];
-#pragma unroll
-            for (int e = 0; e < 8; ++e) v[e] = acc[i][h * 2 + (e >> 2)][e & 3];
-            if (bias) {
-                const u32x4_t bv = *reinterpret_cast<const u32x4_t*>(bias + n);
-#pragma unroll
-                for (int e = 0; e < 4; ++e) { v[2 * e] += bflo(bv[e]); v[2 * e + 1] += bfhi(bv[e]); }
-            }
-            if (residual) {
-                const u32x4_t rv = *reinterpret_cast<const u32x4_t*>(residual + m * ldr + n);
-#pragma unroll
-                for (int e = 0; e < 4; ++e) { v[2 * e] += bflo(rv[e]); v[2 * e + 1] += bfhi(rv[e]); }
-            }
-            if (OUT_F32) {
-                float* cp = reinterpret_cast<float*>(Cv) + m * ldc + n;
-                f32x4_t o0 = {v[0], v[1], v[2], v[3]}, o1 = {v[4], v[5], v[6], v[7]};
-                if (ACCUM) {
-                    const f32x4_t p0 = *reinterpret_cast<const f32x4_t*>(cp), p1 = *reinterpret_cast<const f32x4_t*>(cp + 4);
-                    o0 += p0; o1 += p1;
-                }
-                *reinterpret_cast<f32x4_t*>(cp) = o0;
-                *reinterpret_cast<f32x4_t*>(cp + 4) = o1;
-            } else {
-                bf16_t* cp = reinterpret_cast<bf16_t*>(Cv) + m * ldc + n;
-                u32x4_t o;
-#pragma unroll
-                for (int e = 0; e < 4; ++e) o[e] = pack2bf(v[2 * e], v[2 * e + 1]);
-                *reinterpret_cast<u32x4_t*>(cp) = o;
-            }
-        }
-    }
-}
-
-// Epilogue of the phased 8-wave forms THROUGH LDS.  In the accumulator layout a store instruction of store_acc256 writes 64 separate
+// Epilogue of the phased 8-wave forms THROUGH LDS.  Stored straight from the accumulator layout, an instruction writes 64 separate
 // 16-byte pieces (16 rows x 4 pieces at 64-byte stride for fp32): every 128-byte line is visited by 4-8 instructions, and the fp32
 // read-modify-write of a weight gradient ran at 2.3 TB/s (904 against 1297 TFLOP/s for the same shape with bf16 output).  Here each wave
 // parks CH of its 16-row accumulator tiles in its own slice of the (now dead) operand buffers - 256-byte rows, 16-byte chunks XOR-swizzled
 // with the row so both directions are bank-conflict free - and reads them back row-contiguous: an instruction then covers 4 full fp32 rows
 // (8 bf16 rows) of the wave's 64 columns, i.e. only whole lines.  Values and rounding are unchanged.
-#ifndef TR1_EPI_LDS
-#define TR1_EPI_LDS 1
-#endif
-#define TR1_EPI_STORE(ptr, val) (*(ptr) = (val))      // (non-temporal C stores measured: -0.55 us per round of tiles in a probe, nothing in the step)
 // EPI = 1 ("lm_head -> log-prob / entropy"): nothing is stored to C.  The wave's 64 columns of a row are rounded to bf16 (the logits the
 // reference materialises are bf16) and reduced to the online-softmax triple (max, sum e^(x-max), sum x e^(x-max)); lane c8 = 0 of a row writes it to
 // part[row][ncol0 / 64] (Cv = float4 partials, ldc = column blocks per row, +1 slot per row for the target's logit), and the lane that holds
@@ -265,7 +215,7 @@ TR1_DEV void store_acc256_lds(const f32x4_t (&acc)[RT][4], char* __restrict__ wa
                         }
                         float* cp = reinterpret_cast<float*>(Cv) + m * ldc + n;
                         if (ACCUM) v += *reinterpret_cast<const f32x4_t*>(cp);
-                        TR1_EPI_STORE(reinterpret_cast<f32x4_t*>(cp), v);
+                        *reinterpret_cast<f32x4_t*>(cp) = v;      // (non-temporal C stores measured: -0.55 us per round of tiles in a probe, nothing in the step)
                         if (wire16) *reinterpret_cast<u32x2_t*>(wire16 + m * ldw16 + n) = (u32x2_t){pack2bf(v[0], v[1]), pack2bf(v[2], v[3])};
                         ssq += v[0] * v[0] + v[1] * v[1] + v[2] * v[2] + v[3] * v[3];
                     }
@@ -325,7 +275,7 @@ TR1_DEV void store_acc256_lds(const f32x4_t (&acc)[RT][4], char* __restrict__ wa
                         u32x4_t o;
 #pragma unroll
                         for (int e = 0; e < 4; ++e) o[e] = pack2bf(v[2 * e], v[2 * e + 1]);
-                        TR1_EPI_STORE(reinterpret_cast<u32x4_t*>(reinterpret_cast<bf16_t*>(Cv) + m * ldc + n), o);
+                        *reinterpret_cast<u32x4_t*>(reinterpret_cast<bf16_t*>(Cv) + m * ldc + n) = o;
                     }
                 }
             }
@@ -813,7 +763,6 @@ __global__ __launch_bounds__(512) void gemm_nt8p_kernel(const bf16_t* __restrict
 #ifdef TR1_PROBE_NO_EPI      // measurement build (tools/build_variant.py noepi -DTR1_PROBE_NO_EPI=1): the tile ends here, nothing is stored - what the epilogue costs
     if (K > 0) return;
 #endif
-#if TR1_EPI_LDS
     // every wave is past its last LDS read (the realignment barrier above): the operand buffers become 8 private staging slices
     if (EPI == 2 || EPI == 7 || (EPI == 4 && n0 < (int64_t)ep.i0 + ep.i1))
         store_acc256_pairs<RT, EPI>(acc, smem2 + wave * (((RT % 2 == 0) ? 4 : 3) * 4096), Cv, bias, M, N, ldc, m0 + wm * (RT * 16), n0, wn, lane, ep);
@@ -829,9 +778,6 @@ __global__ __launch_bounds__(512) void gemm_nt8p_kernel(const bf16_t* __restrict
                                               m0 + wm * (RT * 16), n0 + wn * 64, lane,
                                               (OUT_F32 && EPI == 0 && ep.p0) ? reinterpret_cast<float*>(ep.p0) + (int64_t)blockIdx.x * 8 + wave : nullptr,
                                               (OUT_F32 && EPI == 0 && ep.p0) ? reinterpret_cast<bf16_t*>(ep.p1) : nullptr, ep.ld1);
-#else
-    store_acc256<OUT_F32, ACCUM, RT>(acc, Cv, bias, residual, M, N, ldc, ldr, m0 + wm * (RT * 16), n0 + wn * 64, u, g);
-#endif
 }
 
 // ------------------------------------------------------------------------------------------------------------------
@@ -1531,6 +1477,18 @@ extern "C" int tr1_norm_gemm_glu_frag_ok(int64_t M, int64_t N, int64_t K) {
     return M >= 1 && M <= 16 && K % 512 == 0 && (nst == 7 || nst == 4 || nst == 3) && N % 32 == 0;
 }
 
+// The LDS-streamed decode forms (norm_glu_lds_kernel) exist for K = 512 * NST, NST = 7 / 4 / 3 (hidden 3584 / 2048 / 1536): the run-time stage count becomes the
+// template argument here.  One LDS size per form, so the cap is dyn itself.
+template <int RING, int NRED, int MG, int MODE>
+static void launch_norm_glu_lds(int64_t nst, unsigned grid, size_t dyn, hipStream_t s, const void* x, const void* lnw, const void* W, void* out, int64_t M, int64_t N,
+                                int64_t K, int64_t ldx, int64_t ldw, int64_t ldc, float eps, int64_t up_off, const void* bias, const QkvEpi& qe, int c_frag) {
+    tr1_dispatch<7, 4, 3>((int)nst, [&](auto NST) {
+        tr1_launch<norm_glu_lds_kernel<decltype(NST)::value, RING, NRED, MG, MODE>>(dim3(grid), dim3(512), dyn, (int)dyn, s, (const bf16_t*)x, (const bf16_t*)lnw,
+                                                                                  (const bf16_t*)W, (bf16_t*)out, (int)M, N, K, ldx, ldw, ldc, eps, up_off,
+                                                                                  (const bf16_t*)bias, qe, c_frag);
+    });
+}
+
 extern "C" int tr1_norm_gemm_skinny(const void* x, const void* lnw, const void* W, const void* bias, void* out, int64_t M, int64_t N, int64_t K,
                                     int64_t ldx, int64_t ldw, int64_t ldc, float eps, int glu, void* stream) {
     TR1_CHECK_ARG(K % BK == 0 && K >= BK, "norm_gemm_skinny: K must be a positive multiple of 64");
@@ -1545,69 +1503,30 @@ extern "C" int tr1_norm_gemm_skinny(const void* x, const void* lnw, const void* 
                        (int)M, N, K, ldx, ldw, ldc, eps, N)
     // gate/up + SwiGLU at <= 16 rows: UNROLL 2 keeps the kernel at 128 VGPRs = 4 blocks per CU (1024 slots for 1184 blocks); measured 59.2 vs 60.9 us
     const int64_t nst = K / 512;                     // 64-wide stages per wave (8 waves split K)
+    constexpr int RING = 3;
+    // LDS of the two row-group forms: <= 16 rows = ring of 3 + double reduction buffer + the waves' norm-weight KiB + one x stage each (a ring of 4 with a single
+    // buffer and a second barrier per pair measured the same); 17 .. 32 rows = two row groups per wave against the SAME LDS stage, single reduction buffer
+    const size_t dyn1 = 8 * RING * 4096 + (2 * 8 * 2 * 16 * 17 + 8 * 16) * sizeof(float) + 8192 + 16384;
+    const size_t dyn2 = 8 * RING * 4096 + (1 * 8 * 2 * 2 * 16 * 17 + 8 * 2 * 16) * sizeof(float) + 8192;
     if (!glu && M > 16 && M <= 32 && N >= 65536 && N % 32 == 0 && K % 512 == 0 && (nst == 7 || nst == 4 || nst == 3)) {
         // 17 .. 32 rows (config 4): two row groups per wave against the same LDS stage, single reduction buffer
-        constexpr int RING = 3;
-        const size_t dyn = 8 * RING * 4096 + (1 * 8 * 2 * 2 * 16 * 17 + 8 * 2 * 16) * sizeof(float) + 8192;
-        static Tr1PerDevice lds;
-        if (lds.first()) {
-#define HL2_ATTR(NSTV) hipFuncSetAttribute(reinterpret_cast<const void*>(&norm_glu_lds_kernel<NSTV, RING, 1, 2, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn)
-            HL2_ATTR(7); HL2_ATTR(4); HL2_ATTR(3);
-#undef HL2_ATTR
-        }
         const int64_t NPh = N / 32, n_cu = tr1_cu_count();
-        const unsigned gridh = (unsigned)(NPh < n_cu ? NPh : n_cu);
-#define HL2_LAUNCH(NSTV) hipLaunchKernelGGL((norm_glu_lds_kernel<NSTV, RING, 1, 2, 2>), dim3(gridh), dim3(512), dyn, s, (const bf16_t*)x, (const bf16_t*)lnw, (const bf16_t*)W, \
-                                            (bf16_t*)out, (int)M, N, K, ldx, ldw, ldc, eps, N / 2, (const bf16_t*)bias, QkvEpi{})
-        if (nst == 7) HL2_LAUNCH(7); else if (nst == 4) HL2_LAUNCH(4); else HL2_LAUNCH(3);
-#undef HL2_LAUNCH
+        launch_norm_glu_lds<RING, 1, 2, 2>(nst, (unsigned)(NPh < n_cu ? NPh : n_cu), dyn2, s, x, lnw, W, out, M, N, K, ldx, ldw, ldc, eps, N / 2, bias, QkvEpi{}, 0);
         TR1_LAUNCH_CHECK();
     }
     if (!glu && M <= 16 && N >= 65536 && N % 32 == 0 && K % 512 == 0 && (nst == 7 || nst == 4 || nst == 3)) {
         // wide plain projection (the lm_head) through the LDS stream: 256 persistent blocks x 8 waves, column pairs (n, n + N/2)
-        constexpr int RING = 3;
-        const size_t dyn = 8 * RING * 4096 + (2 * 8 * 2 * 16 * 17 + 8 * 16) * sizeof(float) + 8192 + 16384;
-        static Tr1PerDevice lds;
-        if (lds.first()) {
-#define HL_ATTR(NSTV) hipFuncSetAttribute(reinterpret_cast<const void*>(&norm_glu_lds_kernel<NSTV, RING, 2, 1, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn)
-            HL_ATTR(7); HL_ATTR(4); HL_ATTR(3);
-#undef HL_ATTR
-        }
         const int64_t NPh = N / 32, n_cu = tr1_cu_count();
-        const unsigned gridh = (unsigned)(NPh < n_cu ? NPh : n_cu);
-#define HL_LAUNCH(NSTV) hipLaunchKernelGGL((norm_glu_lds_kernel<NSTV, RING, 2, 1, 2>), dim3(gridh), dim3(512), dyn, s, (const bf16_t*)x, (const bf16_t*)lnw, (const bf16_t*)W, \
-                                           (bf16_t*)out, (int)M, N, K, ldx, ldw, ldc, eps, N / 2, (const bf16_t*)bias, QkvEpi{})
-        if (nst == 7) HL_LAUNCH(7); else if (nst == 4) HL_LAUNCH(4); else HL_LAUNCH(3);
-#undef HL_LAUNCH
+        launch_norm_glu_lds<RING, 2, 1, 2>(nst, (unsigned)(NPh < n_cu ? NPh : n_cu), dyn1, s, x, lnw, W, out, M, N, K, ldx, ldw, ldc, eps, N / 2, bias, QkvEpi{}, 0);
         TR1_LAUNCH_CHECK();
     }
     TR1_CHECK_ARG(glu != 2 || tr1_norm_gemm_glu_frag_ok(M, N, K), "norm_gemm_skinny: glu = 2 (fragment-major SwiGLU output) needs M <= 16 and the LDS-streamed form (tr1_norm_gemm_glu_frag_ok)");
     if (glu && M <= 32 && K % 512 == 0 && (nst == 7 || nst == 4 || nst == 3) && N % 16 == 0) {   // hidden 3584 / 2048 / 1536
-        // <= 16 rows: ring of 3 + double reduction buffer (a ring of 4 with a single buffer and a second barrier per pair measured the same).
-        // 17..32 rows (config 4 decodes 2 x 16 rollouts): two row groups per wave against the SAME LDS stage, ring of 3, single reduction
-        // buffer (132 KB of LDS): 77.4 -> 52.8 us at 32 x 18944 x 3584 (5.1 TB/s of weights) over the register-fragment form.
-        constexpr int RING = 3;
-        const size_t dyn1 = 8 * RING * 4096 + (2 * 8 * 2 * 16 * 17 + 8 * 16) * sizeof(float) + 8192 + 16384;      // + the waves' norm-weight KiB + one x stage each
-        const size_t dyn2 = 8 * RING * 4096 + (1 * 8 * 2 * 2 * 16 * 17 + 8 * 2 * 16) * sizeof(float) + 8192;
-        static Tr1PerDevice lds;
-        if (lds.first()) {
-#define GLU_ATTR(NSTV)                                                                                                                          \
-    hipFuncSetAttribute(reinterpret_cast<const void*>(&norm_glu_lds_kernel<NSTV, RING, 2, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn1); \
-    hipFuncSetAttribute(reinterpret_cast<const void*>(&norm_glu_lds_kernel<NSTV, RING, 1, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn2)
-            GLU_ATTR(7); GLU_ATTR(4); GLU_ATTR(3);
-#undef GLU_ATTR
-        }
+        // 17..32 rows (config 4 decodes 2 x 16 rollouts, 132 KB of LDS): 77.4 -> 52.8 us at 32 x 18944 x 3584 (5.1 TB/s of weights) over the register-fragment form.
         const int64_t NP = N / 16, n_cu = tr1_cu_count();
         const unsigned grid = (unsigned)(NP < n_cu ? NP : n_cu);
-#define GLU_LAUNCH(NSTV)                                                                                                                        \
-    do {                                                                                                                                        \
-        if (M <= 16) hipLaunchKernelGGL((norm_glu_lds_kernel<NSTV, RING, 2, 1>), dim3(grid), dim3(512), dyn1, s, (const bf16_t*)x, (const bf16_t*)lnw, \
-                                        (const bf16_t*)W, (bf16_t*)out, (int)M, N, K, ldx, ldw, ldc, eps, N, (const bf16_t*)nullptr, QkvEpi{}, glu == 2 ? 1 : 0); \
-        else hipLaunchKernelGGL((norm_glu_lds_kernel<NSTV, RING, 1, 2>), dim3(grid), dim3(512), dyn2, s, (const bf16_t*)x, (const bf16_t*)lnw,         \
-                                (const bf16_t*)W, (bf16_t*)out, (int)M, N, K, ldx, ldw, ldc, eps, N);                                           \
-    } while (0)
-        if (nst == 7) GLU_LAUNCH(7); else if (nst == 4) GLU_LAUNCH(4); else GLU_LAUNCH(3);
-#undef GLU_LAUNCH
+        if (M <= 16) launch_norm_glu_lds<RING, 2, 1, 0>(nst, grid, dyn1, s, x, lnw, W, out, M, N, K, ldx, ldw, ldc, eps, N, nullptr, QkvEpi{}, glu == 2 ? 1 : 0);
+        else launch_norm_glu_lds<RING, 1, 2, 0>(nst, grid, dyn2, s, x, lnw, W, out, M, N, K, ldx, ldw, ldc, eps, N, nullptr, QkvEpi{}, 0);
     }
     else if (glu) { if (M <= 16) NG(4, 2, 1, true); else if (M <= 32) NG(4, 2, 2, true); else NG(4, 2, 4, true); }
     else if (N >= 100000 && M <= 32) {      // lm_head: 4 column groups per block halve the re-reads of x (228 -> ~195 us at M = 16)
@@ -1646,39 +1565,19 @@ extern "C" int tr1_norm_gemm_qkv(const void* x, const void* lnw, const void* Wqk
     if (M > 16 && M <= 32 && K % 512 == 0 && (nst == 7 || nst == 4 || nst == 3)) {      // 17 .. 32 rows (config 4): two row groups per wave, ring of 3
         constexpr int RING2 = 3;
         const size_t dyn = 8 * RING2 * 4096 + (1 * 8 * 2 * 2 * 16 * 17 + 8 * 2 * 16) * sizeof(float) + 8192;
-        static Tr1PerDevice lds;
-        if (lds.first()) {
-#define QL2_ATTR(NSTV) hipFuncSetAttribute(reinterpret_cast<const void*>(&norm_glu_lds_kernel<NSTV, RING2, 1, 2, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn)
-            QL2_ATTR(7); QL2_ATTR(4); QL2_ATTR(3);
-#undef QL2_ATTR
-        }
-#define QL2_LAUNCH(NSTV) hipLaunchKernelGGL((norm_glu_lds_kernel<NSTV, RING2, 1, 2, 1>), grid, dim3(512), dyn, s, (const bf16_t*)x, (const bf16_t*)lnw, (const bf16_t*)Wqkv, \
-                                            (bf16_t*)nullptr, (int)M, N, K, ldx, ldw, (int64_t)0, eps, (int64_t)(head_dim / 2), (const bf16_t*)bias, qe)
-        if (nst == 7) QL2_LAUNCH(7); else if (nst == 4) QL2_LAUNCH(4); else QL2_LAUNCH(3);
-#undef QL2_LAUNCH
+        launch_norm_glu_lds<RING2, 1, 2, 1>(nst, grid.x, dyn, s, x, lnw, Wqkv, nullptr, M, N, K, ldx, ldw, 0, eps, head_dim / 2, bias, qe, 0);
         TR1_LAUNCH_CHECK();
     }
     if (M <= 16 && K % 512 == 0 && (nst == 7 || nst == 4 || nst == 3)) {
         constexpr int RING = 4;
         const size_t dyn = 8 * RING * 4096 + (1 * 8 * 2 * 16 * 17 + 8 * 16) * sizeof(float) + 8192;      // (ring of 4: the x staging fits without the extra stage area... see XSLOT0)
-        static Tr1PerDevice lds;
-        if (lds.first()) {
-#define QL_ATTR(NSTV) hipFuncSetAttribute(reinterpret_cast<const void*>(&norm_glu_lds_kernel<NSTV, RING, 1, 1, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn)
-            QL_ATTR(7); QL_ATTR(4); QL_ATTR(3);
-#undef QL_ATTR
-        }
-#define QL_LAUNCH(NSTV) hipLaunchKernelGGL((norm_glu_lds_kernel<NSTV, RING, 1, 1, 1>), grid, dim3(512), dyn, s, (const bf16_t*)x, (const bf16_t*)lnw, (const bf16_t*)Wqkv, \
-                                           (bf16_t*)nullptr, (int)M, N, K, ldx, ldw, (int64_t)0, eps, (int64_t)(head_dim / 2), (const bf16_t*)bias, qe)
-        if (nst == 7) QL_LAUNCH(7); else if (nst == 4) QL_LAUNCH(4); else QL_LAUNCH(3);
-#undef QL_LAUNCH
+        launch_norm_glu_lds<RING, 1, 1, 1>(nst, grid.x, dyn, s, x, lnw, Wqkv, nullptr, M, N, K, ldx, ldw, 0, eps, head_dim / 2, bias, qe, 0);
         TR1_LAUNCH_CHECK();
     }
-    if (M <= 16 && K / 64 / 8 >= 2 && K * 32 <= 120 * 1024 && (int64_t)M * ldx * 2 < 0x7fffffffLL) {
-        static Tr1PerDevice lds;
-        if (lds.first()) hipFuncSetAttribute(reinterpret_cast<const void*>(&norm_gemm_skinny_kernel<8, 2, 1, false, 2, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 120 * 1024);
-        hipLaunchKernelGGL((norm_gemm_skinny_kernel<8, 2, 1, false, 2, true, true>), grid, dim3(512), (size_t)(K * 32), s, (const bf16_t*)x, (const bf16_t*)lnw,
-                           (const bf16_t*)Wqkv, (bf16_t*)nullptr, (const bf16_t*)bias, (int)M, N, K, ldx, ldw, (int64_t)0, eps, (int64_t)0, qe);
-    }
+    if (M <= 16 && K / 64 / 8 >= 2 && K * 32 <= 120 * 1024 && (int64_t)M * ldx * 2 < 0x7fffffffLL)
+        tr1_launch<norm_gemm_skinny_kernel<8, 2, 1, false, 2, true, true>>(grid, dim3(512), (size_t)(K * 32), 120 * 1024, s, (const bf16_t*)x, (const bf16_t*)lnw,
+                                                                           (const bf16_t*)Wqkv, (bf16_t*)nullptr, (const bf16_t*)bias, (int)M, N, K, ldx, ldw, (int64_t)0, eps,
+                                                                           (int64_t)0, qe);
     else if (M <= 16) NGQ(8, 2, 1); else if (M <= 32) NGQ(8, 2, 2); else NGQ(4, 2, 4);
 #undef NGQ
     TR1_LAUNCH_CHECK();
@@ -1703,11 +1602,9 @@ static void launch_skinny(const void* A, const void* B, void* C, const void* bia
         else if (ncol == 2) SK(4, 4, 2, 1);
         else {
             if (ksplit == 1 && K / 64 / 4 >= 4 && K * 32 <= 120 * 1024 && (int64_t)M * lda * 2 < 0x7fffffffLL) {
-                static Tr1PerDevice lds;
-                if (lds.first()) hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_skinny_kernel<4, 4, 1, 1, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 120 * 1024);
-                hipLaunchKernelGGL((gemm_skinny_kernel<4, 4, 1, 1, true>), dim3((unsigned)((N + 15) / 16), 1u), dim3(256), (size_t)(K * 32), s, (const bf16_t*)A,
-                                   (const bf16_t*)B, out_f32 ? nullptr : (bf16_t*)C, out_f32 ? (float*)C : nullptr, (const bf16_t*)bias, (const bf16_t*)residual,
-                                   (int)M, N, K, lda, ldb, ldc, ldr, (float*)nullptr, (int*)nullptr);
+                tr1_launch<gemm_skinny_kernel<4, 4, 1, 1, true>>(dim3((unsigned)((N + 15) / 16), 1u), dim3(256), (size_t)(K * 32), 120 * 1024, s, (const bf16_t*)A,
+                                                                 (const bf16_t*)B, out_f32 ? nullptr : (bf16_t*)C, out_f32 ? (float*)C : nullptr, (const bf16_t*)bias,
+                                                                 (const bf16_t*)residual, (int)M, N, K, lda, ldb, ldc, ldr, (float*)nullptr, (int*)nullptr);
             } else SK(4, 4, 1, 1);
         }
     } else if (M <= 32) {       // LDS reduce buffer: WAVES * NCOL * MG * 1088 B <= 64 KB
@@ -1723,6 +1620,40 @@ static void launch_skinny(const void* A, const void* B, void* C, const void* bia
 #undef SK
 }
 
+// ---- tile height and launch of the phased 8-wave GEMM (gemm_nt8p_kernel: 224 / 256 / 288 / 320 rows x 256 columns, one block per CU) ------------------
+// Cost of a tile height: CU-rounds x block area / relative efficiency of the structure (tile-count quantisation).
+// Intrinsic efficiency of the heights relative to 256 x 256 (more A-fragment reuse per B fragment with taller tiles), measured on M = 37888, N = 3584,
+// K = 5120 and 8192^3 after removing tile-count quantisation (tools/microbench.py gemm, tile forced):
+static const double NT8P_EFF[4] = {0.94, 1.0, 1.025, 1.03};      // 224, 256, 288, 320 rows
+static double nt8p_cost(int64_t M, int64_t n_tiles, int64_t rows, double eff) {
+    const int64_t t = ((M + rows - 1) / rows) * n_tiles;
+    return (double)((t + 255) / 256) * 256.0 * (double)(rows * BN2) / eff;
+}
+// RT (rows / 32) of the cheapest height for M rows x n_tiles column tiles; among equals the one tried first wins: first = 256 tries 256, 224, 288, 320,
+// first = 224 tries 224, 256, 288, 320.  224 is the NT dispatch (tr1_gemm_nt_bf16) and the NT weight gradient (tr1_wgrad_f32_sumsq), whose results are
+// bit-identical because they pick alike; every other form starts at 256.
+static int nt8p_pick_rt(int64_t M, int64_t n_tiles, int first) {
+    int rt = first / 32; double best = nt8p_cost(M, n_tiles, first, NT8P_EFF[rt - 7]);
+    for (int r = 7; r <= 10; ++r) { const double c = nt8p_cost(M, n_tiles, r * 32, NT8P_EFF[r - 7]); if (c < best) { best = c; rt = r; } }
+    return rt;
+}
+// what a launch needs of the height: row tiles and dynamic LDS (two buffers of an A tile + a B tile, + the 4 KiB junk page)
+struct Nt8pTile {
+    int rt; int64_t t2m; size_t dyn;
+    Nt8pTile(int rt_, int64_t M) : rt(rt_), t2m((M + rt_ * 32 - 1) / (rt_ * 32)), dyn(2 * ((size_t)rt_ * 32 * BK * 2 + TILE2_BYTES) + 4096) {}
+};
+// the one place where the run-time height becomes the kernel's template argument; the four heights share the 320-row form's LDS limit
+template <bool OUT_F32, bool ACCUM, bool BKM, int EPI>
+static void launch_nt8p(const Nt8pTile& t, int64_t t2n, int64_t blocks, hipStream_t s, const void* A, const void* B, void* C, const void* bias, const void* residual,
+                        int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldb, int64_t ldc, int64_t ldr, const GemmEpi& ep) {
+    constexpr int LDS_CAP = (int)(2 * (320 * BK * 2 + TILE2_BYTES)) + 4096;
+    tr1_dispatch<7, 9, 10, 8>(t.rt, [&](auto R) {
+        tr1_launch<gemm_nt8p_kernel<OUT_F32, ACCUM, decltype(R)::value, BKM, EPI>>(dim3((unsigned)blocks), dim3(512), t.dyn, LDS_CAP, s, (const bf16_t*)A, (const bf16_t*)B, C,
+                                                                                 (const bf16_t*)bias, (const bf16_t*)residual, M, N, K, lda, ldb, ldc, ldr, (int)t.t2m,
+                                                                                 (int)t2n, ep);
+    });
+}
+
 extern "C" int tr1_gemm_nt_bf16(const void* A, const void* B, void* C, const void* bias, const void* residual, int64_t M, int64_t N,
                                 int64_t K, int64_t lda, int64_t ldb, int64_t ldc, int64_t ldr, int out_f32, int accumulate, void* stream) {
     TR1_CHECK_ARG(K % BK == 0, "gemm_nt: K must be a multiple of 64 (pad the operands)");
@@ -1736,50 +1667,21 @@ extern "C" int tr1_gemm_nt_bf16(const void* A, const void* B, void* C, const voi
         launch_skinny(A, B, C, bias, residual, M, N, K, lda, ldb, ldc, ldr, out_f32, 1, s);
         TR1_LAUNCH_CHECK();
     }
-    {   // tile choice: CU-rounds x block area / relative efficiency of the structure (tile-count quantisation).
-        // 128x128 runs 2 blocks per CU (512 slots), the phased 8-wave forms 1 block per CU at ~1.25x the MFMA rate per CU.
-        auto blocks = [&](int64_t bm, int64_t bn) { return ((M + bm - 1) / bm) * ((N + bn - 1) / bn); };
-        auto cost = [&](int64_t bm, int64_t bn, int64_t slots, double eff) {
-            const int64_t t = blocks(bm, bn);
-            return (double)((t + slots - 1) / slots) * (double)slots * (double)(bm * bn) / eff;
-        };
-        int rt = 0;
-        if (M >= 512 && N >= 256) {
-            double best = cost(BM, BN, 512, 0.80);
-            // intrinsic efficiency of the phased 8-wave forms relative to 256 x 256 (more A-fragment reuse per B fragment with taller tiles),
-            // measured on M = 37888, N = 3584, K = 5120 and 8192^3 after removing tile-count quantisation: 224: 0.94, 288: 1.025, 320: 1.03;
-            // the 128 x 128 form reaches 0.80 of the 256 x 256 rate per CU (tools/microbench.py gemm, tile forced)
-            static const double eff[4] = {0.94, 1.0, 1.025, 1.03};
-            for (int r = 7; r <= 10; ++r) {
-                const double c = cost(r * 32, BN2, 256, eff[r - 7]);
-                if (c < best) { best = c; rt = r; }
-            }
-        }
-        if (rt) {
-            const int bmx = rt * 32;
-            const int64_t t2m = (M + bmx - 1) / bmx, t2n = (N + BN2 - 1) / BN2;
-            const size_t dyn = 2 * ((size_t)bmx * BK * 2 + TILE2_BYTES) + 4096;
-            static Tr1PerDevice lds;
-            if (lds.first()) {
-                const int mx = (int)(2 * (320 * BK * 2 + TILE2_BYTES)) + 4096;
-#define SETA(OF, AC, R) hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_nt8p_kernel<OF, AC, R>), hipFuncAttributeMaxDynamicSharedMemorySize, mx)
-#define SETR(R) do { SETA(false, false, R); SETA(true, false, R); SETA(true, true, R); } while (0)
-                SETR(7); SETR(8); SETR(9); SETR(10);
-#undef SETR
-#undef SETA
-            }
-            dim3 grid2((unsigned)(t2m * t2n));
-#define LAUNCH2(OF, AC, R)                                                                                                            \
-    hipLaunchKernelGGL((gemm_nt8p_kernel<OF, AC, R>), grid2, dim3(512), dyn, s, (const bf16_t*)A, (const bf16_t*)B, C, (const bf16_t*)bias, \
-                       (const bf16_t*)residual, M, N, K, lda, ldb, ldc, ldr, (int)t2m, (int)t2n, GemmEpi{})
-#define LAUNCH2R(R) do { if (out_f32) { if (accumulate) LAUNCH2(true, true, R); else LAUNCH2(true, false, R); } else LAUNCH2(false, false, R); } while (0)
-            if (rt == 7) LAUNCH2R(7); else if (rt == 9) LAUNCH2R(9); else if (rt == 10) LAUNCH2R(10); else LAUNCH2R(8);
-#undef LAUNCH2R
-#undef LAUNCH2
+    const int tiles_m = (int)((M + BM - 1) / BM), tiles_n = (int)((N + BN - 1) / BN);
+    if (M >= 512 && N >= 256) {
+        // the cheapest 8-wave height against the 128 x 128 form, which runs 2 blocks per CU (512 slots) at 0.80 of the 256 x 256 rate per CU: the 8-wave
+        // tile only where it is strictly cheaper
+        const int64_t t128 = (int64_t)tiles_m * tiles_n, t2n = (N + BN2 - 1) / BN2;
+        const double cost128 = (double)((t128 + 511) / 512) * 512.0 * (double)(BM * BN) / 0.80;
+        const Nt8pTile t(nt8p_pick_rt(M, t2n, 224), M);
+        if (nt8p_cost(M, t2n, t.rt * 32, NT8P_EFF[t.rt - 7]) < cost128) {
+            auto go = [&](auto OF, auto AC) {
+                launch_nt8p<decltype(OF)::value, decltype(AC)::value, false, 0>(t, t2n, t.t2m * t2n, s, A, B, C, bias, residual, M, N, K, lda, ldb, ldc, ldr, GemmEpi{});
+            };
+            if (!out_f32) go(std::false_type{}, std::false_type{}); else if (accumulate) go(std::true_type{}, std::true_type{}); else go(std::true_type{}, std::false_type{});
             TR1_LAUNCH_CHECK();
         }
     }
-    const int tiles_m = (int)((M + BM - 1) / BM), tiles_n = (int)((N + BN - 1) / BN);
     dim3 grid((unsigned)(tiles_m * tiles_n));
 #define LAUNCH(OF, AC)                                                                                                              \
     hipLaunchKernelGGL((gemm_nt_kernel<OF, AC>), grid, dim3(256), 0, s, (const bf16_t*)A, (const bf16_t*)B, C, (const bf16_t*)bias, \
@@ -1797,30 +1699,9 @@ extern "C" int tr1_gemm_nn_bf16(const void* A, const void* B, void* C, int64_t M
     TR1_CHECK_ARG(K % BK == 0, "gemm_nn: K must be a multiple of 64");
     TR1_CHECK_ARG(N % 8 == 0 && lda % 8 == 0 && ldb % 8 == 0 && ldc % 8 == 0, "gemm_nn: N%8, lda%8, ldb%8, ldc%8 required");
     TR1_CHECK_ARG(M >= 512 && N >= 256, "gemm_nn: M >= 512 and N >= 256 required (smaller problems: transpose B and use gemm_nt)");
-    hipStream_t s = (hipStream_t)stream;
-    auto cost = [&](int64_t bm, double eff) {
-        const int64_t t = ((M + bm - 1) / bm) * ((N + BN2 - 1) / BN2);
-        return (double)((t + 255) / 256) * 256.0 * (double)(bm * BN2) / eff;
-    };
-    static const double eff[4] = {0.94, 1.0, 1.025, 1.03};
-    int rt = 8; double best = cost(256, 1.0);
-    for (int r = 7; r <= 10; ++r) { const double c = cost(r * 32, eff[r - 7]); if (c < best) { best = c; rt = r; } }
-    const int bmx = rt * 32;
-    const int64_t t2m = (M + bmx - 1) / bmx, t2n = (N + BN2 - 1) / BN2;
-    const size_t dyn = 2 * ((size_t)bmx * BK * 2 + TILE2_BYTES) + 4096;
-    static Tr1PerDevice lds;
-    if (lds.first()) {
-        const int mx = (int)(2 * (320 * BK * 2 + TILE2_BYTES)) + 4096;
-        hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_nt8p_kernel<false, false, 7, true>), hipFuncAttributeMaxDynamicSharedMemorySize, mx);
-        hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_nt8p_kernel<false, false, 8, true>), hipFuncAttributeMaxDynamicSharedMemorySize, mx);
-        hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_nt8p_kernel<false, false, 9, true>), hipFuncAttributeMaxDynamicSharedMemorySize, mx);
-        hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_nt8p_kernel<false, false, 10, true>), hipFuncAttributeMaxDynamicSharedMemorySize, mx);
-    }
-    dim3 grid2((unsigned)(t2m * t2n));
-#define LAUNCHNN(R) hipLaunchKernelGGL((gemm_nt8p_kernel<false, false, R, true>), grid2, dim3(512), dyn, s, (const bf16_t*)A, (const bf16_t*)B, C, \
-                                       (const bf16_t*)nullptr, (const bf16_t*)nullptr, M, N, K, lda, ldb, ldc, (int64_t)0, (int)t2m, (int)t2n, GemmEpi{})
-    if (rt == 7) LAUNCHNN(7); else if (rt == 9) LAUNCHNN(9); else if (rt == 10) LAUNCHNN(10); else LAUNCHNN(8);
-#undef LAUNCHNN
+    const int64_t t2n = (N + BN2 - 1) / BN2;
+    const Nt8pTile t(nt8p_pick_rt(M, t2n, 256), M);
+    launch_nt8p<false, false, true, 0>(t, t2n, t.t2m * t2n, (hipStream_t)stream, A, B, C, nullptr, nullptr, M, N, K, lda, ldb, ldc, 0, GemmEpi{});
     TR1_LAUNCH_CHECK();
 }
 
@@ -1834,34 +1715,13 @@ extern "C" int tr1_gemm_nn_acc_f32(const void* A, const void* B, void* C, int64_
     TR1_CHECK_ARG(M >= 512 && N >= 256, "gemm_nn_acc: M >= 512 and N >= 256 required");
     TR1_CHECK_ARG(b_rows >= 1 && b_rows <= K, "gemm_nn_acc: 1 <= b_rows <= K");
     hipStream_t s = (hipStream_t)stream;
-    auto cost = [&](int64_t bm, double eff) {
-        const int64_t t = ((M + bm - 1) / bm) * ((N + BN2 - 1) / BN2);
-        return (double)((t + 255) / 256) * 256.0 * (double)(bm * BN2) / eff;
-    };
-    static const double eff[4] = {0.94, 1.0, 1.025, 1.03};
-    int rt = 8; double best = cost(256, 1.0);
-    for (int r = 7; r <= 10; ++r) { const double c = cost(r * 32, eff[r - 7]); if (c < best) { best = c; rt = r; } }
-    const int bmx = rt * 32;
-    const int64_t t2m = (M + bmx - 1) / bmx, t2n = (N + BN2 - 1) / BN2;
-    const size_t dyn = 2 * ((size_t)bmx * BK * 2 + TILE2_BYTES) + 4096;
-    static Tr1PerDevice lds;
-    if (lds.first()) {
-        const int mx = (int)(2 * (320 * BK * 2 + TILE2_BYTES)) + 4096;
-#define SETN(AC, R) hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_nt8p_kernel<true, AC, R, true>), hipFuncAttributeMaxDynamicSharedMemorySize, mx)
-        SETN(false, 7); SETN(false, 8); SETN(false, 9); SETN(false, 10); SETN(true, 7); SETN(true, 8); SETN(true, 9); SETN(true, 10);
-#undef SETN
-    }
-    dim3 grid2((unsigned)(t2m * t2n));
-#define LAUNCHNA(AC, R) hipLaunchKernelGGL((gemm_nt8p_kernel<true, AC, R, true>), grid2, dim3(512), dyn, s, (const bf16_t*)A, (const bf16_t*)B, C, \
-                                           (const bf16_t*)nullptr, (const bf16_t*)nullptr, M, N, K, lda, ldb, ldc, b_rows, (int)t2m, (int)t2n, GemmEpi{})
-#define LAUNCHNAR(R) do { if (accumulate) LAUNCHNA(true, R); else LAUNCHNA(false, R); } while (0)
-    if (rt == 7) LAUNCHNAR(7); else if (rt == 9) LAUNCHNAR(9); else if (rt == 10) LAUNCHNAR(10); else LAUNCHNAR(8);
-#undef LAUNCHNAR
-#undef LAUNCHNA
+    const int64_t t2n = (N + BN2 - 1) / BN2;
+    const Nt8pTile t(nt8p_pick_rt(M, t2n, 256), M);
+    if (accumulate) launch_nt8p<true, true, true, 0>(t, t2n, t.t2m * t2n, s, A, B, C, nullptr, nullptr, M, N, K, lda, ldb, ldc, b_rows, GemmEpi{});
+    else launch_nt8p<true, false, true, 0>(t, t2n, t.t2m * t2n, s, A, B, C, nullptr, nullptr, M, N, K, lda, ldb, ldc, b_rows, GemmEpi{});
     TR1_LAUNCH_CHECK();
 }
 
-static int epi_pick_rt(int64_t M, int64_t Ntiles);
 // Weight gradient C[M, N] fp32 (+)= A B^T (b_kmajor = 0: B = X^T [N, K]) or A B (b_kmajor = 1: B = X as stored [K, N], its first b_rows rows valid), on the
 // phased 8-wave kernel, which ALSO leaves the sum of squares of every value it stored in sumsq_partials (one float per wave: 8 x blocks; *n_partials receives
 // the count) - in the last micro-step of an accumulation window that is the squared norm of the final gradient, so the optimizer's grad-norm pass does not
@@ -1873,72 +1733,23 @@ extern "C" int tr1_wgrad_f32_sumsq(const void* A, const void* B, void* C, int64_
     TR1_CHECK_ARG(M >= 512 && N >= 256, "wgrad_f32_sumsq: M >= 512 and N >= 256 required (smaller gradients: plain GEMM + tr1_sumsq_accum)");
     TR1_CHECK_ARG(!b_kmajor || (b_rows >= 1 && b_rows <= K), "wgrad_f32_sumsq: 1 <= b_rows <= K");
     TR1_CHECK_ARG(sumsq_partials && n_partials, "wgrad_f32_sumsq: partials buffer required");
-#if !TR1_EPI_LDS
-    // the sums of squares and the bf16 wire copy leave from the LDS-staged epilogue only (store_acc256_lds); a -DTR1_EPI_LDS=0 variant build must not
-    // pretend to have written them (the caller would mark the range as exchanged-ready and all-reduce stale bytes)
-    TR1_CHECK_ARG(false, "wgrad_f32_sumsq: built with TR1_EPI_LDS=0 - the sum-of-squares / wire-copy epilogue does not exist in this build");
-#endif
     hipStream_t s = (hipStream_t)stream;
     const int64_t t2n = (N + BN2 - 1) / BN2;
-    int rt;
-    if (b_kmajor) rt = epi_pick_rt(M, t2n);
-    else {      // the NT dispatch's own choice among the 8-wave tiles (tr1_gemm_nt_bf16), so C is bit-identical to that path
-        auto cost = [&](int64_t bm, double eff) { const int64_t t = ((M + bm - 1) / bm) * t2n; return (double)((t + 255) / 256) * 256.0 * (double)(bm * BN2) / eff; };
-        static const double eff[4] = {0.94, 1.0, 1.025, 1.03};
-        rt = 7; double best = cost(224, eff[0]);
-        for (int r = 8; r <= 10; ++r) { const double c = cost(r * 32, eff[r - 7]); if (c < best) { best = c; rt = r; } }
-    }
-    const int bmx = rt * 32;
-    const int64_t t2m = (M + bmx - 1) / bmx, blocks = t2m * t2n;
+    const Nt8pTile t(nt8p_pick_rt(M, t2n, b_kmajor ? 256 : 224), M);      // each operand form picks like its plain GEMM (tr1_gemm_nn_acc_f32 / the NT dispatch): bit-identical C
+    const int64_t blocks = t.t2m * t2n;
     TR1_CHECK_ARG(blocks * 8 <= partials_capacity, "wgrad_f32_sumsq: partials buffer too small (8 floats per 256-column tile block)");
-    const size_t dyn = 2 * ((size_t)bmx * BK * 2 + TILE2_BYTES) + 4096;
-    {
-        static Tr1PerDevice lds;
-        if (lds.first()) {
-            const int mx = (int)(2 * (320 * BK * 2 + TILE2_BYTES)) + 4096;
-#define SETW(AC, R, KM) hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_nt8p_kernel<true, AC, R, KM>), hipFuncAttributeMaxDynamicSharedMemorySize, mx)
-#define SETWR(R) do { SETW(false, R, false); SETW(true, R, false); SETW(false, R, true); SETW(true, R, true); } while (0)
-            SETWR(7); SETWR(8); SETWR(9); SETWR(10);
-#undef SETWR
-#undef SETW
-        }
-    }
     TR1_CHECK_ARG(!wire_bf16 || ld_wire % 4 == 0, "wgrad_f32_sumsq: ld_wire % 4 required");
     GemmEpi ep{}; ep.p0 = sumsq_partials; ep.p1 = wire_bf16; ep.ld1 = ld_wire;
-#define LW(AC, R, KM) hipLaunchKernelGGL((gemm_nt8p_kernel<true, AC, R, KM>), dim3((unsigned)blocks), dim3(512), dyn, s, (const bf16_t*)A, (const bf16_t*)B, C, \
-                                         (const bf16_t*)nullptr, (const bf16_t*)nullptr, M, N, K, lda, ldb, ldc, (int64_t)(KM ? b_rows : 0), (int)t2m, (int)t2n, ep)
-#define LWR(R) do { if (b_kmajor) { if (accumulate) LW(true, R, true); else LW(false, R, true); } else { if (accumulate) LW(true, R, false); else LW(false, R, false); } } while (0)
-    if (rt == 7) LWR(7); else if (rt == 9) LWR(9); else if (rt == 10) LWR(10); else LWR(8);
-#undef LWR
-#undef LW
+    auto go = [&](auto AC, auto KM) {
+        launch_nt8p<true, decltype(AC)::value, decltype(KM)::value, 0>(t, t2n, blocks, s, A, B, C, nullptr, nullptr, M, N, K, lda, ldb, ldc, b_kmajor ? b_rows : 0, ep);
+    };
+    if (b_kmajor) { if (accumulate) go(std::true_type{}, std::true_type{}); else go(std::false_type{}, std::true_type{}); }
+    else { if (accumulate) go(std::true_type{}, std::false_type{}); else go(std::false_type{}, std::false_type{}); }
     *n_partials = blocks * 8;
     TR1_LAUNCH_CHECK();
 }
 
 // ---- fused-epilogue training GEMMs (EPI 2 / 3 / 4 of gemm_nt8p_kernel) ----------------------------------------------------------------
-static int epi_pick_rt(int64_t M, int64_t Ntiles) {
-    auto cost = [&](int64_t bm, double eff) {
-        const int64_t t = ((M + bm - 1) / bm) * Ntiles;
-        return (double)((t + 255) / 256) * 256.0 * (double)(bm * BN2) / eff;
-    };
-    static const double eff[4] = {0.94, 1.0, 1.025, 1.03};
-    int rt = 8; double best = cost(256, 1.0);
-    for (int r = 7; r <= 10; ++r) { const double c = cost(r * 32, eff[r - 7]); if (c < best) { best = c; rt = r; } }
-    return rt;
-}
-#define EPI_LAUNCH(KERN_ARGS, RTV, ...)                                                                                                   \
-    do { if (RTV == 7) { hipLaunchKernelGGL((gemm_nt8p_kernel<KERN_ARGS(7)>), __VA_ARGS__); }                                             \
-         else if (RTV == 9) { hipLaunchKernelGGL((gemm_nt8p_kernel<KERN_ARGS(9)>), __VA_ARGS__); }                                        \
-         else if (RTV == 10) { hipLaunchKernelGGL((gemm_nt8p_kernel<KERN_ARGS(10)>), __VA_ARGS__); }                                      \
-         else { hipLaunchKernelGGL((gemm_nt8p_kernel<KERN_ARGS(8)>), __VA_ARGS__); } } while (0)
-#define EPI_SETATTR(KERN_ARGS)                                                                                                             \
-    do { static Tr1PerDevice lds_; if (lds_.first()) { const int mx = (int)(2 * (320 * BK * 2 + TILE2_BYTES)) + 4096;                     \
-        hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_nt8p_kernel<KERN_ARGS(7)>), hipFuncAttributeMaxDynamicSharedMemorySize, mx);  \
-        hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_nt8p_kernel<KERN_ARGS(8)>), hipFuncAttributeMaxDynamicSharedMemorySize, mx);  \
-        hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_nt8p_kernel<KERN_ARGS(9)>), hipFuncAttributeMaxDynamicSharedMemorySize, mx);  \
-        hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_nt8p_kernel<KERN_ARGS(10)>), hipFuncAttributeMaxDynamicSharedMemorySize, mx); \
-        } } while (0)
-
 // a[M, I] = silu(x Wg^T) * (x Wu^T) with Wgu = [2I, K] (gate rows, then up rows); gu_out (optional) receives the projection itself [M, 2I] for the backward.
 // Bit-identical to tr1_gemm_nt_bf16 + tr1_swiglu_fwd.
 extern "C" int tr1_gemm_glu_bf16(const void* x, const void* Wgu, const void* bias, void* a_out, void* gu_out, int64_t M, int64_t I, int64_t K, int64_t ldx,
@@ -1946,18 +1757,10 @@ extern "C" int tr1_gemm_glu_bf16(const void* x, const void* Wgu, const void* bia
     TR1_CHECK_ARG(K % BK == 0 && I % 8 == 0 && ldx % 8 == 0 && ldw % 8 == 0 && lda % 8 == 0 && (!gu_out || ldgu % 8 == 0), "gemm_glu: K%64, I%8, ld%8 required");
     TR1_CHECK_ARG(I < (1 << 30), "gemm_glu: I too large");
     if (M == 0 || I == 0) return 0;
-    hipStream_t s = (hipStream_t)stream;
     const int64_t t2n = (I + 127) / 128;
-    const int rt = epi_pick_rt(M, t2n);
-    const int bmx = rt * 32;
-    const int64_t t2m = (M + bmx - 1) / bmx;
-    const size_t dyn = 2 * ((size_t)bmx * BK * 2 + TILE2_BYTES) + 4096;
-#define KA_GLU(R) false, false, R, false, 2
-    EPI_SETATTR(KA_GLU);
+    const Nt8pTile t(nt8p_pick_rt(M, t2n, 256), M);
     GemmEpi ep{}; ep.p0 = gu_out; ep.ld0 = ldgu; ep.i0 = (int)I;
-    EPI_LAUNCH(KA_GLU, rt, dim3((unsigned)(t2m * t2n)), dim3(512), dyn, s, (const bf16_t*)x, (const bf16_t*)Wgu, a_out, (const bf16_t*)bias,
-               (const bf16_t*)nullptr, M, 2 * I, K, ldx, ldw, lda, (int64_t)0, (int)t2m, (int)t2n, ep);
-#undef KA_GLU
+    launch_nt8p<false, false, false, 2>(t, t2n, t.t2m * t2n, (hipStream_t)stream, x, Wgu, a_out, bias, nullptr, M, 2 * I, K, ldx, ldw, lda, 0, ep);
     TR1_LAUNCH_CHECK();
 }
 
@@ -1966,17 +1769,9 @@ extern "C" int tr1_gemm_bias_quickgelu_bf16(const void* x, const void* W, const 
                                             int64_t ldy, void* stream) {
     TR1_CHECK_ARG(K % BK == 0 && N % 8 == 0 && ldx % 8 == 0 && ldw % 8 == 0 && ldy % 8 == 0, "gemm_bias_quickgelu: K%64, N%8, ld%8 required");
     if (M == 0 || N == 0) return 0;
-    hipStream_t s = (hipStream_t)stream;
     const int64_t t2n = (N + BN2 - 1) / BN2;
-    const int rt = epi_pick_rt(M, t2n);
-    const int bmx = rt * 32;
-    const int64_t t2m = (M + bmx - 1) / bmx;
-    const size_t dyn = 2 * ((size_t)bmx * BK * 2 + TILE2_BYTES) + 4096;
-#define KA_QG(R) false, false, R, false, 5
-    EPI_SETATTR(KA_QG);
-    EPI_LAUNCH(KA_QG, rt, dim3((unsigned)(t2m * t2n)), dim3(512), dyn, s, (const bf16_t*)x, (const bf16_t*)W, y, (const bf16_t*)bias,
-               (const bf16_t*)nullptr, M, N, K, ldx, ldw, ldy, (int64_t)0, (int)t2m, (int)t2n, GemmEpi{});
-#undef KA_QG
+    const Nt8pTile t(nt8p_pick_rt(M, t2n, 256), M);
+    launch_nt8p<false, false, false, 5>(t, t2n, t.t2m * t2n, (hipStream_t)stream, x, W, y, bias, nullptr, M, N, K, ldx, ldw, ldy, 0, GemmEpi{});
     TR1_LAUNCH_CHECK();
 }
 
@@ -1988,19 +1783,11 @@ extern "C" int tr1_gemm_qkv_rope_bf16(const void* x, const void* Wqkv, const voi
     TR1_CHECK_ARG(head_dim == 128 && n_heads % 2 == 0 && n_kv % 2 == 0, "gemm_qkv_rope: head_dim 128 and even head counts required");
     TR1_CHECK_ARG(K % BK == 0 && ldx % 8 == 0 && ldw % 8 == 0 && ldq % 8 == 0 && ldk % 8 == 0 && ldv % 8 == 0, "gemm_qkv_rope: K%64, ld%8 required");
     if (M == 0) return 0;
-    hipStream_t s = (hipStream_t)stream;
     const int64_t N = (n_heads + 2 * n_kv) * 128, t2n = N / 256;
-    const int rt = epi_pick_rt(M, t2n);
-    const int bmx = rt * 32;
-    const int64_t t2m = (M + bmx - 1) / bmx;
-    const size_t dyn = 2 * ((size_t)bmx * BK * 2 + TILE2_BYTES) + 4096;
-#define KA_QKV(R) false, false, R, false, 4
-    EPI_SETATTR(KA_QKV);
+    const Nt8pTile t(nt8p_pick_rt(M, t2n, 256), M);
     GemmEpi ep{}; ep.p0 = k_out; ep.ld0 = ldk; ep.p1 = v_out; ep.ld1 = ldv; ep.f0 = (const float*)cosb; ep.f1 = (const float*)sinb;
     ep.i0 = (int)(n_heads * 128); ep.i1 = (int)(n_kv * 128);
-    EPI_LAUNCH(KA_QKV, rt, dim3((unsigned)(t2m * t2n)), dim3(512), dyn, s, (const bf16_t*)x, (const bf16_t*)Wqkv, q_out, (const bf16_t*)bias,
-               (const bf16_t*)nullptr, M, N, K, ldx, ldw, ldq, (int64_t)0, (int)t2m, (int)t2n, ep);
-#undef KA_QKV
+    launch_nt8p<false, false, false, 4>(t, t2n, t.t2m * t2n, (hipStream_t)stream, x, Wqkv, q_out, bias, nullptr, M, N, K, ldx, ldw, ldq, 0, ep);
     TR1_LAUNCH_CHECK();
 }
 
@@ -2013,19 +1800,11 @@ extern "C" int tr1_gemm_qkv_rope_vit_bf16(const void* x, const void* Wqkv, const
     TR1_CHECK_ARG(half % 8 == 0 && half <= 64 && (n_heads * half) % 128 == 0, "gemm_qkv_rope_vit: half % 8 == 0, half <= 64, n_heads * half % 128 == 0 required");
     TR1_CHECK_ARG(K % BK == 0 && ldx % 8 == 0 && ldw % 8 == 0 && ldq % 8 == 0 && ldk % 8 == 0 && ldv % 8 == 0, "gemm_qkv_rope_vit: K%64, ld%8 required");
     if (M == 0) return 0;
-    hipStream_t s = (hipStream_t)stream;
     const int64_t pairs = n_heads * half, N = 6 * pairs, t2n = N / 256;
-    const int rt = epi_pick_rt(M, t2n);
-    const int bmx = rt * 32;
-    const int64_t t2m = (M + bmx - 1) / bmx;
-    const size_t dyn = 2 * ((size_t)bmx * BK * 2 + TILE2_BYTES) + 4096;
-#define KA_VQ(R) false, false, R, false, 7
-    EPI_SETATTR(KA_VQ);
+    const Nt8pTile t(nt8p_pick_rt(M, t2n, 256), M);
     GemmEpi ep{}; ep.p0 = k128; ep.ld0 = ldk; ep.p1 = v128; ep.ld1 = ldv; ep.f0 = (const float*)cosb; ep.f1 = (const float*)sinb;
     ep.i0 = (int)pairs; ep.i1 = (int)half;
-    EPI_LAUNCH(KA_VQ, rt, dim3((unsigned)(t2m * t2n)), dim3(512), dyn, s, (const bf16_t*)x, (const bf16_t*)Wqkv, q128, (const bf16_t*)bias,
-               (const bf16_t*)nullptr, M, N, K, ldx, ldw, ldq, (int64_t)0, (int)t2m, (int)t2n, ep);
-#undef KA_VQ
+    launch_nt8p<false, false, false, 7>(t, t2n, t.t2m * t2n, (hipStream_t)stream, x, Wqkv, q128, bias, nullptr, M, N, K, ldx, ldw, ldq, 0, ep);
     TR1_LAUNCH_CHECK();
 }
 
@@ -2036,18 +1815,10 @@ extern "C" int tr1_gemm_nn_glubwd_bf16(const void* dh, const void* Wd, const voi
     TR1_CHECK_ARG(!dgu_t || (ld_t % 64 == 0 && ld_t >= M && ld_t < M + 64), "gemm_nn_glubwd: dgu^T needs ld_t = tokens rounded up to 64");
     TR1_CHECK_ARG(H % BK == 0 && I % 8 == 0 && lda % 8 == 0 && ldb % 8 == 0 && ldgu % 8 == 0 && lddgu % 8 == 0, "gemm_nn_glubwd: H%64, I%8, ld%8 required");
     TR1_CHECK_ARG(M >= 512 && I >= 256, "gemm_nn_glubwd: M >= 512 and I >= 256 required");
-    hipStream_t s = (hipStream_t)stream;
     const int64_t t2n = (I + BN2 - 1) / BN2;
-    const int rt = epi_pick_rt(M, t2n);
-    const int bmx = rt * 32;
-    const int64_t t2m = (M + bmx - 1) / bmx;
-    const size_t dyn = 2 * ((size_t)bmx * BK * 2 + TILE2_BYTES) + 4096;
-#define KA_GB(R) false, false, R, true, 3
-    EPI_SETATTR(KA_GB);
+    const Nt8pTile t(nt8p_pick_rt(M, t2n, 256), M);
     GemmEpi ep{}; ep.p0 = const_cast<void*>(gu); ep.ld0 = ldgu; ep.i0 = (int)I; ep.p1 = dgu_t; ep.ld1 = ld_t;
-    EPI_LAUNCH(KA_GB, rt, dim3((unsigned)(t2m * t2n)), dim3(512), dyn, s, (const bf16_t*)dh, (const bf16_t*)Wd, dgu, (const bf16_t*)nullptr,
-               (const bf16_t*)nullptr, M, I, H, lda, ldb, lddgu, (int64_t)0, (int)t2m, (int)t2n, ep);
-#undef KA_GB
+    launch_nt8p<false, false, true, 3>(t, t2n, t.t2m * t2n, (hipStream_t)stream, dh, Wd, dgu, nullptr, nullptr, M, I, H, lda, ldb, lddgu, 0, ep);
     TR1_LAUNCH_CHECK();
 }
 
@@ -2085,7 +1856,6 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const float* __restr
 }
 // (RT, S) for a split-K launch: minimise rounds(256 blocks) x tile rows x k tiles per share / efficiency, plus the partial planes' traffic
 static void splitk_pick(int64_t M, int64_t N, int64_t K, int max_s, int* rt_out, int* s_out) {
-    static const double eff[4] = {0.94, 1.0, 1.025, 1.03};
     const int64_t t2n = (N + BN2 - 1) / BN2, nk = K / BK;
     double best = 1e300; int brt = 8, bs = 1;
     for (int r = 7; r <= 10; ++r)
@@ -2093,7 +1863,7 @@ static void splitk_pick(int64_t M, int64_t N, int64_t K, int max_s, int* rt_out,
             const int64_t tiles = ((M + r * 32 - 1) / (r * 32)) * t2n, blocks = tiles * S;
             const double rounds = (double)((blocks + 255) / 256), kshare = (double)((nk + S - 1) / S);
             // block time ~ rows x k tiles; a plane costs one fp32 write + read of M x N per share, priced against the GEMM's per-CU rate (~25 k-tile rows per 4 KB)
-            const double c = rounds * (r * 32) * kshare / eff[r - 7] + (S > 1 ? 0.02 * S * (double)(M * N) / 256.0 / 64.0 : 0.0);
+            const double c = rounds * (r * 32) * kshare / NT8P_EFF[r - 7] + (S > 1 ? 0.02 * S * (double)(M * N) / 256.0 / 64.0 : 0.0);
             if (c < best) { best = c; brt = r; bs = S; }
         }
     *rt_out = brt; *s_out = bs;
@@ -2110,23 +1880,10 @@ extern "C" int tr1_gemm_splitk_bf16(const void* A, const void* B, void* C, const
     splitk_pick(M, N, K, (int)(max_s < 8 ? max_s : 8), &rt, &S);
     if (S < 2) S = 2;        // (the caller asked for the split form: thin outputs; S = 1 would be the plain GEMM)
     const int64_t t2n = (N + BN2 - 1) / BN2;
-    const int bmx = rt * 32;
-    const int64_t t2m = (M + bmx - 1) / bmx;
-    const size_t dyn = 2 * ((size_t)bmx * BK * 2 + TILE2_BYTES) + 4096;
+    const Nt8pTile t(rt, M);
     GemmEpi ep{}; ep.ld0 = M * N; ep.i0 = S;
-#define KA_SK(R) true, false, R, false, 6
-#define KA_SKM(R) true, false, R, true, 6
-    if (b_kmajor) {
-        EPI_SETATTR(KA_SKM);
-        EPI_LAUNCH(KA_SKM, rt, dim3((unsigned)(S * t2m * t2n)), dim3(512), dyn, s, (const bf16_t*)A, (const bf16_t*)B, ws_f32, (const bf16_t*)nullptr,
-                   (const bf16_t*)nullptr, M, N, K, lda, ldb, N, (int64_t)0, (int)t2m, (int)t2n, ep);
-    } else {
-        EPI_SETATTR(KA_SK);
-        EPI_LAUNCH(KA_SK, rt, dim3((unsigned)(S * t2m * t2n)), dim3(512), dyn, s, (const bf16_t*)A, (const bf16_t*)B, ws_f32, (const bf16_t*)nullptr,
-                   (const bf16_t*)nullptr, M, N, K, lda, ldb, N, (int64_t)0, (int)t2m, (int)t2n, ep);
-    }
-#undef KA_SK
-#undef KA_SKM
+    if (b_kmajor) launch_nt8p<true, false, true, 6>(t, t2n, S * t.t2m * t2n, s, A, B, ws_f32, nullptr, nullptr, M, N, K, lda, ldb, N, 0, ep);
+    else launch_nt8p<true, false, false, 6>(t, t2n, S * t.t2m * t2n, s, A, B, ws_f32, nullptr, nullptr, M, N, K, lda, ldb, N, 0, ep);
     hipLaunchKernelGGL(splitk_reduce_kernel, dim3(tr1_grid_1d(M * N / 8, 256, 2048)), dim3(256), 0, s, (const float*)ws_f32, S, M * N,
                        (const bf16_t*)bias, (const bf16_t*)residual, ldr, (bf16_t*)C, ldc, M, N);
     TR1_LAUNCH_CHECK();
@@ -2170,28 +1927,10 @@ extern "C" int tr1_lmhead_lse_fwd(const void* hn, const void* W, const void* tar
     if (M == 0) return 0;
     hipStream_t s = (hipStream_t)stream;
     const int64_t ncb = N / 64;
-    auto cost = [&](int64_t bm, double eff) {
-        const int64_t t = ((M + bm - 1) / bm) * ((N + BN2 - 1) / BN2);
-        return (double)((t + 255) / 256) * 256.0 * (double)(bm * BN2) / eff;
-    };
-    static const double eff[4] = {0.94, 1.0, 1.025, 1.03};
-    int rt = 8; double best = cost(256, 1.0);
-    for (int r = 7; r <= 10; ++r) { const double c = cost(r * 32, eff[r - 7]); if (c < best) { best = c; rt = r; } }
-    const int bmx = rt * 32;
-    const int64_t t2m = (M + bmx - 1) / bmx, t2n = (N + BN2 - 1) / BN2;
-    const size_t dyn = 2 * ((size_t)bmx * BK * 2 + TILE2_BYTES) + 4096;
-    static Tr1PerDevice lds;
-    if (lds.first()) {
-        const int mx = (int)(2 * (320 * BK * 2 + TILE2_BYTES)) + 4096;
-#define SETL(R) hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_nt8p_kernel<false, false, R, false, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, mx)
-        SETL(7); SETL(8); SETL(9); SETL(10);
-#undef SETL
-    }
-    dim3 grid2((unsigned)(t2m * t2n));
-#define LAUNCHL(R) hipLaunchKernelGGL((gemm_nt8p_kernel<false, false, R, false, 1>), grid2, dim3(512), dyn, s, (const bf16_t*)hn, (const bf16_t*)W, part_ws, \
-                                      (const bf16_t*)targets, (const bf16_t*)nullptr, M, N, K, lda, ldb, ncb + 1, (int64_t)0, (int)t2m, (int)t2n, GemmEpi{})
-    if (rt == 7) LAUNCHL(7); else if (rt == 9) LAUNCHL(9); else if (rt == 10) LAUNCHL(10); else LAUNCHL(8);
-#undef LAUNCHL
+    const int64_t t2n = (N + BN2 - 1) / BN2;
+    const Nt8pTile t(nt8p_pick_rt(M, t2n, 256), M);
+    // EPI 1: `bias` carries the int32 targets, C the float4 partials with ldc = column blocks per row + the target's slot
+    launch_nt8p<false, false, false, 1>(t, t2n, t.t2m * t2n, s, hn, W, part_ws, targets, nullptr, M, N, K, lda, ldb, ncb + 1, 0, GemmEpi{});
     hipLaunchKernelGGL(lse_combine_kernel, dim3((unsigned)M), dim3(256), 0, s, (const f32x4_t*)part_ws, ncb, (float*)logp, (float*)ent, (float*)lse);
     TR1_LAUNCH_CHECK();
 }
@@ -2395,35 +2134,18 @@ extern "C" int tr1_gemm_skinny_fixup(const void* A, const void* B, void* C, cons
     hipLaunchKernelGGL((gemm_skinny_kernel<WV, UN, NC, MGR>), dim3((unsigned)groups, (unsigned)ks), dim3(WV * 64), 0, s,            \
                        (const bf16_t*)A, (const bf16_t*)B, (bf16_t*)C, (float*)nullptr, (const bf16_t*)bias, (const bf16_t*)residual, \
                        (int)M, N, K, lda, ldb, ldc, ldr, tiles, ks > 1 ? cnt : (int*)nullptr)
-    if (c56 && mg == 2) {       // round 5, 17 .. 32 rows: 56-column blocks as well (256 blocks), whose 11 KiB stages leave room for a seventh wave
-        static Tr1PerDevice lds;
-        constexpr int DYN = 7 * 2 * (7 * 1024 + 2 * 2048) + 16;
-        if (lds.first()) hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_skinny_lds_fix_kernel<7, 2, 7>), hipFuncAttributeMaxDynamicSharedMemorySize, DYN);
-        hipLaunchKernelGGL((gemm_skinny_lds_fix_kernel<7, 2, 7>), dim3((unsigned)groups, (unsigned)ks), dim3(448), DYN, s, (const bf16_t*)A, (const bf16_t*)B,
-                           (bf16_t*)C, (const bf16_t*)bias, (const bf16_t*)residual, (int)M, N, K, lda, ldb, ldc, ldr, tiles, cnt);
-    }
-    else if (mg == 2 && ncol == 4 && ks > 1 && (K / ks) % 64 == 0 && N % 64 == 0) {       // 17 .. 32 rows: 12 KiB stages, 6 waves
-        static Tr1PerDevice lds;
-        if (lds.first()) hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_skinny_lds_fix_kernel<6, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, 6 * 2 * 12288 + 16);
-        hipLaunchKernelGGL((gemm_skinny_lds_fix_kernel<6, 2>), dim3((unsigned)groups, (unsigned)ks), dim3(384), 6 * 2 * 12288 + 16, s, (const bf16_t*)A, (const bf16_t*)B,
-                           (bf16_t*)C, (const bf16_t*)bias, (const bf16_t*)residual, (int)M, N, K, lda, ldb, ldc, ldr, tiles, cnt);
-    }
-    else if (c56) {
-        static Tr1PerDevice lds;
-        constexpr int DYN = 7 * 2 * (7 * 1024 + 2048) + 16;
-        if (lds.first()) hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_skinny_lds_fix_kernel<7, 1, 7>), hipFuncAttributeMaxDynamicSharedMemorySize, DYN);
-        hipLaunchKernelGGL((gemm_skinny_lds_fix_kernel<7, 1, 7>), dim3((unsigned)groups, (unsigned)ks), dim3(448), DYN, s, (const bf16_t*)A, (const bf16_t*)B,
-                           (bf16_t*)C, (const bf16_t*)bias, (const bf16_t*)residual, (int)M, N, K, lda, ldb, ldc, ldr, tiles, cnt);
-    }
-    else if (mg == 1 && ncol == 4 && ks > 1 && (K / ks) % 64 == 0 && N % 64 == 0) {       // <= 16 rows: 10 KiB stages, 7 waves
-        static Tr1PerDevice lds;
-        if (lds.first()) hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_skinny_lds_fix_kernel<7>), hipFuncAttributeMaxDynamicSharedMemorySize, 7 * 2 * 10240 + 16);
-        hipLaunchKernelGGL((gemm_skinny_lds_fix_kernel<7>), dim3((unsigned)groups, (unsigned)ks), dim3(448), 7 * 2 * 10240 + 16, s, (const bf16_t*)A, (const bf16_t*)B,
-                           (bf16_t*)C, (const bf16_t*)bias, (const bf16_t*)residual, (int)M, N, K, lda, ldb, ldc, ldr, tiles, cnt);
-    }
+    // the LDS-streamed forms (WV waves, MGR row groups, NWI * 8 weight rows per stage; one LDS size each)
+#define SKL(WV, MGR, NWI, DYN)                                                                                                                \
+    tr1_launch<gemm_skinny_lds_fix_kernel<WV, MGR, NWI>>(dim3((unsigned)groups, (unsigned)ks), dim3(WV * 64), DYN, DYN, s, (const bf16_t*)A, (const bf16_t*)B, \
+                                                         (bf16_t*)C, (const bf16_t*)bias, (const bf16_t*)residual, (int)M, N, K, lda, ldb, ldc, ldr, tiles, cnt)
+    if (c56 && mg == 2) SKL(7, 2, 7, 7 * 2 * (7 * 1024 + 2 * 2048) + 16);       // round 5, 17 .. 32 rows: 56-column blocks as well (256 blocks), whose 11 KiB stages leave room for a seventh wave
+    else if (mg == 2 && ncol == 4 && ks > 1 && (K / ks) % 64 == 0 && N % 64 == 0) SKL(6, 2, 8, 6 * 2 * 12288 + 16);       // 17 .. 32 rows: 12 KiB stages, 6 waves
+    else if (c56) SKL(7, 1, 7, 7 * 2 * (7 * 1024 + 2048) + 16);
+    else if (mg == 1 && ncol == 4 && ks > 1 && (K / ks) % 64 == 0 && N % 64 == 0) SKL(7, 1, 8, 7 * 2 * 10240 + 16);       // <= 16 rows: 10 KiB stages, 7 waves
     else if (mg == 1) { if (ncol == 4) SKF(4, 2, 4, 1); else SKF(4, 4, 2, 1); }
     else if (mg == 2) { if (ncol == 4) SKF(4, 2, 4, 2); else SKF(4, 2, 2, 2); }
     else SKF(4, 2, 2, 4);
+#undef SKL
 #undef SKF
     TR1_LAUNCH_CHECK();
 }

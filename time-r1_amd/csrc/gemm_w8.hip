@@ -820,19 +820,13 @@ extern "C" int tr1_gemm_skinny_w8a8(const void* x, const void* lnw, const void* 
         if (glu && M <= 16 && K % 512 == 0 && (nw == 7 || nw == 4 || nw == 3) && N % 16 == 0) {
             constexpr int RING = 3;
             const size_t dyn = (size_t)nw * RING * 4096 + (2 * nw * 2 * 16 * 17 + nw * 16) * sizeof(float) + (size_t)nw * (4096 + 1024);      // + one x stage and the norm-weight KiB per wave
-            static Tr1PerDevice lds;
-            if (lds.first()) {
-                const int mx = 7 * RING * 4096 + (2 * 7 * 2 * 16 * 17 + 7 * 16) * (int)sizeof(float) + 7 * (4096 + 1024);
-                hipFuncSetAttribute(reinterpret_cast<const void*>(&norm_glu_lds_f8_kernel<7, RING>), hipFuncAttributeMaxDynamicSharedMemorySize, mx);
-                hipFuncSetAttribute(reinterpret_cast<const void*>(&norm_glu_lds_f8_kernel<4, RING>), hipFuncAttributeMaxDynamicSharedMemorySize, mx);
-                hipFuncSetAttribute(reinterpret_cast<const void*>(&norm_glu_lds_f8_kernel<3, RING>), hipFuncAttributeMaxDynamicSharedMemorySize, mx);
-            }
+            constexpr int mx = 7 * RING * 4096 + (2 * 7 * 2 * 16 * 17 + 7 * 16) * (int)sizeof(float) + 7 * (4096 + 1024);      // the 7-wave form's: one limit for the three
             const int64_t NP = N / 16, n_cu = tr1_cu_count();
             const unsigned grid = (unsigned)(NP < n_cu ? NP : n_cu);
-#define G8L(NWV) hipLaunchKernelGGL((norm_glu_lds_f8_kernel<NWV, RING>), dim3(grid), dim3(NWV * 64), dyn, s, (const bf16_t*)x, (const bf16_t*)lnw, \
-                                    (const unsigned char*)W_fp8, (const float*)wscale, (bf16_t*)out, (int)M, N, K, ldx, ldw, ldc, eps, N)
-            if (nw == 7) G8L(7); else if (nw == 4) G8L(4); else G8L(3);
-#undef G8L
+            tr1_dispatch<7, 4, 3>((int)nw, [&](auto NW) {
+                tr1_launch<norm_glu_lds_f8_kernel<decltype(NW)::value, RING>>(dim3(grid), dim3(decltype(NW)::value * 64), dyn, mx, s, (const bf16_t*)x, (const bf16_t*)lnw,
+                                                                            (const unsigned char*)W_fp8, (const float*)wscale, (bf16_t*)out, (int)M, N, K, ldx, ldw, ldc, eps, N);
+            });
             TR1_LAUNCH_CHECK();
         }
     }
@@ -844,13 +838,10 @@ extern "C" int tr1_gemm_skinny_w8a8(const void* x, const void* lnw, const void* 
 // x image (32 bytes per k: 16 rows of bf16) + the norm weight, which arrives in whole 1 KiB DMA instructions (the last one may run past K * 2 bytes)
 #define W8X_LDS(K_) ((int64_t)(K_) * 32 + (((int64_t)(K_) * 2 + 1023) / 1024) * 1024)
         const bool x_ok = mg == 1 && K < 8192 && K % 128 == 0 && W8X_LDS(K) <= 128 * 1024 && (int64_t)M * ldx * 2 < 0x7fffffffLL;
-#define W8X(NC, NRM) do {                                                                                                                        \
-            static Tr1PerDevice lds_;                                                                                                            \
-            if (lds_.first()) hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_skinny_w8a8_kernel<4, 2, NC, 1, NRM, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024); \
-            hipLaunchKernelGGL((gemm_skinny_w8a8_kernel<4, 2, NC, 1, NRM, false, true>), dim3((unsigned)((N + 16 * NC - 1) / (16 * NC))), dim3(256), (size_t)W8X_LDS(K), s, \
+#define W8X(NC, NRM)                                                                                                                             \
+            tr1_launch<gemm_skinny_w8a8_kernel<4, 2, NC, 1, NRM, false, true>>(dim3((unsigned)((N + 16 * NC - 1) / (16 * NC))), dim3(256), (size_t)W8X_LDS(K), 128 * 1024, s, \
                                (const bf16_t*)x, (const bf16_t*)lnw, (const unsigned char*)W_fp8, (const float*)wscale, (bf16_t*)out, (const bf16_t*)bias,  \
-                               (const bf16_t*)residual, (int)M, N, K, ldx, ldw, ldc, ldr, eps, N);                                              \
-        } while (0)
+                               (const bf16_t*)residual, (int)M, N, K, ldx, ldw, ldc, ldr, eps, N)
         if (lnw) { if (x_ok) W8X(2, true); else W8_MG(4, 2, 2, true, false); }
         else if (K >= 8192) W8_MG(8, 2, 1, false, false);
         else { if (x_ok) W8X(1, false); else W8_MG(4, 2, 1, false, false); }
@@ -878,9 +869,7 @@ extern "C" int tr1_gemm_skinny_fixup_w8a8(const void* x, const void* W_fp8, cons
         float* tiles56 = (float*)ws_f32;
         int* cnt56 = (int*)(tiles56 + KS * g56 * 4 * 256);
         const size_t dyn56 = WV7 * 2 * (7 * 1024 + 4096) + 16;
-        static Tr1PerDevice lds;
-        if (lds.first()) hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_skinny_lds_fix_f8_kernel<WV7, 7>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn56);
-        hipLaunchKernelGGL((gemm_skinny_lds_fix_f8_kernel<WV7, 7>), dim3((unsigned)g56, KS), dim3(WV7 * 64), dyn56, (hipStream_t)stream, (const bf16_t*)x,
+        tr1_launch<gemm_skinny_lds_fix_f8_kernel<WV7, 7>>(dim3((unsigned)g56, KS), dim3(WV7 * 64), dyn56, (int)dyn56, (hipStream_t)stream, (const bf16_t*)x,
                            (const unsigned char*)W_fp8, (const float*)wscale, (bf16_t*)out, (const bf16_t*)bias, (const bf16_t*)residual, (int)M, N, K, ldx,
                            ldw, ldc, ldr, tiles56, cnt56);
         TR1_LAUNCH_CHECK();
@@ -890,9 +879,7 @@ extern "C" int tr1_gemm_skinny_fixup_w8a8(const void* x, const void* W_fp8, cons
     float* tiles = (float*)ws_f32;
     int* cnt = (int*)(tiles + KS * groups * 4 * 256);
     const size_t dyn = WV * 2 * 12288 + 16;
-    static Tr1PerDevice lds;
-    if (lds.first()) hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_skinny_lds_fix_f8_kernel<WV>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn);
-    hipLaunchKernelGGL((gemm_skinny_lds_fix_f8_kernel<WV>), dim3((unsigned)groups, KS), dim3(WV * 64), dyn, (hipStream_t)stream, (const bf16_t*)x,
+    tr1_launch<gemm_skinny_lds_fix_f8_kernel<WV>>(dim3((unsigned)groups, KS), dim3(WV * 64), dyn, (int)dyn, (hipStream_t)stream, (const bf16_t*)x,
                        (const unsigned char*)W_fp8, (const float*)wscale, (bf16_t*)out, (const bf16_t*)bias, (const bf16_t*)residual, (int)M, N, K, ldx,
                        ldw, ldc, ldr, tiles, cnt);
     TR1_LAUNCH_CHECK();

@@ -137,16 +137,12 @@ extern "C" int tr1_gemm_oproj_frag(const void* Xfrag, const void* W, const void*
     const size_t dyn = (size_t)(K / 64) * (lng ? 1024 : 2048) + (size_t)OPJ_WAVES * mg * 16 * 17 * 4 + 16;
     hipStream_t s = (hipStream_t)stream;
     const dim3 grid((unsigned)(N / cols));
-#define OPJ_LAUNCH(KERNEL)                                                                                                                            \
-    do {                                                                                                                                              \
-        static Tr1PerDevice lds_;                                                                                                                     \
-        if (lds_.first()) hipFuncSetAttribute(reinterpret_cast<const void*>(&KERNEL), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 512);   \
-        hipLaunchKernelGGL((KERNEL), grid, dim3(OPJ_WAVES * 64), dyn, s, (const bf16_t*)Xfrag, (const bf16_t*)W, (const bf16_t*)residual, (bf16_t*)C, (int)M, N, K, \
-                           ldw, ldr, ldc, cols);                                                                                                      \
-    } while (0)
-    if (lng) OPJ_LAUNCH((oproj_frag_kernel<1, OPJ_MAXS_LONG, 1>));
-    else if (mg == 1) OPJ_LAUNCH((oproj_frag_kernel<1, OPJ_MAXS, 2>));
-    else OPJ_LAUNCH((oproj_frag_kernel<2, OPJ_MAXS, 2>));
+#define OPJ_LAUNCH(...)                                                                                                                               \
+    tr1_launch<oproj_frag_kernel<__VA_ARGS__>>(grid, dim3(OPJ_WAVES * 64), dyn, 160 * 1024 - 512, s, (const bf16_t*)Xfrag, (const bf16_t*)W, (const bf16_t*)residual, \
+                                               (bf16_t*)C, (int)M, N, K, ldw, ldr, ldc, cols)
+    if (lng) OPJ_LAUNCH(1, OPJ_MAXS_LONG, 1);
+    else if (mg == 1) OPJ_LAUNCH(1, OPJ_MAXS, 2);
+    else OPJ_LAUNCH(2, OPJ_MAXS, 2);
 #undef OPJ_LAUNCH
     TR1_LAUNCH_CHECK();
 }

@@ -4,6 +4,7 @@
 #include <stdint.h>
 #include <stdio.h>
 #include <string.h>
+#include <type_traits>
 
 typedef unsigned short bf16_t;  // raw bfloat16 bits
 
@@ -119,12 +120,30 @@ inline int tr1_cu_count() {
     }
     return cached[dev];
 }
-// once per device and call site - the launchers raise their kernels' dynamic-LDS limits behind it:
-//     static Tr1PerDevice lds; if (lds.first()) hipFuncSetAttribute(..., hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+// once per device: tr1_launch keeps one per kernel
 struct Tr1PerDevice {
     bool done[16] = {};
     bool first() { const int d = tr1_device(); if (done[d]) return false; return done[d] = true; }
 };
+// Every launch that may need more than 64 KiB of dynamic LDS: tr1_launch<kernel>(grid, block, dyn, lds_cap, stream, kernel arguments...).  lds_cap is the most
+// the kernel is ever launched with (dyn itself where there is one size); above 64 KiB the kernel's limit is raised to it on the kernel's first launch on each
+// device - the template holds one Tr1PerDevice per kernel, so a kernel that is launched is a kernel that was raised.  A failed raise surfaces at the launch
+// (TR1_LAUNCH_CHECK).  The kernel is a function pointer here: its default arguments do not apply, pass every argument.
+template <auto Kernel, class... A>
+inline void tr1_launch(dim3 grid, dim3 block, size_t dyn, int lds_cap, hipStream_t s, A... args) {
+    static Tr1PerDevice raised;
+    if (lds_cap > 64 * 1024 && raised.first())
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, lds_cap);
+    hipLaunchKernelGGL(Kernel, grid, block, dyn, s, args...);
+}
+// f(std::integral_constant<int, V>{}) for the V of the list that equals v (the last of the list where none does): a run-time tile height or stage count
+// becomes a template argument in one place
+template <int V0, int... Vs, class F>
+inline void tr1_dispatch(int v, F f) {
+    if constexpr (sizeof...(Vs) == 0) f(std::integral_constant<int, V0>{});
+    else if (v == V0) f(std::integral_constant<int, V0>{});
+    else tr1_dispatch<Vs...>(v, f);
+}
 
 // dw[c] += sum_b part[b][c] (the fixed-order second level of every per-block column reduction: norm weights, bias gradients), b in ascending order inside each of 16 row groups, groups combined in a fixed order.  64 columns per block.
 static __global__ __launch_bounds__(1024) void norm_dw_reduce_kernel(const float* __restrict__ part, float* __restrict__ dw, int nblk, int cols) {
