@@ -251,6 +251,13 @@ int64_t tr1_lmhead_lse_workspace_floats(int64_t M, int64_t N);
 int tr1_logp_bwd(const void* logits, int64_t ld, const void* targets, const void* lse, const void* dlogp, void* dlogits, int64_t ld_out, int64_t R, int64_t V, void* stream);
 /* ref: timer1_trainer.py:635-639 (k3 KL), :713-737 (both loss branches).  out3 = {loss, mean masked kl, sum mask}. */
 int tr1_grpo_loss(const void* logp, const void* ref_logp, const void* mask, const void* adv, void* dlogp, void* out3, void* row_len, void* row_kl, int64_t G, int64_t C, float beta, int use_grpo, float grad_scale, void* stream);
+/* ref: timer1_trainer.py:730-737 (the PPO-clip branch written out: coef_1 = exp(logp - old_logp), coef_2 = clamp(coef_1, 1 - eps_low, 1 + eps_high)) for
+ * the 2nd .. num_iterations-th update on one rollout, where old_logp is the policy that was current when the completions were drawn; :635-639 (k3 KL).
+ * tok_weight (may be null = 1): constant per-token weight on the advantage term.  out8 = {loss, mean masked kl, sum mask, low / high / either clip
+ * fraction, masked mean of rho - 1 - log rho, max rho}.  One block per row, row partials in ws (TR1_GRPO_LOSS_RATIO_WS_WORDS 4-byte words, zero before the
+ * first call; every call leaves it zero), folded in a fixed order: no floating-point atomics, bit-identical from call to call.  Masked positions are never read. */
+#define TR1_GRPO_LOSS_RATIO_WS_WORDS 528
+int tr1_grpo_loss_ratio(const void* logp, const void* old_logp, const void* ref_logp /*may be null*/, const void* tok_weight /*may be null*/, const void* mask, const void* adv, void* dlogp, void* out8, void* row_len, void* row_kl, void* ws, int64_t G, int64_t C, float beta, int use_grpo, float eps_low, float eps_high, float grad_scale, void* stream);
 /* ref: model.generate(do_sample=True, temperature, top_k) at timer1_trainer.py:568-573.  tokens[row*tok_ld + *step_ptr] = draw.
  * group_rows > 0: rows [b*group_rows, (b+1)*group_rows) belong to prompt b and draw from the stream (seed + b*seed_stride, row % group_rows, step),
  * so several prompts sampled in one launch get exactly the tokens of one launch per prompt. */

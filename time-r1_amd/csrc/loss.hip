@@ -5,6 +5,7 @@
 //   logp / entropy : src/time_r1/rl/timer1_trainer.py:458-481  (log_softmax, gather, H = -sum p log p)
 //   KL (k3)        : :635-639        loss (both branches): :713-737       sampling: HF generate(do_sample, temperature, top_k, top_p, min_p, repetition_penalty)
 #include "tr1_common.h"
+#include "../../include/timer1_hip.h"
 
 // ---------------------------------------------------------------------------------------------------------------------
 // One 256-thread block per row; single pass, online (max, sum exp, sum exp*x).  logits bf16 [R, V] with row stride ld.
@@ -123,6 +124,137 @@ __global__ __launch_bounds__(256) void grpo_loss_kernel(const float* __restrict_
         }
         if (!use_grpo) loss = num / tot_mask;
         out[0] = loss; out[1] = klm; out[2] = tot_mask;
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// GRPO loss + d loss / d logp against an OLD policy (several updates per rollout: rho = exp(logp - old_logp) != 1), the PPO-clip branch of
+// timer1_trainer.py:730-737 written out.  One 256-thread block per completion row:
+//   1. the block counts the live tokens its normalisation needs (its own row for use_grpo, the whole grid for the clip branch: integer
+//      counts, so every block gets the same exact number in any order),
+//   2. one pass over the row writes dlogp and accumulates the row's partial sums,
+//   3. the partials go to ws (release fence), a ticket counter names the last block to finish (acquire fence), and that block alone folds the G rows - one row per lane
+//      of its first wave, the fixed tree of wave_sum - into out8.  No floating-point atomics anywhere: same inputs, same bits.
+// Masked positions are skipped by selection (their logp / old_logp / ref_logp are never read), dlogp is 0 there.
+//   w = tok_weight or 1 (a constant)                 kl = exp(ref - logp) - (ref - logp) - 1
+//   use_grpo : l = -(w*rho*A - beta*kl), loss = mean_g( sum_t l*m / sum_t m ),  d l / d logp = -w*A*rho + beta*(1 - exp(ref - logp))
+//   clip     : l = -w*min(rho*A, clamp(rho, 1-el, 1+eh)*A) + beta*kl, loss = sum l*m / sum m; the advantage term's gradient is -w*A*rho
+//              except where (A > 0 and rho > 1+eh) or (A < 0 and rho < 1-el), where the clamped side is the smaller one and it is 0
+// out8 = {loss, mean_g masked-mean kl, sum mask, low / high / either clip fraction (flag*mask summed over sum mask), masked mean of
+//         rho - 1 - log rho, largest rho};  ws = [ticket, pad to 16 words, G x 8 row partials], TR1_GRPO_LOSS_RATIO_WS_WORDS words, ticket left at 0.
+// ---------------------------------------------------------------------------------------------------------------------
+constexpr int GLR_HEAD = 16, GLR_ROW = 8, GLR_MAX_G = 64;
+constexpr int GLR_WS_WORDS = GLR_HEAD + GLR_ROW * GLR_MAX_G;
+__global__ __launch_bounds__(256) void grpo_loss_ratio_kernel(const float* __restrict__ logp, const float* __restrict__ old_logp,
+                                                              const float* __restrict__ ref_logp, const float* __restrict__ tok_weight,
+                                                              const int* __restrict__ mask, const float* __restrict__ adv, float* __restrict__ dlogp,
+                                                              float* __restrict__ out, float* __restrict__ row_len, float* __restrict__ row_kl,
+                                                              float* ws, int G, int C, float beta, int use_grpo, float eps_low, float eps_high,
+                                                              float grad_scale) {
+    __shared__ float red[16];
+    __shared__ float part[GLR_ROW][4];
+    __shared__ int s_last;
+    const int g = blockIdx.x, tid = threadIdx.x;
+    const int* mrow = mask + (int64_t)g * C;
+    // ---- 1. live-token counts
+    float cnt_row = 0.f, cnt_all = 0.f;
+    for (int t = tid; t < C; t += 256) cnt_row += (mrow[t] != 0) ? 1.f : 0.f;
+    cnt_row = block_sum(cnt_row, red);
+    if (!use_grpo) {
+        const int64_t n = (int64_t)G * C;
+        int c = 0;
+        if ((reinterpret_cast<uintptr_t>(mask) & 15) == 0) {
+            const int64_t n4 = n >> 2;
+            const int4* m4 = reinterpret_cast<const int4*>(mask);
+            for (int64_t i = tid; i < n4; i += 256) { const int4 v = m4[i]; c += (v.x != 0) + (v.y != 0) + (v.z != 0) + (v.w != 0); }
+            for (int64_t i = (n4 << 2) + tid; i < n; i += 256) c += (mask[i] != 0);
+        } else {
+            for (int64_t i = tid; i < n; i += 256) c += (mask[i] != 0);
+        }
+        cnt_all = block_sum((float)c, red);      // per-thread counts and their sum stay below 2^24: exact in fp32
+    }
+    const float norm = use_grpo ? 1.f / (cnt_row * (float)G) : 1.f / cnt_all;
+    // ---- 2. the row
+    const float A = adv[g];
+    const float lo = 1.f - eps_low, hi = 1.f + eps_high;
+    float s_l = 0.f, s_kl = 0.f, n_low = 0.f, n_high = 0.f, n_any = 0.f, s_k3 = 0.f, mx = 0.f;
+    for (int t = tid; t < C; t += 256) {
+        const int64_t i = (int64_t)g * C + t;
+        float dl = 0.f;
+        if (mrow[t] != 0) {
+            const float lp = logp[i];
+            const float d = lp - old_logp[i];
+            const float rho = expf(d);
+            const float w = tok_weight ? tok_weight[i] : 1.f;
+            float kl = 0.f, dkl = 0.f;
+            if (ref_logp) { const float r = ref_logp[i] - lp; const float e = __expf(r); kl = e - r - 1.f; dkl = 1.f - e; }
+            const bool low = (A < 0.f) && (rho < lo), high = (A > 0.f) && (rho > hi);
+            float term = rho * A, dterm = rho * A;
+            if (!use_grpo) {
+                term = fminf(term, fminf(fmaxf(rho, lo), hi) * A);
+                if (low || high) dterm = 0.f;
+            }
+            s_l += -w * term + beta * kl;
+            s_kl += kl;
+            n_low += low ? 1.f : 0.f; n_high += high ? 1.f : 0.f; n_any += (low || high) ? 1.f : 0.f;
+            s_k3 += expm1f(d) - d;
+            mx = fmaxf(mx, rho);
+            dl = (-w * dterm + beta * dkl) * norm * grad_scale;
+        }
+        dlogp[i] = dl;
+    }
+    {
+        float v[GLR_ROW] = {cnt_row, s_l, s_kl, n_low, n_high, n_any, s_k3, 0.f};
+#pragma unroll
+        for (int k = 0; k < GLR_ROW - 1; ++k) v[k] = (k == 0) ? v[k] : wave_sum(v[k]);
+        v[GLR_ROW - 1] = wave_max(mx);
+        if ((tid & 63) == 0) {
+#pragma unroll
+            for (int k = 0; k < GLR_ROW; ++k) part[k][tid >> 6] = v[k];
+        }
+    }
+    __syncthreads();
+    unsigned* ticket = reinterpret_cast<unsigned*>(ws);
+    float* rows = ws + GLR_HEAD;
+    if (tid < GLR_ROW) {
+        const float a = part[tid][0], b = part[tid][1], c = part[tid][2], d = part[tid][3];
+        const float r = (tid == 0) ? a : (tid == GLR_ROW - 1) ? fmaxf(fmaxf(a, b), fmaxf(c, d)) : ((a + b) + (c + d));
+        rows[g * GLR_ROW + tid] = r;
+        if (tid == 0) row_len[g] = r;
+        if (tid == 2 && row_kl) row_kl[g] = r;
+    }
+    // publish: the writers' stores have left the wave, ONE agent-scope release, then the ticket (the counter form of the in-launch hand-off; the explicit
+    // waits stay beside the fences).  The block that draws ticket G - 1 has every row's partials behind its one agent-scope acquire, on whichever XCDs they ran.
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    if (tid == 0) {
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        const unsigned prev = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        s_last = (prev == (unsigned)(G - 1));
+        if (s_last) {
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        }
+    }
+    __syncthreads();
+    if (!s_last || tid >= 64) return;
+    // ---- 3. the last block: lane = row, fixed-order fold
+    const volatile float* vr = rows;
+    const bool on = tid < G;
+    float p[GLR_ROW];
+#pragma unroll
+    for (int k = 0; k < GLR_ROW; ++k) p[k] = on ? vr[tid * GLR_ROW + k] : 0.f;
+    const float tot = wave_sum(p[0]);
+    const float per_row_l = on ? p[1] / p[0] / (float)G : 0.f, per_row_kl = on ? p[2] / p[0] / (float)G : 0.f;
+    const float loss = use_grpo ? wave_sum(per_row_l) : wave_sum(p[1]) / tot;
+    const float klm = wave_sum(per_row_kl);
+    const float f_low = wave_sum(p[3]) / tot, f_high = wave_sum(p[4]) / tot, f_any = wave_sum(p[5]) / tot;
+    const float k3 = wave_sum(p[6]) / tot;
+    const float rmax = wave_max(p[7]);
+    if (tid == 0) {
+        out[0] = loss; out[1] = klm; out[2] = tot; out[3] = f_low; out[4] = f_high; out[5] = f_any; out[6] = k3; out[7] = rmax;
+        *ticket = 0u;         // zero again for the next call
     }
 }
 
@@ -740,6 +872,18 @@ extern "C" int tr1_grpo_loss(const void* logp, const void* ref_logp, const void*
     hipLaunchKernelGGL(grpo_loss_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, (const float*)logp, (const float*)ref_logp,
                        (const int*)mask, (const float*)adv, (float*)dlogp, (float*)out3, (float*)row_len, (float*)row_kl, (int)G, (int)C, beta,
                        use_grpo, grad_scale);
+    TR1_LAUNCH_CHECK();
+}
+static_assert(GLR_WS_WORDS == TR1_GRPO_LOSS_RATIO_WS_WORDS, "include/timer1_hip.h states the workspace size of tr1_grpo_loss_ratio");
+extern "C" int tr1_grpo_loss_ratio(const void* logp, const void* old_logp, const void* ref_logp, const void* tok_weight, const void* mask,
+                                   const void* adv, void* dlogp, void* out8, void* row_len, void* row_kl, void* ws, int64_t G, int64_t C, float beta,
+                                   int use_grpo, float eps_low, float eps_high, float grad_scale, void* stream) {
+    TR1_CHECK_ARG(G >= 1 && G <= GLR_MAX_G, "grpo_loss_ratio: G must be in [1, 64]");
+    TR1_CHECK_ARG(C >= 1 && G * C < ((int64_t)1 << 24), "grpo_loss_ratio: need 1 <= C and G * C < 2^24");
+    TR1_CHECK_ARG(logp && old_logp && mask && adv && dlogp && out8 && row_len && ws, "grpo_loss_ratio: null argument");
+    hipLaunchKernelGGL(grpo_loss_ratio_kernel, dim3((unsigned)G), dim3(256), 0, (hipStream_t)stream, (const float*)logp, (const float*)old_logp,
+                       (const float*)ref_logp, (const float*)tok_weight, (const int*)mask, (const float*)adv, (float*)dlogp, (float*)out8,
+                       (float*)row_len, (float*)row_kl, (float*)ws, (int)G, (int)C, beta, use_grpo, eps_low, eps_high, grad_scale);
     TR1_LAUNCH_CHECK();
 }
 extern "C" int64_t tr1_sample_workspace_words(int64_t rows) { return rows * SAMP_WS_WORDS; }

@@ -64,7 +64,7 @@ class GRPOCore:
             self.work["decode_ms_events"] += e0.elapsed_time(e1)
         self.roll.decode_events = []
 
-    def _count_update(self, st, reused_prefill):
+    def _count_update(self, st, reused_prefill, with_ref=True):
         t = self.cfg.text
         P, G, C = st.P, self.G, self.C
         M = P + G * C
@@ -72,8 +72,8 @@ class GRPOCore:
         pairs_all = P * (P + 1) / 2.0 + pairs_c
         head = 2.0 * G * C * t.vocab_size * t.hidden
         fl = (self._llm_flops(G * C, pairs_c) if reused_prefill else self._llm_flops(M, pairs_all)) + head        # policy forward
-        if self.beta != 0.0:
-            fl += self._llm_flops(M, pairs_all) + head                                                           # reference-policy forward
+        if self.beta != 0.0 and with_ref:
+            fl += self._llm_flops(M, pairs_all) + head                                                           # reference-policy forward (a replay reuses its log-probs)
         lin_all = self._llm_flops(M, 0.0)
         fl += 2.0 * lin_all + 2.5 * (self._llm_flops(M, pairs_all) - lin_all) + 2.0 * head                       # backward (dgrad + wgrad; flash backward = 5 products)
         self.work["train_flops"] += fl
@@ -165,13 +165,22 @@ class GRPOCore:
     def _to_gc(self, st, x_pred_order):
         return x_pred_order[st.inv_perm].view(st.layout.G, st.layout.C)
 
-    def forward_logps(self, st):
-        """Policy log-probs / entropy (activations saved for backward) and reference log-probs (no grad)."""
+    def forward_logps(self, st, replay=False):
+        """Policy log-probs / entropy (activations saved for backward) and reference log-probs (no grad).
+        replay=True: a further update on the SAME rollout after the weights have moved (GRPOConfig.num_iterations > 1).  The vision merger (and the tower,
+        when it trains) runs again on the kept features / pixels, the decoder takes the full-sequence path - the rollout's saved prefill belongs to the old
+        weights - and the reference-policy forward is skipped: its weights are frozen, so st.ref_logp of the first pass still holds."""
         eng, ops = self.eng, self.ops
-        self._packed_inputs(st)
         tr = eng.params.train
+        if replay:
+            if eng.params.train_vit:
+                st.feats = eng.vit_features(st.pixels, st.grid)[0]
+            st.vid_embeds, st.merger_ctx = eng.merger_fwd(tr, st.feats, save=True, perm=st.vis_perm)
+            st.prefill = None
+        else:
+            self._packed_inputs(st)
         pf = getattr(st, "prefill", None)
-        self._count_update(st, pf is not None and pf[0] is not None)
+        self._count_update(st, pf is not None and pf[0] is not None, with_ref=not replay)
         if pf is not None and pf[0] is not None:
             # continuation: only the G*C completion rows; the prompt rows' activations and K/V come from the rollout's prefill
             P, M = st.P, st.layout.M
@@ -190,10 +199,16 @@ class GRPOCore:
             st.prefill = None
         else:
             h0 = eng.embed(tr, st.ids_packed, st.vid_embeds, st.vid_rows)
-            hL, st.llm_ctx = eng.llm_fwd(tr, h0, st.cos, st.sin, st.masks, save=True, tail_from=eng.tail_rows_from(st.P, st.layout.M))    # the head reads rows >= P - 1 only (pred_rows)
+            # a replay writes its saved activations into the engine's slot-0 buffer set (free: every earlier backward of the window has been enqueued), like the
+            # prefill + continuation pair of the first pass - no second set beside the pooled one
+            bufs = eng.alloc_ctx_bufs(st.layout.M, slot=0) if replay else None
+            hL, st.llm_ctx = eng.llm_fwd(tr, h0, st.cos, st.sin, st.masks, save=True, bufs=bufs,
+                                         tail_from=eng.tail_rows_from(st.P, st.layout.M))    # the head reads rows >= P - 1 only (pred_rows)
         logp, ent, st.head_ctx = eng.head_fwd(tr, hL, st.pred_rows, st.targets, save=True)
         st.logp = self._to_gc(st, logp).contiguous()
         st.entropy = self._to_gc(st, ent).contiguous()
+        if replay:
+            return
         st.ref_logp = None
         if self.beta != 0.0:
             ra = self.ref_arena
@@ -206,18 +221,27 @@ class GRPOCore:
             st.ref_logp = self._to_gc(st, rlogp).contiguous()
 
     # ------------------------------------------------------------------------------------------------------- phase 4
-    def loss_backward(self, st, completion_mask, advantages, grad_scale=1.0, grad_sync=None, tok_weight=None):
+    def loss_backward(self, st, completion_mask, advantages, grad_scale=1.0, grad_sync=None, tok_weight=None, old_logp=None, eps=(0.2, 0.2),
+                      keep_pixels=False):
         """completion_mask int32 [G, C], advantages fp32 [G] (device). Accumulates grads into the trainable arena.
         grad_sync: a dist.GradSync in its begin() state when this is the LAST micro-step of the accumulation window - parameter ranges
         are handed to the all-reduce as soon as their gradients are final, overlapping the exchange with the rest of the backward.
+        old_logp (fp32 [G, C]): the log-probs of the policy that drew the completions, for a replayed update (forward_logps(replay=True)): the loss is then
+        the ratio kernel's (rho = exp(logp - old_logp) clipped to [1 - eps[0], 1 + eps[1]], tok_weight inside the kernel) and out8 is returned in place of out3.
+        keep_pixels: further replays of this state follow (the training tower's backward reads st.pixels again).
         Returns (out3 = [loss, mean kl, sum mask], row_len [G]) as device tensors."""
         eng, ops = self.eng, self.ops
         tr = eng.params.train
         hook = None
         if grad_sync is not None and grad_sync.active:
             hook = lambda i: grad_sync.ready(*tr.range_of("l%d." % i))
-        dlogp, out3, row_len, _ = ops.grpo_loss(st.logp, st.ref_logp, completion_mask, advantages, self.beta, self.use_grpo, grad_scale)
-        if tok_weight is not None:
+        if old_logp is not None:
+            tw = None if tok_weight is None else tok_weight.to(torch.float32).contiguous()
+            dlogp, out3, row_len, _ = ops.grpo_loss_ratio(st.logp, old_logp, st.ref_logp, completion_mask, advantages, self.beta, self.use_grpo,
+                                                          float(eps[0]), float(eps[1]), grad_scale, tok_weight=tw)
+        else:
+            dlogp, out3, row_len, _ = ops.grpo_loss(st.logp, st.ref_logp, completion_mask, advantages, self.beta, self.use_grpo, grad_scale)
+        if tok_weight is not None and old_logp is None:
             # optional truncated importance weight rho[g, t] (a constant) on the advantage term, for completions drawn from a quantised sampling
             # policy: l = -rho * A + beta * kl = l_plain + (1 - rho) * A, same normalisation as the kernel.  None (the default) leaves the
             # reference algebra untouched - this branch is then not executed at all.
@@ -243,7 +267,8 @@ class GRPOCore:
             # Its gradient ranges are handed to the exchange by grad_sync.finish() (GradSync / ShardSync cover every range nobody announced).
             _, _, vctx = eng.vit_features(st.pixels, st.grid, save=True)
             eng.vit_bwd(vctx, dfeats)
-            st.pixels = None
+            if not keep_pixels:
+                st.pixels = None
         return out3, row_len
 
 

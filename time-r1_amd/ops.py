@@ -745,6 +745,35 @@ class HipOps:
                     float(beta), int(bool(use_grpo)), float(grad_scale), self._s())
         return dlogp, out3, row_len, row_kl
 
+    @staticmethod
+    def grpo_loss_ratio_ws_words():
+        """Workspace of tr1_grpo_loss_ratio in 4-byte words, as include/timer1_hip.h states it (the library checks the same number when it is built)."""
+        import re
+        from .hip import HEADER
+        return int(re.search(r"#define\s+TR1_GRPO_LOSS_RATIO_WS_WORDS\s+(\d+)", open(HEADER).read()).group(1))
+
+    def grpo_loss_ratio(self, logp, old_logp, ref_logp, mask, adv, beta, use_grpo, eps_low, eps_high, grad_scale=1.0, tok_weight=None):
+        """The GRPO loss against an old policy (rho = exp(logp - old_logp), PPO clip) -> (dlogp, out8, row_len, row_kl); out8 = [loss, mean kl, sum mask,
+        low / high / either clip fraction, k3 distance to the old policy, max rho].  One block per row; the workspace (ticket + row partials) is zeroed
+        ONCE per stream - the kernel leaves it zero - so two calls on the same inputs give the same bits."""
+        G, C = logp.shape
+        assert logp.dtype == F32 and old_logp.dtype == F32 and mask.dtype == I32 and adv.dtype == F32
+        assert logp.is_contiguous() and old_logp.is_contiguous() and mask.is_contiguous() and old_logp.shape == logp.shape and mask.shape == logp.shape
+        assert adv.numel() == G and adv.is_contiguous()
+        for t in (ref_logp, tok_weight):
+            assert t is None or (t.dtype == F32 and t.is_contiguous() and t.shape == logp.shape)
+        key = ("grpo_loss_ratio", self._s())
+        ws = self._ws.get(key)
+        if ws is None:
+            ws = self._ws[key] = torch.zeros(self.grpo_loss_ratio_ws_words(), dtype=F32, device=self.device)
+        dlogp = self.empty(G, C, dtype=F32)
+        out8 = self.empty(8, dtype=F32)
+        row_len = self.empty(G, dtype=F32)
+        row_kl = self.empty(G, dtype=F32)
+        self.L.call("tr1_grpo_loss_ratio", _p(logp), _p(old_logp), _p(ref_logp), _p(tok_weight), _p(mask), _p(adv), _p(dlogp), _p(out8), _p(row_len),
+                    _p(row_kl), _p(ws), G, C, float(beta), int(bool(use_grpo)), float(eps_low), float(eps_high), float(grad_scale), self._s())
+        return dlogp, out8, row_len, row_kl
+
     def sample_tokens(self, logits, temperature, top_k, seed, step_dev, tokens, finished, eos_id, pad_id, stop_at_eos, u_out=None, group_rows=0,
                       seed_stride=0, next_ids=None, top_p=1.0, min_p=0.0):
         """next_ids (int32 [rows], optional): also receives the drawn tokens (the next decode step's embedding gather reads it: no copy kernel).

@@ -352,6 +352,35 @@ def grpo_loss(logp: Tensor, ref_logp: Optional[Tensor], completion_mask: Tensor,
     return out3[0], out3[1]
 
 
+@_op("grpo_loss_ratio")
+def grpo_loss_ratio_op(logp: Tensor, old_logp: Tensor, ref_logp: Optional[Tensor], tok_weight: Optional[Tensor], mask: Tensor, adv: Tensor, beta: float,
+                       use_grpo: bool, eps_low: float, eps_high: float, grad_scale: float) -> Tuple[Tensor, Tensor, Tensor]:
+    dlogp, out8, row_len, _ = _ops(logp).grpo_loss_ratio(logp, old_logp, ref_logp, mask, adv, beta, use_grpo, eps_low, eps_high, grad_scale, tok_weight=tok_weight)
+    return out8, dlogp, row_len
+
+
+@grpo_loss_ratio_op.register_fake
+def _(logp, old_logp, ref_logp, tok_weight, mask, adv, beta, use_grpo, eps_low, eps_high, grad_scale):
+    return logp.new_empty(8), torch.empty_like(logp), logp.new_empty(logp.shape[0])
+
+
+grpo_loss_ratio_op.register_autograd(lambda ctx, dout8, _d1, _d2: (ctx.saved_tensors[0] * dout8[0],) + (None,) * 10,
+                                     setup_context=lambda ctx, inputs, output: ctx.save_for_backward(output[1]))
+
+
+def grpo_loss_ratio(logp: Tensor, old_logp: Tensor, ref_logp: Optional[Tensor], completion_mask: Tensor, advantages: Tensor, beta: float, use_grpo: bool,
+                    epsilon_low: float = 0.2, epsilon_high: Optional[float] = None, tok_weight: Optional[Tensor] = None) -> Tuple[Tensor, Tensor, Tensor]:
+    """-> (loss, mean k3-KL, stats).  The loss of reference timer1_trainer.py:730-737 against the log-probs `old_logp` of the policy that drew the completions
+    (a later one of several updates on one rollout): rho = exp(logp - old_logp), clipped to [1 - epsilon_low, 1 + epsilon_high] on the side the advantage's
+    sign makes matter.  stats = [low, high, either clip fraction, masked mean of rho - 1 - log rho, max rho].  Differentiable in logp only."""
+    eh = epsilon_low if epsilon_high is None else epsilon_high
+    out8, _, _ = torch.ops.timer1.grpo_loss_ratio(logp.contiguous(), old_logp.detach().float().contiguous(), ref_logp,
+                                                  None if tok_weight is None else tok_weight.detach().float().contiguous(),
+                                                  completion_mask.to(I32).contiguous(), advantages.float().contiguous(), float(beta), bool(use_grpo),
+                                                  float(epsilon_low), float(eh), 1.0)
+    return out8[0], out8[1], out8[3:]
+
+
 # ============================================================================================================ sampler / optimizer / video
 @_op("sample_tokens", mutates_args=("tokens", "finished"))
 def sample_tokens(logits: Tensor, temperature: float, top_k: int, seed: int, step: Tensor, tokens: Tensor, finished: Tensor, eos_id: int, pad_id: int,
@@ -416,7 +445,7 @@ def _(frames_u8, out_h, out_w, k_pad):
 
 
 OP_NAMES = ["rmsnorm_fwd", "rmsnorm_bwd", "swiglu_fwd", "swiglu_bwd", "linear_fwd", "linear_bwd", "rope_fwd", "mrope_table", "attn_fwd", "attn_bwd",
-            "logp_entropy_fwd", "logp_bwd", "lmhead_logp_entropy", "grpo_loss", "sample_tokens", "sample_tokens_filtered", "penalize_logits", "mark_seen_ids",
+            "logp_entropy_fwd", "logp_bwd", "lmhead_logp_entropy", "grpo_loss", "grpo_loss_ratio", "sample_tokens", "sample_tokens_filtered", "penalize_logits", "mark_seen_ids",
             "mark_seen_drawn", "adamw_step", "video_preprocess"]
 
 

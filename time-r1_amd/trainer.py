@@ -98,9 +98,23 @@ class GRPOConfig:
             raise ValueError("min_p must be None or in [0, 1], got %r" % (self.min_p,))
         if not 0.0 < self.repetition_penalty < float("inf"):
             raise ValueError("repetition_penalty must be a positive number, got %r" % (self.repetition_penalty,))
+        if int(self.num_iterations) != self.num_iterations or int(self.num_iterations) < 1:
+            raise ValueError("num_iterations must be an integer >= 1, got %r" % (self.num_iterations,))
+        self.num_iterations = int(self.num_iterations)
+        self.epsilon_low = float(self.epsilon_low)
+        if not 0.0 < self.epsilon_low < 1.0:
+            raise ValueError("epsilon_low must be in (0, 1), got %r" % (self.epsilon_low,))
+        if self.epsilon_high is not None:
+            self.epsilon_high = float(self.epsilon_high)
+            if not 0.0 < self.epsilon_high < float("inf"):
+                raise ValueError("epsilon_high must be None or a positive number, got %r" % (self.epsilon_high,))
 
     beta: float = 0.04
     use_grpo: bool = False
+    num_iterations: int = 1                 # mu of the GRPO paper (trl.GRPOConfig.num_iterations): optimizer steps per rollout.  Steps 2 .. mu replay the window's
+                                            # completions against the log-probs of the policy that drew them (PPO clip); 1 = one update per rollout, as the reference runs
+    epsilon_low: float = 0.2                # clip range of the probability ratio: [1 - epsilon_low, 1 + epsilon_high] (the reference hard-codes 0.2 / 0.2, :388-393)
+    epsilon_high: Optional[float] = None    # None = same as epsilon_low
     prompt_type: str = "v1"
     fix_vit: bool = True
     stop_at_eos: bool = False               # the reference's GenerationConfig carries no eos_token_id (a6): always C tokens
@@ -371,7 +385,13 @@ class TimeR1_Trainer:
         self.num_generations = args.num_generations
         self.use_grpo = args.use_grpo
         self.prompt_type = args.prompt_type
-        self.epsilon_low = self.epsilon_high = 0.2          # hard-coded in the reference (:388-393)
+        self.epsilon_low = float(getattr(args, "epsilon_low", 0.2))          # the reference hard-codes 0.2 / 0.2 (:388-393): the defaults
+        eh = getattr(args, "epsilon_high", None)
+        self.epsilon_high = self.epsilon_low if eh is None else float(eh)
+        self.num_iterations = int(getattr(args, "num_iterations", 1) or 1)
+        self._check_reuse_args()
+        self._reuse = None                   # num_iterations > 1: what the window's micro-steps keep for the replayed updates (optimizer_window)
+        self._replays_since_log = 0
         self.train_dataset, self.eval_dataset = train_dataset, eval_dataset
         self.data_collator = lambda features: features       # identity (:360-361)
         self.callbacks = list(callbacks or [])
@@ -414,6 +434,18 @@ class TimeR1_Trainer:
         self.is_deepspeed_enabled = False
         self._micro = 0
         self._loss_acc, self._tr_loss_last, self._steps_per_epoch = [], 0.0, 0
+
+    def _check_reuse_args(self):
+        """num_iterations > 1 against the settings it cannot work with (checked at construction and again when train() starts: args is mutable)."""
+        a, mu = self.args, self.num_iterations
+        if mu <= 1:
+            return
+        if self.use_grpo:
+            raise ValueError("use_grpo=True has no clip on the probability ratio: an update on a rollout of an older policy would be unbounded; "
+                             "num_iterations > 1 needs use_grpo=False")
+        if getattr(a, "save_strategy", "no") == "steps" and a.save_steps and int(a.save_steps) % mu != 0:
+            raise ValueError("save_steps (%d) must be a multiple of num_iterations (%d): checkpoints are written after the last update on a rollout"
+                             % (a.save_steps, mu))
 
     @staticmethod
     def _wants_shard(args, dp=None):
@@ -575,8 +607,12 @@ class TimeR1_Trainer:
                 tokw = torch.exp(d).clamp(max=float(self._is_cap))
         if last_in_window:      # the final gradient passes through this backward's weight-gradient epilogues: they leave its squared norm (AdamWFlat.step)
             self.engine.norm_sink = self.optimizer.norm_sink_begin(self.engine)
+        extra = {"tok_weight": tokw} if tokw is not None else {}
+        if self._reuse is not None:      # num_iterations > 1: keep what the replayed updates read (the policy's log-probs are the OLD policy's from now on)
+            self._reuse.append(dict(st=st, old_logp=st.logp.clone(), mask=mask_dev, adv=adv_dev, tokw=tokw))
+            extra["keep_pixels"] = True
         try:
-            out3, row_len = self.core.loss_backward(st, mask_dev, adv_dev, scale, grad_sync=sync, **({"tok_weight": tokw} if tokw is not None else {}))
+            out3, row_len = self.core.loss_backward(st, mask_dev, adv_dev, scale, grad_sync=sync, **extra)
         finally:
             self.engine.norm_sink = None
         self._clock.mark("backward")
@@ -615,9 +651,12 @@ class TimeR1_Trainer:
         if not pend:
             return
         G, nf = self.num_generations, len(self.reward_funcs)
-        nm = pend[0]["mvals"].shape[1] if pend[0]["mvals"] is not None else 0
+        first = next((r for r in pend if not r.get("replay")), None)
+        nm = first["mvals"].shape[1] if first is not None and first["mvals"] is not None else 0
         dev = torch.stack([r["dev"] for r in pend])                     # [n, nd] on the device
-        host = np.stack([np.concatenate([r["length"], r["rpf"].reshape(-1), r["reward"], r["std"]] +
+        blank = np.zeros(3 * G + G * nf + G * nm, dtype=np.float32)      # replayed updates carry device values only
+        host = np.stack([blank if r.get("replay") else
+                         np.concatenate([r["length"], r["rpf"].reshape(-1), r["reward"], r["std"]] +
                                         ([r["mvals"].reshape(-1)] if nm else [])).astype(np.float32) for r in pend])
         if self.dp.enabled:
             both = torch.cat([self.ops.tensor(host, torch.float32), dev], 1)
@@ -629,6 +668,20 @@ class TimeR1_Trainer:
         o_dev = o_mv + G * nm
         for i, r in enumerate(pend):
             v = allv[:, i]                                               # [world, L]: rank-major, like accelerator.gather's concatenation
+            if r.get("replay"):
+                # a further update on a rollout already counted: the loss-side keys only (dev = loss, kl, entropy, low, high, either, k3 to the old policy);
+                # rewards, lengths, drift and the generated-token count belong to the rollout and were appended by its first update
+                if self.beta != 0.0:
+                    M["kl"].append(v[:, o_dev + 1].mean().item())
+                M["generation_entropy"].append(v[:, o_dev + 2].mean().item())
+                g_low, g_high, g_reg = v[:, o_dev + 3], v[:, o_dev + 4], v[:, o_dev + 5]
+                M["clip_ratio/low_mean"].append(g_low.nanmean().item())
+                M["clip_ratio/low_min"].append(g_low[~g_low.isnan()].min().item() if (~g_low.isnan()).any() else float("nan"))
+                M["clip_ratio/high_mean"].append(g_high.nanmean().item())
+                M["clip_ratio/high_max"].append(g_high[~g_high.isnan()].max().item() if (~g_high.isnan()).any() else float("nan"))
+                M["clip_ratio/region_mean"].append(g_reg.nanmean().item())
+                M["policy_kl_old"].append(v[:, o_dev + 6].mean().item())
+                continue
             M["completion_length"].append(v[:, :G].reshape(-1).mean().item())
             rpf = v[:, o_rpf:o_rew].reshape(-1, nf).mean(0)
             for j, fn in enumerate(self.reward_funcs):
@@ -685,12 +738,61 @@ class TimeR1_Trainer:
     def optimizer_window(self, window, t_start=None):
         """One optimizer step = the unit `train()` repeats: the window's micro-steps, the (clipped, fused) AdamW step with the data-parallel
         gradient exchange, LR schedule, `on_step_end`, logging and step-based checkpoints (TF trainer.py:1892-1961 inner loop body).
-        `bench.py` times exactly this method."""
-        a = self.args
+        `bench.py` times exactly this method.  With `num_iterations` = mu > 1 one call takes mu optimizer steps on the window's one rollout: the first by the
+        same code, the others by `_replay_window`; returns the last step's gradient norm."""
+        mu = self.num_iterations
         if self._t_last_log is None:         # driven without train() (bench.py): the throughput keys count from the first window
             self._t_last_log, self._micro_at_log = time.perf_counter(), self._micro
-        self._loss_acc.extend(self.accumulation_window(window))
+        self._reuse = [] if mu > 1 else None
+        try:
+            self._loss_acc.extend(self.accumulation_window(window))
+        finally:
+            recs, self._reuse = self._reuse, None
         self._micro += len(window)
+        gnorm = self._optimizer_step(t_start, save=(mu == 1))
+        # num_iterations > 1: mu - 1 further optimizer steps on the same completions.  Each replays every micro-step of the window (policy forward on the moved
+        # weights, ratio loss against the kept log-probs, backward) with the first pass's last-in-window handling, so every rank runs the same collectives
+        for it in range(1, mu):
+            if self.control.should_training_stop or (self.state.max_steps > 0 and self.state.global_step >= self.state.max_steps):
+                break
+            self._loss_acc.extend(self._replay_window(recs, more=(it < mu - 1)))
+            gnorm = self._optimizer_step(t_start, save=(it == mu - 1))
+        return gnorm
+
+    def _replay_window(self, recs, more):
+        """One further optimizer step's micro-steps on a window already rolled out (recs: what _step_finish kept).  No decode loop, no reference-policy
+        forward, no reward calls; more: another replay follows (the states keep their pixels)."""
+        clock = self._clock
+        clock.mark("start")
+        scale = 1.0 / max(1, self.args.gradient_accumulation_steps)
+        losses = []
+        for i, r in enumerate(recs):
+            last, st = i == len(recs) - 1, r["st"]
+            self.core.forward_logps(st, replay=True)
+            clock.mark("logps")
+            sync = None
+            if last and self.dp.enabled:
+                sync = self.optimizer.sync
+                sync.begin()
+            maskf = r["mask"].to(torch.float32)
+            ent_mean = ((st.entropy.float() * maskf).sum(1) / maskf.sum(1).clamp(min=1)).mean()
+            if last:
+                self.engine.norm_sink = self.optimizer.norm_sink_begin(self.engine)
+            try:
+                out8, _ = self.core.loss_backward(st, r["mask"], r["adv"], scale, grad_sync=sync, tok_weight=r["tokw"], old_logp=r["old_logp"],
+                                                  eps=(self.epsilon_low, self.epsilon_high), keep_pixels=more)
+            finally:
+                self.engine.norm_sink = None
+            clock.mark("backward")
+            o = out8.float()
+            self._pending.append(dict(replay=True, dev=torch.cat([o[:2], ent_mean.reshape(1).float(), o[3:7]])))      # loss, kl, entropy, clip x 3, k3 to the old policy
+            self._replays_since_log += 1
+            losses.append(o[0])
+        return losses
+
+    def _optimizer_step(self, t_start, save=True):
+        """AdamW step + schedule + callbacks + logging (+ step-based checkpoint when `save`: with num_iterations > 1 only after a rollout's last update)."""
+        a = self.args
         gnorm = self.optimizer.step(lr=self._lr(self.state.global_step))
         self._clock.mark("optimizer")
         self.state.global_step += 1
@@ -705,7 +807,7 @@ class TimeR1_Trainer:
             mean_loss = float(torch.stack([torch.as_tensor(x).float().reshape(()) for x in losses]).mean()) if losses else 0.0
             self._tr_loss_last = mean_loss
             self.log({"loss": round(mean_loss, 6), "grad_norm": float(gnorm), "learning_rate": self._lr(self.state.global_step - 1)}, t_start)
-        if a.save_strategy == "steps" and a.save_steps and self.state.global_step % a.save_steps == 0:
+        if save and a.save_strategy == "steps" and a.save_steps and self.state.global_step % a.save_steps == 0:
             self._save_checkpoint()
         return gnorm
 
@@ -801,12 +903,16 @@ class TimeR1_Trainer:
     def train(self, resume_from_checkpoint=None):
         """The loop that replaces transformers.Trainer.train for main.py:589-625: accumulation windows of `gradient_accumulation_steps`
         micro-steps, optimizer step + LR schedule, callbacks, checkpoints, and HF's resume arithmetic: a checkpoint at global step s
-        restarts in epoch s // steps_per_epoch after skipping the (s % steps_per_epoch) * GA batches that epoch already consumed; the
+        restarts in epoch s // steps_per_epoch after skipping the (s % steps_per_epoch) * GA batches that epoch already consumed (with
+        num_iterations = mu > 1 a loader window yields mu optimizer steps: steps_per_epoch = windows_per_epoch * mu, ((s // mu) % windows_per_epoch) * GA batches); the
         run ends at state.max_steps (main.py sets max_steps = global_step + epochs * steps_per_epoch before resuming, :600-618)."""
         a = self.args
         loader = self.get_train_dataloader()
         ga = max(1, a.gradient_accumulation_steps)
-        steps_per_epoch = max(len(loader) // ga, 1)
+        self._check_reuse_args()
+        mu = self.num_iterations
+        windows_per_epoch = max(len(loader) // ga, 1)
+        steps_per_epoch = windows_per_epoch * mu              # optimizer steps: one loader window yields num_iterations of them
         self._steps_per_epoch = steps_per_epoch
         if self.state.max_steps <= 0:
             self.state.max_steps = a.max_steps if a.max_steps > 0 else math.ceil(a.num_train_epochs * steps_per_epoch)
@@ -818,7 +924,7 @@ class TimeR1_Trainer:
             start_step = self._load_checkpoint(ckpt)
         epoch = start_step // steps_per_epoch                  # fully trained epochs: the sampler is advanced, nothing is replayed
         loader.skip_epochs(epoch)
-        skip_batches = (start_step % steps_per_epoch) * ga      # consumed part of the current epoch (skipped before any prefetch work)
+        skip_batches = ((start_step // mu) % windows_per_epoch) * ga      # consumed part of the current epoch (skipped before any prefetch work)
         self.state.epoch = self.state.global_step / steps_per_epoch
         for cb in self.callbacks:
             _call(cb, "on_train_begin", a, self.state, self.control)
@@ -888,7 +994,9 @@ class TimeR1_Trainer:
         roll_ms = ph.get("rollout", 0.0)
         if roll_ms > 0 and toks > 0:
             out["rollout_tokens_per_sec"] = toks / (roll_ms * 1e-3)
-        if n_micro > 0:
+        n_replay, self._replays_since_log = self._replays_since_log, 0      # replayed micro-steps: phase time and FLOPs, no new samples or tokens
+        n_work = n_micro + n_replay
+        if n_work > 0:
             w = self.core.drain_work()
             dec_ms = w.get("decode_ms_events") or 0.0
             if w.get("decode_bytes") and roll_ms > 0:
@@ -899,7 +1007,7 @@ class TimeR1_Trainer:
                 # log-prob forwards + backward: MFMA-bound family, peak 2.5 PFLOP/s dense bf16
                 out["perf/train_mfma_frac"] = w["train_flops"] / (mm_ms * 1e-3) / 2.5e15
         for k, v in ph.items():
-            out["perf/ms_%s" % k] = v / max(n_micro, 1)
+            out["perf/ms_%s" % k] = v / max(n_work, 1)
             self.phase_ms_total[k] += v
         self._t_last_log, self._micro_at_log = now, self._micro
         return out

@@ -90,7 +90,7 @@ def main():
     if ckpt and os.path.isdir(ckpt):
         st = json.load(open(os.path.join(ckpt, "trainer_state.json")))
         ga = max(1, args.gradient_accumulation_steps)
-        per_epoch = max(len(trainer.get_train_dataloader()) // ga, 1)
+        per_epoch = max(len(trainer.get_train_dataloader()) // ga, 1) * max(1, args.num_iterations)      # optimizer steps: num_iterations per loader window
         trainer.state.max_steps = int(st["global_step"]) + math.ceil(args.num_train_epochs * per_epoch)
         trainer.train(resume_from_checkpoint=ckpt)
     else:
