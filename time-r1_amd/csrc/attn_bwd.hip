@@ -20,15 +20,10 @@
 #ifdef TR1_PROBE
 __device__ unsigned long long* tr1_bwd_probe = nullptr;
 extern "C" int probe_bwd_set_ptr(void* ptr) { return (int)hipMemcpyToSymbol(HIP_SYMBOL(tr1_bwd_probe), &ptr, sizeof(ptr)); }
-// the stamps of a tile stay in scalar registers and are written in one burst by BWD_FLUSH: reading an s_memtime result costs an
-// s_waitcnt lgkmcnt(0), which would drain the LDS reads in flight at the stamped point
-#define BWD_STAMPS unsigned long long bwd_st_[8] = {0, 0, 0, 0, 0, 0, 0, 0}
-#define BWD_STAMP(it, slot) do { bwd_st_[slot] = __builtin_amdgcn_s_memtime(); } while (0)
+// (ATT_STAMPS / ATT_STAMP of attn_common.h; the stamps of a tile are written in one burst by BWD_FLUSH)
 #define BWD_FLUSH(it) do { if (tr1_bwd_probe && blockIdx.x == 0 && blockIdx.z == 2 && (threadIdx.x & 63) == 0 && (it) < 64) { \
-    _Pragma("unroll") for (int s_ = 0; s_ < 8; ++s_) tr1_bwd_probe[(((threadIdx.x >> 6) * 64 + (it)) * 8 + s_)] = bwd_st_[s_]; } } while (0)
+    _Pragma("unroll") for (int s_ = 0; s_ < 8; ++s_) tr1_bwd_probe[(((threadIdx.x >> 6) * 64 + (it)) * 8 + s_)] = att_st_[s_]; } } while (0)
 #else
-#define BWD_STAMPS do { } while (0)
-#define BWD_STAMP(it, slot) do { } while (0)
 #define BWD_FLUSH(it) do { } while (0)
 #endif
 
@@ -88,13 +83,6 @@ __global__ __launch_bounds__(256) void attn_delta_kernel(const bf16_t* __restric
         const float l0 = lse[(int64_t)h * T + t];
         lse2[(int64_t)h * T + t] = (l0 == NEG_INF) ? INFINITY : l0 * 1.4426950408889634f;
     }
-}
-
-// Transposed MFMA operands straight from a ROW-major LDS tile: ds_read_b64_tr_b16.  Every lane supplies its own 8-byte address; inside a 16-lane
-// group lane i supplies row i/4, columns 4(i%4)..+3 of a 4 x 16 block and receives column i of that block (probed on MI355X).
-TR1_DEV u32x2_t lds_read_tr16(const char* p) {
-    const s16x4_t v = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4_t*)(p));
-    return __builtin_bit_cast(u32x2_t, v);
 }
 
 // ---------------------------------------------------------------------------------------------------------------- dQ
@@ -235,7 +223,7 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_kernel(AttnParams p) {
                 for (int dt = 0; dt < D / 16; ++dt) {
                     // K^T[d = dt*16 + u][kv = kk*32 + g*4 .. +3 | kk*32 + 16 + g*4 .. +3] from the K rows
                     const char* base = lds_k + (kk * 32 + g * 4 + (u >> 2)) * KSTR + dt * 32 + (u & 3) * 8;
-                    const bf16x8_t ktf = make_frag(lds_read_tr16(base), lds_read_tr16(base + 16 * KSTR));
+                    const bf16x8_t ktf = make_frag(att_lds_tr16(base), att_lds_tr16(base + 16 * KSTR));
                     dq[dt][0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ktf, dsf[kk][0], dq[dt][0], 0, 0, 0);
                     dq[dt][1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ktf, dsf[kk][1], dq[dt][1], 0, 0, 0);
                 }
@@ -493,15 +481,15 @@ __global__ __launch_bounds__(NW * 64) void attn_bwd_dkdv_kernel(AttnParams p, in
             const char* to = lds_do + (g * 4 + (u >> 2)) * KSTR + (u & 3) * 8;
 #pragma unroll
             for (int dt = 0; dt < D / 16; ++dt) {
-                const bf16x8_t q0 = make_frag(lds_read_tr16(tq + dt * 32), lds_read_tr16(tq + 16 * KSTR + dt * 32));
-                const bf16x8_t o0 = make_frag(lds_read_tr16(to + dt * 32), lds_read_tr16(to + 16 * KSTR + dt * 32));
+                const bf16x8_t q0 = make_frag(att_lds_tr16(tq + dt * 32), att_lds_tr16(tq + 16 * KSTR + dt * 32));
+                const bf16x8_t o0 = make_frag(att_lds_tr16(to + dt * 32), att_lds_tr16(to + 16 * KSTR + dt * 32));
                 _Pragma("unroll") for (int kt = 0; kt < KT; ++kt) dv[kt][dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(o0, pf0[kt], dv[kt][dt], 0, 0, 0);
                 _Pragma("unroll") for (int kt = 0; kt < KT; ++kt) dk[kt][dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(q0, df0[kt], dk[kt][dt], 0, 0, 0);
             }
 #pragma unroll
             for (int dt = 0; dt < D / 16; ++dt) {
-                const bf16x8_t q1 = make_frag(lds_read_tr16(tq + 32 * KSTR + dt * 32), lds_read_tr16(tq + 48 * KSTR + dt * 32));
-                const bf16x8_t o1 = make_frag(lds_read_tr16(to + 32 * KSTR + dt * 32), lds_read_tr16(to + 48 * KSTR + dt * 32));
+                const bf16x8_t q1 = make_frag(att_lds_tr16(tq + 32 * KSTR + dt * 32), att_lds_tr16(tq + 48 * KSTR + dt * 32));
+                const bf16x8_t o1 = make_frag(att_lds_tr16(to + 32 * KSTR + dt * 32), att_lds_tr16(to + 48 * KSTR + dt * 32));
                 _Pragma("unroll") for (int kt = 0; kt < KT; ++kt) dv[kt][dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(o1, pf1[kt], dv[kt][dt], 0, 0, 0);
                 _Pragma("unroll") for (int kt = 0; kt < KT; ++kt) dk[kt][dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(q1, df1[kt], dk[kt][dt], 0, 0, 0);
             }
@@ -789,8 +777,8 @@ __global__ __launch_bounds__(NW * 64) void attn_bwd_dkdv_dma_kernel(AttnParams p
 #pragma unroll
             for (int dt = 0; dt < D / 16; ++dt) {
                 const int off = hh * 32 * 256 + tr_lo + (((dt * 2 + tr_c) ^ keyt) << 4);
-                const bf16x8_t q0 = make_frag(lds_read_tr16(lds_q + off), lds_read_tr16(lds_q + off + 16 * 256));
-                const bf16x8_t o0 = make_frag(lds_read_tr16(lds_do + off), lds_read_tr16(lds_do + off + 16 * 256));
+                const bf16x8_t q0 = make_frag(att_lds_tr16(lds_q + off), att_lds_tr16(lds_q + off + 16 * 256));
+                const bf16x8_t o0 = make_frag(att_lds_tr16(lds_do + off), att_lds_tr16(lds_do + off + 16 * 256));
                 _Pragma("unroll") for (int kt = 0; kt < KT; ++kt) dv[kt][dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(o0, hh ? pf1[kt] : pf0[kt], dv[kt][dt], 0, 0, 0);
                 _Pragma("unroll") for (int kt = 0; kt < KT; ++kt) dk[kt][dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(q0, hh ? df1[kt] : df0[kt], dk[kt][dt], 0, 0, 0);
             }
@@ -933,35 +921,29 @@ __global__ __launch_bounds__(NP * 128) void attn_bwd_dkdv32_kernel(AttnParams p,
             ta.st_si = (unsigned)(kvh * p.group + (int)(R - tu * (unsigned)p.group)) * (unsigned)p.T + tu;
         }
     };
-    // The DMA instructions are written in assembly: for the builtin, hipcc tracks the asynchronous LDS write and puts an s_waitcnt vmcnt(0)
-    // in front of the next LDS read it cannot prove disjoint (all of them: one dynamic LDS array) - the "prefetch" then completes before the
-    // first operand read of the tile, i.e. nothing is prefetched.  Landing is ordered by the hand-placed vmcnt wait + barrier at the loop top.
+    // (asm-issued LDS DMA: tr1_dma16 / tr1_dma4 of tr1_common.h.  Landing is ordered by the hand-placed vmcnt wait + barrier at the loop top.)
     const unsigned lds_base = (unsigned)(uintptr_t)(att_lptr_t)dyn_lds;
     const float* dlt_base = p.delta;
     const int *pre_base = p.pre, *lo_base = p.lo, *hi_base = p.hi;
-#define DMA16(voff, sbase, m0v) asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2" ::"s"(m0v), "v"(voff), "s"(sbase) : "memory", "m0")
-#define DMA4(voff, sbase, m0v) asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dword %1, %2" ::"s"(m0v), "v"(voff), "s"(sbase) : "memory", "m0")
     auto issue_tile = [&](const TileAddr& ta, int slot) {
         const unsigned buf = lds_base + slot * BUF;
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
             if (!dma_wave) break;
             const unsigned dst = buf + (wave * 2 + j) * 1024;
-            DMA16(ta.q[j], qbase, dst);
-            DMA16(ta.o[j], dobase, dst + TILE);
+            tr1_dma16(ta.q[j], qbase, dst);
+            tr1_dma16(ta.o[j], dobase, dst + TILE);
         }
         if (wave == SW) {                                             // row statistics (a role-1 wave: its tile work is the lighter one)
             const unsigned mb = buf + 2 * TILE;
             const unsigned so = ta.st_si * 4u, to = ta.st_t * 4u;
-            DMA4(so, lse2, mb);
-            DMA4(so, dlt_base, mb + 256);
-            DMA4(to, pre_base, mb + 512);
-            DMA4(to, lo_base, mb + 768);
-            DMA4(to, hi_base, mb + 1024);
+            tr1_dma4(so, lse2, mb);
+            tr1_dma4(so, dlt_base, mb + 256);
+            tr1_dma4(to, pre_base, mb + 512);
+            tr1_dma4(to, lo_base, mb + 768);
+            tr1_dma4(to, hi_base, mb + 1024);
         }
     };
-#undef DMA16
-#undef DMA4
     TileAddr ta;
     if (n_my > 0) { tile_addr(__builtin_amdgcn_readfirstlane(lds_tiles[0]), ta); issue_tile(ta, 0); }
     if (n_my > 1) { tile_addr(__builtin_amdgcn_readfirstlane(lds_tiles[1]), ta); issue_tile(ta, 1); }
@@ -971,19 +953,13 @@ __global__ __launch_bounds__(NP * 128) void attn_bwd_dkdv32_kernel(AttnParams p,
     // + an immediate offset - ONE v_xor per distinct fragment column (8 + 8 per tile).  Written as pointer arithmetic, hipcc spent ~3 VALU on
     // every one of the 60 LDS reads of a tile (v_add3 / v_xad / v_subrev against the rotating slot base): 395 VALU per wave and tile made
     // the kernel VALU-bound (44 % VALU busy against 29 % MFMA busy).
-    typedef const __attribute__((address_space(3))) bf16x8_t* lds_b128_t;
     typedef const __attribute__((address_space(3))) f32x4_t* lds_f128_t;
     typedef __attribute__((ext_vector_type(4))) int i32x4_t;
     typedef const __attribute__((address_space(3))) i32x4_t* lds_i128_t;
-#define LDS_B128(addr) (*(lds_b128_t)(uintptr_t)(addr))
 #define LDS_F128(addr) (*(lds_f128_t)(uintptr_t)(addr))
 #define LDS_I128(addr) (*(lds_i128_t)(uintptr_t)(addr))
-#define LDS_TR16(addr) __builtin_bit_cast(u32x2_t, __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4_t*)(uintptr_t)(addr)))
     const int ti = lane & 15, tgrp = (lane >> 4) & 1;
-    // b128 A fragment of row c32 (+32 per half): chunk (ks*2 + h) ^ skey(row)      -> byte (ks*32) ^ a_lane inside the row
-    const unsigned a_lane = (unsigned)(c32 * 256 + ((h ^ skey(c32 & 15)) << 4));
-    // transposing read: row 4h + ti/4 (+8: second half, chunk key ^ 2), chunk (db*4 + tgrp*2 + (ti&3)/2) ^ skey(row), 8 bytes at (ti&1)*8
-    const unsigned t_lane = (unsigned)((4 * h + (ti >> 2)) * 256 + (ti & 1) * 8 + (((tgrp * 2 + ((ti & 3) >> 1)) ^ (((ti >> 2) << 2) | h)) << 4));
+    const unsigned a_lane = att_a_lane(c32, h), t_lane = ATT_T_LANE(h, ti, tgrp);      // (the tile image and its two read shapes: attn_common.h)
     const unsigned pex_lane = lds_base + NB * BUF + pair * PEX + lane * 16;
     const unsigned st_lane = (unsigned)(16 * h);                      // row statistics: 4 floats / ints from row 4h (+ 8i + 32 qb)
 
@@ -1000,10 +976,10 @@ __global__ __launch_bounds__(NP * 128) void attn_bwd_dkdv32_kernel(AttnParams p,
         constexpr int AH = NP == 4 ? 3 : 2;                           // k-steps of lookahead
         bf16x8_t a[AH + 1];
 #pragma unroll
-        for (int ks = 0; ks < AH; ++ks) a[ks] = LDS_B128(xa ^ (ks * 32));
+        for (int ks = 0; ks < AH; ++ks) a[ks] = att_lds_b128(xa ^ (ks * 32));
 #pragma unroll
         for (int ks = 0; ks < D / 16; ++ks) {
-            if (ks + AH < D / 16) a[(ks + AH) % (AH + 1)] = LDS_B128(xa ^ ((ks + AH) * 32));
+            if (ks + AH < D / 16) a[(ks + AH) % (AH + 1)] = att_lds_b128(xa ^ ((ks + AH) * 32));
             if (TWO && (ks & 1)) c1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[ks % (AH + 1)], sf[ks], c1, 0, 0, 0);
             else c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[ks % (AH + 1)], sf[ks], c, 0, 0, 0);
             __builtin_amdgcn_sched_barrier(0);
@@ -1017,16 +993,14 @@ __global__ __launch_bounds__(NP * 128) void attn_bwd_dkdv32_kernel(AttnParams p,
     auto product2 = [&](unsigned ya, const bf16x8_t& f0, const bf16x8_t& f1) {      // ya: tile rows + first chunk * 4096 + t_lane
         constexpr int TH = NP == 4 ? 3 : 2;                           // MFMAs of lookahead
         bf16x8_t a[TH + 1];
-#define P2_LD(n) make_frag(LDS_TR16((ya ^ (((n) & 3) * 64)) + ((n) >> 2) * 4096), LDS_TR16((ya ^ (((n) & 3) * 64 + 32)) + ((n) >> 2) * 4096 + 2048))
 #pragma unroll
-        for (int n = 0; n < TH; ++n) a[n] = P2_LD(n);
+        for (int n = 0; n < TH; ++n) a[n] = att_p2_ld<4>(ya, n);
 #pragma unroll
         for (int n = 0; n < 8; ++n) {                                 // n = chunk * 4 + db
-            if (n + TH < 8) a[(n + TH) % (TH + 1)] = P2_LD(n + TH);
+            if (n + TH < 8) a[(n + TH) % (TH + 1)] = att_p2_ld<4>(ya, n + TH);
             acc[n & 3] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[n % (TH + 1)], (n >> 2) ? f1 : f0, acc[n & 3], 0, 0, 0);
             __builtin_amdgcn_sched_barrier(0);
         }
-#undef P2_LD
     };
     // role 0: S of one 32-row half (in c) -> P, packed to two B fragments of the dV product and written to the exchange buffer
     auto make_p = [&](f32x16_t& c, int qb, unsigned sa, bool full, int rows_valid, bf16x8_t& f0, bf16x8_t& f1, unsigned pex) {   // sa: statistics + st_lane
@@ -1064,7 +1038,7 @@ __global__ __launch_bounds__(NP * 128) void attn_bwd_dkdv32_kernel(AttnParams p,
     auto make_ds = [&](const f32x16_t& c, int qb, unsigned sa, unsigned pex, bf16x8_t& f0, bf16x8_t& f1) {
 #pragma unroll
         for (int hf = 0; hf < 2; ++hf) {
-            const u32x4_t pw = __builtin_bit_cast(u32x4_t, LDS_B128(pex + (2 * qb + hf) * 1024));     // P[q rows of the chunk][key]: 8 bf16 in k-slot order
+            const u32x4_t pw = __builtin_bit_cast(u32x4_t, att_lds_b128(pex + (2 * qb + hf) * 1024));     // P[q rows of the chunk][key]: 8 bf16 in k-slot order
             const f32x4_t d0 = LDS_F128(sa + 256 + (qb * 32 + hf * 16) * 4), d1 = LDS_F128(sa + 256 + (qb * 32 + hf * 16 + 8) * 4);
             const int b = hf * 8;
             u32x4_t w;
@@ -1100,23 +1074,23 @@ __global__ __launch_bounds__(NP * 128) void attn_bwd_dkdv32_kernel(AttnParams p,
     // One tile loop PER ROLE (same trip count, same barriers): with both roles inside one loop body hipcc gave the accumulators different
     // registers on the two paths and moved all 64 of them at the join - 130-190 v_mov per tile.
 #define TILE_TOP()                                                                                                                        \
-        BWD_STAMPS;                                                                                                                       \
-        BWD_STAMP(it, 0);                                                                                                                 \
+        ATT_STAMPS;                                                                                                                       \
+        ATT_STAMP(0);                                                                                                                     \
         if (it + 2 < n_my) tile_addr(__builtin_amdgcn_readfirstlane(lds_tiles[it + 2]), ta);   /* DMA addresses of the tile requested behind the barrier */ \
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");          /* this wave's share of tile it+1 (requested one iteration ago) has landed */ \
-        BWD_STAMP(it, 1);                                                                                                                 \
+        ATT_STAMP(1);                                                                                                                     \
         __builtin_amdgcn_s_barrier();                              /* tile it+1 and P(it) are published; everybody is done with tile it-1 */ \
         asm volatile("" ::: "memory");                                                                                                    \
-        BWD_STAMP(it, 2);                                                                                                                 \
+        ATT_STAMP(2);                                                                                                                     \
         if (it + 2 < n_my) issue_tile(ta, (it + 2) % NB);         /* = the slot of tile it-1 */                                           \
-        BWD_STAMP(it, 3);                                                                                                                 \
+        ATT_STAMP(3);                                                                                                                     \
         const unsigned buf = lds_base + (unsigned)(it % NB) * BUF;                                                                        \
         const unsigned pex = pex_lane + (unsigned)(it & 1) * (NP * PEX);   /* P(it): written by the pair's role-0 wave one iteration ago */ \
         f32x16_t c;                                                                                                                       \
         bf16x8_t f0, f1
 #define TILE_BOTTOM()                                                                                                                     \
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");        /* all LDS traffic of this tile is complete before the barrier that publishes / frees */ \
-        BWD_STAMP(it, 7);                                                                                                                 \
+        ATT_STAMP(7);                                                                                                                     \
         BWD_FLUSH(it)
     if (role == 0) {
         for (int it = 0; it < n_my; ++it) {
@@ -1135,14 +1109,14 @@ __global__ __launch_bounds__(NP * 128) void attn_bwd_dkdv32_kernel(AttnParams p,
 #pragma unroll
             for (int hf = 0; hf < 2; ++hf) {
                 if (more) product1(xa + hf * 8192, c);
-                if (hf == 0) BWD_STAMP(it, 4);
-                f0 = LDS_B128(pex + (2 * hf) * 1024);
-                f1 = LDS_B128(pex + (2 * hf + 1) * 1024);
+                if (hf == 0) ATT_STAMP(4);
+                f0 = att_lds_b128(pex + (2 * hf) * 1024);
+                f1 = att_lds_b128(pex + (2 * hf + 1) * 1024);
                 product2(ya + hf * 8192, f0, f1);
                 if (more) make_p(c, hf, sa, fulln, rv, f0, f1, npex);
-                if (hf == 0) BWD_STAMP(it, 5);
+                if (hf == 0) ATT_STAMP(5);
             }
-            BWD_STAMP(it, 6);
+            ATT_STAMP(6);
             TILE_BOTTOM();
         }
     } else {
@@ -1152,21 +1126,19 @@ __global__ __launch_bounds__(NP * 128) void attn_bwd_dkdv32_kernel(AttnParams p,
 #pragma unroll
             for (int hf = 0; hf < 2; ++hf) {
                 product1(xa + hf * 8192, c);                          // dP = dO V^T, 32 rows
-                if (hf == 0) BWD_STAMP(it, 4);
+                if (hf == 0) ATT_STAMP(4);
                 make_ds(c, hf, sa, pex, f0, f1);
                 product2(ya + hf * 8192, f0, f1);                     // dK^T += Q^T dS
-                if (hf == 0) BWD_STAMP(it, 5);
+                if (hf == 0) ATT_STAMP(5);
             }
-            BWD_STAMP(it, 6);
+            ATT_STAMP(6);
             TILE_BOTTOM();
         }
     }
 #undef TILE_TOP
 #undef TILE_BOTTOM
-#undef LDS_B128
 #undef LDS_F128
 #undef LDS_I128
-#undef LDS_TR16
     // lane holds acc^T[feature = db*32 + 8i + 4h + j][key c32]: role 0 -> dV, role 1 -> dK (scaled).  The lane coordinates are rebuilt from a
     // laundered thread id: values kept live across the tile loop for the epilogue get spilled, and ANY scratch access makes hipcc wait on
     // vmcnt inside the loop - which would also wait for the hand-issued DMA
@@ -1219,31 +1191,16 @@ __global__ __launch_bounds__(512) void attn_bwd_dq32_kernel(AttnParams p, const 
     int tq, hq;
     att_split_row(p, valid ? R : nR - 1, tq, hq);
     const int pre = valid ? p.pre[tq] : 0, lo = valid ? p.lo[tq] : 1, hi = valid ? p.hi[tq] : 0;
-    const int hi_c = hi < p.n_slots ? hi : p.n_slots - 1;             // the two visible intervals clamped to the cache's slots (see attn_fwd32_kernel)
-    const int pre_e = pre < p.n_slots ? pre : p.n_slots, lo_e = hi_c >= lo ? lo : 0x7fffffff, hi_d = hi_c >= lo ? hi_c - lo : 0;
+    const AttRowMask rm = ATT_ROW_MASK(pre, lo, hi, p.n_slots);
     const int64_t si = (int64_t)(kvh * p.group + hq) * p.T + tq;
     const bool fused_delta = p.lse2_out != nullptr;                   // wave-uniform (kernel argument)
     float lse = INFINITY, dlt = 0.f;                                  // log2-scaled LSE; +inf (no visible key / padding row) -> P = 0
     if (!fused_delta) { lse = valid ? lse2[si] : INFINITY; dlt = valid ? p.delta[si] : 0.f; }
     // wave summary of the masks: which tiles every row of the wave sees completely, which it sees at all
-    int wmaxpre = valid ? pre : 0, wminpre = valid ? pre : 0x7fffffff;
-    int wminlo = (valid && hi >= lo) ? lo : 0x7fffffff, wmaxhi = (valid && hi >= lo) ? hi : -1;
-    int wmaxlo = valid ? (hi >= lo ? lo : 0x7fffffff) : -1, wminhi = valid ? (hi >= lo ? hi : -1) : 0x7fffffff;
-#pragma unroll
-    for (int o = 1; o < 32; o <<= 1) {
-        wmaxpre = max(wmaxpre, __shfl_xor(wmaxpre, o, 64)); wminpre = min(wminpre, __shfl_xor(wminpre, o, 64));
-        wminlo = min(wminlo, __shfl_xor(wminlo, o, 64)); wmaxhi = max(wmaxhi, __shfl_xor(wmaxhi, o, 64));
-        wmaxlo = max(wmaxlo, __shfl_xor(wmaxlo, o, 64)); wminhi = min(wminhi, __shfl_xor(wminhi, o, 64));
-    }
-    wmaxpre = __builtin_amdgcn_readfirstlane(wmaxpre); wminpre = __builtin_amdgcn_readfirstlane(wminpre);
-    wminlo = __builtin_amdgcn_readfirstlane(wminlo); wmaxhi = __builtin_amdgcn_readfirstlane(wmaxhi);
-    wmaxlo = __builtin_amdgcn_readfirstlane(wmaxlo); wminhi = __builtin_amdgcn_readfirstlane(wminhi);
-    // (rows past nR - the padding of the last block - never force the masked path: they compute finite garbage that is not stored.  With an
-    //  `all 32 rows valid` term in `full`, the ONE partially valid wave of the heaviest block took the per-element mask path on every tile:
-    //  3 900 instead of 1 200 cycles of softmax, all other waves waiting for it at the barrier - wave timeline in DESIGN.md)
+    const AttWaveMask wm = ATT_WAVE_MASK(valid, pre, lo, hi);
     if (lane == 0) {
-        lds_meta[wave * 6 + 0] = wmaxpre; lds_meta[wave * 6 + 1] = wminlo; lds_meta[wave * 6 + 2] = wmaxhi;
-        lds_meta[wave * 6 + 3] = wminpre; lds_meta[wave * 6 + 4] = wmaxlo; lds_meta[wave * 6 + 5] = wminhi;
+        lds_meta[wave * 6 + 0] = wm.maxpre; lds_meta[wave * 6 + 1] = wm.minlo; lds_meta[wave * 6 + 2] = wm.maxhi;
+        lds_meta[wave * 6 + 3] = wm.minpre; lds_meta[wave * 6 + 4] = wm.maxlo; lds_meta[wave * 6 + 5] = wm.minhi;
     }
     // stationary B fragments: Q / dO row of this lane, features ks*16 + h*8 .. +7
     bf16x8_t qf[D / 16], dof[D / 16];
@@ -1281,10 +1238,7 @@ __global__ __launch_bounds__(512) void attn_bwd_dq32_kernel(AttnParams p, const 
     for (int ks = 0; ks < D / 16; ++ks) asm volatile("" ::"v"(qf[ks]), "v"(dof[ks]));
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
-    int bmaxpre = 0, bminlo = 0x7fffffff, bmaxhi = -1;
-#pragma unroll
-    for (int w = 0; w < 8; ++w) { bmaxpre = max(bmaxpre, lds_meta[w * 6]); bminlo = min(bminlo, lds_meta[w * 6 + 1]); bmaxhi = max(bmaxhi, lds_meta[w * 6 + 2]); }
-    const TileRange tr = att_tile_range(bmaxpre, bminlo, bmaxhi, p.n_slots);
+    const TileRange tr = att_block_range(lds_meta, 6, p.n_slots);
     const int n_my = tr.n_rel;
     if (p.qmeta_out && kvh == 0 && (wave & 1) == 0 && lane < 6) {
         // the mask summary of 64-row tile (this wave's 32 rows + the next wave's): attn_qmeta_tile's six values (max pre, min lo, max hi, min pre, max lo, min hi)
@@ -1301,32 +1255,13 @@ __global__ __launch_bounds__(512) void attn_bwd_dq32_kernel(AttnParams p, const 
     const char* kbase = reinterpret_cast<const char*>(p.K) + (int64_t)kvh * 256;
     const char* vbase = reinterpret_cast<const char*>(p.V) + (int64_t)kvh * 256;
     const unsigned k_ldb = (unsigned)p.k_ld * 2u, v_ldb = (unsigned)p.v_ld * 2u;
-#define DMA16(voff, sbase, m0v) asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2" ::"s"(m0v), "v"(voff), "s"(sbase) : "memory", "m0")
-    auto issue_tile = [&](int tile, int slot) {
-        const unsigned buf = lds_base + slot * BUF;
-        int ln = lane;
-        asm volatile("" : "+v"(ln));
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            const unsigned row = 4u * (wave * 2 + j) + ((unsigned)ln >> 4);
-            unsigned kv = (unsigned)tile * 64u + row; kv = kv < (unsigned)p.n_slots ? kv : (unsigned)p.n_slots - 1u;
-            const unsigned ch = (unsigned)(((ln & 15) ^ skey(row & 15)) << 4);
-            const unsigned dst = buf + (wave * 2 + j) * 1024;
-            DMA16(kv * k_ldb + ch, kbase, dst);
-            DMA16(kv * v_ldb + ch, vbase, dst + TILE);
-        }
-    };
-#undef DMA16
+    auto issue_tile = [&](int tile, int slot) { att_issue_kv_tile(lane, wave, tile, lds_base, slot, p.n_slots, kbase, k_ldb, vbase, v_ldb); };
 #pragma unroll
     for (int j = 0; j < NB - 1; ++j)
         if (j < n_my) issue_tile(att_tile_at(tr, j), j);
 
-    typedef const __attribute__((address_space(3))) bf16x8_t* lds_b128_t;
-#define LDS_B128(addr) (*(lds_b128_t)(uintptr_t)(addr))
-#define LDS_TR16(addr) __builtin_bit_cast(u32x2_t, __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4_t*)(uintptr_t)(addr)))
     const int ti = lane & 15, tgrp = (lane >> 4) & 1;
-    const unsigned a_lane = (unsigned)(c32 * 256 + ((h ^ skey(c32 & 15)) << 4));
-    const unsigned t_lane = (unsigned)((4 * h + (ti >> 2)) * 256 + (ti & 1) * 8 + (((tgrp * 2 + ((ti & 3) >> 1)) ^ (((ti >> 2) << 2) | h)) << 4));
+    const unsigned a_lane = att_a_lane(c32, h), t_lane = ATT_T_LANE(h, ti, tgrp);
 
     for (int it = 0; it < n_my; ++it) {
         {   // this wave's share of tile `it` has landed when at most (tiles requested after it) x 4 instructions are outstanding
@@ -1340,8 +1275,8 @@ __global__ __launch_bounds__(512) void attn_bwd_dq32_kernel(AttnParams p, const 
         if (it + NB - 1 < n_my) issue_tile(att_tile_at(tr, it + NB - 1), (it + NB - 1) % NB);
         const int kv0 = att_tile_at(tr, it) * 64;
         // wave-uniform: does any row of the wave see a key of the tile / does every row see every key
-        const bool any = (kv0 < wmaxpre) || (kv0 + 63 >= wminlo && kv0 <= wmaxhi);
-        const bool full = (kv0 + 64 <= p.n_slots) && ((kv0 + 64 <= wminpre) || (wmaxlo <= kv0 && kv0 + 63 <= wminhi));
+        const bool any = (kv0 < wm.maxpre) || (kv0 + 63 >= wm.minlo && kv0 <= wm.maxhi);
+        const bool full = (kv0 + 64 <= p.n_slots) && ((kv0 + 64 <= wm.minpre) || (wm.maxlo <= kv0 && kv0 + 63 <= wm.minhi));
         if (any) {
             const unsigned kb_ = lds_base + (unsigned)(it % NB) * BUF;
 #pragma unroll
@@ -1353,10 +1288,10 @@ __global__ __launch_bounds__(512) void attn_bwd_dq32_kernel(AttnParams p, const 
                 constexpr int AH = 2;
                 bf16x8_t ka[AH + 1], va[AH + 1];
 #pragma unroll
-                for (int ks = 0; ks < AH; ++ks) { ka[ks] = LDS_B128(xa ^ (ks * 32)); va[ks] = LDS_B128((xa ^ (ks * 32)) + TILE); }
+                for (int ks = 0; ks < AH; ++ks) { ka[ks] = att_lds_b128(xa ^ (ks * 32)); va[ks] = att_lds_b128((xa ^ (ks * 32)) + TILE); }
 #pragma unroll
                 for (int ks = 0; ks < D / 16; ++ks) {
-                    if (ks + AH < D / 16) { ka[(ks + AH) % (AH + 1)] = LDS_B128(xa ^ ((ks + AH) * 32)); va[(ks + AH) % (AH + 1)] = LDS_B128((xa ^ ((ks + AH) * 32)) + TILE); }
+                    if (ks + AH < D / 16) { ka[(ks + AH) % (AH + 1)] = att_lds_b128(xa ^ ((ks + AH) * 32)); va[(ks + AH) % (AH + 1)] = att_lds_b128((xa ^ ((ks + AH) * 32)) + TILE); }
                     cs = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ka[ks % (AH + 1)], qf[ks], cs, 0, 0, 0);
                     cp = __builtin_amdgcn_mfma_f32_32x32x16_bf16(va[ks % (AH + 1)], dof[ks], cp, 0, 0, 0);
                     __builtin_amdgcn_sched_barrier(0);
@@ -1372,8 +1307,8 @@ __global__ __launch_bounds__(512) void attn_bwd_dq32_kernel(AttnParams p, const 
                     // (round 6) the interval mask as vector instructions only (two compares + two selects on the clamped intervals, see attn_fwd32_kernel): a masked
                     // score becomes -inf, so P = exp2(-inf) = +0 - the value the select on the lane masks produced
                     const int base = kv0 + kb * 32 + 4 * h;
-                    const unsigned mA = (unsigned)(base - lo_e), mD = (unsigned)hi_d;
-                    const int mB = pre_e - base;
+                    const unsigned mA = (unsigned)(base - rm.lo_e), mD = (unsigned)rm.hi_d;
+                    const int mB = rm.pre_e - base;
 #pragma unroll
                     for (int r = 0; r < 16; ++r) {
                         const int c = (r & 3) + 8 * (r >> 2);
@@ -1389,22 +1324,18 @@ __global__ __launch_bounds__(512) void attn_bwd_dq32_kernel(AttnParams p, const 
                 const unsigned ya = kb_ + kb * 8192 + t_lane;
                 constexpr int TH = 2;
                 bf16x8_t a[TH + 1];
-#define P2_LD(n) make_frag(LDS_TR16((ya ^ (((n) & 3) * 64)) + ((n) >> 2) * 4096), LDS_TR16((ya ^ (((n) & 3) * 64 + 32)) + ((n) >> 2) * 4096 + 2048))
 #pragma unroll
-                for (int n = 0; n < TH; ++n) a[n] = P2_LD(n);
+                for (int n = 0; n < TH; ++n) a[n] = att_p2_ld<4>(ya, n);
 #pragma unroll
                 for (int n = 0; n < 8; ++n) {
-                    if (n + TH < 8) a[(n + TH) % (TH + 1)] = P2_LD(n + TH);
+                    if (n + TH < 8) a[(n + TH) % (TH + 1)] = att_p2_ld<4>(ya, n + TH);
                     acc[n & 3] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[n % (TH + 1)], (n >> 2) ? f1 : f0, acc[n & 3], 0, 0, 0);
                     __builtin_amdgcn_sched_barrier(0);
                 }
-#undef P2_LD
             }
         }
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");           // all LDS reads of this tile have returned before the barrier that frees its slot
     }
-#undef LDS_B128
-#undef LDS_TR16
     // lane holds dQ^T[feature = db*32 + 8i + 4h + j][its query row]
     int tid2 = threadIdx.x;
     asm volatile("" : "+v"(tid2));

@@ -62,6 +62,7 @@ struct AttnParams {
 };
 
 #define ATT_KV 64          // keys per tile
+#define ATT_LIST_CAP 1024   // split-KV decode: most tile ids in a block's relevant-tile list / plan entry ([ATT_LIST_CAP ids | count], see attn_fwd.hip)
 #define NEG_INF (-INFINITY)
 
 // ---- merge of split-KV partials: attn_combine_kernel and the merged tail of attn_dec32_kernel run THESE operations in this order (bit-identical results)
@@ -314,19 +315,133 @@ TR1_DEV TileRange att_tile_range(int max_pre, int min_lo, int max_hi, int n_slot
 }
 TR1_DEV int att_tile_at(const TileRange& tr, int i) { return i < tr.pre_tiles ? i : tr.start2 + (i - tr.pre_tiles); }
 
-// ---- pieces shared by the 32x32x16-MFMA kernels (round 3: attn_bwd_dkdv32 / attn_bwd_dq32 / attn_fwd32) -------------------------------
+// ---- pieces shared by the 32x32x16-MFMA kernels at head dim 128 (attn_fwd32 / attn_fwd64 / attn_dec32, attn_bwd_dkdv32 / attn_bwd_dq32) ------------------
+// They all read ONE LDS tile image - 64 rows x 256 B, unpadded, 16-byte chunk c of a row stored at chunk c ^ skey(row) - filled by LDS DMA (tr1_dma16) with
+// the swizzle applied on the SOURCE address and read back as b128 "A" fragments (att_a_lane) and as transposing 8-byte pairs (ATT_T_LANE, att_p2_ld).
+// Every piece of that contract is defined here and nowhere else: the kernels must agree on it bit for bit (attn_fwd64_kernel is tested against attn_fwd32_kernel).
+// These kernels are scheduled by hand, so a helper must leave their generated code exactly as the open-coded text did.  Four pieces are MACROS for that reason
+// (ATT_T_LANE, ATT_ROW_MASK, ATT_WAVE_MASK, ATT_BLOCK_MAP): as functions their bodies are optimised on their own before they are inlined - by-value arguments
+// count as defined (a freeze disappears), a loop is unrolled before the kernel's passes see it, a subexpression shared with the kernel is folded separately,
+// an early exit becomes a flag - and each of these moved instructions in attn_fwd32_kernel / attn_fwd64_kernel.  Before turning one into a function (or changing
+// a parameter between value and reference), compare `hipcc --cuda-device-only -S` of every kernel that uses it.
 typedef __attribute__((ext_vector_type(16))) float f32x16_t;       // 32x32 accumulator: lane (column n = lane & 31, half h = lane >> 5), register r -> row (r&3) + 8(r>>2) + 4h
 typedef __attribute__((ext_vector_type(4))) short s16x4_t;
 typedef const __attribute__((address_space(1))) void* att_gptr_t;
 typedef __attribute__((address_space(3))) void* att_lptr_t;
 // swizzle key of row (mod 16) of an unpadded 256-byte-row tile image: logical 16-byte chunk c of the row is stored at chunk c ^ skey(row)
 TR1_DEV int skey(int row) { return ((row & 3) << 2) | ((row >> 2) & 3); }
-// max of three without the canonicalising v_max x, x that fmaxf() costs per operand (no NaN can reach the score tiles: -inf masks, finite inputs)
+// max of two / three without the canonicalising v_max x, x that fmaxf() costs per operand (no NaN can reach the score tiles: -inf masks, finite inputs)
+TR1_DEV float att_max2(float a, float b) { float o; asm("v_max_f32 %0, %1, %2" : "=v"(o) : "v"(a), "v"(b)); return o; }
 TR1_DEV float att_max3(float a, float b, float c) { float o; asm("v_max3_f32 %0, %1, %2, %3" : "=v"(o) : "v"(a), "v"(b), "v"(c)); return o; }
-// both halves of a wave meet (tr1_common.h: v_permlane32_swap instead of the ds_bpermute behind __shfl_xor(x, 32)): fmaxf(a, b) / a + b give what fmaxf(x, shfl) / x + shfl gave
+// both halves of a wave meet (tr1_common.h: v_permlane32_swap instead of the ds_bpermute behind __shfl_xor(x, 32), whose lgkmcnt(0) wait also drains every
+// fragment read in flight): fmaxf(a, b) / a + b give what fmaxf(x, shfl) / x + shfl gave
 TR1_DEV void att_halves(float x, float& a, float& b) { tr1_halves32(x, a, b); }
 // registers b .. b+7 of a 32x32 accumulator -> one bf16 MFMA operand fragment (k-slot j of lane half h = accumulator row 16(b/8) + (j&3) + 8(j>>2) + 4h)
 TR1_DEV bf16x8_t pack8(const f32x16_t& c, int b) {
     u32x4_t w = {pack2bf(c[b], c[b + 1]), pack2bf(c[b + 2], c[b + 3]), pack2bf(c[b + 4], c[b + 5]), pack2bf(c[b + 6], c[b + 7])};
     return __builtin_bit_cast(bf16x8_t, w);
 }
+// Lazy running maximum of the forward kernels, log2 units (0 = rescale whenever a row's maximum moves): ONE value, attn_fwd32_kernel and attn_fwd64_kernel
+// must take the same rescale decisions
+#ifndef ATT_LAZY_MAX
+#define ATT_LAZY_MAX 6
+#endif
+
+// LDS reads through 32-bit LDS byte addresses built by hand: every tile image, ring slot and half-tile offset is a multiple of 256 bytes and the swizzle only
+// touches address bits 4..7, so a fragment address is (per-tile base) ^ (compile-time constant) + an immediate offset
+TR1_DEV bf16x8_t att_lds_b128(unsigned addr) { return *(const __attribute__((address_space(3))) bf16x8_t*)(uintptr_t)addr; }
+// Transposed MFMA operands straight from a ROW-major LDS tile: ds_read_b64_tr_b16.  Every lane supplies its own 8-byte address; inside a 16-lane
+// group lane i supplies row i/4, columns 4(i%4)..+3 of a 4 x 16 block and receives column i of that block (probed on MI355X).
+TR1_DEV u32x2_t att_lds_tr16(unsigned addr) {
+    return __builtin_bit_cast(u32x2_t, __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4_t*)(uintptr_t)addr));
+}
+TR1_DEV u32x2_t att_lds_tr16(const char* p) { return att_lds_tr16((unsigned)(uintptr_t)(att_lptr_t)p); }      // (the padded-stride images of the 16x16x32 backward kernels)
+// b128 A fragment of row c32 of 32-row half `half` of a tile image: chunk (ks*2 + h) ^ skey(row)      -> byte (ks*32) ^ att_a_lane inside the row
+TR1_DEV unsigned att_a_lane(int c32, int h, int half = 0) { return (unsigned)(half * 8192 + c32 * 256 + ((h ^ skey(c32 & 15)) << 4)); }
+// transposing read: row 4h + ti/4 (+8: second half, chunk key ^ 2), chunk (db*4 + tgrp*2 + (ti&3)/2) ^ skey(row), 8 bytes at (ti&1)*8   (h = lane >> 5, ti = lane & 15, tgrp = (lane >> 4) & 1)
+#define ATT_T_LANE(h, ti, tgrp) ((unsigned)((4 * (h) + ((ti) >> 2)) * 256 + ((ti) & 1) * 8 + ((((tgrp) * 2 + (((ti) & 3) >> 1)) ^ ((((ti) >> 2) << 2) | (h))) << 4)))
+// transposed A fragment n = chunk (16 rows) * NDB + 32-feature block of the second product (ya: tile rows + ATT_T_LANE; NDB = feature blocks in use)
+template <int NDB>
+TR1_DEV bf16x8_t att_p2_ld(unsigned ya, int n) {
+    return make_frag(att_lds_tr16((ya ^ ((n % NDB) * 64)) + (n / NDB) * 4096), att_lds_tr16((ya ^ ((n % NDB) * 64 + 32)) + (n / NDB) * 4096 + 2048));
+}
+
+// One 64-key tile into slot `slot` of a ring of [K rows | V rows] image pairs at LDS address lds_base: 4 instructions per wave of an 8-wave block, 32-bit byte
+// offsets from the uniform bases (kbase / vbase: the kv head's column of row 0; k_ldb / v_ldb: row pitch in bytes).  Rows past the cache's last slot re-read that slot.
+// (wave by reference, not by value: see the note on generated code at the top of this section)
+TR1_DEV void att_issue_kv_tile(int lane, const int& wave, int tile, unsigned lds_base, int slot, int n_slots, const char* kbase, unsigned k_ldb, const char* vbase, unsigned v_ldb) {
+    constexpr int TILE = 64 * 256, BUF = 2 * TILE;
+    const unsigned buf = lds_base + slot * BUF;
+    int ln = lane;
+    asm volatile("" : "+v"(ln));                                      // lane constants are rebuilt here (a handful of VALU), not kept live / spilled
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+        const unsigned row = 4u * (wave * 2 + j) + ((unsigned)ln >> 4);
+        unsigned kv = (unsigned)tile * 64u + row; kv = kv < (unsigned)n_slots ? kv : (unsigned)n_slots - 1u;
+        const unsigned ch = (unsigned)(((ln & 15) ^ skey(row & 15)) << 4);
+        const unsigned dst = buf + (wave * 2 + j) * 1024;
+        tr1_dma16(kv * k_ldb + ch, kbase, dst);
+        const unsigned dst_v = dst + TILE;                            // (computed before the offset, as the DMA's operands always were: the order reaches the schedule)
+        tr1_dma16(kv * v_ldb + ch, vbase, dst_v);
+    }
+}
+
+// A row's two visible intervals clamped to the cache's slots: visible(kv) = kv < pre_e | (unsigned)(kv - lo_e) <= hi_d  (lo_e = INT_MAX: no second interval)
+struct AttRowMask { int pre_e, lo_e, hi_d; };
+#define ATT_ROW_MASK(pre, lo, hi, n_slots) ({ \
+    const int hi_c_ = (hi) < (n_slots) ? (hi) : (n_slots) - 1; \
+    const int pre_e_ = (pre) < (n_slots) ? (pre) : (n_slots), lo_e_ = hi_c_ >= (lo) ? (lo) : 0x7fffffff, hi_d_ = hi_c_ >= (lo) ? hi_c_ - (lo) : 0; \
+    AttRowMask{pre_e_, lo_e_, hi_d_}; })
+// The masks of a wave's 32 rows (one per lane & 31; both lane halves hold the same row) in scalar registers: a tile starting at kv0 is seen by SOME row iff
+// kv0 < maxpre || (kv0 + 63 >= minlo && kv0 <= maxhi), and completely by EVERY row iff kv0 + 64 <= minpre || (maxlo <= kv0 && kv0 + 63 <= minhi).
+// (rows past nR - the padding of the last block, valid = false - never force the masked path: they compute finite garbage that is not stored.  With an
+//  `all 32 rows valid` term in `full`, the ONE partially valid wave of the heaviest block took the per-element mask path on every tile:
+//  3 900 instead of 1 200 cycles of softmax, all other waves waiting for it at the barrier - wave timeline in DESIGN.md)
+struct AttWaveMask { int maxpre, minpre, minlo, maxhi, maxlo, minhi; };
+#define ATT_WAVE_MASK(valid, pre, lo, hi) ({ \
+    int wmaxpre_ = (valid) ? (pre) : 0, wminpre_ = (valid) ? (pre) : 0x7fffffff; \
+    int wminlo_ = ((valid) && (hi) >= (lo)) ? (lo) : 0x7fffffff, wmaxhi_ = ((valid) && (hi) >= (lo)) ? (hi) : -1; \
+    int wmaxlo_ = (valid) ? ((hi) >= (lo) ? (lo) : 0x7fffffff) : -1, wminhi_ = (valid) ? ((hi) >= (lo) ? (hi) : -1) : 0x7fffffff; \
+    _Pragma("unroll") for (int o_ = 1; o_ < 32; o_ <<= 1) { \
+        wmaxpre_ = max(wmaxpre_, __shfl_xor(wmaxpre_, o_, 64)); wminpre_ = min(wminpre_, __shfl_xor(wminpre_, o_, 64)); \
+        wminlo_ = min(wminlo_, __shfl_xor(wminlo_, o_, 64)); wmaxhi_ = max(wmaxhi_, __shfl_xor(wmaxhi_, o_, 64)); \
+        wmaxlo_ = max(wmaxlo_, __shfl_xor(wmaxlo_, o_, 64)); wminhi_ = min(wminhi_, __shfl_xor(wminhi_, o_, 64)); \
+    } \
+    wmaxpre_ = __builtin_amdgcn_readfirstlane(wmaxpre_); wminpre_ = __builtin_amdgcn_readfirstlane(wminpre_); \
+    wminlo_ = __builtin_amdgcn_readfirstlane(wminlo_); wmaxhi_ = __builtin_amdgcn_readfirstlane(wmaxhi_); \
+    wmaxlo_ = __builtin_amdgcn_readfirstlane(wmaxlo_); wminhi_ = __builtin_amdgcn_readfirstlane(wminhi_); \
+    AttWaveMask{wmaxpre_, wminpre_, wminlo_, wmaxhi_, wmaxlo_, wminhi_}; })
+// The block's key tiles from the 8 wave summaries in LDS: entry w holds (maxpre, minlo, maxhi) in lds_meta[w * stride + 0 .. 2]
+TR1_DEV TileRange att_block_range(const int* lds_meta, int stride, int n_slots) {
+    int bmaxpre = 0, bminlo = 0x7fffffff, bmaxhi = -1;
+#pragma unroll
+    for (int w = 0; w < 8; ++w) { bmaxpre = max(bmaxpre, lds_meta[w * stride]); bminlo = min(bminlo, lds_meta[w * stride + 1]); bmaxhi = max(bmaxhi, lds_meta[w * stride + 2]); }
+    return att_tile_range(bmaxpre, bminlo, bmaxhi, n_slots);
+}
+
+// block -> (kv head, query block) of the row-major forward launches (nqb query blocks of 256 packed rows; the caller walks them from the last - heaviest: most
+// visible keys - to the first).  The hardware deals consecutive workgroups to the 8 XCDs round-robin; with 8 % n_kv == 0 (xcd_pad: the grid is padded to whole
+// rounds) every XCD serves ONE kv head (its K / V stay in that XCD's L2).  pad_block: what a padding block (qb >= nqb) does - the kernel's `return`.
+#define ATT_BLOCK_MAP(p, nqb, kvh, qb, pad_block) do { \
+    if ((p).xcd_pad) { \
+        const int id_ = (int)blockIdx.x, xcd_ = id_ & 7, per_ = 8 / (p).n_kv; \
+        (kvh) = xcd_ % (p).n_kv; (qb) = (id_ >> 3) * per_ + xcd_ / (p).n_kv; \
+        if ((qb) >= (nqb)) pad_block; \
+    } else if (((p).n_kv & 7) == 0) { \
+        /* >= 8 kv heads (the vision towers: 16 heads, group 1): head h is served by XCD h % 8, which walks that head's query blocks in order - a segment's */ \
+        /* K / V (0.4 MB at config 3) is then fetched into ONE L2 instead of into all eight (the plain map dealt the query blocks of a head round-robin */ \
+        /* over the XCDs: 8 x the operand bytes from HBM, the round-2 finding for the 96-wide kernel) */ \
+        const int id_ = (int)blockIdx.x, xcd_ = id_ & 7, sq_ = id_ >> 3; \
+        (kvh) = xcd_ + 8 * (sq_ / (nqb)); (qb) = sq_ - (sq_ / (nqb)) * (nqb); \
+    } else { (qb) = (int)blockIdx.x % (nqb); (kvh) = (int)blockIdx.x / (nqb); } } while (0)
+
+// wave-timeline probes (-DTR1_PROBE builds, tools/build_probe_lib.py): the stamps of a tile stay in scalar registers - reading an s_memtime result costs an
+// s_waitcnt lgkmcnt(0), which would drain the LDS reads in flight at the stamped point - and each kernel's own *_FLUSH / *_DUMP macro writes att_st_ out
+#ifdef TR1_PROBE
+#define ATT_STAMPS_N(n) unsigned long long att_st_[n] = {}
+#define ATT_STAMP(slot) do { att_st_[slot] = __builtin_amdgcn_s_memtime(); } while (0)
+#else
+#define ATT_STAMPS_N(n) do { } while (0)
+#define ATT_STAMP(slot) do { } while (0)
+#endif
+#define ATT_STAMPS ATT_STAMPS_N(8)

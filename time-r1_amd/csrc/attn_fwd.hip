@@ -20,8 +20,7 @@ __device__ unsigned long long* tr1_probe = nullptr;
 // suffix start to the last group's newest slot; with the cache laid out group by group (slot = P + g*C + s) that interval also spans the
 // NOT YET GENERATED slots of every group but the last - at C = 1024 a 64-row block walked 144 suffix tiles at every decode step, 8 of them
 // useful on average (config 4: 35 us per layer, constant over the rollout).  The list keeps the prefix tiles and, of the suffix range, the
-// tiles that intersect some token's [lo, hi]; one wave evaluates 64 candidate tiles per pass against the <= 11 tokens of the block.
-#define ATT_LIST_CAP 1024
+// tiles that intersect some token's [lo, hi]; one wave evaluates 64 candidate tiles per pass against the <= 11 tokens of the block.  (ATT_LIST_CAP: attn_common.h)
 template <int D, int CB, int PF>
 __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(AttnParams p) {
     TR1_PROBE_AT(0);

@@ -5,8 +5,8 @@
 // Block = 8 waves x 32 packed query rows.  Q stays in registers as the B operand of S^T[kv][q] = K Q^T, so a lane owns ONE query row and half of
 // a tile's 64 keys: the online softmax is in-lane (32 values per lane + one exchange with lane ^ 32), and P^T comes out of the accumulator in the
 // layout that is the B operand of the PV product after the k-permutation (attn_common.h: pack8).  64-key K / V row tiles stream through a 4-deep
-// LDS ring by asm-issued LDS DMA (hipcc would otherwise serialise every LDS read behind the pending DMA; see csrc/attn_bwd.hip), swizzled on
-// the source address with skey().  32 MFMAs per wave and tile against 16 b128 + 32 transposing LDS reads.
+// LDS ring by asm-issued LDS DMA (hipcc would otherwise serialise every LDS read behind the pending DMA; see tr1_dma16 in tr1_common.h), swizzled on
+// the source address with skey() - the tile image of attn_common.h.  32 MFMAs per wave and tile against 16 b128 + 32 transposing LDS reads.
 #include "attn_common.h"
 #include <stdlib.h>
 #ifndef FWD_AH
@@ -25,25 +25,18 @@
 __device__ unsigned long long* tr1_fwd_probe = nullptr;
 extern "C" int probe_fwd_set_ptr(void* ptr) { return (int)hipMemcpyToSymbol(HIP_SYMBOL(tr1_fwd_probe), &ptr, sizeof(ptr)); }
 #define FWD_PROBE_LDS (8 * 48 * 8 * 8)
-#define FWD_STAMPS unsigned long long fwd_st_[8] = {0, 0, 0, 0, 0, 0, 0, 0}
-#define FWD_STAMP(slot) do { fwd_st_[slot] = __builtin_amdgcn_s_memtime(); } while (0)
 #define FWD_FLUSH(it) do { if (blockIdx.x == 0 && (threadIdx.x & 63) == 0 && (it) < 48) { \
     unsigned long long* pl_ = reinterpret_cast<unsigned long long*>(dyn_lds + 4 * (2 * 64 * 256) + 128); \
-    _Pragma("unroll") for (int s_ = 0; s_ < 8; ++s_) pl_[(((threadIdx.x >> 6) * 48 + (it)) * 8 + s_)] = fwd_st_[s_]; } } while (0)
+    _Pragma("unroll") for (int s_ = 0; s_ < 8; ++s_) pl_[(((threadIdx.x >> 6) * 48 + (it)) * 8 + s_)] = att_st_[s_]; } } while (0)
 #define FWD_DUMP() do { if (tr1_fwd_probe && blockIdx.x == 0) { __syncthreads(); \
     const unsigned long long* pl_ = reinterpret_cast<const unsigned long long*>(dyn_lds + 4 * (2 * 64 * 256) + 128); \
     for (int i_ = threadIdx.x; i_ < 8 * 48 * 8; i_ += 512) tr1_fwd_probe[i_] = pl_[i_]; } } while (0)
 #else
 #define FWD_PROBE_LDS 0
-#define FWD_STAMPS do { } while (0)
-#define FWD_STAMP(slot) do { } while (0)
 #define FWD_FLUSH(it) do { } while (0)
 #define FWD_DUMP() do { } while (0)
 #endif
 
-#ifndef FWD_LAZY_MAX
-#define FWD_LAZY_MAX 6      // log2 units; 0 = rescale whenever a row's maximum moves (round-3 behaviour)
-#endif
 // KS = k-steps (16 features each) of the S product that can be non-zero, NDB = KS / 2 = 32-feature blocks of O that are computed and stored.  KS = 8: head dim 128.
 // KS = 6 (round 6, the vision towers' head dim 80 on 128-wide zero-padded heads, features d < 40 at d and d + 40 at 48 + d): features 96..127 of Q / K / V are zero
 // by construction, so 12 + 12 of the 16 + 16 MFMAs of a tile (and the matching LDS fragment reads) carry everything; O columns 96..127 are not written.
@@ -56,45 +49,17 @@ __global__ __launch_bounds__(512) void attn_fwd32_kernel(AttnParams p) {
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), c32 = lane & 31, h = lane >> 5;
     const unsigned nR = (unsigned)p.T * (unsigned)p.group;
     const int nqb = (int)((nR + 255u) / 256u);
-    // block -> (query block, kv head).  The hardware deals consecutive workgroups to the 8 XCDs round-robin; with 8 % n_kv == 0 every XCD serves ONE
-    // kv head (its K / V stay in that XCD's L2) and walks the query blocks from the last (heaviest: most visible keys) to the first.
     int kvh, qb;
-    if (p.xcd_pad) {
-        const int id = (int)blockIdx.x, xcd = id & 7, per = 8 / p.n_kv;
-        kvh = xcd % p.n_kv; qb = (id >> 3) * per + xcd / p.n_kv;
-        if (qb >= nqb) return;
-    } else if ((p.n_kv & 7) == 0) {
-        // >= 8 kv heads (the vision towers: 16 heads, group 1): head h is served by XCD h % 8, which walks that head's query blocks in order - a segment's
-        // K / V (0.4 MB at config 3) is then fetched into ONE L2 instead of into all eight (the plain map dealt the query blocks of a head round-robin
-        // over the XCDs: 8 x the operand bytes from HBM, the round-2 finding for the 96-wide kernel)
-        const int id = (int)blockIdx.x, xcd = id & 7, sq = id >> 3;
-        kvh = xcd + 8 * (sq / nqb); qb = sq - (sq / nqb) * nqb;
-    } else { qb = (int)blockIdx.x % nqb; kvh = (int)blockIdx.x / nqb; }
+    ATT_BLOCK_MAP(p, nqb, kvh, qb, return);
     const unsigned Rw0 = (unsigned)(nqb - 1 - qb) * 256u + (unsigned)wave * 32u;
     const unsigned R = Rw0 + (unsigned)c32;
     const bool valid = R < nR;
     int tq, hq;
     att_split_row(p, valid ? R : nR - 1, tq, hq);
     const int pre = valid ? p.pre[tq] : 0, lo = valid ? p.lo[tq] : 1, hi = valid ? p.hi[tq] : 0;
-    // the row's two visible intervals clamped to the cache's slots: visible(kv) = kv < pre_e | (unsigned)(kv - lo_e) <= hi_d  (lo_e = INT_MAX: no second interval)
-    const int hi_c = hi < p.n_slots ? hi : p.n_slots - 1;
-    const int pre_e = pre < p.n_slots ? pre : p.n_slots, lo_e = hi_c >= lo ? lo : 0x7fffffff, hi_d = hi_c >= lo ? hi_c - lo : 0;
-    int wmaxpre = valid ? pre : 0, wminpre = valid ? pre : 0x7fffffff;
-    int wminlo = (valid && hi >= lo) ? lo : 0x7fffffff, wmaxhi = (valid && hi >= lo) ? hi : -1;
-    int wmaxlo = valid ? (hi >= lo ? lo : 0x7fffffff) : -1, wminhi = valid ? (hi >= lo ? hi : -1) : 0x7fffffff;
-#pragma unroll
-    for (int o = 1; o < 32; o <<= 1) {
-        wmaxpre = max(wmaxpre, __shfl_xor(wmaxpre, o, 64)); wminpre = min(wminpre, __shfl_xor(wminpre, o, 64));
-        wminlo = min(wminlo, __shfl_xor(wminlo, o, 64)); wmaxhi = max(wmaxhi, __shfl_xor(wmaxhi, o, 64));
-        wmaxlo = max(wmaxlo, __shfl_xor(wmaxlo, o, 64)); wminhi = min(wminhi, __shfl_xor(wminhi, o, 64));
-    }
-    wmaxpre = __builtin_amdgcn_readfirstlane(wmaxpre); wminpre = __builtin_amdgcn_readfirstlane(wminpre);
-    wminlo = __builtin_amdgcn_readfirstlane(wminlo); wmaxhi = __builtin_amdgcn_readfirstlane(wmaxhi);
-    wmaxlo = __builtin_amdgcn_readfirstlane(wmaxlo); wminhi = __builtin_amdgcn_readfirstlane(wminhi);
-    // (rows past nR - the padding of the last block - never force the masked path: they compute finite garbage that is not stored.  With an
-    //  `all 32 rows valid` term in `full`, the ONE partially valid wave of the heaviest block took the per-element mask path on every tile:
-    //  3 900 instead of 1 200 cycles of softmax, all other waves waiting for it at the barrier - wave timeline in DESIGN.md)
-    if (lane == 0) { lds_meta[wave * 3 + 0] = wmaxpre; lds_meta[wave * 3 + 1] = wminlo; lds_meta[wave * 3 + 2] = wmaxhi; }
+    const AttRowMask rm = ATT_ROW_MASK(pre, lo, hi, p.n_slots);
+    const AttWaveMask wm = ATT_WAVE_MASK(valid, pre, lo, hi);
+    if (lane == 0) { lds_meta[wave * 3 + 0] = wm.maxpre; lds_meta[wave * 3 + 1] = wm.minlo; lds_meta[wave * 3 + 2] = wm.maxhi; }
     bf16x8_t qf[KS];                                                  // Q row of this lane, features ks*16 + h*8 .. +7 (B operand)
     {
         const bf16_t* qrow = p.Q + (int64_t)tq * p.q_ld + (int64_t)(kvh * p.group + hq) * D;
@@ -111,46 +76,24 @@ __global__ __launch_bounds__(512) void attn_fwd32_kernel(AttnParams p) {
     for (int ks = 0; ks < KS; ++ks) asm volatile("" ::"v"(qf[ks]));            // hipcc places the wait for the Q loads here (see attn_bwd.hip)
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
-    int bmaxpre = 0, bminlo = 0x7fffffff, bmaxhi = -1;
-#pragma unroll
-    for (int w = 0; w < 8; ++w) { bmaxpre = max(bmaxpre, lds_meta[w * 3]); bminlo = min(bminlo, lds_meta[w * 3 + 1]); bmaxhi = max(bmaxhi, lds_meta[w * 3 + 2]); }
-    const TileRange tr = att_tile_range(bmaxpre, bminlo, bmaxhi, p.n_slots);
+    const TileRange tr = att_block_range(lds_meta, 3, p.n_slots);
     const int n_my = tr.n_rel;
 
     const unsigned lds_base = (unsigned)(uintptr_t)(att_lptr_t)dyn_lds;
     const char* kbase = reinterpret_cast<const char*>(p.K) + (int64_t)kvh * 256;
     const char* vbase = reinterpret_cast<const char*>(p.V) + (int64_t)kvh * 256;
     const unsigned k_ldb = (unsigned)p.k_ld * 2u, v_ldb = (unsigned)p.v_ld * 2u;
-#define DMA16(voff, sbase, m0v) asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2" ::"s"(m0v), "v"(voff), "s"(sbase) : "memory", "m0")
-    auto issue_tile = [&](int tile, int slot) {
-        const unsigned buf = lds_base + slot * BUF;
-        int ln = lane;
-        asm volatile("" : "+v"(ln));
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            const unsigned row = 4u * (wave * 2 + j) + ((unsigned)ln >> 4);
-            unsigned kv = (unsigned)tile * 64u + row; kv = kv < (unsigned)p.n_slots ? kv : (unsigned)p.n_slots - 1u;
-            const unsigned ch = (unsigned)(((ln & 15) ^ skey(row & 15)) << 4);
-            const unsigned dst = buf + (wave * 2 + j) * 1024;
-            DMA16(kv * k_ldb + ch, kbase, dst);
-            DMA16(kv * v_ldb + ch, vbase, dst + TILE);
-        }
-    };
-#undef DMA16
+    auto issue_tile = [&](int tile, int slot) { att_issue_kv_tile(lane, wave, tile, lds_base, slot, p.n_slots, kbase, k_ldb, vbase, v_ldb); };
 #pragma unroll
     for (int j = 0; j < NB - 1; ++j)
         if (j < n_my) issue_tile(att_tile_at(tr, j), j);
 
-    typedef const __attribute__((address_space(3))) bf16x8_t* lds_b128_t;
-#define LDS_B128(addr) (*(lds_b128_t)(uintptr_t)(addr))
-#define LDS_TR16(addr) __builtin_bit_cast(u32x2_t, __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4_t*)(uintptr_t)(addr)))
     const int ti = lane & 15, tgrp = (lane >> 4) & 1;
-    const unsigned a_lane = (unsigned)(c32 * 256 + ((h ^ skey(c32 & 15)) << 4));
-    const unsigned t_lane = (unsigned)((4 * h + (ti >> 2)) * 256 + (ti & 1) * 8 + (((tgrp * 2 + ((ti & 3) >> 1)) ^ (((ti >> 2) << 2) | h)) << 4));
+    const unsigned a_lane = att_a_lane(c32, h), t_lane = ATT_T_LANE(h, ti, tgrp);
 
     for (int it = 0; it < n_my; ++it) {
-        FWD_STAMPS;
-        FWD_STAMP(0);
+        ATT_STAMPS;
+        ATT_STAMP(0);
         {
             const int after = (n_my - 1 - it) < (NB - 2) ? (n_my - 1 - it) : (NB - 2);
             if (after >= 2) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
@@ -161,11 +104,11 @@ __global__ __launch_bounds__(512) void attn_fwd32_kernel(AttnParams p) {
         __builtin_amdgcn_s_barrier();                                 // tile `it` is complete for everybody; everybody is done with tile it-1
 #endif
         asm volatile("" ::: "memory");
-        FWD_STAMP(1);
+        ATT_STAMP(1);
         if (it + NB - 1 < n_my) issue_tile(att_tile_at(tr, it + NB - 1), (it + NB - 1) % NB);
         const int kv0 = att_tile_at(tr, it) * 64;
-        const bool any = (kv0 < wmaxpre) || (kv0 + 63 >= wminlo && kv0 <= wmaxhi);
-        const bool full = (kv0 + 64 <= p.n_slots) && ((kv0 + 64 <= wminpre) || (wmaxlo <= kv0 && kv0 + 63 <= wminhi));
+        const bool any = (kv0 < wm.maxpre) || (kv0 + 63 >= wm.minlo && kv0 <= wm.maxhi);
+        const bool full = (kv0 + 64 <= p.n_slots) && ((kv0 + 64 <= wm.minpre) || (wm.maxlo <= kv0 && kv0 + 63 <= wm.minhi));
         if (any) {
             const unsigned kb_ = lds_base + (unsigned)(it % NB) * BUF;
             // S^T[kv][q]: two independent chains (the tile's 32-key halves)
@@ -177,10 +120,10 @@ __global__ __launch_bounds__(512) void attn_fwd32_kernel(AttnParams p) {
                 constexpr int AH = FWD_AH;
                 bf16x8_t k0[AH + 1], k1[AH + 1];
 #pragma unroll
-                for (int ks = 0; ks < AH; ++ks) { k0[ks] = LDS_B128(xa ^ (ks * 32)); k1[ks] = LDS_B128((xa ^ (ks * 32)) + 8192); }
+                for (int ks = 0; ks < AH; ++ks) { k0[ks] = att_lds_b128(xa ^ (ks * 32)); k1[ks] = att_lds_b128((xa ^ (ks * 32)) + 8192); }
 #pragma unroll
                 for (int ks = 0; ks < KS; ++ks) {
-                    if (ks + AH < KS) { k0[(ks + AH) % (AH + 1)] = LDS_B128(xa ^ ((ks + AH) * 32)); k1[(ks + AH) % (AH + 1)] = LDS_B128((xa ^ ((ks + AH) * 32)) + 8192); }
+                    if (ks + AH < KS) { k0[(ks + AH) % (AH + 1)] = att_lds_b128(xa ^ ((ks + AH) * 32)); k1[(ks + AH) % (AH + 1)] = att_lds_b128((xa ^ ((ks + AH) * 32)) + 8192); }
 #if !(TR1_ABL & 4)
                     cs[0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(k0[ks % (AH + 1)], qf[ks], cs[0], 0, 0, 0);
                     cs[1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(k1[ks % (AH + 1)], qf[ks], cs[1], 0, 0, 0);
@@ -190,7 +133,7 @@ __global__ __launch_bounds__(512) void attn_fwd32_kernel(AttnParams p) {
                     __builtin_amdgcn_sched_barrier(0);
                 }
             }
-            FWD_STAMP(2);
+            ATT_STAMP(2);
             // lane holds S^T[kv = kv0 + kb*32 + 8i + 4h + j][its query row] in cs[kb][4i + j]; lane ^ 32 holds the other 32 keys of the row
             // (vector-ALU work is what this kernel pays for next to its MFMAs - the two do not overlap on a SIMD, see DESIGN.md: the masked path
             //  only rewrites cs in place, so both paths share ONE copy of the code below and no register copies appear at the join; the max runs
@@ -200,8 +143,8 @@ __global__ __launch_bounds__(512) void attn_fwd32_kernel(AttnParams p) {
                 // (v_cmp -> s_and / s_or on the masks -> v_cndmask) put scalar instructions that wait for vector results between the selects (attn_fwd64.hip measured
                 // 4 600 against 2 600 cycles per masked tile); same values
                 const int base = kv0 + 4 * h;
-                const unsigned mA = (unsigned)(base - lo_e), mD = (unsigned)hi_d;
-                const int mB = pre_e - base;
+                const unsigned mA = (unsigned)(base - rm.lo_e), mD = (unsigned)rm.hi_d;
+                const int mB = rm.pre_e - base;
 #pragma unroll
                 for (int kb = 0; kb < 2; ++kb)
 #pragma unroll
@@ -219,13 +162,13 @@ __global__ __launch_bounds__(512) void attn_fwd32_kernel(AttnParams p) {
             for (int r = 0; r < 16; r += 2) { mxa = att_max3(mxa, cs[0][r], cs[0][r + 1]); mxb = att_max3(mxb, cs[1][r], cs[1][r + 1]); }
             float mx = fmaxf(mxa, mxb);
             { float mx0_, mx1_; att_halves(mx, mx0_, mx1_); mx = fmaxf(mx0_, mx1_); }
-            // Lazy running maximum: when no row of the wave would raise its maximum by more than FWD_LAZY_MAX (log2 units), the OLD maximum stays the
+            // Lazy running maximum: when no row of the wave would raise its maximum by more than ATT_LAZY_MAX (log2 units), the OLD maximum stays the
             // reference point of this tile - alpha == 1 for every row, so the 64 accumulator multiplies per lane are skipped and P = exp2(s - m_old) <= 2^6;
             // l, the accumulators and the LSE (m + log2 l) stay mutually consistent because all three use the same reference.  With the exact test
             // (maximum unchanged) the skip only fired late in a row's key range: a tile of 64 new keys holds a new row maximum with probability 1 / (t + 1).
             const float m_cand = fmaxf(m, mx * p.scale_log2);         // max over RAW scores (scale > 0 commutes with max)
-#if FWD_LAZY_MAX > 0
-            const float m_new = __all(m_cand - m <= (float)FWD_LAZY_MAX) ? m : m_cand;      // (m = -inf: the difference is inf or NaN -> false -> take the new maximum)
+#if ATT_LAZY_MAX > 0
+            const float m_new = __all(m_cand - m <= (float)ATT_LAZY_MAX) ? m : m_cand;      // (m = -inf: the difference is inf or NaN -> false -> take the new maximum)
 #else
             const float m_new = m_cand;
 #endif
@@ -257,17 +200,16 @@ __global__ __launch_bounds__(512) void attn_fwd32_kernel(AttnParams p) {
 #pragma unroll
                     for (int r = 0; r < 16; ++r) acc[db][r] *= alpha;
             }
-            FWD_STAMP(3);
+            ATT_STAMP(3);
             // O^T[feature][q] += V^T[feature][kv] P^T[kv][q], 16 keys per MFMA; V^T fragments are transposing reads of the V row tile
             const unsigned ya = kb_ + TILE + t_lane;
             constexpr int TH = FWD_TH;
             bf16x8_t a[TH + 1];
-#define P2_LD(n) make_frag(LDS_TR16((ya ^ (((n) % NDB) * 64)) + ((n) / NDB) * 4096), LDS_TR16((ya ^ (((n) % NDB) * 64 + 32)) + ((n) / NDB) * 4096 + 2048))
 #pragma unroll
-            for (int n = 0; n < TH; ++n) a[n] = P2_LD(n);
+            for (int n = 0; n < TH; ++n) a[n] = att_p2_ld<NDB>(ya, n);
 #pragma unroll
             for (int n = 0; n < 4 * NDB; ++n) {                       // n = chunk (16 keys) * NDB + feature block
-                if (n + TH < 4 * NDB) a[(n + TH) % (TH + 1)] = P2_LD(n + TH);
+                if (n + TH < 4 * NDB) a[(n + TH) % (TH + 1)] = att_p2_ld<NDB>(ya, n + TH);
                 const bf16x8_t f = pack8(cs[(n / NDB) >> 1], ((n / NDB) & 1) * 8);
 #if !(TR1_ABL & 2)
                 acc[n % NDB] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[n % (TH + 1)], f, acc[n % NDB], 0, 0, 0);
@@ -276,16 +218,13 @@ __global__ __launch_bounds__(512) void attn_fwd32_kernel(AttnParams p) {
 #endif
                 __builtin_amdgcn_sched_barrier(0);
             }
-#undef P2_LD
-            FWD_STAMP(4);
+            ATT_STAMP(4);
         }
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");           // all LDS reads of this tile have returned before the barrier that frees its slot
-        FWD_STAMP(5);
+        ATT_STAMP(5);
         FWD_FLUSH(it);
     }
     FWD_DUMP();
-#undef LDS_B128
-#undef LDS_TR16
     // lane holds O^T[feature = db*32 + 8i + 4h + j][its query row]
     int tid2 = threadIdx.x;
     asm volatile("" : "+v"(tid2));
@@ -313,23 +252,18 @@ __global__ __launch_bounds__(512) void attn_fwd32_kernel(AttnParams p) {
 // before each tile is written to LDS; here all of a block's tiles (2-3 at config 3) are requested at once by asm-issued LDS DMA and consumed
 // behind hand-counted vmcnt waits, so a block costs ONE memory round trip.  K tile: 64 rows x 256 B (swizzled with skey); V^T tile: 128 feature
 // rows x 128 B straight from the cache's V^T layout (chunk ^ (row & 7)).  Partials go to the same workspace the combine kernel reads.
-#define DEC32_CAP 1024      // = ATT_LIST_CAP of attn_fwd.hip (plan entry layout: [CAP ids | count])
 #ifdef TR1_PROBE
 __device__ unsigned long long* tr1_dec_probe = nullptr;          // [blocks][4 waves][12 stamps]  (tools/bench_attn_decode.py PROBE=1, -DTR1_PROBE build)
 extern "C" int probe_dec_set_ptr(void* ptr) { return (int)hipMemcpyToSymbol(HIP_SYMBOL(tr1_dec_probe), &ptr, sizeof(ptr)); }
-#define DEC_STAMPS unsigned long long dst_[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}
-#define DEC_STAMP(i) do { dst_[i] = __builtin_amdgcn_s_memtime(); } while (0)
 #define DEC_FLUSH() do { if (tr1_dec_probe && (threadIdx.x & 63) == 0) { const size_t bid_ = ((size_t)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x; \
-    _Pragma("unroll") for (int s_ = 0; s_ < 12; ++s_) tr1_dec_probe[(bid_ * 4 + (threadIdx.x >> 6)) * 12 + s_] = dst_[s_]; } } while (0)
+    _Pragma("unroll") for (int s_ = 0; s_ < 12; ++s_) tr1_dec_probe[(bid_ * 4 + (threadIdx.x >> 6)) * 12 + s_] = att_st_[s_]; } } while (0)
 #else
-#define DEC_STAMPS do { } while (0)
-#define DEC_STAMP(i) do { } while (0)
 #define DEC_FLUSH() do { } while (0)
 #endif
 __global__ __launch_bounds__(512) void attn_dec32_kernel(AttnParams p) {
     constexpr int D = 128, NB = 4, KT = 64 * 256, VT = 128 * 128, BUF = KT + VT;
-    DEC_STAMPS;
-    DEC_STAMP(0);
+    ATT_STAMPS_N(12);
+    ATT_STAMP(0);
     extern __shared__ __attribute__((aligned(256))) char dyn_lds[];  // [NB][K rows | V^T rows] | Q rows (64 x 256 B) | pre, lo, hi [64] | meta
     constexpr int QOFF = NB * BUF, MOFF = QOFF + 64 * 256;
     int* lds_meta = reinterpret_cast<int*>(dyn_lds + MOFF + 768);    // [2][3]
@@ -339,13 +273,13 @@ __global__ __launch_bounds__(512) void attn_dec32_kernel(AttnParams p) {
     const int qtile = gx - 1 - (int)blockIdx.x;
     p.Q += (int64_t)b * p.T * p.q_ld; p.pre += (int64_t)b * p.T; p.lo += (int64_t)b * p.T; p.hi += (int64_t)b * p.T;
     const unsigned nR = (unsigned)p.T * (unsigned)p.group;
-    const int* plan_blk = p.plan + ((int64_t)b * gx + qtile) * (DEC32_CAP + 1);
+    const int* plan_blk = p.plan + ((int64_t)b * gx + qtile) * (ATT_LIST_CAP + 1);
     // the plan words this block can need for its first NB tiles, requested TOGETHER at kernel entry (independent scalar loads, one wait much
     // later): read one by one where they are used, they were four dependent L2 round trips (~3 us) in front of the late tiles' DMA
     int plan_w[NB + 1];
-    plan_w[NB] = plan_blk[DEC32_CAP];
+    plan_w[NB] = plan_blk[ATT_LIST_CAP];
 #pragma unroll
-    for (int j = 0; j < NB; ++j) { const int idx = split + j * p.nsplit; plan_w[j] = plan_blk[idx < DEC32_CAP ? idx : DEC32_CAP - 1]; }
+    for (int j = 0; j < NB; ++j) { const int idx = split + j * p.nsplit; plan_w[j] = plan_blk[idx < ATT_LIST_CAP ? idx : ATT_LIST_CAP - 1]; }
 
     const unsigned lds_base = (unsigned)(uintptr_t)(att_lptr_t)dyn_lds;
     const char* kbase = reinterpret_cast<const char*>(p.K) + ((int64_t)b * p.kv_batch_slots * p.k_ld + (int64_t)kvh * D) * 2;
@@ -364,17 +298,17 @@ __global__ __launch_bounds__(512) void attn_dec32_kernel(AttnParams p) {
         voff[j] = vrow * vt_ldb + (unsigned)(((lane & 7) ^ (vrow & 7)) << 4);
         kdst[j] = (unsigned)i * 1024u; vdst[j] = (unsigned)KT + (unsigned)i * 1024u;
     }
-#define DMA16(voff_, sbase, m0v) asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2" ::"s"(m0v), "v"(voff_), "s"(sbase) : "memory", "m0")
     auto issue_tile = [&](int tile, int slot) {                       // (cache regions are whole tiles: s_cap % 64 == 0, checked by the launcher)
         const unsigned buf = lds_base + slot * BUF;
         const unsigned tk = (unsigned)tile * 64u * k_ldb, tv = (unsigned)tile * 128u;
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
-            DMA16(koff[j] + tk, kbase, buf + __builtin_amdgcn_readfirstlane(kdst[j]));
-            DMA16(voff[j] + tv, vbase, buf + __builtin_amdgcn_readfirstlane(vdst[j]));
+            const unsigned kd = buf + __builtin_amdgcn_readfirstlane(kdst[j]);
+            tr1_dma16(koff[j] + tk, kbase, kd);
+            const unsigned vd = buf + __builtin_amdgcn_readfirstlane(vdst[j]);
+            tr1_dma16(voff[j] + tv, vbase, vd);
         }
     };
-#undef DMA16
     const bool cw = wave < 4;                                         // compute wave
     const int rw = wave & 1, kh = (wave >> 1) & 1;
     const unsigned Rw0 = (unsigned)qtile * 64u + (unsigned)rw * 32u;
@@ -393,13 +327,11 @@ __global__ __launch_bounds__(512) void attn_dec32_kernel(AttnParams p) {
     const bool spec = spec_tile * 64 < p.n_slots;
 #endif
     if (spec) issue_tile(spec_tile, 0);
-    DEC_STAMP(1);
+    ATT_STAMP(1);
     // Q rows and the row masks travel by LDS DMA like the tiles (2 + (wave 0: 3) instructions): EVERY input is then ordered by the hand-counted
     // vmcnt waits, and hipcc sees LDS reads only.  (Plain loads written in asm were tried: hipcc may copy their destination registers before the
     // hand-placed wait - it believes them defined at the asm statement - and the copies then hold stale data.)
     {
-#define DMA16Q(voff_, sbase, m0v) asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2" ::"s"(m0v), "v"(voff_), "s"(sbase) : "memory", "m0")
-#define DMA4Q(voff_, sbase, m0v) asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dword %1, %2" ::"s"(m0v), "v"(voff_), "s"(sbase) : "memory", "m0")
         const char* qbase = reinterpret_cast<const char*>(p.Q) + (int64_t)kvh * p.group * 256;
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
@@ -408,21 +340,19 @@ __global__ __launch_bounds__(512) void attn_dec32_kernel(AttnParams p) {
             unsigned Rr = (unsigned)qtile * 64u + row; Rr = Rr < nR ? Rr : nR - 1u;
             const unsigned tu = p.group == 1 ? Rr : __umulhi(Rr, p.group_magic);
             const unsigned off = tu * ((unsigned)p.q_ld * 2u) + (Rr - tu * (unsigned)p.group) * 256u + (unsigned)(((lane & 15) ^ skey(row & 15)) << 4);
-            DMA16Q(off, qbase, lds_base + QOFF + (unsigned)i * 1024u);
+            tr1_dma16(off, qbase, lds_base + QOFF + (unsigned)i * 1024u);
         }
         if (wave == 0) {
             unsigned Rr = (unsigned)qtile * 64u + (unsigned)lane; Rr = Rr < nR ? Rr : nR - 1u;
             const unsigned to = (p.group == 1 ? Rr : __umulhi(Rr, p.group_magic)) * 4u;
-            DMA4Q(to, p.pre, lds_base + MOFF);
-            DMA4Q(to, p.lo, lds_base + MOFF + 256);
-            DMA4Q(to, p.hi, lds_base + MOFF + 512);
+            tr1_dma4(to, p.pre, lds_base + MOFF);
+            tr1_dma4(to, p.lo, lds_base + MOFF + 256);
+            tr1_dma4(to, p.hi, lds_base + MOFF + 512);
         }
-#undef DMA16Q
-#undef DMA4Q
     }
-    DEC_STAMP(2);
+    ATT_STAMP(2);
     const int plan_n = __builtin_amdgcn_readfirstlane(plan_w[NB]);
-    DEC_STAMP(3);
+    ATT_STAMP(3);
     int n_my; TileRange tr{0, 0, 0};
     bool spec_hit = false;
     int first_late = 0;                                               // tiles requested after the plain loads (their DMA is younger than Q / masks)
@@ -454,7 +384,7 @@ __global__ __launch_bounds__(512) void attn_dec32_kernel(AttnParams p) {
         for (int j = 0; j < NB; ++j)
             if (j < n_my && !(j == 0 && spec_hit)) { issue_tile(att_tile_at(tr, split + j * p.nsplit), j); ++first_late; }
     }
-    DEC_STAMP(4);
+    ATT_STAMP(4);
     const int pw0 = __builtin_amdgcn_readfirstlane(plan_w[0]), pw1 = __builtin_amdgcn_readfirstlane(plan_w[1]), pw2 = __builtin_amdgcn_readfirstlane(plan_w[2]),
               pw3 = __builtin_amdgcn_readfirstlane(plan_w[3]);
     auto dec_tile = [&](int i) -> int {      // tile id of the block's i-th tile (scalar selects: no register-relative indexing)
@@ -475,29 +405,26 @@ __global__ __launch_bounds__(512) void attn_dec32_kernel(AttnParams p) {
         else if (first_late == 1) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
         else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     } else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    DEC_STAMP(5);
+    ATT_STAMP(5);
     __builtin_amdgcn_s_barrier();                                     // Q rows, masks (and tile 0) of every wave's DMA share are in LDS
     asm volatile("" ::: "memory");
     bf16x8_t qf[D / 16];
     int pre, lo, hi;
     {
-        const unsigned qa = lds_base + QOFF + (unsigned)(rw * 8192 + c32 * 256 + ((h ^ skey(c32 & 15)) << 4));
+        const unsigned qa = lds_base + QOFF + att_a_lane(c32, h, rw);
 #pragma unroll
-        for (int ks = 0; ks < D / 16; ++ks) qf[ks] = *(const __attribute__((address_space(3))) bf16x8_t*)(uintptr_t)(qa ^ (ks * 32));
+        for (int ks = 0; ks < D / 16; ++ks) qf[ks] = att_lds_b128(qa ^ (ks * 32));
         const int* mk = reinterpret_cast<const int*>(dyn_lds + MOFF) + rw * 32 + c32;
         pre = mk[0]; lo = mk[64]; hi = mk[128];
     }
     if (!valid) { pre = 0; lo = 1; hi = 0; }
-    const int hi_c = hi < p.n_slots ? hi : p.n_slots - 1;             // the row's two visible intervals clamped to the cache's slots
-    const int pre_e = pre < p.n_slots ? pre : p.n_slots, lo_e = hi_c >= lo ? lo : 0x7fffffff, hi_d = hi_c >= lo ? hi_c - lo : 0;
+    const AttRowMask rm = ATT_ROW_MASK(pre, lo, hi, p.n_slots);
     int landed = spec_hit ? 1 : (n_my < NB ? n_my : NB);             // tiles whose DMA (this wave's share) is known complete
     const int first_batch = n_my < NB ? n_my : NB;                    // tiles requested before the loop
 
-    typedef const __attribute__((address_space(3))) bf16x8_t* lds_b128_t;
     typedef const __attribute__((address_space(3))) u32x2_t* lds_b64_t;
-#define LDS_B128(addr) (*(lds_b128_t)(uintptr_t)(addr))
 #define LDS_B64(addr) (*(lds_b64_t)(uintptr_t)(addr))
-    const unsigned a_lane = (unsigned)(kh * 8192 + c32 * 256 + ((h ^ skey(c32 & 15)) << 4));      // K rows kh*32 + c32
+    const unsigned a_lane = att_a_lane(c32, h, kh);      // K rows kh*32 + c32
     // V^T A fragment of feature row d = db*32 + c32, 16-key chunk cc (of this wave's key half: chunks 2kh, 2kh+1): keys 4h..4h+3 (first 8 bytes)
     // and 8+4h..8+4h+3 (second): byte cc*32 + 8h (+16) of the 128-byte row -> logical 16-byte chunk 2cc (+1), half h; physical = logical ^ (row & 7)
     const unsigned v_lane = (unsigned)(c32 * 128 + 8 * h), v_key = (unsigned)((c32 & 7) << 4);
@@ -513,7 +440,7 @@ __global__ __launch_bounds__(512) void attn_dec32_kernel(AttnParams p) {
         }
         if (it > 0) __builtin_amdgcn_s_barrier();                     // (tile 0: the barrier in front of the Q / mask reads already covered it)
         asm volatile("" ::: "memory");
-        if (it < 3) DEC_STAMP(6 + it);
+        if (it < 3) ATT_STAMP(6 + it);
         if (it >= 1 && it + NB - 1 < n_my) issue_tile(DEC_TILE(it + NB - 1), (it + NB - 1) % NB);
         if (!cw) { continue; }
         const int kv0 = DEC_TILE(it) * 64 + kh * 32;                  // first key of this wave's half tile
@@ -523,7 +450,7 @@ __global__ __launch_bounds__(512) void attn_dec32_kernel(AttnParams p) {
         {
             const unsigned xa = kb_ + a_lane;
 #pragma unroll
-            for (int ks = 0; ks < D / 16; ++ks) kf[ks] = LDS_B128(xa ^ (ks * 32));
+            for (int ks = 0; ks < D / 16; ++ks) kf[ks] = att_lds_b128(xa ^ (ks * 32));
         }
         f32x16_t cs, c1;
 #pragma unroll
@@ -560,8 +487,8 @@ __global__ __launch_bounds__(512) void attn_dec32_kernel(AttnParams p) {
         } else {
             // (round 6) vector-only interval mask (two compares + two selects on the clamped intervals; see attn_fwd32_kernel): every suffix tile of a decode step takes this path
             const int base = kv0 + 4 * h;
-            const unsigned mA = (unsigned)(base - lo_e), mD = (unsigned)hi_d;
-            const int mB = pre_e - base;
+            const unsigned mA = (unsigned)(base - rm.lo_e), mD = (unsigned)rm.hi_d;
+            const int mB = rm.pre_e - base;
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 const int c = (r & 3) + 8 * (r >> 2);
@@ -595,10 +522,9 @@ __global__ __launch_bounds__(512) void attn_dec32_kernel(AttnParams p) {
         for (int n = 0; n < 8; ++n) acc[n & 3] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf[n], (n >> 2) ? f1 : f0, acc[n & 3], 0, 0, 0);
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     }
-#undef LDS_B128
 #undef LDS_B64
 #undef DEC_TILE
-    DEC_STAMP(9);
+    ATT_STAMP(9);
     // merge the two key halves of every row (waves rw + 2 hand their running state to waves rw through LDS; ring slot 0 is free by now)
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
@@ -633,7 +559,7 @@ __global__ __launch_bounds__(512) void attn_dec32_kernel(AttnParams p) {
             }
         if (h == 0) { p.mpart[slot] = M; p.lpart[slot] = L; }
     }
-    DEC_STAMP(10);
+    ATT_STAMP(10);
     DEC_FLUSH();
 }
 

@@ -24,40 +24,23 @@
 #ifndef F64_KREG
 #define F64_KREG "v"
 #endif
-#ifndef FWD64_LAZY_MAX
-#define FWD64_LAZY_MAX 6      // = FWD_LAZY_MAX of attn_fwd32.hip (the two kernels must take the same rescale decisions)
-#endif
 
 #ifdef TR1_PROBE
 // wave-timeline probe (tools/check_fwd64.py --probe against tools/_probe_lib.so): stamps stay in scalar registers, go to a spare LDS area per tile, one dump at the end
 __device__ unsigned long long* tr1_fwd64_probe = nullptr;          // [4 waves][64 tiles][8 stamps]
 extern "C" int probe_fwd64_set_ptr(void* ptr) { return (int)hipMemcpyToSymbol(HIP_SYMBOL(tr1_fwd64_probe), &ptr, sizeof(ptr)); }
 #define F64_PROBE_LDS (4 * 64 * 8 * 8)
-#define F64_STAMPS unsigned long long f64_st_[8] = {0, 0, 0, 0, 0, 0, 0, 0}
-#define F64_STAMP(slot) do { f64_st_[slot] = __builtin_amdgcn_s_memtime(); } while (0)
 #define F64_FLUSH(it) do { if (blockIdx.x == 0 && (threadIdx.x & 63) == 0 && (it) < 64) { \
     unsigned long long* pl_ = reinterpret_cast<unsigned long long*>(dyn_lds + 8 * (64 * 256) + 128); \
-    _Pragma("unroll") for (int s_ = 0; s_ < 8; ++s_) pl_[(((threadIdx.x >> 6) * 64 + (it)) * 8 + s_)] = f64_st_[s_]; } } while (0)
+    _Pragma("unroll") for (int s_ = 0; s_ < 8; ++s_) pl_[(((threadIdx.x >> 6) * 64 + (it)) * 8 + s_)] = att_st_[s_]; } } while (0)
 #define F64_DUMP() do { if (tr1_fwd64_probe && blockIdx.x == 0) { __syncthreads(); \
     const unsigned long long* pl_ = reinterpret_cast<const unsigned long long*>(dyn_lds + 8 * (64 * 256) + 128); \
     for (int i_ = threadIdx.x; i_ < 4 * 64 * 8; i_ += 256) tr1_fwd64_probe[i_] = pl_[i_]; } } while (0)
 #else
 #define F64_PROBE_LDS 0
-#define F64_STAMPS do { } while (0)
-#define F64_STAMP(slot) do { } while (0)
 #define F64_FLUSH(it) do { } while (0)
 #define F64_DUMP() do { } while (0)
 #endif
-// both key halves of a query row meet: x -> (value of the row's lane < 32, value of its lane >= 32) in every lane.  v_permlane32_swap is a vector instruction;
-// __shfl_xor(x, 32) is a ds_bpermute whose lgkmcnt(0) wait also drains every fragment read in flight - four of those per tile cost 600 of the body's 4 000 cycles
-// (profiles/r06_fwd64_timeline.txt).  (The builtin's second result is mis-assigned by this hipcc - both halves read back vdst - hence assembly; the leading
-// nops are the VALU-write -> permlane read wait states.)
-TR1_DEV void f64_halves(float x, float& a, float& b) {
-    a = x; b = x;
-    asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1" : "+v"(a), "+v"(b));
-}
-// max of two without the canonicalising v_max x, x that fmaxf() costs per operand (no NaN reaches the statistics: -inf masks, finite inputs)
-TR1_DEV float f64_max(float a, float b) { float o; asm("v_max_f32 %0, %1, %2" : "=v"(o) : "v"(a), "v"(b)); return o; }
 // The S product's MFMAs are written in assembly to pin their register files: hipcc gives a kernel with a 512-register budget the accumulator-file form of
 // EVERY MFMA (C / D in AGPRs), and the softmax - vector instructions cannot read AGPRs - then costs 200+ v_accvgpr moves per tile.  S lives in arch VGPRs
 // (C / D "v"), the K fragment in VGPRs, the Q fragment in the accumulator file ("a": it is only ever an MFMA operand); O's accumulators stay with the builtin
@@ -74,18 +57,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), c32 = lane & 31, h = lane >> 5;
     const unsigned nR = (unsigned)p.T * (unsigned)p.group;
     const int nqb = (int)((nR + 255u) / 256u);
-    int kvh, qblk;                                                    // block -> (query block, kv head): the map of attn_fwd32_kernel
-    if (p.xcd_pad) {
-        const int id = (int)blockIdx.x, xcd = id & 7, per = 8 / p.n_kv;
-        kvh = xcd % p.n_kv; qblk = (id >> 3) * per + xcd / p.n_kv;
-        if (qblk >= nqb) return;
-    } else if ((p.n_kv & 7) == 0) {
-        const int id = (int)blockIdx.x, xcd = id & 7, sq = id >> 3;
-        kvh = xcd + 8 * (sq / nqb); qblk = sq - (sq / nqb) * nqb;
-    } else { qblk = (int)blockIdx.x % nqb; kvh = (int)blockIdx.x / nqb; }
+    int kvh, qblk;
+    ATT_BLOCK_MAP(p, nqb, kvh, qblk, return);
     const unsigned Rw0 = (unsigned)(nqb - 1 - qblk) * 256u + (unsigned)wave * 64u;
-    int pre_e[2], lo_e[2], hi_d[2];                                   // per row: visible(kv) = kv < pre_e | (unsigned)(kv - lo_e) <= hi_d   (clamped to the cache's slots; lo_e = INT_MAX: no second interval)
-    int wmaxpre[2], wminpre[2], wmaxlo[2], wminhi[2];
+    AttRowMask rm[2];                                                 // per q-block: the lane's row, the wave summary of its 32 rows
+    AttWaveMask wm[2];
     bf16x8_t qf[2][KS];                                               // Q rows of this lane (q-blocks A / B), features ks*16 + h*8 .. +7 (B operands)
 #pragma unroll
     for (int b = 0; b < 2; ++b) {
@@ -94,24 +70,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
         int tq, hq;
         att_split_row(p, valid ? R : nR - 1, tq, hq);
         const int pre_b = valid ? p.pre[tq] : 0, lo_b = valid ? p.lo[tq] : 1, hi_b = valid ? p.hi[tq] : 0;
-        {
-            const int hc = hi_b < p.n_slots ? hi_b : p.n_slots - 1;
-            pre_e[b] = pre_b < p.n_slots ? pre_b : p.n_slots;
-            lo_e[b] = hc >= lo_b ? lo_b : 0x7fffffff; hi_d[b] = hc >= lo_b ? hc - lo_b : 0;
-        }
-        int a0 = valid ? pre_b : 0, a1 = valid ? pre_b : 0x7fffffff;
-        int a2 = (valid && hi_b >= lo_b) ? lo_b : 0x7fffffff, a3 = (valid && hi_b >= lo_b) ? hi_b : -1;
-        int a4 = valid ? (hi_b >= lo_b ? lo_b : 0x7fffffff) : -1, a5 = valid ? (hi_b >= lo_b ? hi_b : -1) : 0x7fffffff;
-#pragma unroll
-        for (int o = 1; o < 32; o <<= 1) {
-            a0 = max(a0, __shfl_xor(a0, o, 64)); a1 = min(a1, __shfl_xor(a1, o, 64));
-            a2 = min(a2, __shfl_xor(a2, o, 64)); a3 = max(a3, __shfl_xor(a3, o, 64));
-            a4 = max(a4, __shfl_xor(a4, o, 64)); a5 = min(a5, __shfl_xor(a5, o, 64));
-        }
-        wmaxpre[b] = __builtin_amdgcn_readfirstlane(a0); wminpre[b] = __builtin_amdgcn_readfirstlane(a1);
-        const int wminlo = __builtin_amdgcn_readfirstlane(a2), wmaxhi = __builtin_amdgcn_readfirstlane(a3);
-        wmaxlo[b] = __builtin_amdgcn_readfirstlane(a4); wminhi[b] = __builtin_amdgcn_readfirstlane(a5);
-        if (lane == 0) { lds_meta[(wave * 2 + b) * 3 + 0] = wmaxpre[b]; lds_meta[(wave * 2 + b) * 3 + 1] = wminlo; lds_meta[(wave * 2 + b) * 3 + 2] = wmaxhi; }
+        rm[b] = ATT_ROW_MASK(pre_b, lo_b, hi_b, p.n_slots);
+        wm[b] = ATT_WAVE_MASK(valid, pre_b, lo_b, hi_b);
+        if (lane == 0) { lds_meta[(wave * 2 + b) * 3 + 0] = wm[b].maxpre; lds_meta[(wave * 2 + b) * 3 + 1] = wm[b].minlo; lds_meta[(wave * 2 + b) * 3 + 2] = wm[b].maxhi; }
         const bf16_t* qrow = p.Q + (int64_t)tq * p.q_ld + (int64_t)(kvh * p.group + hq) * D;
 #pragma unroll
         for (int ks = 0; ks < KS; ++ks) qf[b][ks] = load_row_frag(qrow, ks * 16 + h * 8, D, valid);
@@ -138,10 +99,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
 #pragma unroll
         for (int ks = 0; ks < KS; ++ks) asm volatile("" : "+a"(qf[b][ks]));    // Q lives in the accumulator file from here on (else: 64 v_accvgpr_write per tile in front of the S MFMAs)
     __syncthreads();
-    int bmaxpre = 0, bminlo = 0x7fffffff, bmaxhi = -1;
-#pragma unroll
-    for (int w = 0; w < 8; ++w) { bmaxpre = max(bmaxpre, lds_meta[w * 3]); bminlo = min(bminlo, lds_meta[w * 3 + 1]); bmaxhi = max(bmaxhi, lds_meta[w * 3 + 2]); }
-    TileRange tr = att_tile_range(bmaxpre, bminlo, bmaxhi, p.n_slots);
+    TileRange tr = att_block_range(lds_meta, 3, p.n_slots);
     tr.pre_tiles = __builtin_amdgcn_readfirstlane(tr.pre_tiles); tr.start2 = __builtin_amdgcn_readfirstlane(tr.start2);      // tile ids stay in scalar registers
     const int n_my = __builtin_amdgcn_readfirstlane(tr.n_rel);
 
@@ -160,19 +118,18 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     // rows past the cache's last slot (the one partial tile): the offset is clamped to the LAST 16-byte chunk of the last row - wrong chunk, real (finite) bf16 data,
     // and those keys are masked to P = 0 exactly (kv >= n_slots)
     const unsigned klim = ((unsigned)p.n_slots - 1u) * k_ldb + 240u, vlim = ((unsigned)p.n_slots - 1u) * v_ldb + 240u;
-#define F64_DMA16(voff_, sbase, m0v) asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2" ::"s"(m0v), "v"(voff_), "s"(sbase) : "memory", "m0")
     // one DMA instruction: d < 4 -> K row group wave*4 + d of tile index ik, else V row group wave*4 + d - 4 of tile index iv (indices into the block's tile list, clamped)
     auto dma_one = [&](int d, int ik, int iv) {
         if (d < 4) {
             const int i = ik < n_my ? ik : n_my - 1;
             const unsigned t64 = (unsigned)att_tile_at(tr, i) * 64u;
             unsigned off = koff[d] + t64 * k_ldb; off = off < klim ? off : klim;
-            F64_DMA16(off, kbase, lds_base + (unsigned)(ik % NB) * TILE + (unsigned)(wave * 4 + d) * 1024u);
+            tr1_dma16(off, kbase, lds_base + (unsigned)(ik % NB) * TILE + (unsigned)(wave * 4 + d) * 1024u);
         } else {
             const int i = iv < n_my ? iv : n_my - 1;
             const unsigned t64 = (unsigned)att_tile_at(tr, i) * 64u;
             unsigned off = voff[d - 4] + t64 * v_ldb; off = off < vlim ? off : vlim;
-            F64_DMA16(off, vbase, lds_base + (unsigned)(NB + iv % NB) * TILE + (unsigned)(wave * 4 + d - 4) * 1024u);
+            tr1_dma16(off, vbase, lds_base + (unsigned)(NB + iv % NB) * TILE + (unsigned)(wave * 4 + d - 4) * 1024u);
         }
     };
     if (n_my > 0) {       // request order K0 V0 K1 V1 K2 K3 (24 instructions per wave); body t adds K(t+4), V(t+2)
@@ -190,13 +147,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
         for (int d = 0; d < 4; ++d) dma_one(d, 3, 0);
     }
 
-    typedef const __attribute__((address_space(3))) bf16x8_t* lds_b128_t;
-#define LDS_B128(addr) (*(lds_b128_t)(uintptr_t)(addr))
-#define LDS_TR16(addr) __builtin_bit_cast(u32x2_t, __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4_t*)(uintptr_t)(addr)))
-#define P2_LD(ya, n) make_frag(LDS_TR16(((ya) ^ (((n) & 3) * 64)) + ((n) >> 2) * 4096), LDS_TR16(((ya) ^ (((n) & 3) * 64 + 32)) + ((n) >> 2) * 4096 + 2048))
     const int ti = lane & 15, tgrp = (lane >> 4) & 1;
-    const unsigned a_lane = (unsigned)(c32 * 256 + ((h ^ skey(c32 & 15)) << 4));
-    const unsigned t_lane = (unsigned)((4 * h + (ti >> 2)) * 256 + (ti & 1) * 8 + (((tgrp * 2 + ((ti & 3) >> 1)) ^ (((ti >> 2) << 2) | h)) << 4));
+    const unsigned a_lane = att_a_lane(c32, h), t_lane = ATT_T_LANE(h, ti, tgrp);
 
     // (F64_PIN: an empty asm that makes a value opaque where it stands - without it the IR passes, which do not see the scheduling fences, sink and SLP-pack the
     //  row sums into one late v_pk_add chain and keep all 64 exponentials alive for it)
@@ -221,16 +173,16 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
                   "v"(sC[b][1][r0]), "v"(sC[b][1][r0 + 1]), "v"(sC[b][1][r0 + 2]), "v"(sC[b][1][r0 + 3]));
         } else if (s == 8 || s == 10) {
             const int b = (s - 8) >> 1;
-            float mx = f64_max(mxa[b], mxb[b]), mx0, mx1;
-            f64_halves(mx, mx0, mx1);
-            mx = f64_max(mx0, mx1);
-            mcand[b] = f64_max(m[b], mx * p.scale_log2);               // max over RAW scores (scale > 0 commutes with max)
+            float mx = att_max2(mxa[b], mxb[b]), mx0, mx1;
+            att_halves(mx, mx0, mx1);
+            mx = att_max2(mx0, mx1);
+            mcand[b] = att_max2(m[b], mx * p.scale_log2);               // max over RAW scores (scale > 0 commutes with max)
             F64_PIN(mcand[b]);
         } else if (s == 9 || s == 11) {
             const int b = (s - 9) >> 1;
             // lazy running maximum, exactly as attn_fwd32_kernel: the old maximum stays the reference while no row of the 32-row group would move by more than 2^6
-#if FWD64_LAZY_MAX > 0
-            const float m_new = __all(mcand[b] - m[b] <= (float)FWD64_LAZY_MAX) ? m[b] : mcand[b];
+#if ATT_LAZY_MAX > 0
+            const float m_new = __all(mcand[b] - m[b] <= (float)ATT_LAZY_MAX) ? m[b] : mcand[b];
 #else
             const float m_new = mcand[b];
 #endif
@@ -260,7 +212,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
         } else if (s < 62) {
             const int b = s - 60;
             float rs = rsE[b] + rsO[b], rs0, rs1;
-            f64_halves(rs, rs0, rs1);
+            att_halves(rs, rs0, rs1);
             rs = rs0 + rs1;
             l[b] = l[b] * alpha[b] + rs;
             F64_PIN(l[b]);
@@ -271,13 +223,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
         const int kv0 = att_tile_at(tr, it) * 64;
 #pragma unroll
         for (int b = 0; b < 2; ++b) {
-            const bool full = (kv0 + 64 <= p.n_slots) && ((kv0 + 64 <= wminpre[b]) || (wmaxlo[b] <= kv0 && kv0 + 63 <= wminhi[b]));
+            const bool full = (kv0 + 64 <= p.n_slots) && ((kv0 + 64 <= wm[b].minpre) || (wm[b].maxlo <= kv0 && kv0 + 63 <= wm[b].minhi));
             if (!full) {
                 // vector instructions only (two compares + two selects per score): combining the intervals as lane masks (v_cmp -> s_or_b64 -> v_cndmask) put a
                 // scalar instruction that depends on vector results between every pair of selects - 4 600 cycles per masked tile, more than a whole unmasked body
                 const int base = kv0 + 4 * h;
-                const unsigned A = (unsigned)(base - lo_e[b]), Dm = (unsigned)hi_d[b];
-                const int B = pre_e[b] - base;
+                const unsigned A = (unsigned)(base - rm[b].lo_e), Dm = (unsigned)rm[b].hi_d;
+                const int B = rm[b].pre_e - base;
 #pragma unroll
                 for (int kb = 0; kb < 2; ++kb)
 #pragma unroll
@@ -297,10 +249,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
         const unsigned xa = lds_base + (unsigned)(ik % NB) * TILE + a_lane;
         bf16x8_t k0[AH + 1], k1[AH + 1];
 #pragma unroll
-        for (int ks = 0; ks < AH; ++ks) { k0[ks] = LDS_B128(xa ^ (ks * 32)); k1[ks] = LDS_B128((xa ^ (ks * 32)) + 8192); }
+        for (int ks = 0; ks < AH; ++ks) { k0[ks] = att_lds_b128(xa ^ (ks * 32)); k1[ks] = att_lds_b128((xa ^ (ks * 32)) + 8192); }
 #pragma unroll
         for (int ks = 0; ks < KS; ++ks) {
-            if (ks + AH < KS) { k0[(ks + AH) % (AH + 1)] = LDS_B128(xa ^ ((ks + AH) * 32)); k1[(ks + AH) % (AH + 1)] = LDS_B128((xa ^ ((ks + AH) * 32)) + 8192); }
+            if (ks + AH < KS) { k0[(ks + AH) % (AH + 1)] = att_lds_b128(xa ^ ((ks + AH) * 32)); k1[(ks + AH) % (AH + 1)] = att_lds_b128((xa ^ ((ks + AH) * 32)) + 8192); }
 #pragma unroll
             for (int w = 0; w < 4; ++w) {
                 if (ks == 0) f64_mfma_s0(sN[w >> 1][w & 1], (w & 1) ? k1[ks % (AH + 1)] : k0[ks % (AH + 1)], qf[w >> 1][ks]);
@@ -317,7 +269,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     auto pv_prefetch = [&](int iv) {
         const unsigned ya = lds_base + (unsigned)(NB + iv % NB) * TILE + t_lane;
 #pragma unroll
-        for (int n = 0; n < TH; ++n) vnext[n] = P2_LD(ya, n);
+        for (int n = 0; n < TH; ++n) vnext[n] = att_p2_ld<4>(ya, n);
     };
     auto pv_product = [&](int iv, u32x4_t (&pP)[2][4], bool with_steps, int ik_dma, int iv_dma, f32x16_t (&sC)[2][2], u32x4_t (&pC)[2][4]) {
         const unsigned ya = lds_base + (unsigned)(NB + iv % NB) * TILE + t_lane;
@@ -326,7 +278,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
         for (int n = 0; n < TH; ++n) a[n] = vnext[n];
 #pragma unroll
         for (int n = 0; n < 16; ++n) {                                // n = chunk (16 keys) * 4 + feature block
-            if (n + TH < 16) a[(n + TH) % (TH + 1)] = P2_LD(ya, n + TH);
+            if (n + TH < 16) a[(n + TH) % (TH + 1)] = att_p2_ld<4>(ya, n + TH);
 #pragma unroll
             for (int b = 0; b < 2; ++b) {
                 acc[b][n & 3] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[n % (TH + 1)], __builtin_bit_cast(bf16x8_t, pP[b][n >> 2]), acc[b][n & 3], 0, 0, 0);
@@ -340,21 +292,21 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     };
     // body t: [wait + barrier] mask(t) | PV(t-1) + S(t+1) MFMAs with softmax(t) in their gaps | rescale when a running maximum moved
     auto body = [&](int it, f32x16_t (&sC)[2][2], f32x16_t (&sN)[2][2], u32x4_t (&pP)[2][4], u32x4_t (&pC)[2][4]) {
-        F64_STAMPS;
-        F64_STAMP(0);
+        ATT_STAMPS;
+        ATT_STAMP(0);
         // this wave's share of K(it+1) and V(it) has landed: everything but the most recent body's requests (it < 2: K3 + body 0's / K3, K4, V2).  V(it) is only
         // multiplied in the NEXT body; waiting for it here lets this body's end read that product's first fragments ahead of the barrier in between
         if (it >= 2) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
         else asm volatile("s_waitcnt vmcnt(12)" ::: "memory");
         __builtin_amdgcn_s_barrier();                                 // ... and everybody's; everybody is done with K(it) and V(it-2)
         asm volatile("" ::: "memory");
-        F64_STAMP(1);
+        ATT_STAMP(1);
         mask_tile(it, sC);
-        F64_STAMP(2);
+        ATT_STAMP(2);
         pv_product(it > 0 ? it - 1 : 0, pP, true, it + 4, it + 2, sC, pC);
-        F64_STAMP(3);
+        ATT_STAMP(3);
         s_product(it + 1, sN, 32, sC, pC);
-        F64_STAMP(4);
+        ATT_STAMP(4);
         if (it > 0 && !__all((alpha[0] == 1.0f) & (alpha[1] == 1.0f))) {      // (it = 0: the accumulators are still zero)
             // cold path (lazy maximum: a running maximum moved by more than 2^6).  Written in assembly, one register at a time through ONE vector temporary:
             // as C++ (acc *= alpha) hipcc reads tiles out of the accumulator file wholesale, and the extra live VGPRs of this rarely taken block made it
@@ -376,7 +328,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
             asm volatile("s_nop 3" ::: "memory");
         }
         pv_prefetch(it);                                              // V(it) for body it+1 (its slot is not requested again before body it+2's barrier)
-        F64_STAMP(5);
+        ATT_STAMP(5);
         F64_FLUSH(it);
     };
 
@@ -406,10 +358,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");              // (the clamped requests of the last bodies: nothing may be in flight into LDS when the block ends)
     }
     F64_DUMP();
-#undef LDS_B128
-#undef LDS_TR16
-#undef P2_LD
-#undef F64_DMA16
 #undef F64_PIN
     // lane holds O^T[feature = db*32 + 8i + 4h + j][its query row of q-block b]
     int tid2 = threadIdx.x;

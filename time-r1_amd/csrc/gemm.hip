@@ -851,7 +851,7 @@ __global__ __launch_bounds__(WAVES * 64) void gemm_skinny_kernel(const bf16_t* _
             const int r = (i & 1) * 8 + r8;
             const unsigned off = (unsigned)((r < M ? r : M - 1) * (int)ldx + (i >> 1) * 64 + (((lane & 7) ^ keyA(r)) << 3)) * 2u;
             const unsigned dst = xs_base + (unsigned)i * 1024u;
-            asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2" ::"s"(dst), "v"(off), "s"(X) : "memory", "m0");
+            tr1_dma16(off, X, dst);
         }
     }
     const unsigned xs_lane = xs_base + (unsigned)(u * 128);
@@ -1083,7 +1083,7 @@ __global__ __launch_bounds__(WAVES * 64) void norm_gemm_skinny_kernel(const bf16
             const int r = (i & 1) * 8 + r8;
             const unsigned off = (unsigned)((r < M ? r : M - 1) * (int)ldx + (i >> 1) * 64 + (((lane & 7) ^ keyA(r)) << 3)) * 2u;
             const unsigned dst = xs_base + (unsigned)i * 1024u;
-            asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2" ::"s"(dst), "v"(off), "s"(X) : "memory", "m0");
+            tr1_dma16(off, X, dst);
         }
     }
     const unsigned xs_lane = xs_base + (unsigned)(u * 128);

@@ -242,13 +242,13 @@ __global__ __launch_bounds__(WAVES * 64) void gemm_skinny_w8a8_kernel(const bf16
             const int r = (i & 3) * 4 + (lane >> 4);
             const unsigned off = (unsigned)((r < M ? r : M - 1) * (int)ldx + (i >> 2) * 128 + (((lane & 15) ^ r) << 3)) * 2u;
             const unsigned dst = xs_base + (unsigned)i * 1024u;
-            asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2" ::"s"(dst), "v"(off), "s"(X) : "memory", "m0");
+            tr1_dma16(off, X, dst);
         }
         for (int i = w0; i < n_l; i += WAVES) {
             int64_t col = (int64_t)i * 512 + lane * 8;
             if (col + 8 > K) col = K - 8;
             const unsigned off = (unsigned)col * 2u, dst = ls_base + (unsigned)i * 1024u;
-            asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2" ::"s"(dst), "v"(off), "s"(lnw) : "memory", "m0");
+            tr1_dma16(off, lnw, dst);
         }
     }
     // XLDS: the weight loads of a trip are requested one trip ahead (wn), the first ones BEFORE the wait for the x copy - only they may still be in

@@ -86,6 +86,18 @@ TR1_DEV float block_max(float v, float* red) {
     return t;
 }
 
+// ---- LDS DMA (global -> LDS without a register round trip): each lane's 16 (tr1_dma16) / 4 (tr1_dma4) bytes at sbase + voff land at LDS byte address
+// lds_addr (wave-uniform, it travels in m0) + lane * 16 / 4.  The instructions are written in assembly: for the builtin, hipcc tracks the asynchronous LDS
+// write and puts an s_waitcnt vmcnt(0) in front of the next LDS read it cannot prove disjoint (all of them: one dynamic LDS array) - the "prefetch" then
+// completes before the first operand read of the tile, i.e. nothing is prefetched (and a weight stream in flight is drained).  Landing is ordered by the
+// caller's hand-counted vmcnt wait + barrier.
+TR1_DEV void tr1_dma16(unsigned voff, const void* sbase, unsigned lds_addr) {
+    asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2" ::"s"(lds_addr), "v"(voff), "s"(sbase) : "memory", "m0");
+}
+TR1_DEV void tr1_dma4(unsigned voff, const void* sbase, unsigned lds_addr) {
+    asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dword %1, %2" ::"s"(lds_addr), "v"(voff), "s"(sbase) : "memory", "m0");
+}
+
 // ---- host side error plumbing (C ABI returns int; message via tr1_last_error) ----
 extern "C" void tr1_set_error_(const char* msg);
 

@@ -1,4 +1,4 @@
-"""Build tools/_probe_lib.so: the same C-ABI library compiled with -DTR1_PROBE (in-kernel s_memtime stamps; see BWD_STAMP in csrc/attn_bwd.hip).
+"""Build tools/_probe_lib.so: the same C-ABI library compiled with -DTR1_PROBE (in-kernel s_memtime stamps; see ATT_STAMP in csrc/attn_common.h).
 Load it with TR1_HIP_LIB=tools/_probe_lib.so (e.g. `python tools/bench_attn.py --probe`).  Not part of the product build."""
 import os, subprocess, sys
 from concurrent.futures import ThreadPoolExecutor
