@@ -258,6 +258,14 @@ int tr1_grpo_loss(const void* logp, const void* ref_logp, const void* mask, cons
  * first call; every call leaves it zero), folded in a fixed order: no floating-point atomics, bit-identical from call to call.  Masked positions are never read. */
 #define TR1_GRPO_LOSS_RATIO_WS_WORDS 528
 int tr1_grpo_loss_ratio(const void* logp, const void* old_logp, const void* ref_logp /*may be null*/, const void* tok_weight /*may be null*/, const void* mask, const void* adv, void* dlogp, void* out8, void* row_len, void* row_kl, void* ws, int64_t G, int64_t C, float beta, int use_grpo, float eps_low, float eps_high, float grad_scale, void* stream);
+/* ref: timer1_trainer.py:713-737 (both loss branches), extended by the trl.GRPOConfig options loss_type ("grpo" / "bnpo" / "dr_grpo": norm_mode 0 = mean over
+ * each row then over rows, 1 = mean over all live tokens, 2 = sum / (G * C)), importance_sampling_level (seq_level 0 = per-token ratio exp(logp - old_logp),
+ * 1 = one ratio per row, exp of the row's mean log-ratio) and delta (upper cap on the ratio in the unclipped term; <= 0 = off) on top of epsilon_low /
+ * epsilon_high.  old_logp may be null (the old policy is the policy), ref_logp and tok_weight as in tr1_grpo_loss_ratio, and so are the outputs, with the
+ * coefficient in use for rho.  Every division by a token count uses max(count, 1): a row without a live token contributes 0 and nothing is non-finite.
+ * One block per row, ws of TR1_GRPO_POLICY_LOSS_WS_WORDS 4-byte words (zero before the first call; every call leaves it zero), no floating-point atomics. */
+#define TR1_GRPO_POLICY_LOSS_WS_WORDS 528
+int tr1_grpo_policy_loss(const void* logp, const void* old_logp /*may be null*/, const void* ref_logp /*may be null*/, const void* tok_weight /*may be null*/, const void* mask, const void* adv, void* dlogp, void* out8, void* row_len, void* row_kl, void* ws, int64_t G, int64_t C, float beta, int norm_mode, int seq_level, float eps_low, float eps_high, float delta, float grad_scale, void* stream);
 /* ref: model.generate(do_sample=True, temperature, top_k) at timer1_trainer.py:568-573.  tokens[row*tok_ld + *step_ptr] = draw.
  * group_rows > 0: rows [b*group_rows, (b+1)*group_rows) belong to prompt b and draw from the stream (seed + b*seed_stride, row % group_rows, step),
  * so several prompts sampled in one launch get exactly the tokens of one launch per prompt. */

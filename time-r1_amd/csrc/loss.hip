@@ -259,7 +259,171 @@ __global__ __launch_bounds__(256) void grpo_loss_ratio_kernel(const float* __res
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
-// Sampler: one 1024-thread block per rollout row.  x = logits / temperature; keep the top_k largest (ties with the k-th
+// The GRPO objective family (trl.GRPOConfig loss_type / importance_sampling_level / delta on top of epsilon_low / epsilon_high): the clipped loss of
+// timer1_trainer.py:713-737 with a choice of normaliser, a token- or sequence-level importance coefficient and an upper cap on it.  One 256-thread block
+// per completion row, the layout and the ticket hand-off of grpo_loss_ratio_kernel above (kept as it is: the default settings still run it).  Per live token
+//   d = logp - old_logp (0 when old_logp is null)     kl = exp(ref - logp) - (ref - logp) - 1 (0 when ref_logp is null)     w = tok_weight or 1
+//   c = exp(d)                                  (seq_level 0)        c = s_g = exp(sum_t d m / max(len_g, 1)), one value per row          (seq_level 1)
+//   a = min(min(c, delta) A, clamp(c, 1-el, 1+eh) A)   (delta <= 0: no cap)         l = -w a + beta kl         loss = sum n l
+//   n = 1 / (max(len_g, 1) G)  (norm_mode 0, row mean)   1 / max(tot, 1)  (1, token mean)   1 / (G C)  (2, fixed length);  len_g = sum_t m, tot = sum m
+// Every count is clamped to 1, so a row (or a grid) without a live token gives zeros, never NaN.  The advantage term moves with c except where
+// (A > 0, c > 1+eh), (A < 0, c < 1-el) or (delta on, A < 0, c > delta): g(c) = 0 there, 1 elsewhere (delta > 1+eh is the caller's contract).
+//   token level    : dlogp = gs n (-w A c g(c) + beta (1 - exp(ref - logp)))
+//   sequence level : d s_g / d logp_t = s_g / max(len_g, 1) on every live token, so dlogp = gs n (-A s_g g(s_g) (sum_t w m) / max(len_g, 1) + beta (1 - exp(ref - logp)))
+// Two passes over the row: (1) len_g and, at sequence level, sum d and sum w - both in fp64, one double per thread: s_g multiplies every token of the row, its
+// exponent is a mean of up to C differences, and the pass only waits for loads - (2) dlogp and the row partials.  tot is counted from the mask grid by every
+// block (integers: exact, the same in every block).  out8 as the ratio kernel's with c for rho; the clip fractions count tokens, so a clipped sequence counts
+// with all of them.  ws = TR1_GRPO_POLICY_LOSS_WS_WORDS words, zero before the first call, left zero.  No floating-point atomics: same inputs, same bits.
+// ---------------------------------------------------------------------------------------------------------------------
+constexpr int GPL_WS_WORDS = GLR_WS_WORDS;      // [ticket, pad to 16 words, G x 8 row partials]
+TR1_DEV double block_sum_f64(double v, double* red4) {      // 256 threads, fixed tree; every thread gets the sum
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) red4[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return (red4[0] + red4[1]) + (red4[2] + red4[3]);
+}
+__global__ __launch_bounds__(256) void grpo_policy_loss_kernel(const float* __restrict__ logp, const float* __restrict__ old_logp,
+                                                               const float* __restrict__ ref_logp, const float* __restrict__ tok_weight,
+                                                               const int* __restrict__ mask, const float* __restrict__ adv, float* __restrict__ dlogp,
+                                                               float* __restrict__ out, float* __restrict__ row_len, float* __restrict__ row_kl,
+                                                               float* ws, int G, int C, float beta, int norm_mode, int seq_level, float eps_low,
+                                                               float eps_high, float delta, float grad_scale) {
+    __shared__ float red[16];
+    __shared__ double red4[4];
+    __shared__ float part[GLR_ROW][4];
+    __shared__ int s_last;
+    const int g = blockIdx.x, tid = threadIdx.x;
+    const int64_t row0 = (int64_t)g * C;
+    const int* mrow = mask + row0;
+    // ---- 1. live-token counts; at sequence level the row's sum of log-ratios and of weights
+    float cnt_row = 0.f, cnt_all = 0.f;
+    double sd = 0.0, sw = 0.0;
+    for (int t = tid; t < C; t += 256) {
+        if (mrow[t] == 0) continue;
+        cnt_row += 1.f;
+        if (seq_level) {
+            if (old_logp) sd += (double)logp[row0 + t] - (double)old_logp[row0 + t];
+            sw += tok_weight ? (double)tok_weight[row0 + t] : 1.0;
+        }
+    }
+    cnt_row = block_sum(cnt_row, red);
+    if (seq_level) { sd = block_sum_f64(sd, red4); sw = block_sum_f64(sw, red4); }
+    if (norm_mode == 1) {
+        const int64_t n = (int64_t)G * C;
+        int c = 0;
+        if ((reinterpret_cast<uintptr_t>(mask) & 15) == 0) {
+            const int64_t n4 = n >> 2;
+            const int4* m4 = reinterpret_cast<const int4*>(mask);
+            for (int64_t i = tid; i < n4; i += 256) { const int4 v = m4[i]; c += (v.x != 0) + (v.y != 0) + (v.z != 0) + (v.w != 0); }
+            for (int64_t i = (n4 << 2) + tid; i < n; i += 256) c += (mask[i] != 0);
+        } else {
+            for (int64_t i = tid; i < n; i += 256) c += (mask[i] != 0);
+        }
+        cnt_all = block_sum((float)c, red);      // per-thread counts and their sum stay below 2^24: exact in fp32
+    }
+    const float len1 = fmaxf(cnt_row, 1.f);
+    const float norm = norm_mode == 0 ? 1.f / (len1 * (float)G) : norm_mode == 1 ? 1.f / fmaxf(cnt_all, 1.f) : 1.f / ((float)G * (float)C);
+    // ---- 2. the row
+    const float A = adv[g];
+    const float lo = 1.f - eps_low, hi = 1.f + eps_high;
+    const bool cap = delta > 0.f;
+    float s_g = 1.f, k3_g = 0.f, seq_term = 0.f;
+    if (seq_level) {
+        const double dbar = sd / (double)len1;
+        s_g = (float)exp(dbar);
+        k3_g = (float)(expm1(dbar) - dbar);
+        const bool stuck = ((A > 0.f) && (s_g > hi)) || ((A < 0.f) && (s_g < lo)) || (cap && (A < 0.f) && (s_g > delta));
+        seq_term = stuck ? 0.f : -A * s_g * (float)(sw / (double)len1);      // the mean weight is exactly 1 without tok_weight: the token-level bits at s_g = 1
+    }
+    float s_l = 0.f, s_kl = 0.f, n_low = 0.f, n_high = 0.f, n_any = 0.f, s_k3 = 0.f, mx = 0.f;
+    for (int t = tid; t < C; t += 256) {
+        const int64_t i = row0 + t;
+        float dl = 0.f;
+        if (mrow[t] != 0) {
+            const float lp = logp[i];
+            float c = s_g, k3 = k3_g;
+            if (!seq_level) {
+                const float d = old_logp ? lp - old_logp[i] : 0.f;
+                c = expf(d); k3 = expm1f(d) - d;
+            }
+            const float w = tok_weight ? tok_weight[i] : 1.f;
+            float kl = 0.f, dkl = 0.f;
+            if (ref_logp) { const float r = ref_logp[i] - lp; const float e = __expf(r); kl = e - r - 1.f; dkl = 1.f - e; }
+            const bool low = (A < 0.f) && (c < lo), high = (A > 0.f) && (c > hi);
+            const float term = fminf((cap ? fminf(c, delta) : c) * A, fminf(fmaxf(c, lo), hi) * A);
+            s_l += -w * term + beta * kl;
+            s_kl += kl;
+            n_low += low ? 1.f : 0.f; n_high += high ? 1.f : 0.f; n_any += (low || high) ? 1.f : 0.f;
+            s_k3 += k3;
+            mx = fmaxf(mx, c);
+            if (seq_level) {
+                dl = (seq_term + beta * dkl) * norm * grad_scale;
+            } else {
+                const bool stuck = low || high || (cap && (A < 0.f) && (c > delta));
+                dl = ((stuck ? 0.f : -w * A * c) + beta * dkl) * norm * grad_scale;
+            }
+        }
+        dlogp[i] = dl;
+    }
+    {
+        float v[GLR_ROW] = {cnt_row, s_l, s_kl, n_low, n_high, n_any, s_k3, 0.f};
+#pragma unroll
+        for (int k = 0; k < GLR_ROW - 1; ++k) v[k] = (k == 0) ? v[k] : wave_sum(v[k]);
+        v[GLR_ROW - 1] = wave_max(mx);
+        if ((tid & 63) == 0) {
+#pragma unroll
+            for (int k = 0; k < GLR_ROW; ++k) part[k][tid >> 6] = v[k];
+        }
+    }
+    __syncthreads();
+    unsigned* ticket = reinterpret_cast<unsigned*>(ws);
+    float* rows = ws + GLR_HEAD;
+    if (tid < GLR_ROW) {
+        const float a = part[tid][0], b = part[tid][1], c = part[tid][2], d = part[tid][3];
+        const float r = (tid == 0) ? a : (tid == GLR_ROW - 1) ? fmaxf(fmaxf(a, b), fmaxf(c, d)) : ((a + b) + (c + d));
+        rows[g * GLR_ROW + tid] = r;
+        if (tid == 0) row_len[g] = r;
+        if (tid == 2 && row_kl) row_kl[g] = r;
+    }
+    // publish / ticket / acquire: the hand-off of grpo_loss_ratio_kernel, step for step
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    if (tid == 0) {
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        const unsigned prev = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        s_last = (prev == (unsigned)(G - 1));
+        if (s_last) {
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        }
+    }
+    __syncthreads();
+    if (!s_last || tid >= 64) return;
+    // ---- 3. the last block: lane = row, fixed-order fold
+    const volatile float* vr = rows;
+    const bool on = tid < G;
+    float p[GLR_ROW];
+#pragma unroll
+    for (int k = 0; k < GLR_ROW; ++k) p[k] = on ? vr[tid * GLR_ROW + k] : 0.f;
+    const float tot = wave_sum(p[0]), tot1 = fmaxf(tot, 1.f);
+    const float plen1 = fmaxf(p[0], 1.f);
+    const float sum_l = wave_sum(p[1]), row_mean_l = wave_sum(p[1] / plen1 / (float)G);
+    const float loss = norm_mode == 0 ? row_mean_l : norm_mode == 1 ? sum_l / tot1 : sum_l / ((float)G * (float)C);
+    const float klm = wave_sum(p[2] / plen1 / (float)G);
+    const float f_low = wave_sum(p[3]) / tot1, f_high = wave_sum(p[4]) / tot1, f_any = wave_sum(p[5]) / tot1;
+    const float k3 = wave_sum(p[6]) / tot1;
+    const float rmax = wave_max(p[7]);
+    if (tid == 0) {
+        out[0] = loss; out[1] = klm; out[2] = tot; out[3] = f_low; out[4] = f_high; out[5] = f_any; out[6] = k3; out[7] = rmax;
+        *ticket = 0u;         // zero again for the next call
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Sampler: one 1024-thread block per rollout row. x = logits / temperature; keep the top_k largest (ties with the k-th
 // value kept, as HF's TopKLogitsWarper does); softmax over the kept set; inverse-CDF draw in vocabulary order with a
 // Philox4x32-10 uniform keyed by (seed, row, step).  top_k <= 0 disables the filter.
 // ---------------------------------------------------------------------------------------------------------------------
@@ -884,6 +1048,20 @@ extern "C" int tr1_grpo_loss_ratio(const void* logp, const void* old_logp, const
     hipLaunchKernelGGL(grpo_loss_ratio_kernel, dim3((unsigned)G), dim3(256), 0, (hipStream_t)stream, (const float*)logp, (const float*)old_logp,
                        (const float*)ref_logp, (const float*)tok_weight, (const int*)mask, (const float*)adv, (float*)dlogp, (float*)out8,
                        (float*)row_len, (float*)row_kl, (float*)ws, (int)G, (int)C, beta, use_grpo, eps_low, eps_high, grad_scale);
+    TR1_LAUNCH_CHECK();
+}
+static_assert(GPL_WS_WORDS == TR1_GRPO_POLICY_LOSS_WS_WORDS, "include/timer1_hip.h states the workspace size of tr1_grpo_policy_loss");
+extern "C" int tr1_grpo_policy_loss(const void* logp, const void* old_logp, const void* ref_logp, const void* tok_weight, const void* mask,
+                                    const void* adv, void* dlogp, void* out8, void* row_len, void* row_kl, void* ws, int64_t G, int64_t C, float beta,
+                                    int norm_mode, int seq_level, float eps_low, float eps_high, float delta, float grad_scale, void* stream) {
+    TR1_CHECK_ARG(G >= 1 && G <= GLR_MAX_G, "grpo_policy_loss: G must be in [1, 64]");
+    TR1_CHECK_ARG(C >= 1 && G * C < ((int64_t)1 << 24), "grpo_policy_loss: need 1 <= C and G * C < 2^24");
+    TR1_CHECK_ARG(logp && mask && adv && dlogp && out8 && row_len && ws, "grpo_policy_loss: null argument");
+    TR1_CHECK_ARG(norm_mode >= 0 && norm_mode <= 2 && (seq_level == 0 || seq_level == 1),
+                  "grpo_policy_loss: norm_mode is 0 (row mean), 1 (token mean) or 2 (fixed length), seq_level 0 or 1");
+    hipLaunchKernelGGL(grpo_policy_loss_kernel, dim3((unsigned)G), dim3(256), 0, (hipStream_t)stream, (const float*)logp, (const float*)old_logp,
+                       (const float*)ref_logp, (const float*)tok_weight, (const int*)mask, (const float*)adv, (float*)dlogp, (float*)out8,
+                       (float*)row_len, (float*)row_kl, (float*)ws, (int)G, (int)C, beta, norm_mode, seq_level, eps_low, eps_high, delta, grad_scale);
     TR1_LAUNCH_CHECK();
 }
 extern "C" int64_t tr1_sample_workspace_words(int64_t rows) { return rows * SAMP_WS_WORDS; }

@@ -25,8 +25,11 @@ class StepState:
 class GRPOCore:
     def __init__(self, engine: Engine, ref_arena=None, num_generations=8, max_completion_length=200, beta=0.04, use_grpo=False,
                  temperature=1.0, top_k=50, seed=1234, rope_index_mode="hf4", stop_at_eos=False, reuse_prefill=True, greedy=False,
-                 top_p=1.0, min_p=None, repetition_penalty=1.0):
+                 top_p=1.0, min_p=None, repetition_penalty=1.0, objective=None):
         self.eng = engine
+        # None: the two loss branches of the reference (grpo_loss, grpo_loss_ratio on a replay).  A dict(norm, level, eps_low, eps_high, delta): every update
+        # goes through grpo_policy_loss (trl's loss_type / importance_sampling_level / delta, rows without a live token) - policy_objective() below builds it
+        self.objective = objective
         self.ops = engine.ops
         self.cfg = engine.cfg
         self.ref_arena = ref_arena
@@ -228,6 +231,7 @@ class GRPOCore:
         are handed to the all-reduce as soon as their gradients are final, overlapping the exchange with the rest of the backward.
         old_logp (fp32 [G, C]): the log-probs of the policy that drew the completions, for a replayed update (forward_logps(replay=True)): the loss is then
         the ratio kernel's (rho = exp(logp - old_logp) clipped to [1 - eps[0], 1 + eps[1]], tok_weight inside the kernel) and out8 is returned in place of out3.
+        With self.objective set, first pass and replays alike run grpo_policy_loss with the objective's clip range (`eps` is the ratio kernel's) and return out8.
         keep_pixels: further replays of this state follow (the training tower's backward reads st.pixels again).
         Returns (out3 = [loss, mean kl, sum mask], row_len [G]) as device tensors."""
         eng, ops = self.eng, self.ops
@@ -235,7 +239,14 @@ class GRPOCore:
         hook = None
         if grad_sync is not None and grad_sync.active:
             hook = lambda i: grad_sync.ready(*tr.range_of("l%d." % i))
-        if old_logp is not None:
+        if self.objective is not None:
+            # the objective family: first pass (old_logp None: ratio 1, tok_weight inside the kernel) and replays alike; out8 is returned in place of out3
+            o = self.objective
+            tw = None if tok_weight is None else tok_weight.to(torch.float32).contiguous()
+            dlogp, out3, row_len, _ = ops.grpo_policy_loss(st.logp, old_logp, st.ref_logp, completion_mask, advantages, self.beta, o["norm"], o["level"],
+                                                           o["eps_low"], o["eps_high"], o["delta"], grad_scale, tok_weight=tw)
+            tok_weight = None
+        elif old_logp is not None:
             tw = None if tok_weight is None else tok_weight.to(torch.float32).contiguous()
             dlogp, out3, row_len, _ = ops.grpo_loss_ratio(st.logp, old_logp, st.ref_logp, completion_mask, advantages, self.beta, self.use_grpo,
                                                           float(eps[0]), float(eps[1]), grad_scale, tok_weight=tw)
@@ -283,11 +294,35 @@ def eos_mask(completion_ids, eos_token_id):
     return (np.arange(C)[None, :] <= eos_idx[:, None]).astype(np.int32)
 
 
-def group_advantages(rewards_per_func, num_generations):
+def truncation_mask(completion_ids, eos_token_id, mask):
+    """trl's mask_truncated_completions: a completion that holds no EOS among its C tokens ran into the length limit; its mask row is zeroed, so it leaves
+    the loss.  completion_ids numpy int [G, C], mask numpy int32 [G, C] (eos_mask) -> (mask with those rows zeroed, truncated bool [G])."""
+    truncated = ~(completion_ids == eos_token_id).any(1)
+    return (mask * (~truncated)[:, None]).astype(np.int32), truncated
+
+
+NO_CLIP_EPS = (1.0, 3.0e38)     # clip range [0, 3e38]: a ratio is positive and finite in fp32, so neither side of the clamp is ever taken
+
+
+def policy_objective(use_grpo=False, loss_type=None, importance_sampling_level="token", delta=None, mask_truncated_completions=False,
+                     epsilon_low=0.2, epsilon_high=0.2):
+    """GRPOCore's `objective` for the settings of GRPOConfig: None while every one of them is at its default (the reference's two branches run unchanged),
+    else the arguments of grpo_policy_loss.  loss_type None keeps the branch's own normaliser: the row mean for use_grpo, the token mean for the clip branch.
+    use_grpo has no clip; it gets here only through mask_truncated_completions and then runs with NO_CLIP_EPS."""
+    if loss_type is None and importance_sampling_level == "token" and delta is None and not mask_truncated_completions:
+        return None
+    from .ops import GRPO_LEVELS, GRPO_NORM_MODES, LOSS_TYPE_NORM
+    norm = LOSS_TYPE_NORM[loss_type] if loss_type is not None else GRPO_NORM_MODES["row" if use_grpo else "token"]
+    lo, hi = NO_CLIP_EPS if use_grpo else (float(epsilon_low), float(epsilon_high))
+    return dict(norm=norm, level=GRPO_LEVELS[importance_sampling_level], eps_low=lo, eps_high=hi, delta=float(delta) if delta else 0.0)
+
+
+def group_advantages(rewards_per_func, num_generations, scale=True):
     """rewards_per_func: torch fp32 [B*G, n_funcs] -> (rewards, advantages, std) exactly as reference timer1_trainer.py:700-712
-    (sum over funcs, per-group mean, UNBIASED std, eps 1e-4)."""
+    (sum over funcs, per-group mean, UNBIASED std, eps 1e-4).  scale=False (trl's scale_rewards=False, Dr. GRPO): advantages = rewards - group mean, not
+    divided by the group's std; the returned std is the same."""
     rewards = rewards_per_func.sum(dim=1)
     mean = rewards.view(-1, num_generations).mean(dim=1).repeat_interleave(num_generations, dim=0)
     std = rewards.view(-1, num_generations).std(dim=1).repeat_interleave(num_generations, dim=0)
-    adv = (rewards - mean) / (std + 1e-4)
+    adv = (rewards - mean) / (std + 1e-4) if scale else rewards - mean
     return rewards, adv, std

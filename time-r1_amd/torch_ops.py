@@ -18,7 +18,7 @@ from typing import Optional, Tuple
 import torch
 from torch import Tensor
 
-from .ops import HipOps
+from .ops import GRPO_LEVELS, LOSS_TYPE_NORM, HipOps
 
 BF16, F32, I32 = torch.bfloat16, torch.float32, torch.int32
 _OPS = {}
@@ -381,6 +381,39 @@ def grpo_loss_ratio(logp: Tensor, old_logp: Tensor, ref_logp: Optional[Tensor], 
     return out8[0], out8[1], out8[3:]
 
 
+@_op("grpo_policy_loss")
+def grpo_policy_loss_op(logp: Tensor, old_logp: Optional[Tensor], ref_logp: Optional[Tensor], tok_weight: Optional[Tensor], mask: Tensor, adv: Tensor,
+                        beta: float, norm_mode: int, seq_level: int, eps_low: float, eps_high: float, delta: float, grad_scale: float) -> Tuple[Tensor, Tensor, Tensor]:
+    dlogp, out8, row_len, _ = _ops(logp).grpo_policy_loss(logp, old_logp, ref_logp, mask, adv, beta, norm_mode, seq_level, eps_low, eps_high, delta, grad_scale,
+                                                          tok_weight=tok_weight)
+    return out8, dlogp, row_len
+
+
+@grpo_policy_loss_op.register_fake
+def _(logp, old_logp, ref_logp, tok_weight, mask, adv, beta, norm_mode, seq_level, eps_low, eps_high, delta, grad_scale):
+    return logp.new_empty(8), torch.empty_like(logp), logp.new_empty(logp.shape[0])
+
+
+grpo_policy_loss_op.register_autograd(lambda ctx, dout8, _d1, _d2: (ctx.saved_tensors[0] * dout8[0],) + (None,) * 12,
+                                      setup_context=lambda ctx, inputs, output: ctx.save_for_backward(output[1]))
+
+
+def grpo_policy_loss(logp: Tensor, old_logp: Optional[Tensor], ref_logp: Optional[Tensor], completion_mask: Tensor, advantages: Tensor, beta: float,
+                     loss_type: str = "grpo", importance_sampling_level: str = "token", epsilon_low: float = 0.2, epsilon_high: Optional[float] = None,
+                     delta: Optional[float] = None, tok_weight: Optional[Tensor] = None) -> Tuple[Tensor, Tensor, Tensor]:
+    """-> (loss, mean k3-KL, stats).  The clipped GRPO loss with trl.GRPOConfig's loss_type ("grpo": mean over each completion, then over completions; "bnpo":
+    mean over all live tokens; "dr_grpo": sum over G * C), importance_sampling_level ("token" | "sequence": one ratio per completion, the exp of its mean
+    log-ratio) and delta (upper cap on the ratio in the unclipped term).  old_logp None: the old policy is the policy.  Completions without a live token
+    contribute 0.  stats as grpo_loss_ratio's, with the coefficient in use for rho.  Differentiable in logp only."""
+    eh = epsilon_low if epsilon_high is None else epsilon_high
+    out8, _, _ = torch.ops.timer1.grpo_policy_loss(logp.contiguous(), None if old_logp is None else old_logp.detach().float().contiguous(), ref_logp,
+                                                   None if tok_weight is None else tok_weight.detach().float().contiguous(),
+                                                   completion_mask.to(I32).contiguous(), advantages.float().contiguous(), float(beta),
+                                                   LOSS_TYPE_NORM[loss_type], GRPO_LEVELS[importance_sampling_level], float(epsilon_low), float(eh),
+                                                   float(delta) if delta else 0.0, 1.0)
+    return out8[0], out8[1], out8[3:]
+
+
 # ============================================================================================================ sampler / optimizer / video
 @_op("sample_tokens", mutates_args=("tokens", "finished"))
 def sample_tokens(logits: Tensor, temperature: float, top_k: int, seed: int, step: Tensor, tokens: Tensor, finished: Tensor, eos_id: int, pad_id: int,
@@ -445,7 +478,7 @@ def _(frames_u8, out_h, out_w, k_pad):
 
 
 OP_NAMES = ["rmsnorm_fwd", "rmsnorm_bwd", "swiglu_fwd", "swiglu_bwd", "linear_fwd", "linear_bwd", "rope_fwd", "mrope_table", "attn_fwd", "attn_bwd",
-            "logp_entropy_fwd", "logp_bwd", "lmhead_logp_entropy", "grpo_loss", "grpo_loss_ratio", "sample_tokens", "sample_tokens_filtered", "penalize_logits", "mark_seen_ids",
+            "logp_entropy_fwd", "logp_bwd", "lmhead_logp_entropy", "grpo_loss", "grpo_loss_ratio", "grpo_policy_loss", "sample_tokens", "sample_tokens_filtered", "penalize_logits", "mark_seen_ids",
             "mark_seen_drawn", "adamw_step", "video_preprocess"]
 
 

@@ -23,7 +23,7 @@ import torch
 
 from .config import ModelConfig, PRESETS
 from .dist import DataParallel, shard_world_ok
-from .grpo import GRPOCore, eos_mask, group_advantages
+from .grpo import GRPOCore, eos_mask, group_advantages, policy_objective, truncation_mask
 from .model import Engine
 from .optim import AdamWFlat
 from .params import ModelParams
@@ -108,6 +108,21 @@ class GRPOConfig:
             self.epsilon_high = float(self.epsilon_high)
             if not 0.0 < self.epsilon_high < float("inf"):
                 raise ValueError("epsilon_high must be None or a positive number, got %r" % (self.epsilon_high,))
+        if self.loss_type is not None and self.loss_type not in ("grpo", "bnpo", "dr_grpo"):
+            raise ValueError('loss_type must be None, "grpo", "bnpo" or "dr_grpo", got %r (trl\'s "dapo" normalises over the whole accumulated batch across '
+                             'ranks, which one micro-step\'s kernel cannot see: out of scope)' % (self.loss_type,))
+        if self.loss_type is not None and self.use_grpo:
+            raise ValueError("loss_type=%r selects a clipped objective and use_grpo=True the unclipped one: set one of the two" % (self.loss_type,))
+        if self.importance_sampling_level not in ("token", "sequence"):
+            raise ValueError('importance_sampling_level must be "token" or "sequence", got %r' % (self.importance_sampling_level,))
+        if self.delta is not None:
+            self.delta = float(self.delta)
+            top = 1.0 + (self.epsilon_low if self.epsilon_high is None else self.epsilon_high)
+            if not top < self.delta < float("inf"):
+                raise ValueError("delta (%r) must exceed the upper clip bound 1 + epsilon_high = %r" % (self.delta, top))
+        if self.use_grpo and (self.importance_sampling_level != "token" or self.delta is not None):
+            raise ValueError("use_grpo=True has no clip on the probability ratio: importance_sampling_level and delta must stay at their defaults")
+        self.scale_rewards, self.mask_truncated_completions = bool(self.scale_rewards), bool(self.mask_truncated_completions)
 
     beta: float = 0.04
     use_grpo: bool = False
@@ -115,6 +130,12 @@ class GRPOConfig:
                                             # completions against the log-probs of the policy that drew them (PPO clip); 1 = one update per rollout, as the reference runs
     epsilon_low: float = 0.2                # clip range of the probability ratio: [1 - epsilon_low, 1 + epsilon_high] (the reference hard-codes 0.2 / 0.2, :388-393)
     epsilon_high: Optional[float] = None    # None = same as epsilon_low
+    loss_type: Optional[str] = None         # trl.GRPOConfig.loss_type: "grpo" = clip + mean over each completion, then over completions; "bnpo" = clip + mean over all
+                                            # live tokens; "dr_grpo" = clip + sum / (num_generations * max_completion_length).  None = the reference's two branches (use_grpo)
+    importance_sampling_level: str = "token"   # "sequence" (GSPO): one ratio per completion, the exp of its mean per-token log-ratio, clipped as a whole
+    delta: Optional[float] = None           # two-sided clipping: the ratio in the unclipped term is capped at delta (bounds the loss for negative advantages); > 1 + epsilon_high
+    scale_rewards: bool = True              # False: advantages = rewards - group mean, without the division by the group's std (Dr. GRPO)
+    mask_truncated_completions: bool = False   # completions without an EOS among their max_completion_length tokens leave the loss
     prompt_type: str = "v1"
     fix_vit: bool = True
     stop_at_eos: bool = False               # the reference's GenerationConfig carries no eos_token_id (a6): always C tokens
@@ -389,6 +410,12 @@ class TimeR1_Trainer:
         eh = getattr(args, "epsilon_high", None)
         self.epsilon_high = self.epsilon_low if eh is None else float(eh)
         self.num_iterations = int(getattr(args, "num_iterations", 1) or 1)
+        self.scale_rewards = bool(getattr(args, "scale_rewards", True))
+        self.mask_truncated = bool(getattr(args, "mask_truncated_completions", False))
+        # None while loss_type / importance_sampling_level / delta / mask_truncated_completions are at their defaults: then the loss kernels and metric keys are the
+        # reference branches'.  Otherwise every update, first pass and replay, runs grpo_policy_loss and logs the clip_ratio/* keys and policy_kl_old
+        self._objective = policy_objective(self.use_grpo, getattr(args, "loss_type", None), getattr(args, "importance_sampling_level", "token"),
+                                           getattr(args, "delta", None), self.mask_truncated, self.epsilon_low, self.epsilon_high)
         self._check_reuse_args()
         self._reuse = None                   # num_iterations > 1: what the window's micro-steps keep for the replayed updates (optimizer_window)
         self._replays_since_log = 0
@@ -401,7 +428,7 @@ class TimeR1_Trainer:
         self.core = GRPOCore(self.engine, self.ref_model, self.num_generations, self.max_completion_length, beta=self.beta,
                              use_grpo=self.use_grpo, temperature=args.temperature, top_k=args.top_k, seed=args.seed + 1000 * self.dp.rank,
                              rope_index_mode=args.rope_index_mode, stop_at_eos=args.stop_at_eos, top_p=getattr(args, "top_p", 1.0),
-                             min_p=getattr(args, "min_p", None), repetition_penalty=getattr(args, "repetition_penalty", 1.0))
+                             min_p=getattr(args, "min_p", None), repetition_penalty=getattr(args, "repetition_penalty", 1.0), objective=self._objective)
         self.core.roll.weight_dtype = getattr(args, "rollout_weight_dtype", "bf16")
         keep = getattr(args, "rollout_fp8_keep_bf16", None)
         if keep is None:
@@ -569,6 +596,9 @@ class TimeR1_Trainer:
             comp_host = tokens.cpu().numpy()
         self.core.forward_logps(st)
         mask_np = eos_mask(comp_host, self.processing_class.eos_token_id)
+        lengths, truncated = mask_np.sum(1).astype(np.float32), None      # completion_length and the token counts keep the rollout's lengths
+        if self.mask_truncated:
+            mask_np, truncated = truncation_mask(comp_host, self.processing_class.eos_token_id, mask_np)
         completions = self.processing_class.batch_decode(torch.as_tensor(comp_host), skip_special_tokens=True)
         prompts_rep = [p for p in prompts for _ in range(G)]
         reward_kwargs = {k: [] for k in inputs[0].keys() if k not in ("prompt", "completion") and not k.startswith("_")}
@@ -578,7 +608,7 @@ class TimeR1_Trainer:
         rewards_per_func = torch.zeros(len(prompts_rep), len(self.reward_funcs))
         for i, fn in enumerate(self.reward_funcs):
             rewards_per_func[:, i] = torch.tensor(fn(prompts=prompts_rep, completions=completions, **reward_kwargs), dtype=torch.float32)
-        rewards, advantages, std = group_advantages(rewards_per_func, G)
+        rewards, advantages, std = group_advantages(rewards_per_func, G) if self.scale_rewards else group_advantages(rewards_per_func, G, scale=False)
         metric_vals = None
         if self._is_ft and self.metric_funcs:
             metric_vals = torch.stack([torch.tensor(fn(prompts=prompts_rep, completions=completions, **reward_kwargs), dtype=torch.float32)
@@ -595,7 +625,7 @@ class TimeR1_Trainer:
         maskf = mask_dev.to(torch.float32)
         ent_mean = ((st.entropy.float() * maskf).sum(1) / maskf.sum(1).clamp(min=1)).mean()
         clip3 = None
-        if self._is_ft and not self.use_grpo:   # reference timer1_trainer_ft.py:820-842 (undefined there for use_grpo: coef_1 does not exist)
+        if self._is_ft and not self.use_grpo and self._objective is None:   # reference timer1_trainer_ft.py:820-842 (undefined there for use_grpo: coef_1 does not exist)
             lp = st.logp.float()
             clip3 = torch.stack(clip_ratio_metrics(lp, lp, adv_dev, maskf, self.epsilon_low, self.epsilon_high))   # old policy == policy (one update per rollout)
         drift_t, tokw = None, None
@@ -618,11 +648,15 @@ class TimeR1_Trainer:
         self._clock.mark("backward")
         out3f = out3.float()
         z = torch.zeros(3, dtype=torch.float32, device=out3f.device)
+        if self._objective is not None:
+            clip3 = out3f[3:6]               # out8 of grpo_policy_loss: the clip fractions and the k3 distance to the old policy come from the kernel
         dev = torch.cat([out3f[:2], ent_mean.reshape(1).float(), clip3.float() if clip3 is not None else z,
                          drift_t.reshape(1).float() if drift_t is not None else z[:1]])      # fixed layout: loss, kl, entropy, clip x 3, drift
+        if self._objective is not None:
+            dev = torch.cat([dev, out3f[6:7]])      # ... and an eighth value on that path (first pass and replay alike): policy_kl_old
         # ---- metrics (reference :739-777; ft adds metrics/<fn> and clip ratios :789-842): per-sample host values + the device vector,
         # turned into the reference's gathered means by _flush_metrics
-        self._pending.append(dict(length=mask_np.sum(1).astype(np.float32), rpf=rewards_per_func.numpy().copy(), reward=rewards.numpy().copy(),
+        self._pending.append(dict(length=lengths, truncated=truncated, family=self._objective is not None, rpf=rewards_per_func.numpy().copy(), reward=rewards.numpy().copy(),
                                   std=std.numpy().copy(), mvals=None if metric_vals is None else metric_vals.numpy(), dev=dev,
                                   has_clip=clip3 is not None, has_drift=drift_t is not None))
         self.last_completions = completions
@@ -654,10 +688,11 @@ class TimeR1_Trainer:
         first = next((r for r in pend if not r.get("replay")), None)
         nm = first["mvals"].shape[1] if first is not None and first["mvals"] is not None else 0
         dev = torch.stack([r["dev"] for r in pend])                     # [n, nd] on the device
-        blank = np.zeros(3 * G + G * nf + G * nm, dtype=np.float32)      # replayed updates carry device values only
+        nt = G if self.mask_truncated else 0                             # mask_truncated_completions: one more host value per row, 1 = no EOS
+        blank = np.zeros(3 * G + G * nf + G * nm + nt, dtype=np.float32)      # replayed updates carry device values only
         host = np.stack([blank if r.get("replay") else
                          np.concatenate([r["length"], r["rpf"].reshape(-1), r["reward"], r["std"]] +
-                                        ([r["mvals"].reshape(-1)] if nm else [])).astype(np.float32) for r in pend])
+                                        ([r["mvals"].reshape(-1)] if nm else []) + ([r["truncated"]] if nt else [])).astype(np.float32) for r in pend])
         if self.dp.enabled:
             both = torch.cat([self.ops.tensor(host, torch.float32), dev], 1)
             allv = self.dp.gather(both[None]).cpu()                      # [world, n, L]
@@ -665,7 +700,8 @@ class TimeR1_Trainer:
             allv = torch.cat([torch.as_tensor(host), dev.cpu()], 1)[None]
         M = self._metrics_store
         o_rpf, o_rew, o_std, o_mv = G, G + G * nf, 2 * G + G * nf, 3 * G + G * nf
-        o_dev = o_mv + G * nm
+        o_tr = o_mv + G * nm
+        o_dev = o_tr + nt
         for i, r in enumerate(pend):
             v = allv[:, i]                                               # [world, L]: rank-major, like accelerator.gather's concatenation
             if r.get("replay"):
@@ -680,7 +716,7 @@ class TimeR1_Trainer:
                 M["clip_ratio/high_mean"].append(g_high.nanmean().item())
                 M["clip_ratio/high_max"].append(g_high[~g_high.isnan()].max().item() if (~g_high.isnan()).any() else float("nan"))
                 M["clip_ratio/region_mean"].append(g_reg.nanmean().item())
-                M["policy_kl_old"].append(v[:, o_dev + 6].mean().item())
+                M["policy_kl_old"].append(v[:, o_dev + (7 if r.get("family") else 6)].mean().item())
                 continue
             M["completion_length"].append(v[:, :G].reshape(-1).mean().item())
             rpf = v[:, o_rpf:o_rew].reshape(-1, nf).mean(0)
@@ -692,7 +728,7 @@ class TimeR1_Trainer:
                 M["kl"].append(v[:, o_dev + 1].mean().item())
             M["generation_entropy"].append(v[:, o_dev + 2].mean().item())
             if nm:
-                mv = v[:, o_mv:o_dev].reshape(-1, nm)
+                mv = v[:, o_mv:o_tr].reshape(-1, nm)
                 for j, fn in enumerate(self.metric_funcs):
                     M["metrics/%s" % fn.__name__].append(mv[:, j].mean().item())
             if r["has_clip"]:
@@ -702,6 +738,10 @@ class TimeR1_Trainer:
                 M["clip_ratio/high_mean"].append(g_high.nanmean().item())
                 M["clip_ratio/high_max"].append(g_high[~g_high.isnan()].max().item() if (~g_high.isnan()).any() else float("nan"))
                 M["clip_ratio/region_mean"].append(g_reg.nanmean().item())
+            if r.get("family"):
+                M["policy_kl_old"].append(v[:, o_dev + 7].mean().item())
+            if nt:
+                M["completions/clipped_ratio"].append(v[:, o_tr:o_dev].reshape(-1).mean().item())
             if r.get("has_drift"):
                 M["rollout_logp_drift"].append(v[:, o_dev + 6].mean().item())
             self._tok_since_log += float(v[:, :G].sum())
@@ -785,7 +825,10 @@ class TimeR1_Trainer:
                 self.engine.norm_sink = None
             clock.mark("backward")
             o = out8.float()
-            self._pending.append(dict(replay=True, dev=torch.cat([o[:2], ent_mean.reshape(1).float(), o[3:7]])))      # loss, kl, entropy, clip x 3, k3 to the old policy
+            if self._objective is not None:      # the first pass's eight values: the drift slot stays empty, k3 sits behind it
+                self._pending.append(dict(replay=True, family=True, dev=torch.cat([o[:2], ent_mean.reshape(1).float(), o[3:6], torch.zeros_like(o[:1]), o[6:7]])))
+            else:
+                self._pending.append(dict(replay=True, dev=torch.cat([o[:2], ent_mean.reshape(1).float(), o[3:7]])))      # loss, kl, entropy, clip x 3, k3 to the old policy
             self._replays_since_log += 1
             losses.append(o[0])
         return losses

@@ -1,6 +1,6 @@
 """What several policy updates per rollout (GRPOConfig.num_iterations = mu) buy, and what the ratio-loss kernel costs.
 
-    python tools/bench_policy_reuse.py --kernels                         # tr1_grpo_loss_ratio against tr1_grpo_loss, us per launch
+    python tools/bench_policy_reuse.py --kernels                         # tr1_grpo_loss_ratio and tr1_grpo_policy_loss against tr1_grpo_loss, us per launch
     python tools/bench_policy_reuse.py --model qwen2-vl-7b               # bench.py's config 3 workload (32 frames, G 8, C 200, beta 0.04, GA 2), mu = 1, 2, 4
     python tools/bench_policy_reuse.py --model qwen2-vl-2b --frames 16   # config 2
 
@@ -40,6 +40,11 @@ def kernel_times(ops, launches, warmup, shapes):
             "grpo_loss_ratio": lambda: ops.grpo_loss_ratio(logp, old, ref, mask, adv, 0.04, False, 0.2, 0.2, 0.5),
             "grpo_loss_ratio + tok_weight": lambda: ops.grpo_loss_ratio(logp, old, ref, mask, adv, 0.04, False, 0.2, 0.2, 0.5, tok_weight=tokw),
             "grpo_loss_ratio, use_grpo": lambda: ops.grpo_loss_ratio(logp, old, ref, mask, adv, 0.04, True, 0.2, 0.2, 0.5),
+            "grpo_policy_loss, token level (bnpo)": lambda: ops.grpo_policy_loss(logp, old, ref, mask, adv, 0.04, "token", "token", 0.2, 0.2, None, 0.5),
+            "grpo_policy_loss, token level, row mean + delta": lambda: ops.grpo_policy_loss(logp, old, ref, mask, adv, 0.04, "row", "token", 0.2, 0.2, 1.5, 0.5),
+            "grpo_policy_loss, sequence level": lambda: ops.grpo_policy_loss(logp, old, ref, mask, adv, 0.04, "token", "sequence", 0.2, 0.2, None, 0.5),
+            "grpo_policy_loss, sequence level + delta + tok_weight": lambda: ops.grpo_policy_loss(logp, old, ref, mask, adv, 0.04, "fixed", "sequence", 0.2, 0.2, 1.5, 0.5,
+                                                                                                  tok_weight=tokw),
         }
         row = {}
         for name, fn in fns.items():
