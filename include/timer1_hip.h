@@ -249,6 +249,19 @@ int tr1_logp_entropy_fwd(const void* logits, int64_t ld, const void* targets, vo
 int tr1_lmhead_lse_fwd(const void* hn, const void* W, const void* targets, void* part_ws, int64_t ws_floats, void* logp, void* ent, void* lse, int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldb, void* stream);
 int64_t tr1_lmhead_lse_workspace_floats(int64_t M, int64_t N);
 int tr1_logp_bwd(const void* logits, int64_t ld, const void* targets, const void* lse, const void* dlogp, void* dlogits, int64_t ld_out, int64_t R, int64_t V, void* stream);
+/* tr1_logp_bwd with a gradient at the entropy too: dlogits[r, v] = dlogp[r] (1[v == t_r] - p) - dent[r] p ((x - lse[r]) + ent[r]), p = exp(x - lse[r])
+ * (d H / d x_v = -p_v (log p_v + H)).  ref: src/time_r1/rl/timer1_trainer.py:473-481 computes this entropy under no_grad, a logged number; here it can carry a
+ * loss term - the entropy bonus of verl's actor.entropy_coeff (GRPOConfig.entropy_coef) - and it feeds the token selection of trl.GRPOConfig.top_entropy_quantile
+ * below.  lse, ent: the forward's outputs as they are (fp32 [R]); dlogp, dent fp32 [R]; dlogits bf16 with its own ld_out, may alias logits; ld, ld_out, V multiples
+ * of 8.  dent NULL: tr1_logp_bwd itself, bit for bit; rows with dent[r] == 0 give its values, rows with dlogp[r] == dent[r] == 0 are exactly 0. */
+int tr1_logp_entropy_bwd(const void* logits, int64_t ld, const void* targets, const void* lse, const void* ent, const void* dlogp, const void* dent /*may be null*/, void* dlogits, int64_t ld_out, int64_t R, int64_t V, void* stream);
+/* trl.GRPOConfig.top_entropy_quantile (trl GRPOTrainer.get_high_entropy_mask) for one micro-step, without a host synchronisation: over the live positions
+ * (mask != 0, int32) of ent (fp32 [N], the entropy of timer1_trainer.py:473-481 on the [G, C] grid) thr = the quantile of order 1 - rho, linearly interpolated between
+ * the order statistics as torch.quantile does; weight[i] (fp32) = 1 where the position is live and ent[i] >= thr (ties kept), else 0 - the tok_weight of the loss
+ * kernels below; stats3 = {thr, number kept, n live}.  n = 0: zeros.  0 < rho <= 1; N <= TR1_ENTROPY_QUANTILE_MAX_N (one block).  Masked positions are never read.
+ * No workspace, no floating-point atomics: bit-identical from call to call. */
+#define TR1_ENTROPY_QUANTILE_MAX_N 1048576
+int tr1_entropy_quantile_weight(const void* ent, const void* mask, void* weight, void* stats3, int64_t N, float rho, void* stream);
 /* ref: timer1_trainer.py:635-639 (k3 KL), :713-737 (both loss branches).  out3 = {loss, mean masked kl, sum mask}. */
 int tr1_grpo_loss(const void* logp, const void* ref_logp, const void* mask, const void* adv, void* dlogp, void* out3, void* row_len, void* row_kl, int64_t G, int64_t C, float beta, int use_grpo, float grad_scale, void* stream);
 /* ref: timer1_trainer.py:730-737 (the PPO-clip branch written out: coef_1 = exp(logp - old_logp), coef_2 = clamp(coef_1, 1 - eps_low, 1 + eps_high)) for

@@ -78,6 +78,143 @@ __global__ void logp_bwd_kernel(const bf16_t* __restrict__ logits, int64_t ld, c
     }
 }
 
+// The same pass with a gradient arriving at the entropy as well (an entropy term in the loss: verl's entropy_coeff).  H = -sum_v p log p, so
+// d H / d x_v = -p_v (log p_v + H) and
+//   dlogits[r, v] = dlogp[r] * (1[v == target] - p) - dent[r] * p * ((x - lse[r]) + ent[r]),     p = exp(x - lse[r])
+// lse and ent are the forward's outputs as they are (in the chunked backward they come from the fused lm_head and the logits from a second GEMM).  Grid, loads,
+// stores and aliasing as logp_bwd_kernel; a row with dent[r] == 0 runs that kernel's expression, so it gives that kernel's values.
+__global__ void logp_entropy_bwd_kernel(const bf16_t* __restrict__ logits, int64_t ld, const int* __restrict__ targets, const float* __restrict__ lse,
+                                        const float* __restrict__ ent, const float* __restrict__ dlogp, const float* __restrict__ dent,
+                                        bf16_t* __restrict__ dlogits, int64_t ld_out, int V) {
+    const int r = blockIdx.y;
+    const float g = dlogp[r], de = dent[r], ls = lse[r], H = ent[r];
+    const int tg = targets[r];
+    const bf16_t* row = logits + (int64_t)r * ld;
+    bf16_t* orow = dlogits + (int64_t)r * ld_out;
+    const int nch = V >> 3;
+    const bool plain = de == 0.f;       // uniform over the block
+    for (int c = blockIdx.x * blockDim.x + threadIdx.x; c < nch; c += gridDim.x * blockDim.x) {
+        const u32x4_t p = *reinterpret_cast<const u32x4_t*>(row + c * 8);
+        u32x4_t o;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int v0 = c * 8 + 2 * j;
+            const float la = bflo(p[j]) - ls, lb = bfhi(p[j]) - ls;
+            const float pa = __expf(la), pb = __expf(lb);
+            float a = g * ((v0 == tg ? 1.f : 0.f) - pa);
+            float b = g * ((v0 + 1 == tg ? 1.f : 0.f) - pb);
+            if (!plain) { a -= de * pa * (la + H); b -= de * pb * (lb + H); }
+            o[j] = pack2bf(a, b);
+        }
+        *reinterpret_cast<u32x4_t*>(orow + c * 8) = o;
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Top-entropy token selection (trl.GRPOConfig.top_entropy_quantile, get_high_entropy_mask): over the live positions (mask != 0) of ent[N], thr = the quantile of
+// order q = 1 - rho with linear interpolation between the order statistics around pos = q (n - 1), as torch.quantile defines it; weight[i] = 1 where the position is
+// live and ent[i] >= thr (ties kept), else 0; stats3 = {thr, number kept, n}.  n == 0: all zeros.  One 1024-thread block (N = G * C, a few tens of thousands at most):
+//   1. n = number of live positions
+//   2. radix select of the floor(pos)-th smallest value on an order-preserving 32-bit key (the sampler's bfkey for fp32; -0 is keyed as +0, so the order is the
+//      floats' own), most significant byte first, one 256-bin LDS histogram per pass; the ceil(pos)-th is the same value when its ties reach that far, else the
+//      smallest key above it (one more pass)
+//   3. thr in fp64 with torch's lerp, the comparison in fp64, the count of kept positions
+// Masked positions are never read.  Integer LDS atomics only (a histogram's counts do not depend on the order of arrival): same inputs, same bits.  No workspace.
+// rho arrives as a float, so pos is known to (n - 1) 2^-23 only: a pos that close to an integer IS that integer (thr = an order statistic, and its ties are kept).
+// ---------------------------------------------------------------------------------------------------------------------
+TR1_DEV unsigned f32key(float x) {
+    if (x == 0.f) x = 0.f;
+    const unsigned u = __float_as_uint(x);
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+TR1_DEV float f32key_value(unsigned k) { return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k); }
+// by the block's first 256 threads (one bin each, ascending): the bin b with (count in bins < b) <= k < (count in bins <= b), and that first count.  k < the histogram's total.
+TR1_DEV void eq_find_bin(const unsigned* hist, unsigned k, unsigned* scr, unsigned* bin_out, unsigned* below_out) {
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    unsigned val = 0u, incl = 0u;
+    if (tid < 256) {
+        val = hist[tid];
+        incl = val;
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) { const unsigned t = __shfl_up(incl, d, 64); if (lane >= d) incl += t; }
+        if (lane == 63) scr[w] = incl;
+    }
+    __syncthreads();
+    if (tid < 256) {
+        unsigned off = 0u;
+        for (int j = 0; j < w; ++j) off += scr[j];
+        incl += off;
+        const unsigned excl = incl - val;
+        if (excl <= k && k < incl) { *bin_out = (unsigned)tid; *below_out = excl; }      // exactly one thread
+    }
+    __syncthreads();
+}
+__global__ __launch_bounds__(1024) void entropy_quantile_weight_kernel(const float* __restrict__ ent, const int* __restrict__ mask, float* __restrict__ weight,
+                                                                       float* __restrict__ stats3, int N, float rho) {
+    __shared__ unsigned hist[256], scr[4];
+    __shared__ unsigned s_n, s_bin, s_below, s_min, s_kept;
+    const int tid = threadIdx.x;
+    if (tid == 0) { s_n = 0u; s_min = 0xffffffffu; s_kept = 0u; }
+    __syncthreads();
+    // ---- 1. live positions
+    unsigned c = 0u;
+    for (int i = tid; i < N; i += 1024) c += (mask[i] != 0) ? 1u : 0u;
+    if (c) atomicAdd(&s_n, c);
+    __syncthreads();
+    const unsigned n = s_n;
+    if (n == 0u) {
+        for (int i = tid; i < N; i += 1024) weight[i] = 0.f;
+        if (tid == 0) { stats3[0] = 0.f; stats3[1] = 0.f; stats3[2] = 0.f; }
+        return;
+    }
+    // ---- 2. the two order statistics around pos (ascending ranks, from 0)
+    double pos = (1.0 - (double)rho) * (double)(n - 1u);
+    const double near = rint(pos);
+    if (fabs(pos - near) <= (double)(n - 1u) * 0x1p-23) pos = near;
+    const unsigned k_lo = (unsigned)floor(pos), k_hi = (unsigned)ceil(pos);
+    const double frac = pos - (double)k_lo;
+    unsigned prefix = 0u, pmask = 0u, k = k_lo, cnt_eq = 0u;
+    for (int shift = 24; shift >= 0; shift -= 8) {
+        if (tid < 256) hist[tid] = 0u;
+        __syncthreads();
+        for (int i = tid; i < N; i += 1024) {
+            if (mask[i] == 0) continue;
+            const unsigned key = f32key(ent[i]);
+            if ((key & pmask) == prefix) atomicAdd(&hist[(key >> shift) & 255u], 1u);
+        }
+        __syncthreads();
+        eq_find_bin(hist, k, scr, &s_bin, &s_below);
+        k -= s_below; prefix |= s_bin << shift; pmask |= 0xffu << shift;
+        cnt_eq = hist[s_bin];
+        __syncthreads();      // every thread has read the bin before the next pass clears the histogram
+    }
+    const unsigned key_lo = prefix;
+    unsigned key_hi = key_lo;
+    if (k_hi != k_lo && k + 1u >= cnt_eq) {      // k = rank of the floor statistic among its ties: the next rank leaves them
+        unsigned mn = 0xffffffffu;
+        for (int i = tid; i < N; i += 1024) {
+            if (mask[i] == 0) continue;
+            const unsigned key = f32key(ent[i]);
+            if (key > key_lo) mn = min(mn, key);
+        }
+        if (mn != 0xffffffffu) atomicMin(&s_min, mn);
+        __syncthreads();
+        key_hi = s_min;
+    }
+    // ---- 3. threshold (torch's lerp), weights, count
+    const double v_lo = (double)f32key_value(key_lo), v_hi = (double)f32key_value(key_hi);
+    const double thr = frac < 0.5 ? v_lo + frac * (v_hi - v_lo) : v_hi - (v_hi - v_lo) * (1.0 - frac);
+    unsigned kept = 0u;
+    for (int i = tid; i < N; i += 1024) {
+        float w = 0.f;
+        if (mask[i] != 0 && (double)ent[i] >= thr) { w = 1.f; ++kept; }
+        weight[i] = w;
+    }
+    if (kept) atomicAdd(&s_kept, kept);
+    __syncthreads();
+    if (tid == 0) { stats3[0] = (float)thr; stats3[1] = (float)s_kept; stats3[2] = (float)n; }
+}
+
 // ---------------------------------------------------------------------------------------------------------------------
 // GRPO loss + d loss / d logp on the [G, C] grid (one block; G*C is a few thousand elements).
 //   mode 1 (use_grpo): l = -(rho*A - beta*kl), loss = mean_g( sum_t l*m / sum_t m )
@@ -1028,6 +1165,25 @@ extern "C" int tr1_logp_bwd(const void* logits, int64_t ld, const void* targets,
     dim3 grid((unsigned)tr1_grid_1d(V / 8, 256, 64), (unsigned)R);
     hipLaunchKernelGGL(logp_bwd_kernel, grid, dim3(256), 0, (hipStream_t)stream, (const bf16_t*)logits, ld, (const int*)targets,
                        (const float*)lse, (const float*)dlogp, (bf16_t*)dlogits, ld_out, (int)V);
+    TR1_LAUNCH_CHECK();
+}
+extern "C" int tr1_logp_entropy_bwd(const void* logits, int64_t ld, const void* targets, const void* lse, const void* ent, const void* dlogp,
+                                    const void* dent, void* dlogits, int64_t ld_out, int64_t R, int64_t V, void* stream) {
+    if (!dent) return tr1_logp_bwd(logits, ld, targets, lse, dlogp, dlogits, ld_out, R, V, stream);      // no entropy gradient: the kernel that always ran
+    TR1_CHECK_ARG(ld % 8 == 0 && ld_out % 8 == 0 && V % 8 == 0, "logp_entropy_bwd: ld and V must be multiples of 8");
+    TR1_CHECK_ARG(ent, "logp_entropy_bwd: dent needs the forward's entropy");
+    if (R == 0) return 0;
+    dim3 grid((unsigned)tr1_grid_1d(V / 8, 256, 64), (unsigned)R);
+    hipLaunchKernelGGL(logp_entropy_bwd_kernel, grid, dim3(256), 0, (hipStream_t)stream, (const bf16_t*)logits, ld, (const int*)targets,
+                       (const float*)lse, (const float*)ent, (const float*)dlogp, (const float*)dent, (bf16_t*)dlogits, ld_out, (int)V);
+    TR1_LAUNCH_CHECK();
+}
+extern "C" int tr1_entropy_quantile_weight(const void* ent, const void* mask, void* weight, void* stats3, int64_t N, float rho, void* stream) {
+    TR1_CHECK_ARG(N >= 1 && N <= TR1_ENTROPY_QUANTILE_MAX_N, "entropy_quantile_weight: need 1 <= N <= 2^20 (one block walks the grid)");
+    TR1_CHECK_ARG(rho > 0.f && rho <= 1.f, "entropy_quantile_weight: rho must be in (0, 1]");
+    TR1_CHECK_ARG(ent && mask && weight && stats3, "entropy_quantile_weight: null argument");
+    hipLaunchKernelGGL(entropy_quantile_weight_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, (const float*)ent, (const int*)mask, (float*)weight,
+                       (float*)stats3, (int)N, rho);
     TR1_LAUNCH_CHECK();
 }
 extern "C" int tr1_grpo_loss(const void* logp, const void* ref_logp, const void* mask, const void* adv, void* dlogp, void* out3,

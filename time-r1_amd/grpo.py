@@ -25,8 +25,20 @@ class StepState:
 class GRPOCore:
     def __init__(self, engine: Engine, ref_arena=None, num_generations=8, max_completion_length=200, beta=0.04, use_grpo=False,
                  temperature=1.0, top_k=50, seed=1234, rope_index_mode="hf4", stop_at_eos=False, reuse_prefill=True, greedy=False,
-                 top_p=1.0, min_p=None, repetition_penalty=1.0, objective=None):
+                 top_p=1.0, min_p=None, repetition_penalty=1.0, objective=None, entropy_coef=0.0, top_entropy_quantile=1.0):
         self.eng = engine
+        # entropy_coef (verl's actor.entropy_coeff): the loss gains -entropy_coef * sum n H, H the per-token entropy of the policy and n the per-token normaliser of the
+        # policy term (a positive coefficient rewards entropy).  top_entropy_quantile = rho < 1 (trl): only the live tokens whose entropy is at or above the
+        # (1 - rho) quantile of this micro-step's live entropies carry the advantage term; KL, the normaliser and the bonus keep every live token.  trl selects
+        # over the batch gathered across ranks, here the selection is per micro-step - one prompt's G completions on one rank - like loss_type="bnpo"'s normaliser.
+        # At the defaults (0, 1) neither reaches any code below.
+        self.entropy_coef = float(entropy_coef)
+        self.top_entropy_quantile = 1.0 if top_entropy_quantile is None else float(top_entropy_quantile)
+        missing = [n for n, on in (("logp_entropy_bwd", self.entropy_coef != 0.0), ("entropy_quantile_weight", self.top_entropy_quantile < 1.0))
+                   if on and not hasattr(engine.ops, n)]
+        if missing:
+            raise NotImplementedError("entropy_coef = %g / top_entropy_quantile = %g: the %r backend has no %s"
+                                      % (self.entropy_coef, self.top_entropy_quantile, getattr(engine.ops, "name", type(engine.ops).__name__), " / ".join(missing)))
         # None: the two loss branches of the reference (grpo_loss, grpo_loss_ratio on a replay).  A dict(norm, level, eps_low, eps_high, delta): every update
         # goes through grpo_policy_loss (trl's loss_type / importance_sampling_level / delta, rows without a live token) - policy_objective() below builds it
         self.objective = objective
@@ -239,6 +251,10 @@ class GRPOCore:
         hook = None
         if grad_sync is not None and grad_sync.active:
             hook = lambda i: grad_sync.ready(*tr.range_of("l%d." % i))
+        if self.top_entropy_quantile < 1.0:
+            # the entropy of THIS forward (a replay selects on its own, as trl recomputes the mask in every compute_loss); it multiplies with an importance cap
+            sel, _ = ops.entropy_quantile_weight(st.entropy, completion_mask, self.top_entropy_quantile)
+            tok_weight = sel if tok_weight is None else tok_weight.to(torch.float32) * sel
         if self.objective is not None:
             # the objective family: first pass (old_logp None: ratio 1, tok_weight inside the kernel) and replays alike; out8 is returned in place of out3
             o = self.objective
@@ -263,7 +279,26 @@ class GRPOCore:
             out3 = out3.clone()
             out3[0] = out3[0] + corr.sum().to(out3.dtype)
         dl_pred = dlogp.reshape(-1)[st.perm].contiguous()
-        dh = eng.head_bwd(st.head_ctx, dl_pred, st.layout.G)
+        if self.entropy_coef != 0.0:
+            # loss - entropy_coef * sum n H over ALL live tokens (the selection above does not apply), n = the normaliser of the policy term on this path, built from
+            # the kernel's own counts on the device; a row (or a grid) without a live token contributes 0
+            G, C = st.layout.G, st.layout.C
+            live = completion_mask != 0
+            m = live.to(torch.float32)
+            norm = self.objective["norm"] if self.objective is not None else (0 if self.use_grpo else 1)
+            if norm == 0:
+                n = m / (row_len.reshape(-1, 1).to(torch.float32).clamp(min=1.0) * float(G))
+            elif norm == 1:
+                n = m / out3[2].to(torch.float32).clamp(min=1.0)
+            else:
+                n = m / (float(G) * float(C))
+            H = torch.where(live, st.entropy.to(torch.float32), torch.zeros_like(n))
+            dent_gc = (-self.entropy_coef * float(grad_scale)) * n
+            out3 = out3.clone()
+            out3[0] = out3[0] - (self.entropy_coef * (n * H).sum()).to(out3.dtype)
+            dh = eng.head_bwd(st.head_ctx, dl_pred, G, dent=dent_gc.reshape(-1)[st.perm].contiguous())
+        else:
+            dh = eng.head_bwd(st.head_ctx, dl_pred, st.layout.G)
         if hook is not None and not self.cfg.text.tie_word_embeddings:
             grad_sync.ready(*tr.range_of("norm"))          # final norm + untied lm_head gradients are complete after the head backward
             grad_sync.ready(*tr.range_of("lm_head"))

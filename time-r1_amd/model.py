@@ -665,15 +665,20 @@ class Engine:
                 parts.append(ops.logp_entropy_fwd(lg, targets[a:a + ch].contiguous()))
                 del lg
             logp, ent, lse = [torch.cat([p[i] for p in parts]) for i in range(3)]
-        ctx = dict(hp=hp, hn=hn, rstd=rstd, logits=logits, lse=lse, targets=targets, pred_rows=pred_rows, M=h_last.shape[0]) if save else None
+        ctx = dict(hp=hp, hn=hn, rstd=rstd, logits=logits, lse=lse, ent=ent, targets=targets, pred_rows=pred_rows, M=h_last.shape[0]) if save else None
         return logp, ent, ctx
 
-    def head_bwd(self, ctx, dlogp, n_dup):
-        """dlogp: [R] fp32 in pred_rows order. The first n_dup pred rows all alias one hidden row (the last prompt token)."""
+    def head_bwd(self, ctx, dlogp, n_dup, dent=None):
+        """dlogp: [R] fp32 in pred_rows order. The first n_dup pred rows all alias one hidden row (the last prompt token).
+        dent (fp32 [R], pred_rows order): the gradient arriving at the entropy (an entropy term in the loss); it joins dlogp in the one pass over the logits
+        (logp_entropy_bwd, with the forward's own lse and entropy).  None: the entropy is a logged number and the pass is logp_bwd."""
         ops, t, tr = self.ops, self.cfg.text, self.params.train
         w, gw = self.params.lm_head_w(), self.params.lm_head_g()
         if ctx["logits"] is not None:
-            dlogits = ops.logp_bwd(ctx["logits"], ctx["targets"], ctx["lse"], dlogp, inplace=True)
+            if dent is None:
+                dlogits = ops.logp_bwd(ctx["logits"], ctx["targets"], ctx["lse"], dlogp, inplace=True)
+            else:
+                dlogits = ops.logp_entropy_bwd(ctx["logits"], ctx["targets"], ctx["lse"], ctx["ent"], dlogp, dent, inplace=True)
             self._wgrad(dlogits, ctx["hn"], gw, key="lm_head.w")        # first micro-step of a window: overwrite (the optimizer left it zero: same result, no 2.2 GB read)
             dhn = self._dgrad(dlogits, w, key="lm_head")
             ctx["logits"] = None
@@ -683,7 +688,11 @@ class Engine:
             for a in range(0, R, ch):
                 b = min(R, a + ch)
                 lg = ops.gemm_nt(hn[a:b], w)
-                dl = ops.logp_bwd(lg, ctx["targets"][a:b].contiguous(), ctx["lse"][a:b].contiguous(), dlogp[a:b].contiguous(), inplace=True)
+                if dent is None:
+                    dl = ops.logp_bwd(lg, ctx["targets"][a:b].contiguous(), ctx["lse"][a:b].contiguous(), dlogp[a:b].contiguous(), inplace=True)
+                else:
+                    dl = ops.logp_entropy_bwd(lg, ctx["targets"][a:b].contiguous(), ctx["lse"][a:b].contiguous(), ctx["ent"][a:b].contiguous(),
+                                              dlogp[a:b].contiguous(), dent[a:b].contiguous(), inplace=True)
                 self._wgrad(dl, hn[a:b], gw, key="lm_head.w")           # (only the window's first chunk overwrites; later chunks and micro-steps accumulate)
                 dhn[a:b] = self._dgrad(dl, w, key="lm_head")
                 del lg, dl

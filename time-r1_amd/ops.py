@@ -738,6 +738,26 @@ class HipOps:
         self.L.call("tr1_logp_bwd", _p(logits), _ld(logits), _p(targets), _p(lse), _p(dlogp), _p(out), _ld(out), R, V, self._s())
         return out
 
+    def logp_entropy_bwd(self, logits, targets, lse, ent, dlogp, dent, inplace=True):
+        """logp_bwd with a gradient at the entropy as well: dlogits = dlogp (onehot - p) - dent p (log p + ent).  lse / ent: the forward's outputs (fp32 [R]);
+        dent None: logp_bwd itself."""
+        self._chk(logits)
+        R, V = logits.shape
+        for t in (lse, ent, dlogp, dent):
+            assert t is None or (t.dtype == F32 and t.is_contiguous() and t.numel() == R)
+        out = logits if inplace else torch.empty_like(logits)
+        self.L.call("tr1_logp_entropy_bwd", _p(logits), _ld(logits), _p(targets), _p(lse), _p(ent), _p(dlogp), _p(dent), _p(out), _ld(out), R, V, self._s())
+        return out
+
+    def entropy_quantile_weight(self, ent, mask, rho):
+        """trl's top_entropy_quantile mask on the device -> (weight fp32 shaped like ent, stats3 = [threshold, kept, live]): 1 where mask != 0 and ent is at or above
+        the (1 - rho) quantile of the live entropies (torch.quantile's linear interpolation), else 0.  Masked positions are never read; no host synchronisation."""
+        assert ent.dtype == F32 and mask.dtype == I32 and ent.is_contiguous() and mask.is_contiguous() and mask.shape == ent.shape
+        w = self.empty(*ent.shape, dtype=F32)
+        stats3 = self.empty(3, dtype=F32)
+        self.L.call("tr1_entropy_quantile_weight", _p(ent), _p(mask), _p(w), _p(stats3), ent.numel(), float(rho), self._s())
+        return w, stats3
+
     def grpo_loss(self, logp, ref_logp, mask, adv, beta, use_grpo, grad_scale=1.0):
         G, C = logp.shape
         assert logp.dtype == F32 and mask.dtype == I32 and adv.dtype == F32 and logp.is_contiguous() and mask.is_contiguous()

@@ -294,13 +294,29 @@ def _(logits, targets, lse, dlogp):
     return torch.empty_like(logits)
 
 
+@_op("logp_entropy_bwd")
+def logp_entropy_bwd(logits: Tensor, targets: Tensor, lse: Tensor, ent: Tensor, dlogp: Tensor, dent: Tensor) -> Tensor:
+    return _ops(logits).logp_entropy_bwd(logits, targets, lse, ent, dlogp, dent, inplace=False)
+
+
+@logp_entropy_bwd.register_fake
+def _(logits, targets, lse, ent, dlogp, dent):
+    return torch.empty_like(logits)
+
+
 def _lp_setup(ctx, inputs, output):
-    ctx.save_for_backward(inputs[0], inputs[1], output[2])
+    ctx.set_materialize_grads(False)                   # an output the graph never uses arrives as None in the backward, not as zeros
+    ctx.save_for_backward(inputs[0], inputs[1], output[2], output[1])
 
 
-def _lp_backward(ctx, dlogp, _dent, _dlse):
-    logits, targets, lse = ctx.saved_tensors           # the entropy is a logged metric (reference :473-481 computes it under no_grad)
-    return torch.ops.timer1.logp_bwd(logits, targets, lse, dlogp.contiguous().float()), None
+def _lp_backward(ctx, dlogp, dent, _dlse):
+    logits, targets, lse, ent = ctx.saved_tensors
+    if dent is None:                                   # the entropy is only a logged metric (reference :473-481 computes it under no_grad): logp_bwd, as ever
+        if dlogp is None:
+            return None, None
+        return torch.ops.timer1.logp_bwd(logits, targets, lse, dlogp.contiguous().float()), None
+    dlogp = torch.zeros_like(lse) if dlogp is None else dlogp.contiguous().float()
+    return torch.ops.timer1.logp_entropy_bwd(logits, targets, lse, ent, dlogp, dent.contiguous().float()), None
 
 
 logp_entropy_fwd.register_autograd(_lp_backward, setup_context=_lp_setup)
@@ -308,9 +324,26 @@ logp_entropy_fwd.register_autograd(_lp_backward, setup_context=_lp_setup)
 
 def logp_entropy(logits: Tensor, targets: Tensor) -> Tuple[Tensor, Tensor]:
     """Per-row log-softmax gathered at `targets` + entropy of the row distribution, one pass over [R, V] bf16 logits
-    (reference timer1_trainer.py:458-481).  Differentiable in logits through logp."""
+    (reference timer1_trainer.py:458-481).  Differentiable in logits through both outputs: a loss that uses the entropy (an entropy bonus) runs
+    timer1::logp_entropy_bwd, one that uses logp alone runs timer1::logp_bwd."""
     lp, ent, _ = torch.ops.timer1.logp_entropy_fwd(logits.contiguous(), targets.to(I32).contiguous())
     return lp, ent
+
+
+@_op("entropy_quantile_weight")
+def entropy_quantile_weight_op(ent: Tensor, mask: Tensor, rho: float) -> Tuple[Tensor, Tensor]:
+    return _ops(ent).entropy_quantile_weight(ent, mask, rho)
+
+
+@entropy_quantile_weight_op.register_fake
+def _(ent, mask, rho):
+    return torch.empty_like(ent), ent.new_empty(3)
+
+
+def entropy_quantile_weight(entropy: Tensor, completion_mask: Tensor, top_entropy_quantile: float) -> Tuple[Tensor, Tensor]:
+    """-> (weight, stats).  trl.GRPOConfig.top_entropy_quantile: weight is 1 on the live tokens whose entropy is at or above the (1 - top_entropy_quantile) quantile
+    of the live entropies and 0 elsewhere - the tok_weight of grpo_loss_ratio / grpo_policy_loss.  stats = [threshold, tokens kept, live tokens].  No gradient."""
+    return torch.ops.timer1.entropy_quantile_weight(entropy.detach().float().contiguous(), completion_mask.to(I32).contiguous(), float(top_entropy_quantile))
 
 
 @_op("lmhead_logp_entropy")
@@ -478,7 +511,7 @@ def _(frames_u8, out_h, out_w, k_pad):
 
 
 OP_NAMES = ["rmsnorm_fwd", "rmsnorm_bwd", "swiglu_fwd", "swiglu_bwd", "linear_fwd", "linear_bwd", "rope_fwd", "mrope_table", "attn_fwd", "attn_bwd",
-            "logp_entropy_fwd", "logp_bwd", "lmhead_logp_entropy", "grpo_loss", "grpo_loss_ratio", "grpo_policy_loss", "sample_tokens", "sample_tokens_filtered", "penalize_logits", "mark_seen_ids",
+            "logp_entropy_fwd", "logp_bwd", "logp_entropy_bwd", "entropy_quantile_weight", "lmhead_logp_entropy", "grpo_loss", "grpo_loss_ratio", "grpo_policy_loss", "sample_tokens", "sample_tokens_filtered", "penalize_logits", "mark_seen_ids",
             "mark_seen_drawn", "adamw_step", "video_preprocess"]
 
 

@@ -123,6 +123,15 @@ class GRPOConfig:
         if self.use_grpo and (self.importance_sampling_level != "token" or self.delta is not None):
             raise ValueError("use_grpo=True has no clip on the probability ratio: importance_sampling_level and delta must stay at their defaults")
         self.scale_rewards, self.mask_truncated_completions = bool(self.scale_rewards), bool(self.mask_truncated_completions)
+        try:
+            self.entropy_coef = float(self.entropy_coef)
+        except (TypeError, ValueError):
+            raise ValueError("entropy_coef must be a finite number, got %r" % (self.entropy_coef,))
+        if not math.isfinite(self.entropy_coef):
+            raise ValueError("entropy_coef must be a finite number, got %r" % (self.entropy_coef,))
+        self.top_entropy_quantile = 1.0 if self.top_entropy_quantile is None else float(self.top_entropy_quantile)
+        if not 0.0 < self.top_entropy_quantile <= 1.0:
+            raise ValueError("top_entropy_quantile must be in (0, 1], got %r" % (self.top_entropy_quantile,))
 
     beta: float = 0.04
     use_grpo: bool = False
@@ -136,6 +145,10 @@ class GRPOConfig:
     delta: Optional[float] = None           # two-sided clipping: the ratio in the unclipped term is capped at delta (bounds the loss for negative advantages); > 1 + epsilon_high
     scale_rewards: bool = True              # False: advantages = rewards - group mean, without the division by the group's std (Dr. GRPO)
     mask_truncated_completions: bool = False   # completions without an EOS among their max_completion_length tokens leave the loss
+    entropy_coef: float = 0.0               # entropy bonus (verl's actor.entropy_coeff): loss - entropy_coef * (the policy's per-token entropy under the loss's own normaliser);
+                                            # > 0 rewards entropy, < 0 penalises it, 0 = off (the entropy stays the logged generation_entropy only)
+    top_entropy_quantile: float = 1.0       # trl.GRPOConfig.top_entropy_quantile: only the top share of the live tokens by entropy carries the policy-gradient term
+                                            # (selected per micro-step: one prompt's completions on one rank; trl selects over the gathered batch); 1 or None = all
     prompt_type: str = "v1"
     fix_vit: bool = True
     stop_at_eos: bool = False               # the reference's GenerationConfig carries no eos_token_id (a6): always C tokens
@@ -428,7 +441,8 @@ class TimeR1_Trainer:
         self.core = GRPOCore(self.engine, self.ref_model, self.num_generations, self.max_completion_length, beta=self.beta,
                              use_grpo=self.use_grpo, temperature=args.temperature, top_k=args.top_k, seed=args.seed + 1000 * self.dp.rank,
                              rope_index_mode=args.rope_index_mode, stop_at_eos=args.stop_at_eos, top_p=getattr(args, "top_p", 1.0),
-                             min_p=getattr(args, "min_p", None), repetition_penalty=getattr(args, "repetition_penalty", 1.0), objective=self._objective)
+                             min_p=getattr(args, "min_p", None), repetition_penalty=getattr(args, "repetition_penalty", 1.0), objective=self._objective,
+                             entropy_coef=getattr(args, "entropy_coef", 0.0), top_entropy_quantile=getattr(args, "top_entropy_quantile", 1.0))
         self.core.roll.weight_dtype = getattr(args, "rollout_weight_dtype", "bf16")
         keep = getattr(args, "rollout_fp8_keep_bf16", None)
         if keep is None:
