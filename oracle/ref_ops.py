@@ -19,7 +19,7 @@ I32 = torch.int32
 
 
 def philox4x32_10(c0, c1, c2, c3, k0, k1):
-    """Philox4x32-10 (Salmon et al. 2011), same constants as csrc/loss.hip."""
+    """Philox4x32-10 (Salmon et al. 2011), same constants as csrc/sampler.hip."""
     M0, M1, W0, W1 = 0xD2511F53, 0xCD9E8D57, 0x9E3779B9, 0xBB67AE85
     mask = 0xFFFFFFFF
     for _ in range(10):

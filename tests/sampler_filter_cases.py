@@ -1,4 +1,4 @@
-"""fp64 reference and cases for the sampler's top-p / min-p filters and the repetition penalty (csrc/loss.hip).
+"""fp64 reference and cases for the sampler's top-p / min-p filters and the repetition penalty (csrc/sampler.hip).
 
 Shared by tests/test_sampler_filter_ref.py (CPU: this reference against the transformers warpers, and the host plumbing) and
 tests/test_sampler_filter_gpu.py (the HIP kernels against this reference).  Plain torch on the CPU, written from the rules:

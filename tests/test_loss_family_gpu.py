@@ -50,15 +50,16 @@ def test_rows_without_a_live_token(hip_ops, G, C):
             assert all(bool((t == 0).all()) for t in got), (norm, level, got[1])
 
 
-@pytest.mark.parametrize("G,C", [(8, 200), (3, 257), (1, 1)])
+@pytest.mark.parametrize("G,C", [(8, 200), (3, 257), (1, 1), (64, 300)])
 def test_token_mean_at_token_level_without_a_cap_is_the_ratio_kernel(hip_ops, G, C):
+    """Both entry points launch one kernel, here with the same arguments but the floor of the token counts, which no row of these cases reaches: equal floats."""
     eps = rc.EPS_PAIRS[1]
     d = _dev(fc.family_case(G, C, eps), hip_ops)
     for beta, gs, w in ((0.0, 1.0, None), (0.04, 0.5, d["tok_weight"])):
         a = hip_ops.grpo_policy_loss(d["logp"], d["old_logp"], d["ref_logp"], d["mask"], d["adv"], beta, "token", "token", eps[0], eps[1], None, gs, tok_weight=w)
         b = hip_ops.grpo_loss_ratio(d["logp"], d["old_logp"], d["ref_logp"], d["mask"], d["adv"], beta, False, eps[0], eps[1], gs, tok_weight=w)
         for x, y in zip(a, b):
-            assert vc.worst(x, y, vc.TOL_GRPO)[0] <= 1.0
+            assert torch.isfinite(x).all() and torch.equal(x, y)
         assert torch.equal(a[1][2:6], b[1][2:6])          # counts: exact
 
 

@@ -1,4 +1,4 @@
-"""GPU: the vocabulary-side HIP kernels (csrc/loss.hip, the lmhead_lse tail of csrc/gemm.hip) against the fp64 references of tests/vocab_cases.py.
+"""GPU: the vocabulary-side HIP kernels (csrc/loss.hip, csrc/sampler.hip, the lmhead_lse tail of csrc/gemm.hip) against the fp64 references of tests/vocab_cases.py.
 
 Cases, references and tolerances live in vocab_cases.py; tests/test_vocab_side_ref.py shows on the CPU that the fp32 oracle sits within a tenth of
 every tolerance on the same cases.  The tolerances are the project's own (tests/test_ops_gpu.py); every check prints the worst error it saw

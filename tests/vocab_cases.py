@@ -1,4 +1,4 @@
-"""Seeded cases and fp64 references for the vocabulary-side kernels (csrc/loss.hip and the lmhead_lse tail of csrc/gemm.hip).
+"""Seeded cases and fp64 references for the vocabulary-side kernels (csrc/loss.hip, csrc/sampler.hip and the lmhead_lse tail of csrc/gemm.hip).
 
 Shared by tests/test_vocab_side_ref.py (CPU: the fp32 oracle against these references) and tests/test_vocab_side_gpu.py (the HIP kernels against
 the same references on the same cases).  Everything here is plain torch / numpy on the CPU, written from the formulas:

@@ -4,6 +4,7 @@
 tests can drive the same host logic with `oracle.ref_ops.RefOps` on CPU - the product never imports oracle/.
 """
 import os
+import re
 
 import torch
 
@@ -770,66 +771,58 @@ class HipOps:
         return dlogp, out3, row_len, row_kl
 
     @staticmethod
+    def _header_define(name):
+        """An integer #define of include/timer1_hip.h (the library checks the same number when it is built)."""
+        return int(re.search(rf"#define\s+{name}\s+(\d+)", open(hip.HEADER).read()).group(1))
+
+    @staticmethod
     def grpo_loss_ratio_ws_words():
         """Workspace of tr1_grpo_loss_ratio in 4-byte words, as include/timer1_hip.h states it (the library checks the same number when it is built)."""
-        import re
-        from .hip import HEADER
-        return int(re.search(r"#define\s+TR1_GRPO_LOSS_RATIO_WS_WORDS\s+(\d+)", open(HEADER).read()).group(1))
+        return HipOps._header_define("TR1_GRPO_LOSS_RATIO_WS_WORDS")
+
+    @staticmethod
+    def grpo_policy_loss_ws_words():
+        """Workspace of tr1_grpo_policy_loss in 4-byte words, as include/timer1_hip.h states it (the library checks the same number when it is built)."""
+        return HipOps._header_define("TR1_GRPO_POLICY_LOSS_WS_WORDS")
+
+    def _grpo_row_loss(self, name, logp, old_logp, ref_logp, tok_weight, mask, adv, beta, *mode):
+        """What grpo_loss_ratio and grpo_policy_loss share (one kernel, one block per row): the argument checks, the per-stream workspace, the four outputs
+        and the call of tr1_<name>; mode = the entry point's own arguments between beta and the stream."""
+        G, C = logp.shape
+        assert logp.dtype == F32 and mask.dtype == I32 and adv.dtype == F32
+        assert logp.is_contiguous() and mask.is_contiguous() and mask.shape == logp.shape
+        assert adv.numel() == G and adv.is_contiguous()
+        for t in (old_logp, ref_logp, tok_weight):
+            assert t is None or (t.dtype == F32 and t.is_contiguous() and t.shape == logp.shape)
+        key = (name, self._s())
+        ws = self._ws.get(key)
+        if ws is None:
+            ws = self._ws[key] = torch.zeros(getattr(self, name + "_ws_words")(), dtype=F32, device=self.device)
+        dlogp = self.empty(G, C, dtype=F32)
+        out8 = self.empty(8, dtype=F32)
+        row_len = self.empty(G, dtype=F32)
+        row_kl = self.empty(G, dtype=F32)
+        self.L.call("tr1_" + name, _p(logp), _p(old_logp), _p(ref_logp), _p(tok_weight), _p(mask), _p(adv), _p(dlogp), _p(out8), _p(row_len), _p(row_kl),
+                    _p(ws), G, C, float(beta), *mode, self._s())
+        return dlogp, out8, row_len, row_kl
 
     def grpo_loss_ratio(self, logp, old_logp, ref_logp, mask, adv, beta, use_grpo, eps_low, eps_high, grad_scale=1.0, tok_weight=None):
         """The GRPO loss against an old policy (rho = exp(logp - old_logp), PPO clip) -> (dlogp, out8, row_len, row_kl); out8 = [loss, mean kl, sum mask,
         low / high / either clip fraction, k3 distance to the old policy, max rho].  One block per row; the workspace (ticket + row partials) is zeroed
         ONCE per stream - the kernel leaves it zero - so two calls on the same inputs give the same bits."""
-        G, C = logp.shape
-        assert logp.dtype == F32 and old_logp.dtype == F32 and mask.dtype == I32 and adv.dtype == F32
-        assert logp.is_contiguous() and old_logp.is_contiguous() and mask.is_contiguous() and old_logp.shape == logp.shape and mask.shape == logp.shape
-        assert adv.numel() == G and adv.is_contiguous()
-        for t in (ref_logp, tok_weight):
-            assert t is None or (t.dtype == F32 and t.is_contiguous() and t.shape == logp.shape)
-        key = ("grpo_loss_ratio", self._s())
-        ws = self._ws.get(key)
-        if ws is None:
-            ws = self._ws[key] = torch.zeros(self.grpo_loss_ratio_ws_words(), dtype=F32, device=self.device)
-        dlogp = self.empty(G, C, dtype=F32)
-        out8 = self.empty(8, dtype=F32)
-        row_len = self.empty(G, dtype=F32)
-        row_kl = self.empty(G, dtype=F32)
-        self.L.call("tr1_grpo_loss_ratio", _p(logp), _p(old_logp), _p(ref_logp), _p(tok_weight), _p(mask), _p(adv), _p(dlogp), _p(out8), _p(row_len),
-                    _p(row_kl), _p(ws), G, C, float(beta), int(bool(use_grpo)), float(eps_low), float(eps_high), float(grad_scale), self._s())
-        return dlogp, out8, row_len, row_kl
-
-    @staticmethod
-    def grpo_policy_loss_ws_words():
-        """Workspace of tr1_grpo_policy_loss in 4-byte words, as include/timer1_hip.h states it (the library checks the same number when it is built)."""
-        import re
-        from .hip import HEADER
-        return int(re.search(r"#define\s+TR1_GRPO_POLICY_LOSS_WS_WORDS\s+(\d+)", open(HEADER).read()).group(1))
+        assert old_logp is not None
+        return self._grpo_row_loss("grpo_loss_ratio", logp, old_logp, ref_logp, tok_weight, mask, adv, beta, int(bool(use_grpo)), float(eps_low),
+                                   float(eps_high), float(grad_scale))
 
     def grpo_policy_loss(self, logp, old_logp, ref_logp, mask, adv, beta, norm, level, eps_low, eps_high, delta=None, grad_scale=1.0, tok_weight=None):
         """The GRPO objective family -> (dlogp, out8, row_len, row_kl), outputs as grpo_loss_ratio's.  norm: "row" | "token" | "fixed" (or 0 | 1 | 2: mean over
         each row then over rows / over all live tokens / sum over G * C); level: "token" | "sequence" (or 0 | 1: per-token ratio / one ratio per row);
         delta: upper cap on the ratio in the unclipped term (None or <= 0 = off); old_logp None: the old policy is the policy.  Token counts are clamped
         to 1, so rows without a live token give zeros.  The workspace is zeroed ONCE per stream - the kernel leaves it zero."""
-        G, C = logp.shape
         norm, level = GRPO_NORM_MODES.get(norm, norm), GRPO_LEVELS.get(level, level)
         assert norm in (0, 1, 2) and level in (0, 1), (norm, level)
-        assert logp.dtype == F32 and mask.dtype == I32 and adv.dtype == F32
-        assert logp.is_contiguous() and mask.is_contiguous() and mask.shape == logp.shape
-        assert adv.numel() == G and adv.is_contiguous()
-        for t in (old_logp, ref_logp, tok_weight):
-            assert t is None or (t.dtype == F32 and t.is_contiguous() and t.shape == logp.shape)
-        key = ("grpo_policy_loss", self._s())
-        ws = self._ws.get(key)
-        if ws is None:
-            ws = self._ws[key] = torch.zeros(self.grpo_policy_loss_ws_words(), dtype=F32, device=self.device)
-        dlogp = self.empty(G, C, dtype=F32)
-        out8 = self.empty(8, dtype=F32)
-        row_len = self.empty(G, dtype=F32)
-        row_kl = self.empty(G, dtype=F32)
-        self.L.call("tr1_grpo_policy_loss", _p(logp), _p(old_logp), _p(ref_logp), _p(tok_weight), _p(mask), _p(adv), _p(dlogp), _p(out8), _p(row_len),
-                    _p(row_kl), _p(ws), G, C, float(beta), int(norm), int(level), float(eps_low), float(eps_high), float(delta) if delta else 0.0,
-                    float(grad_scale), self._s())
-        return dlogp, out8, row_len, row_kl
+        return self._grpo_row_loss("grpo_policy_loss", logp, old_logp, ref_logp, tok_weight, mask, adv, beta, int(norm), int(level), float(eps_low),
+                                   float(eps_high), float(delta) if delta else 0.0, float(grad_scale))
 
     def sample_tokens(self, logits, temperature, top_k, seed, step_dev, tokens, finished, eos_id, pad_id, stop_at_eos, u_out=None, group_rows=0,
                       seed_stride=0, next_ids=None, top_p=1.0, min_p=0.0):

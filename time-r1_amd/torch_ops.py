@@ -13,6 +13,7 @@ Device contract: the implementations are HIP only (`device_types="cuda"`); a CPU
 there is no fallback.  Kernels are launched on torch's CURRENT stream of the tensor's device; nothing is retained past the call.
 Activations are bf16, statistics / gradients of parameters fp32 (cast to the parameter dtype by the wrappers).
 """
+import inspect
 from typing import Optional, Tuple
 
 import torch
@@ -362,19 +363,31 @@ def _(hn, w, targets):
     return hn.new_empty(R, dtype=F32), hn.new_empty(R, dtype=F32), hn.new_empty(R, dtype=F32)
 
 
-@_op("grpo_loss")
+def _grpo_op(name, n_out):
+    """_op for the three GRPO loss ops, which share everything but their arguments: -> (out [n_out], dlogp [G, C], row_len [G]); the kernel has already written
+    d loss / d logp, so the backward is dlogp * d out[0] for logp and None for every other argument."""
+    def deco(fn):
+        op = _op(name)(fn)
+        n_in = len(inspect.signature(fn).parameters)
+        op.register_fake(lambda logp, *a, **k: (logp.new_empty(n_out), torch.empty_like(logp), logp.new_empty(logp.shape[0])))
+        op.register_autograd(lambda ctx, dout, _d1, _d2: (ctx.saved_tensors[0] * dout[0],) + (None,) * (n_in - 1),
+                             setup_context=lambda ctx, inputs, output: ctx.save_for_backward(output[1]))
+        return op
+    return deco
+
+
+def _grpo_call(op, logp, old_logp, ref_logp, tok_weight, completion_mask, advantages, beta, *mode):
+    """The public wrappers' side of grpo_loss_ratio / grpo_policy_loss: constants detached and made fp32, grad_scale 1 -> (loss, mean k3-KL, stats)."""
+    const = lambda t: None if t is None else t.detach().float().contiguous()  # noqa: E731
+    out8, _, _ = op(logp.contiguous(), const(old_logp), ref_logp, const(tok_weight), completion_mask.to(I32).contiguous(), advantages.float().contiguous(),
+                    float(beta), *mode, 1.0)
+    return out8[0], out8[1], out8[3:]
+
+
+@_grpo_op("grpo_loss", 3)
 def grpo_loss_op(logp: Tensor, ref_logp: Optional[Tensor], mask: Tensor, adv: Tensor, beta: float, use_grpo: bool, grad_scale: float) -> Tuple[Tensor, Tensor, Tensor]:
     dlogp, out3, row_len, _ = _ops(logp).grpo_loss(logp, ref_logp, mask, adv, beta, use_grpo, grad_scale)
     return out3, dlogp, row_len
-
-
-@grpo_loss_op.register_fake
-def _(logp, ref_logp, mask, adv, beta, use_grpo, grad_scale):
-    return logp.new_empty(3), torch.empty_like(logp), logp.new_empty(logp.shape[0])
-
-
-grpo_loss_op.register_autograd(lambda ctx, dout3, _d1, _d2: (ctx.saved_tensors[0] * dout3[0], None, None, None, None, None, None),
-                               setup_context=lambda ctx, inputs, output: ctx.save_for_backward(output[1]))
 
 
 def grpo_loss(logp: Tensor, ref_logp: Optional[Tensor], completion_mask: Tensor, advantages: Tensor, beta: float, use_grpo: bool) -> Tuple[Tensor, Tensor]:
@@ -385,20 +398,11 @@ def grpo_loss(logp: Tensor, ref_logp: Optional[Tensor], completion_mask: Tensor,
     return out3[0], out3[1]
 
 
-@_op("grpo_loss_ratio")
+@_grpo_op("grpo_loss_ratio", 8)
 def grpo_loss_ratio_op(logp: Tensor, old_logp: Tensor, ref_logp: Optional[Tensor], tok_weight: Optional[Tensor], mask: Tensor, adv: Tensor, beta: float,
                        use_grpo: bool, eps_low: float, eps_high: float, grad_scale: float) -> Tuple[Tensor, Tensor, Tensor]:
     dlogp, out8, row_len, _ = _ops(logp).grpo_loss_ratio(logp, old_logp, ref_logp, mask, adv, beta, use_grpo, eps_low, eps_high, grad_scale, tok_weight=tok_weight)
     return out8, dlogp, row_len
-
-
-@grpo_loss_ratio_op.register_fake
-def _(logp, old_logp, ref_logp, tok_weight, mask, adv, beta, use_grpo, eps_low, eps_high, grad_scale):
-    return logp.new_empty(8), torch.empty_like(logp), logp.new_empty(logp.shape[0])
-
-
-grpo_loss_ratio_op.register_autograd(lambda ctx, dout8, _d1, _d2: (ctx.saved_tensors[0] * dout8[0],) + (None,) * 10,
-                                     setup_context=lambda ctx, inputs, output: ctx.save_for_backward(output[1]))
 
 
 def grpo_loss_ratio(logp: Tensor, old_logp: Tensor, ref_logp: Optional[Tensor], completion_mask: Tensor, advantages: Tensor, beta: float, use_grpo: bool,
@@ -407,28 +411,16 @@ def grpo_loss_ratio(logp: Tensor, old_logp: Tensor, ref_logp: Optional[Tensor], 
     (a later one of several updates on one rollout): rho = exp(logp - old_logp), clipped to [1 - epsilon_low, 1 + epsilon_high] on the side the advantage's
     sign makes matter.  stats = [low, high, either clip fraction, masked mean of rho - 1 - log rho, max rho].  Differentiable in logp only."""
     eh = epsilon_low if epsilon_high is None else epsilon_high
-    out8, _, _ = torch.ops.timer1.grpo_loss_ratio(logp.contiguous(), old_logp.detach().float().contiguous(), ref_logp,
-                                                  None if tok_weight is None else tok_weight.detach().float().contiguous(),
-                                                  completion_mask.to(I32).contiguous(), advantages.float().contiguous(), float(beta), bool(use_grpo),
-                                                  float(epsilon_low), float(eh), 1.0)
-    return out8[0], out8[1], out8[3:]
+    return _grpo_call(torch.ops.timer1.grpo_loss_ratio, logp, old_logp, ref_logp, tok_weight, completion_mask, advantages, beta, bool(use_grpo),
+                      float(epsilon_low), float(eh))
 
 
-@_op("grpo_policy_loss")
+@_grpo_op("grpo_policy_loss", 8)
 def grpo_policy_loss_op(logp: Tensor, old_logp: Optional[Tensor], ref_logp: Optional[Tensor], tok_weight: Optional[Tensor], mask: Tensor, adv: Tensor,
                         beta: float, norm_mode: int, seq_level: int, eps_low: float, eps_high: float, delta: float, grad_scale: float) -> Tuple[Tensor, Tensor, Tensor]:
     dlogp, out8, row_len, _ = _ops(logp).grpo_policy_loss(logp, old_logp, ref_logp, mask, adv, beta, norm_mode, seq_level, eps_low, eps_high, delta, grad_scale,
                                                           tok_weight=tok_weight)
     return out8, dlogp, row_len
-
-
-@grpo_policy_loss_op.register_fake
-def _(logp, old_logp, ref_logp, tok_weight, mask, adv, beta, norm_mode, seq_level, eps_low, eps_high, delta, grad_scale):
-    return logp.new_empty(8), torch.empty_like(logp), logp.new_empty(logp.shape[0])
-
-
-grpo_policy_loss_op.register_autograd(lambda ctx, dout8, _d1, _d2: (ctx.saved_tensors[0] * dout8[0],) + (None,) * 12,
-                                      setup_context=lambda ctx, inputs, output: ctx.save_for_backward(output[1]))
 
 
 def grpo_policy_loss(logp: Tensor, old_logp: Optional[Tensor], ref_logp: Optional[Tensor], completion_mask: Tensor, advantages: Tensor, beta: float,
@@ -439,12 +431,8 @@ def grpo_policy_loss(logp: Tensor, old_logp: Optional[Tensor], ref_logp: Optiona
     log-ratio) and delta (upper cap on the ratio in the unclipped term).  old_logp None: the old policy is the policy.  Completions without a live token
     contribute 0.  stats as grpo_loss_ratio's, with the coefficient in use for rho.  Differentiable in logp only."""
     eh = epsilon_low if epsilon_high is None else epsilon_high
-    out8, _, _ = torch.ops.timer1.grpo_policy_loss(logp.contiguous(), None if old_logp is None else old_logp.detach().float().contiguous(), ref_logp,
-                                                   None if tok_weight is None else tok_weight.detach().float().contiguous(),
-                                                   completion_mask.to(I32).contiguous(), advantages.float().contiguous(), float(beta),
-                                                   LOSS_TYPE_NORM[loss_type], GRPO_LEVELS[importance_sampling_level], float(epsilon_low), float(eh),
-                                                   float(delta) if delta else 0.0, 1.0)
-    return out8[0], out8[1], out8[3:]
+    return _grpo_call(torch.ops.timer1.grpo_policy_loss, logp, old_logp, ref_logp, tok_weight, completion_mask, advantages, beta, LOSS_TYPE_NORM[loss_type],
+                      GRPO_LEVELS[importance_sampling_level], float(epsilon_low), float(eh), float(delta) if delta else 0.0)
 
 
 # ============================================================================================================ sampler / optimizer / video
