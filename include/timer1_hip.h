@@ -335,6 +335,14 @@ int tr1_sumsq_ranges_periodic(const void* g_f32, int64_t base, int64_t stride, i
  * next accumulation window).  ref: optimizer.zero_grad() in HF Trainer.training_step / DeepSpeed engine.step (scripts/zero3.json). */
 int tr1_zero_ranges_periodic(void* g_f32, int64_t base, int64_t stride, int64_t count, const int64_t* rel_ranges, int64_t n_ranges, void* stream);
 int tr1_sumsq_accum_bf16(const void* g_bf16, int64_t n, void* out_scalar, void* ws_f32, int64_t ws_floats, void* stream);
+/* Reference-policy sync: trl.GRPOConfig.sync_ref_model / ref_model_mixup_alpha (trl's SyncRefModelCallback, the TR-DPO rule); the reference re-anchors its
+ * frozen policy (timer1_trainer.py:295-307) only by starting a new process per epoch.  In place on ref: ref[i] = bf16_rne(fadd(fmul(1 - alpha, ref[i]),
+ * fmul(alpha, policy[i]))) with three separately rounded fp32 operations (1 - alpha rounded once on the host) and ONE rounding to bf16, where trl's bf16
+ * mul_ then add_ round twice.  alpha in [0, 1]; for finite data alpha = 0 returns ref and alpha = 1 returns policy (a zero comes out as +0 where the other
+ * term is a zero of the opposite sign, as in IEEE addition).  sums_f32[0] = sum (policy - ref)^2 and sums_f32[1] = sum ref^2 of the values BEFORE the mix
+ * (fp32, per-block partials added in a fixed order: the same inputs give the same bits); written, not accumulated; n = 0 writes two zeros.
+ * Both arrays 16-byte aligned and distinct, any n.  ws_f32: >= 4096 floats of scratch. */
+int tr1_ref_mixup(void* ref_bf16, const void* policy_bf16, int64_t n, float alpha, void* sums_f32, void* ws_f32, int64_t ws_floats, void* stream);
 
 /* ---- Collectives (rccl_{init, allreduce, reduce_scatter, allgather}) ------------------------------------------------------------------
  * There is ONE exchange path: time-r1_amd/dist.py drives RCCL through torch.distributed's "nccl" backend (which IS librccl on ROCm): per-segment

@@ -216,3 +216,67 @@ extern "C" int tr1_sumsq_ranges_periodic(const void* g_f32, int64_t base, int64_
     hipLaunchKernelGGL(partials_sum_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, (const float*)ws_f32, (int64_t)gx * count, (float*)out_scalar);
     TR1_LAUNCH_CHECK();
 }
+
+// Reference-policy sync (trl.GRPOConfig.sync_ref_model, the TR-DPO rule): ref = (1 - alpha) ref + alpha policy, in place on the bf16 reference arena.
+// Three fp32 roundings, pinned (no fma contraction: ref_mix), then ONE rounding to bf16: ref[i] = bf16_rne(fadd(fmul(keep, ref[i]), fmul(alpha, policy[i]))),
+// keep = 1 - alpha rounded once on the host.  Two products, so a pair of opposite sign near the largest bf16 does not overflow where the mix is finite.
+// The same pass leaves sum (policy - ref)^2 and sum ref^2 of the values BEFORE the mix as per-block partials (part[b] and part[gridDim.x + b]): the
+// weight-space distance costs no traffic of its own.  HBM-bound: 4 B read + 2 B written per element, every array streamed once.
+// (__fmul_rn / __fadd_rn are plain * and + to this compiler and were contracted into v_pk_fma_f32 here; the pragma takes the contract flag off these three operations)
+TR1_DEV float ref_mix(float keep, float alpha, float r, float p) {
+#pragma clang fp contract(off)
+    const float t1 = keep * r, t2 = alpha * p;
+    return t1 + t2;
+}
+__global__ __launch_bounds__(256) void ref_mixup_kernel(bf16_t* __restrict__ ref, const bf16_t* __restrict__ pol, int64_t n, float alpha, float keep,
+                                                        float* __restrict__ part) {
+    __shared__ float red[16];
+    float sd = 0.f, sr = 0.f;
+    const int64_t n8 = n >> 3;
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n8; i += (int64_t)gridDim.x * blockDim.x) {
+        const u32x4_t rv = OPT_LD(reinterpret_cast<const u32x4_t*>(ref) + i), pv = OPT_LD(reinterpret_cast<const u32x4_t*>(pol) + i);
+        u32x4_t o;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const float ra = bflo(rv[e]), rb = bfhi(rv[e]), pa = bflo(pv[e]), pb = bfhi(pv[e]);
+            const float da = pa - ra, db = pb - rb;
+            sd += da * da + db * db;
+            sr += ra * ra + rb * rb;
+            o[e] = pack2bf(ref_mix(keep, alpha, ra, pa), ref_mix(keep, alpha, rb, pb));
+        }
+        OPT_ST(o, reinterpret_cast<u32x4_t*>(ref) + i);
+    }
+    if (blockIdx.x == 0) {
+        for (int64_t i = n8 * 8 + threadIdx.x; i < n; i += blockDim.x) {
+            const float r = bf2f(ref[i]), p = bf2f(pol[i]), d = p - r;
+            sd += d * d;
+            sr += r * r;
+            ref[i] = f2bf(ref_mix(keep, alpha, r, p));
+        }
+    }
+    sd = block_sum(sd, red);
+    sr = block_sum(sr, red);
+    if (threadIdx.x == 0) { part[blockIdx.x] = sd; part[gridDim.x + blockIdx.x] = sr; }
+}
+// sums[0] = sum of part[0 .. nb), sums[1] = sum of part[nb .. 2 nb), each in the fixed order of partials_sum_kernel; written, not accumulated (nb = 0: both 0)
+__global__ __launch_bounds__(256) void ref_mixup_sums_kernel(const float* __restrict__ part, int nb, float* __restrict__ sums) {
+    __shared__ float red[16];
+    float sd = 0.f, sr = 0.f;
+    for (int i = threadIdx.x; i < nb; i += 256) { sd += part[i]; sr += part[nb + i]; }
+    sd = block_sum(sd, red);
+    sr = block_sum(sr, red);
+    if (threadIdx.x == 0) { sums[0] = sd; sums[1] = sr; }
+}
+// ws_f32: >= 4096 floats (two partials per block, at most 2048 blocks).  No float atomics: the same inputs give the same two sums on every run.
+extern "C" int tr1_ref_mixup(void* ref_bf16, const void* policy_bf16, int64_t n, float alpha, void* sums_f32, void* ws_f32, int64_t ws_floats, void* stream) {
+    TR1_CHECK_ARG(n >= 0 && sums_f32 && (n == 0 || (ref_bf16 && policy_bf16 && ref_bf16 != policy_bf16)), "ref_mixup: null or aliased pointer");
+    TR1_CHECK_ARG(alpha >= 0.f && alpha <= 1.f, "ref_mixup: alpha must be in [0, 1]");
+    TR1_CHECK_ARG((((uintptr_t)ref_bf16 | (uintptr_t)policy_bf16) & 15) == 0, "ref_mixup: both arrays must be 16-byte aligned");
+    const int nb = n ? tr1_grid_1d(n / 8 + 1, 256, 2048) : 0;
+    TR1_CHECK_ARG(nb == 0 || (ws_f32 && ws_floats >= 2 * (int64_t)nb), "ref_mixup: workspace too small");
+    if (nb)
+        hipLaunchKernelGGL(ref_mixup_kernel, dim3(nb), dim3(256), 0, (hipStream_t)stream, (bf16_t*)ref_bf16, (const bf16_t*)policy_bf16, n, alpha, 1.0f - alpha,
+                           (float*)ws_f32);
+    hipLaunchKernelGGL(ref_mixup_sums_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, (const float*)ws_f32, nb, (float*)sums_f32);
+    TR1_LAUNCH_CHECK();
+}

@@ -909,6 +909,16 @@ class HipOps:
         ws = self._workspace("sumsq", 2048, F32)              # per-block partials (at most 2048 blocks), summed in a fixed order
         self.L.call("tr1_sumsq_accum" if g.dtype == F32 else "tr1_sumsq_accum_bf16", _p(g), g.numel(), _p(out_scalar), _p(ws), 2048, self._s())
 
+    def ref_mixup(self, ref_w16, policy_w16, alpha):
+        """ref_w16 = (1 - alpha) ref_w16 + alpha policy_w16 in place (fp32 arithmetic, one rounding to bf16: GRPOConfig.sync_ref_model) -> device fp32 [2]:
+        sum (policy - ref)^2 and sum ref^2 of the values before the mix, out of the same pass."""
+        self._chk(ref_w16, policy_w16)
+        assert ref_w16.is_contiguous() and policy_w16.is_contiguous() and ref_w16.numel() == policy_w16.numel()
+        sums = torch.empty(2, dtype=F32, device=self.device)
+        ws = self._workspace("ref_mixup", 4096, F32)          # two partials per block, at most 2048 blocks, summed in a fixed order
+        self.L.call("tr1_ref_mixup", _p(ref_w16), _p(policy_w16), ref_w16.numel(), float(alpha), _p(sums), _p(ws), 4096, self._s())
+        return sums
+
     def wgrad_sumsq(self, a, b, gw, accumulate, partials, offset, b_kmajor=False, b_rows=0, wire=None):
         """gw[N, K] fp32 (+)= a[N, Mp] @ b^T (b = X^T [K, Mp]) or a @ b (b_kmajor: b = X [>= b_rows, K] as stored), and partials[offset : offset + n] receives
         the per-wave sums of squares of the values stored (n returned; -1 when the shape is not covered and nothing was launched)."""

@@ -164,6 +164,7 @@ class Arena:
         a = Arena.__new__(Arena)
         a.ops, a.specs, a.offsets, a.numel, a.segments, a.shard = self.ops, self.specs, self.offsets, self.numel, self.segments, None
         a.w16 = self.w16.clone()
+        a.version = 0                    # its own counter: bumped when the snapshot is rewritten (the trainer's sync_ref_model), like the source arena's
         a.grad = a.master = a.m = a.v = None
         return a
 

@@ -486,6 +486,18 @@ def _(p32, m, v, g, p16, lr, beta1, beta2, eps, weight_decay, step, max_norm, gr
     return p32.new_empty(1)
 
 
+@_op("ref_mixup", mutates_args=("ref",))
+def ref_mixup(ref: Tensor, policy: Tensor, alpha: float) -> Tensor:
+    """trl.GRPOConfig.sync_ref_model's update: ref = (1 - alpha) ref + alpha policy in place on flat bf16 weights (fp32 arithmetic, one rounding to bf16).
+    Returns fp32 [2]: sum (policy - ref)^2 and sum ref^2 of the values before the mix."""
+    return _ops(ref).ref_mixup(ref, policy, alpha)
+
+
+@ref_mixup.register_fake
+def _(ref, policy, alpha):
+    return ref.new_empty(2, dtype=F32)
+
+
 @_op("video_preprocess")
 def video_preprocess(frames_u8: Tensor, out_h: int, out_w: int, k_pad: int) -> Tensor:
     """uint8 [T,3,H,W] -> bf16 [N_v, k_pad] normalised patches in the HF video processor's layout (resize + rescale + normalise + patchify)."""
@@ -500,7 +512,7 @@ def _(frames_u8, out_h, out_w, k_pad):
 
 OP_NAMES = ["rmsnorm_fwd", "rmsnorm_bwd", "swiglu_fwd", "swiglu_bwd", "linear_fwd", "linear_bwd", "rope_fwd", "mrope_table", "attn_fwd", "attn_bwd",
             "logp_entropy_fwd", "logp_bwd", "logp_entropy_bwd", "entropy_quantile_weight", "lmhead_logp_entropy", "grpo_loss", "grpo_loss_ratio", "grpo_policy_loss", "sample_tokens", "sample_tokens_filtered", "penalize_logits", "mark_seen_ids",
-            "mark_seen_drawn", "adamw_step", "video_preprocess"]
+            "mark_seen_drawn", "adamw_step", "ref_mixup", "video_preprocess"]
 
 
 # ================================================================================================ dropping the ops into an HF model

@@ -132,6 +132,25 @@ class GRPOConfig:
         self.top_entropy_quantile = 1.0 if self.top_entropy_quantile is None else float(self.top_entropy_quantile)
         if not 0.0 < self.top_entropy_quantile <= 1.0:
             raise ValueError("top_entropy_quantile must be in (0, 1], got %r" % (self.top_entropy_quantile,))
+        self.sync_ref_model = bool(self.sync_ref_model)
+        try:
+            self.ref_model_mixup_alpha = float(self.ref_model_mixup_alpha)
+        except (TypeError, ValueError):
+            raise ValueError("ref_model_mixup_alpha must be in (0, 1], got %r" % (self.ref_model_mixup_alpha,))
+        if not 0.0 < self.ref_model_mixup_alpha <= 1.0:
+            raise ValueError("ref_model_mixup_alpha must be in (0, 1], got %r" % (self.ref_model_mixup_alpha,))
+        try:
+            whole = int(self.ref_model_sync_steps) == float(self.ref_model_sync_steps) and int(self.ref_model_sync_steps) >= 1
+        except (TypeError, ValueError, OverflowError):
+            whole = False
+        if not whole:
+            raise ValueError("ref_model_sync_steps must be an integer >= 1, got %r" % (self.ref_model_sync_steps,))
+        self.ref_model_sync_steps = int(self.ref_model_sync_steps)
+        if self.sync_ref_model and float(self.beta) == 0.0:
+            raise ValueError("sync_ref_model needs a reference policy: beta = 0 keeps none")
+        if self.sync_ref_model and self.ref_model_sync_steps % self.num_iterations != 0:
+            raise ValueError("ref_model_sync_steps (%d) must be a multiple of num_iterations (%d): the reference moves after the last update on a rollout "
+                             "(the replayed updates reuse the reference log-probs of the first)" % (self.ref_model_sync_steps, self.num_iterations))
 
     beta: float = 0.04
     use_grpo: bool = False
@@ -149,6 +168,10 @@ class GRPOConfig:
                                             # > 0 rewards entropy, < 0 penalises it, 0 = off (the entropy stays the logged generation_entropy only)
     top_entropy_quantile: float = 1.0       # trl.GRPOConfig.top_entropy_quantile: only the top share of the live tokens by entropy carries the policy-gradient term
                                             # (selected per micro-step: one prompt's completions on one rank; trl selects over the gathered batch); 1 or None = all
+    sync_ref_model: bool = False            # trl.GRPOConfig.sync_ref_model (the TR-DPO rule): every ref_model_sync_steps optimizer steps the reference policy becomes
+                                            # (1 - ref_model_mixup_alpha) * reference + ref_model_mixup_alpha * policy; False = the snapshot taken at construction never moves
+    ref_model_mixup_alpha: float = 0.6      # in (0, 1]; 1 = the reference becomes the policy
+    ref_model_sync_steps: int = 512         # a multiple of num_iterations: the reference moves after the last update on a rollout
     prompt_type: str = "v1"
     fix_vit: bool = True
     stop_at_eos: bool = False               # the reference's GenerationConfig carries no eos_token_id (a6): always C tokens
@@ -430,6 +453,8 @@ class TimeR1_Trainer:
         self._objective = policy_objective(self.use_grpo, getattr(args, "loss_type", None), getattr(args, "importance_sampling_level", "token"),
                                            getattr(args, "delta", None), self.mask_truncated, self.epsilon_low, self.epsilon_high)
         self._check_reuse_args()
+        self._check_ref_sync_args()
+        self._ref_sync_sums = []             # sync_ref_model: the [2] device sums of the syncs since the last log (ref_sync/weight_distance)
         self._reuse = None                   # num_iterations > 1: what the window's micro-steps keep for the replayed updates (optimizer_window)
         self._replays_since_log = 0
         self.train_dataset, self.eval_dataset = train_dataset, eval_dataset
@@ -487,6 +512,32 @@ class TimeR1_Trainer:
         if getattr(a, "save_strategy", "no") == "steps" and a.save_steps and int(a.save_steps) % mu != 0:
             raise ValueError("save_steps (%d) must be a multiple of num_iterations (%d): checkpoints are written after the last update on a rollout"
                              % (a.save_steps, mu))
+
+    def _check_ref_sync_args(self):
+        """sync_ref_model against the settings it cannot work with (at construction and again when train() starts: args is mutable) -> the option is on."""
+        a = self.args
+        if not getattr(a, "sync_ref_model", False):
+            return False
+        if self.ref_model is None:
+            raise ValueError("sync_ref_model needs a reference policy: beta = 0 keeps none")
+        if not 0.0 < float(a.ref_model_mixup_alpha) <= 1.0:
+            raise ValueError("ref_model_mixup_alpha must be in (0, 1], got %r" % (a.ref_model_mixup_alpha,))
+        if int(a.ref_model_sync_steps) != a.ref_model_sync_steps or int(a.ref_model_sync_steps) < 1:
+            raise ValueError("ref_model_sync_steps must be an integer >= 1, got %r" % (a.ref_model_sync_steps,))
+        if int(a.ref_model_sync_steps) % self.num_iterations != 0:
+            raise ValueError("ref_model_sync_steps (%d) must be a multiple of num_iterations (%d): the reference moves after the last update on a rollout "
+                             "(the replayed updates reuse the reference log-probs of the first)" % (a.ref_model_sync_steps, self.num_iterations))
+        if not hasattr(self.ops, "ref_mixup"):
+            raise NotImplementedError("sync_ref_model: the %s op backend has no ref_mixup" % type(self.ops).__name__)
+        return True
+
+    def _sync_ref_model(self):
+        """reference <- (1 - alpha) reference + alpha policy over the whole arena (with fix_vit=False the tower's copy in the reference arena too).  Runs after
+        optimizer.step has returned (sharded optimizer: the all-gathers have been waited for, params.train.w16 is whole on every rank); every rank launches
+        the same kernel on identical inputs, so the references stay bit-identical without a collective."""
+        ref = self.ref_model
+        self._ref_sync_sums.append(self.ops.ref_mixup(ref.w16, self.params.train.w16, float(self.args.ref_model_mixup_alpha)))
+        ref.version = getattr(ref, "version", 0) + 1       # the kernel's writes are invisible to torch: what the engine derived from the old weights is stale now
 
     @staticmethod
     def _wants_shard(args, dp=None):
@@ -848,11 +899,14 @@ class TimeR1_Trainer:
         return losses
 
     def _optimizer_step(self, t_start, save=True):
-        """AdamW step + schedule + callbacks + logging (+ step-based checkpoint when `save`: with num_iterations > 1 only after a rollout's last update)."""
+        """AdamW step + schedule + callbacks + logging (+ step-based checkpoint when `save`: with num_iterations > 1 only after a rollout's last update).
+        `save` also marks the last update on a rollout: the only place the reference policy may move (sync_ref_model), ahead of the log and the checkpoint."""
         a = self.args
         gnorm = self.optimizer.step(lr=self._lr(self.state.global_step))
-        self._clock.mark("optimizer")
         self.state.global_step += 1
+        if save and getattr(a, "sync_ref_model", False) and self.state.global_step % int(a.ref_model_sync_steps) == 0:
+            self._sync_ref_model()
+        self._clock.mark("optimizer")
         if self._steps_per_epoch:
             self.state.epoch = self.state.global_step / self._steps_per_epoch
         for cb in self.callbacks:
@@ -967,6 +1021,7 @@ class TimeR1_Trainer:
         loader = self.get_train_dataloader()
         ga = max(1, a.gradient_accumulation_steps)
         self._check_reuse_args()
+        self._check_ref_sync_args()
         mu = self.num_iterations
         windows_per_epoch = max(len(loader) // ga, 1)
         steps_per_epoch = windows_per_epoch * mu              # optimizer steps: one loader window yields num_iterations of them
@@ -1028,6 +1083,12 @@ class TimeR1_Trainer:
         SURVEY 5.5 asks this build to emit beside them: `samples_per_sec` / `rollout_tokens_per_sec` (whole job) and the two roofline
         fractions of the step's dominant kernel families (`perf/*`, from HIP-event phase times and the algorithmic work of the shapes run)."""
         metrics = {k: sum(v) / len(v) for k, v in self.flush_metrics().items()}     # reference :784-793 (all ranks are here: see _metrics)
+        if self._ref_sync_sums:
+            # sync_ref_model: ||policy - reference|| / ||reference|| just before each sync since the last log (identical on every rank: no gather); the two
+            # sums stayed on the device until here, where the host fetches the step's values anyway
+            sums, self._ref_sync_sums = torch.stack(self._ref_sync_sums).double().cpu(), []
+            dist_ = sums[:, 0].sqrt() / sums[:, 1].clamp(min=torch.finfo(torch.float32).tiny).sqrt()
+            metrics["ref_sync/weight_distance"] = float(dist_.mean())
         logs = {**logs, **metrics, **self._throughput_keys()}
         if self.state.epoch is not None:
             logs["epoch"] = round(self.state.epoch, 4)
