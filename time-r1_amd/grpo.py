@@ -25,8 +25,11 @@ class StepState:
 class GRPOCore:
     def __init__(self, engine: Engine, ref_arena=None, num_generations=8, max_completion_length=200, beta=0.04, use_grpo=False,
                  temperature=1.0, top_k=50, seed=1234, rope_index_mode="hf4", stop_at_eos=False, reuse_prefill=True, greedy=False,
-                 top_p=1.0, min_p=None, repetition_penalty=1.0, objective=None, entropy_coef=0.0, top_entropy_quantile=1.0):
+                 top_p=1.0, min_p=None, repetition_penalty=1.0, objective=None, entropy_coef=0.0, top_entropy_quantile=1.0, activation_recompute=None):
         self.eng = engine
+        # "none" | "mlp" (Engine.activation_recompute): what the update's forwards save for the backward; None keeps the engine's own setting
+        if activation_recompute is not None:
+            engine.set_activation_recompute(activation_recompute)
         # entropy_coef (verl's actor.entropy_coeff): the loss gains -entropy_coef * sum n H, H the per-token entropy of the policy and n the per-token normaliser of the
         # policy term (a positive coefficient rewards entropy).  top_entropy_quantile = rho < 1 (trl): only the live tokens whose entropy is at or above the
         # (1 - rho) quantile of this micro-step's live entropies carry the advantage term; KL, the normaliser and the bonus keep every live token.  trl selects

@@ -1,8 +1,9 @@
 """Qwen2-VL forward and hand-written backward, expressed on the op interface of ops.py (HipOps in production).
 
 No autograd: the GRPO update needs exactly one backward through a fixed architecture, so the engine saves what the HIP backward
-kernels need (288 GB of HBM holds every activation of a 7B step - no recomputation, unlike the reference's gradient
-checkpointing, scripts/posttrain/train_rl.sh:32) and walks the layers in reverse.
+kernels need (288 GB of HBM holds every activation of a 7B step - no recomputation by default, unlike the reference's gradient
+checkpointing, scripts/posttrain/train_rl.sh:32; Engine(activation_recompute="mlp") rebuilds the MLP block's inputs in the backward
+instead of saving them) and walks the layers in reverse.
 
 Reference call sites restated here (transformers/models/qwen2_vl/modeling_qwen2_vl.py, v5.15.0):
   vision tower   :251-274 PatchEmbed, :425-449 VisionBlock, :277-290 PatchMerger, :1021-1033 get_video_features
@@ -21,9 +22,20 @@ I32 = torch.int32
 F32 = torch.float32
 
 
+ACTIVATION_RECOMPUTE_MODES = ("none", "mlp")
+
+
+def check_activation_recompute(mode):
+    if mode not in ACTIVATION_RECOMPUTE_MODES:
+        raise ValueError('activation_recompute must be "none" or "mlp", got %r' % (mode,))
+    return mode
+
+
 class Engine:
-    def __init__(self, cfg: ModelConfig, ops, params: ModelParams):
+    def __init__(self, cfg: ModelConfig, ops, params: ModelParams, activation_recompute="none"):
         self.cfg, self.ops, self.params = cfg, ops, params
+        # "mlp": llm_fwd(save=True) keeps no xn / xn2 / gu / a; llm_bwd rebuilds them per layer with the forward's own launches (see RECOMPUTED)
+        self.activation_recompute = check_activation_recompute(activation_recompute)
         self.overlap_wgrad = True      # weight gradients on a second HIP stream (attribute for A/B runs; measured equal in rounds 4-5: the backward is a serial sum)
         self.wgrad_overwrite_first = True    # see _wgrad: relies on the optimizer zeroing the gradient arena and bumping arena.version (AdamWFlat.step)
         self._gw_ver = {}
@@ -378,6 +390,20 @@ class Engine:
         return h
 
     SAVED = ("h", "xn", "v", "q", "o", "h2", "xn2", "gu", "a")
+    # activation_recompute="mlp": these four are not saved (81 % of a row's bytes at 7B width).  The backward rebuilds them, one layer at a time, into ONE
+    # transient set: xn = rmsnorm(h), xn2 = rmsnorm(h2), (a, gu) = gemm_glu(xn2, Wgu) - the forward's kernels over the forward's row ranges, so bit for bit
+    RECOMPUTED = ("xn", "xn2", "gu", "a")
+
+    @property
+    def recompute_mlp(self):
+        return self.activation_recompute == "mlp"
+
+    def set_activation_recompute(self, mode):
+        """Switch the mode between micro-steps: the pooled buffer sets of the other mode are released (their key sets differ)."""
+        if check_activation_recompute(mode) != self.activation_recompute:
+            self.activation_recompute = mode
+            self.__dict__.pop("_ctx_pool", None)
+            self.__dict__.pop("_rc_set", None)
 
     # A full set of saved-activation buffers above this size is kept ONCE: further prompts of the accumulation window stash only their
     # prompt rows (written by the rollout prefill) and move them into the one full set when their update starts (unstash_ctx).
@@ -386,7 +412,26 @@ class Engine:
 
     def ctx_bytes(self, rows):
         t = self.cfg.text
+        if self.recompute_mlp:      # h, h2, v, q, o + rstd1 / rstd2
+            return rows * t.n_layers * (2 * (2 * t.hidden + t.kv_dim + 2 * t.q_dim) + 8)
         return rows * t.n_layers * (2 * (4 * t.hidden + t.kv_dim + 2 * t.q_dim + 3 * t.intermediate) + 8)
+
+    def recompute_set_bytes(self, rows):
+        """The backward's one transient set (recompute_set) for `rows` rows: xn, xn2 [rows, hidden], gu [rows, 2I], a [rows, I]."""
+        t = self.cfg.text
+        return rows * 2 * (2 * t.hidden + 3 * t.intermediate)
+
+    def recompute_set(self, rows):
+        """activation_recompute="mlp": the [rows, .] tensors every layer's backward rebuilds xn / xn2 / gu / a into.  Owned by the engine and recycled like the
+        pooled context buffers: it only grows, and a layer overwrites what the layer above it left (llm_bwd keeps every reader on the main stream)."""
+        ops, t = self.ops, self.cfg.text
+        ent = self.__dict__.get("_rc_set")
+        if ent is None or ent[0] < rows:
+            self._rc_set = None          # release the smaller set before allocating the larger one
+            cap = (rows + 255) // 256 * 256
+            ent = self._rc_set = (cap, dict(xn=ops.empty(cap, t.hidden), xn2=ops.empty(cap, t.hidden), gu=ops.empty(cap, 2 * t.intermediate),
+                                            a=ops.empty(cap, t.intermediate)))
+        return {k: v[:rows] for k, v in ent[1].items()}
 
     def alloc_ctx_bufs(self, total_rows, slot=0, prefill_rows=None):
         """Saved-activation buffers for a packed sequence of `total_rows` rows that is run in two pieces (prompt rows during the rollout
@@ -406,11 +451,14 @@ class Engine:
             pool[key] = None          # release the smaller set before allocating the larger one
             cap = (rows + 255) // 256 * 256
             cols = dict(h=t.hidden, xn=t.hidden, v=t.kv_dim, q=t.q_dim, o=t.q_dim, h2=t.hidden, xn2=t.hidden, gu=2 * t.intermediate, a=t.intermediate)
+            if self.recompute_mlp:
+                cols = {k: c for k, c in cols.items() if k not in self.RECOMPUTED}
             # Large sequences (the stashed-prefill regime): ONE SwiGLU-output buffer for all layers instead of one per layer - a = silu(g) u is consumed by its own
             # layer's down projection in the forward, and the backward rebuilds it from the saved gate/up tensor right before the down projection's weight gradient
             # (one elementwise pass, bit-identical: the fused epilogue computes a from the bf16-rounded g / u).  Config 4: 27 x 0.74 GB = 20 GB less on a
             # 250 GB step, which is what lets the tail-row and dgu^T fast paths stay on there without allocator retries.
-            a_shared = ops.empty(cap, t.intermediate) if (self.SHARE_A and self.ctx_bytes(total_rows) > self.CTX_STASH_GB * 1e9 and t.n_layers > 1) else None
+            a_shared = ops.empty(cap, t.intermediate) if (self.SHARE_A and not self.recompute_mlp and self.ctx_bytes(total_rows) > self.CTX_STASH_GB * 1e9
+                                                          and t.n_layers > 1) else None
             full = []
             for _ in range(t.n_layers):
                 L = {k: (a_shared if (k == "a" and a_shared is not None) else ops.empty(cap, c)) for k, c in cols.items()}
@@ -426,7 +474,7 @@ class Engine:
         been enqueued on this stream, so the set is free.  ~1 read + 1 write of the prompt rows (config 4: 15 GB, 6 ms on a 3.4 s micro-step)."""
         full = self.alloc_ctx_bufs(total_rows, slot=0)
         P = prefill_rows
-        shared_a = len(full) > 1 and full[0]["a"].data_ptr() == full[1]["a"].data_ptr()
+        shared_a = len(full) > 1 and "a" in full[0] and full[0]["a"].data_ptr() == full[1]["a"].data_ptr()
         for dst, src in zip(full, pctx["bufs"]):
             for k, v in src.items():
                 if k == "a" and shared_a:
@@ -457,7 +505,10 @@ class Engine:
         rows; rollout prefill: the last prompt row).  The LAST layer's o projection and MLP then run on those rows only - the other rows' outputs feed
         nothing (their K / V, which later rows and the decode do read, come from the layer's input) - and rows < tail_from of the returned tensor and of the
         last layer's saved h2 / xn2 / gu / a / rstd2 are undefined; llm_bwd skips them the same way (their gradient is exactly zero).
-        Returns (h_out, ctx) where ctx holds the saved activations when save=True."""
+        Returns (h_out, ctx) where ctx holds the saved activations when save=True.
+        activation_recompute="mlp": a saved layer holds no xn / xn2 / gu / a (the gate/up GEMM runs with save_gu=False, like the reference-policy forward); it
+        notes instead which packed rows each launch covered - rows: the layer's input norm, mlp_rows: its post-attention norm and gate/up GEMM - and llm_bwd
+        rebuilds the four over exactly those ranges."""
         ops, t = self.ops, self.cfg.text
         M = h.shape[0]
         S = row0 + M
@@ -467,9 +518,17 @@ class Engine:
         scale = hd ** -0.5
         layers = []
         inplace = save and bufs is not None
+        rc = save and self.recompute_mlp
 
         def dst(i, key):
-            return bufs[i][key][row0:S] if inplace else None
+            return bufs[i][key][row0:S] if inplace and key in bufs[i] else None
+
+        def record(**L):
+            if rc:
+                for key in self.RECOMPUTED:
+                    del L[key]
+                L["rows"], L["mlp_rows"] = [(row0, S)], [(row0 + (t0 if len(layers) == t.n_layers - 1 else 0), S)]
+            layers.append(L)
         if inplace:
             bufs[0]["h"][row0:S].copy_(h)
             h = bufs[0]["h"][row0:S]
@@ -507,12 +566,12 @@ class Engine:
                 tl = lambda x: None if x is None else x[t0:]
                 h2t = ops.gemm_nt(o[t0:], arena.w(p + "o.w"), residual=h[t0:], out=tl(dst(i, "h2")))
                 xn2t, rstd2t, _ = ops.rmsnorm_fwd(h2t, arena.w(p + "ln2"), t.rms_eps, need_rstd=save, out=tl(dst(i, "xn2")), rstd_out=tl(dst(i, "rstd2")))
-                at, gut = ops.gemm_glu(xn2t, arena.w(p + "gu.w"), a_out=tl(dst(i, "a")), gu_out=tl(dst(i, "gu")), save_gu=save)
+                at, gut = ops.gemm_glu(xn2t, arena.w(p + "gu.w"), a_out=tl(dst(i, "a")), gu_out=tl(dst(i, "gu")), save_gu=save and not rc)
                 h_out = ops.empty(M, t.hidden)
                 ops.gemm_nt(at, arena.w(p + "down.w"), residual=h2t, out=h_out[t0:])
                 if save:
                     def full(x_t, key, **kw):         # [M, .] views for the backward: the shared buffers when there are some, else a tensor whose head is never read
-                        if x_t is None:
+                        if x_t is None or (rc and key in self.RECOMPUTED):
                             return None
                         if inplace:
                             return bufs[i][key][row0:S]
@@ -521,15 +580,15 @@ class Engine:
                         return f
                     h2, xn2, a, gu = full(h2t, "h2"), full(xn2t, "xn2"), full(at, "a"), full(gut, "gu")
                     rstd2 = full(rstd2t, "rstd2", dtype=F32)
-                    layers.append(dict(h=h, rstd1=rstd1, xn=xn, v=v, q=q, k=k, o=o, lse=lse, h2=h2, rstd2=rstd2, xn2=xn2, gu=gu, a=a))
+                    record(h=h, rstd1=rstd1, xn=xn, v=v, q=q, k=k, o=o, lse=lse, h2=h2, rstd2=rstd2, xn2=xn2, gu=gu, a=a)
                 h = h_out
                 continue
             h2 = ops.gemm_nt(o, arena.w(p + "o.w"), residual=h, out=dst(i, "h2"))
             xn2, rstd2, _ = ops.rmsnorm_fwd(h2, arena.w(p + "ln2"), t.rms_eps, need_rstd=save, out=dst(i, "xn2"), rstd_out=dst(i, "rstd2"))
-            a, gu = ops.gemm_glu(xn2, arena.w(p + "gu.w"), a_out=dst(i, "a"), gu_out=dst(i, "gu"), save_gu=save)     # SwiGLU in the GEMM epilogue
+            a, gu = ops.gemm_glu(xn2, arena.w(p + "gu.w"), a_out=dst(i, "a"), gu_out=dst(i, "gu"), save_gu=save and not rc)     # SwiGLU in the GEMM epilogue
             h_out = ops.gemm_nt(a, arena.w(p + "down.w"), residual=h2, out=dst(i + 1, "h") if inplace and i + 1 < t.n_layers else None)
             if save:
-                layers.append(dict(h=h, rstd1=rstd1, xn=xn, v=v, q=q, k=k, o=o, lse=lse, h2=h2, rstd2=rstd2, xn2=xn2, gu=gu, a=a))
+                record(h=h, rstd1=rstd1, xn=xn, v=v, q=q, k=k, o=o, lse=lse, h2=h2, rstd2=rstd2, xn2=xn2, gu=gu, a=a)
             h = h_out
         ctx = dict(layers=layers, masks=masks, cos=cos, sin=sin, h_last=h, bufs=bufs if inplace else None, tail_from=row0 + t0) if save else None
         return h, ctx
@@ -544,7 +603,11 @@ class Engine:
         for i, (a, b) in enumerate(zip(ctx_a["layers"], ctx_b["layers"])):
             L = {}
             for key in ("h", "xn", "v", "q", "o", "h2", "xn2", "gu", "a", "rstd1", "rstd2"):
-                L[key] = ctx_a["bufs"][i][key][:M] if shared else torch.cat([a[key], b[key]], 0)
+                if key in a:         # (activation_recompute="mlp" saves no xn / xn2 / gu / a)
+                    L[key] = ctx_a["bufs"][i][key][:M] if shared else torch.cat([a[key], b[key]], 0)
+            for key in ("rows", "mlp_rows"):      # ... and notes the row ranges of both pieces' launches instead
+                if key in a:
+                    L[key] = a[key] + b[key]
             L["lse"] = torch.cat([a["lse"], b["lse"]], 1).contiguous()
             L["k"] = kv_cache[i][0][:M]
             layers.append(L)
@@ -566,15 +629,26 @@ class Engine:
         # stream a few layers behind, the allocator grew to 300 GB reserved for 250 GB allocated and went into retries (backward 0.65 -> 2.2 s) as soon as anything
         # else was added.  On one stream reserved == allocated (231 GB at config 4), and the second stream buys nothing there anyway (the backward is a
         # serial sum of its kernels).
-        side = None if self.ctx_bytes(dh.shape[0]) > self.CTX_STASH_GB * 1e9 else self._side_stream()
+        # activation_recompute="mlp": the same, for another reason.  Every layer rebuilds xn / xn2 / gu / a into the ONE transient set (recompute_set) on the main
+        # stream; a weight gradient still reading the layer above's xn2 or xn on the side stream would race with that.  On one stream launch order is the order.
+        rc = self.recompute_mlp
+        side = None if (rc or self.ctx_bytes(dh.shape[0]) > self.CTX_STASH_GB * 1e9) else self._side_stream()
         pending = None
-        a_shared = t.n_layers > 1 and ctx["layers"][0]["a"].data_ptr() == ctx["layers"][1]["a"].data_ptr()
+        a_shared = not rc and t.n_layers > 1 and ctx["layers"][0]["a"].data_ptr() == ctx["layers"][1]["a"].data_ptr()
+        T = self.recompute_set(dh.shape[0]) if rc else None
         t0 = int(ctx.get("tail_from", 0) or 0)      # rows < t0 never went through the last layer's o projection / MLP (llm_fwd tail_from): dh is zero there
         for i in reversed(range(t.n_layers)):
             p = "l%d." % i
             L = ctx["layers"][i]
             M = dh.shape[0]
             tail = t0 > 0 and i == t.n_layers - 1
+            if rc:
+                # the forward's launches again, over the forward's row ranges (prompt and completion rows apart after a prefill + continuation; the tail layer's
+                # rows >= t0 only): gemm_glu changes form at 64 rows, its tile picker and rmsnorm's kernel vary with the row count - same launches, same bits
+                L = dict(L, xn2=T["xn2"], gu=T["gu"], a=T["a"])
+                for r0, r1 in L["mlp_rows"]:
+                    ops.rmsnorm_fwd(L["h2"][r0:r1], tr.w(p + "ln2"), t.rms_eps, need_rstd=False, out=T["xn2"][r0:r1])
+                    ops.gemm_glu(T["xn2"][r0:r1], tr.w(p + "gu.w"), a_out=T["a"][r0:r1], gu_out=T["gu"][r0:r1], save_gu=True)
             if tail:
                 dh_full, Lf = dh, L
                 dh = dh[t0:]
@@ -605,6 +679,10 @@ class Engine:
             # kernels' epilogues); the bias gradient is summed by the transpose that feeds the weight gradient
             ops.attn_bwd(L["q"], L["k"], L["v"], L["o"], do, L["lse"], pre, lo, hi, t.n_heads, t.n_kv_heads, M, hd, scale,
                          dq_out=dqkv[:, :qd], dk_out=dqkv[:, qd:qd + kvd], dv_out=dqkv[:, qd + kvd:], rope=(cos, sin))
+            if rc:
+                L = dict(L, xn=T["xn"])
+                for r0, r1 in L["rows"]:
+                    ops.rmsnorm_fwd(L["h"][r0:r1], tr.w(p + "ln1"), t.rms_eps, need_rstd=False, out=T["xn"][r0:r1])
             self._wgrad_async(dqkv, L["xn"], tr.g(p + "qkv.w"), side, key=p + "qkv.w", bias_g=tr.g(p + "qkv.b"))
             dxn = self._dgrad(dqkv, tr.w(p + "qkv.w"), key=p + "qkv.w")
             dh = ops.rmsnorm_bwd(dxn, L["h"], tr.w(p + "ln1"), L["rstd1"], dres=dh2, dw=tr.g(p + "ln1"))

@@ -146,6 +146,8 @@ class GRPOConfig:
         if not whole:
             raise ValueError("ref_model_sync_steps must be an integer >= 1, got %r" % (self.ref_model_sync_steps,))
         self.ref_model_sync_steps = int(self.ref_model_sync_steps)
+        if self.activation_recompute not in ("none", "mlp"):
+            raise ValueError('activation_recompute must be "none" or "mlp", got %r' % (self.activation_recompute,))
         if self.sync_ref_model and float(self.beta) == 0.0:
             raise ValueError("sync_ref_model needs a reference policy: beta = 0 keeps none")
         if self.sync_ref_model and self.ref_model_sync_steps % self.num_iterations != 0:
@@ -172,6 +174,10 @@ class GRPOConfig:
                                             # (1 - ref_model_mixup_alpha) * reference + ref_model_mixup_alpha * policy; False = the snapshot taken at construction never moves
     ref_model_mixup_alpha: float = 0.6      # in (0, 1]; 1 = the reference becomes the policy
     ref_model_sync_steps: int = 512         # a multiple of num_iterations: the reference moves after the last update on a rollout
+    activation_recompute: str = "none"      # "mlp": the update saves no xn / xn2 / gate-up / SwiGLU tensors (81 % of the saved activation bytes at 7B width: 157 704 ->
+                                            # 29 704 B per row and layer); the backward rebuilds them layer by layer with the forward's own launches - one more gate/up GEMM
+                                            # per layer, every gradient bit for bit the "none" run's.  This is what buys the memory the reference
+                                            # gets from --gradient_checkpointing
     prompt_type: str = "v1"
     fix_vit: bool = True
     stop_at_eos: bool = False               # the reference's GenerationConfig carries no eos_token_id (a6): always C tokens
@@ -222,7 +228,8 @@ class GRPOConfig:
     save_only_model: bool = False
     report_to: Any = None
     resume_from_checkpoint: Optional[str] = None
-    # accepted for CLI compatibility; no effect on the MI355X engine (no recomputation / no DeepSpeed / no sliding window)
+    # accepted for CLI compatibility; no effect on the MI355X engine (no DeepSpeed / no sliding window).  gradient_checkpointing changes nothing either, so the
+    # reference's scripts keep their speed: its memory effect is obtained with --activation_recompute mlp
     gradient_checkpointing: bool = False
     deepspeed: Optional[str] = None
     model_init_kwargs: Optional[dict] = None
@@ -411,7 +418,7 @@ class TimeR1_Trainer:
         else:
             raise TypeError("model must be a checkpoint path, a preset name, a ModelConfig, a ModelParams or a loaded transformers model")
         self.model = self.params
-        self.engine = Engine(self.cfg, ops, self.params)
+        self.engine = Engine(self.cfg, ops, self.params, activation_recompute=getattr(args, "activation_recompute", "none"))
         self.beta = args.beta
         self.ref_model = self.params.train.clone_weights_only() if self.beta != 0.0 else None    # reference :295-307
         # ---- processor
@@ -467,7 +474,8 @@ class TimeR1_Trainer:
                              use_grpo=self.use_grpo, temperature=args.temperature, top_k=args.top_k, seed=args.seed + 1000 * self.dp.rank,
                              rope_index_mode=args.rope_index_mode, stop_at_eos=args.stop_at_eos, top_p=getattr(args, "top_p", 1.0),
                              min_p=getattr(args, "min_p", None), repetition_penalty=getattr(args, "repetition_penalty", 1.0), objective=self._objective,
-                             entropy_coef=getattr(args, "entropy_coef", 0.0), top_entropy_quantile=getattr(args, "top_entropy_quantile", 1.0))
+                             entropy_coef=getattr(args, "entropy_coef", 0.0), top_entropy_quantile=getattr(args, "top_entropy_quantile", 1.0),
+                             activation_recompute=getattr(args, "activation_recompute", "none"))
         self.core.roll.weight_dtype = getattr(args, "rollout_weight_dtype", "bf16")
         keep = getattr(args, "rollout_fp8_keep_bf16", None)
         if keep is None:
