@@ -929,7 +929,10 @@ def test_norm_gemm_fused(hip_ops, ref_ops, M, N, K, glu):
 
 
 @pytest.mark.parametrize("M,N,K", [(16, 3584, 18944), (16, 3584, 3584), (8, 1536, 8960), (5, 200, 2048), (32, 3584, 18944), (24, 1536, 1536), (64, 512, 4096),
-                                   (16, 128, 256), (3, 128, 18944), (1, 64, 8192)])
+                                   (16, 128, 256), (3, 128, 18944), (1, 64, 8192),
+                                   # the 56-column LDS-streamed forms away from 7B width (skinny_fix_cfg / skinny_fix_cols56: 448 = 8 x 56 columns against 7 groups of 64).
+                                   # 5 rows: one row group, 7 x 4 < 192 blocks -> 16 K slabs, gemm_skinny_lds_fix_kernel<7, 1, 7>; 20 rows: two row groups keep 4 slabs, <7, 2, 7>
+                                   (5, 448, 8192), (20, 448, 8192)])
 def test_gemm_skinny_fixup(hip_ops, M, N, K):
     """Cross-block split-K with in-kernel fixup == the single-pass skinny GEMM (fp32 sums in a different order: bf16-ulp tolerance),
     launched repeatedly to exercise the self re-arming ticket counters."""
@@ -965,7 +968,10 @@ def test_quantize_fp8_rows_bit_exact(hip_ops, ref_ops, N, K):
                                         # full-width 7B decode shapes: lm_head over V = 152064 and the gate/up projection
                                         (16, 152064, 3584, "norm"), (16, 18944, 3584, "glu"),
                                         # LDS-streamed fp8 gate/up (a8, M <= 16, hidden 3584 / 2048 / 1536): ragged rows, fewer pairs than CUs
-                                        (5, 18944, 3584, "glu"), (7, 3584, 18944, "res"), (16, 8960, 1536, "glu"), (9, 4112, 1536, "glu"), (16, 11008, 2048, "glu"), (1, 48, 3584, "glu")])
+                                        (5, 18944, 3584, "glu"), (7, 3584, 18944, "res"), (16, 8960, 1536, "glu"), (9, 4112, 1536, "glu"), (16, 11008, 2048, "glu"), (1, 48, 3584, "glu"),
+                                        # a8: split-K + fixup (HipOps.gemm_w8: no norm, M <= 16, K >= 8192, N % 64 == 0 -> tr1_gemm_skinny_fixup_w8a8).  128 columns are no multiple of 56:
+                                        # the 64-column gemm_skinny_lds_fix_f8_kernel<6>; 448 = 8 x 56 > 7 x 64 groups: the 56-column <7, 7>.  (a8=False: the 8-wave W8A16 kernel.)
+                                        (3, 128, 8192, "res"), (5, 448, 8192, "res")])
 @pytest.mark.parametrize("a8", [False, True])
 def test_gemm_w8(hip_ops, ref_ops, M, N, K, mode, a8):
     """fp8-weight decode GEMM vs the oracle on the SAME quantised weights.  a8=False: register dequantisation + bf16 MFMA (W8A16);
@@ -987,6 +993,20 @@ def test_gemm_w8(hip_ops, ref_ops, M, N, K, mode, a8):
     if mode == "plain":
         full = x.float() @ w.float().t() + bias.float()
         assert (h.float().cpu() - full).norm() / full.norm() < (0.07 if a8 else 0.05)
+
+
+@pytest.mark.parametrize("M,N,K", [(3, 128, 8192), (5, 448, 8192)])      # the 64-column and the 56-column gemm_skinny_lds_fix_f8_kernel (see test_gemm_w8)
+def test_gemm_w8a8_fixup_rearms(hip_ops, ref_ops, M, N, K):
+    """The W8A8 split-K + fixup projection ten times on ONE workspace (HipOps keeps it per (M, N, K)), fresh activations every launch: the ticket counters re-arm
+    themselves, and a stale partial tile of the previous launch would show up as an error.  Each launch against the oracle under test_gemm_w8's tolerance."""
+    w = rnd(N, K, seed=3, scale=0.1)
+    res = rnd(M, N, seed=5)
+    q, sc = hip_ops.quantize_fp8_rows(w.cuda())
+    for rep in range(10):
+        x = rnd(M, K, seed=200 + rep)
+        h = hip_ops.gemm_w8(x.cuda(), q, sc, residual=res.cuda(), a8=True)
+        r = ref_ops.gemm_w8(x.float(), q.cpu(), sc.cpu(), lnw=None, eps=1e-6, bias=None, residual=res.float(), glu=False, a8=True)
+        close(h, r, 0.02 * math.sqrt(K) * 0.1 + 0.03, rtol=0.02, what="gemm_w8 a8 fixup, launch %d" % rep)
 
 
 @pytest.mark.parametrize("R,nh,nkv,hd,K", [(16, 28, 4, 128, 3584), (8, 4, 2, 32, 128), (32, 12, 2, 128, 1536), (5, 4, 1, 64, 256), (64, 4, 2, 32, 128)])

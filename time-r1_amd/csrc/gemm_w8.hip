@@ -5,10 +5,11 @@
 // activations (W8A16): activations keep their precision, the row scale is applied to the fp32 accumulator in the epilogue.
 // Only the SAMPLING policy is quantised - log-probs, KL and the update use the bf16 weights.
 //
-// Kernel structure = gemm_skinny_kernel / norm_gemm_skinny_kernel (gemm.hip) with a 128-element k-step:
+// Kernel structure = gemm_skinny_kernel / norm_gemm_skinny_kernel (gemm_skinny.hip) with a 128-element k-step; the pieces the two families share (tile index,
+// wave K slice, rmsnorm / SwiGLU fragment helpers, split-K fixup, LDS-stream launch helpers) are in skinny_common.h:
 //   lane (u, g) of a 16-row weight fragment loads W[row u][k0 + h*64 + g*16 .. +16] (h = 0, 1) and splits it into two bf16x8 MFMA operands
 //   (bytes 0-7, bytes 8-15); the activation fragments are loaded from the same k positions, so any k permutation cancels.
-#include "tr1_common.h"
+#include "skinny_common.h"
 #include <stdlib.h>
 
 typedef __attribute__((ext_vector_type(2))) float f32x2_t;
@@ -23,19 +24,6 @@ TR1_DEV void fp8x16_to_bf16(u32x4_t q, bf16x8_t& lo, bf16x8_t& hi) {
         b[2 * w] = pack2bf(r0[0], r0[1]); b[2 * w + 1] = pack2bf(r1[0], r1[1]);
     }
     lo = __builtin_bit_cast(bf16x8_t, a); hi = __builtin_bit_cast(bf16x8_t, b);
-}
-
-TR1_DEV float silu_w8(float x) { return x / (1.f + __expf(-x)); }
-TR1_DEV bf16x8_t scale_frag_sumsq_w8(bf16x8_t x, bf16x8_t w, float& ss) {
-    const u32x4_t xu = __builtin_bit_cast(u32x4_t, x), wu = __builtin_bit_cast(u32x4_t, w);
-    u32x4_t o;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-        const float a = bflo(xu[e]), b = bfhi(xu[e]);
-        ss = fmaf(a, a, fmaf(b, b, ss));
-        o[e] = pack2bf(a * bflo(wu[e]), b * bfhi(wu[e]));
-    }
-    return __builtin_bit_cast(bf16x8_t, o);
 }
 
 // out[M, N] = act(x)[M, K] * dequant(W)[N, K]^T (* wscale[n]) (+ bias) (+ residual);  NORM: act = rmsnorm(.; lnw) folded in;  GLU: W holds
@@ -65,10 +53,8 @@ __global__ __launch_bounds__(WAVES * 64) void gemm_skinny_w8_kernel(const bf16_t
 #pragma unroll
     for (int mg = 0; mg < MG; ++mg) xp[mg] = X + (int64_t)(mg * 16 + u < M ? mg * 16 + u : (M - 1)) * ldx + g * 16;
     const bf16_t* lp = NORM ? lnw + g * 16 : nullptr;
-    const int64_t nsteps = K / 128;
-    const int64_t s_per = (nsteps + WAVES - 1) / WAVES;
-    const int64_t s0 = wave * s_per;
-    int64_t s1 = s0 + s_per; if (s1 > nsteps) s1 = nsteps;
+    int64_t s0, s1;
+    skinny_wave_kslice<WAVES>(K / 128, wave, s0, s1);
     f32x4_t acc[NCOL][MG];
     float ss[MG];
 #pragma unroll
@@ -109,7 +95,7 @@ __global__ __launch_bounds__(WAVES * 64) void gemm_skinny_w8_kernel(const bf16_t
                     for (int mg = 0; mg < MG; ++mg)
 #pragma unroll
                         for (int j = 0; j < 2; ++j)
-                            xf[mg][j] = NORM ? scale_frag_sumsq_w8(xa[q][mg][h][j], la[q][h][j], ss[mg]) : xa[q][mg][h][j];
+                            xf[mg][j] = NORM ? scale_frag_sumsq(xa[q][mg][h][j], la[q][h][j], ss[mg]) : xa[q][mg][h][j];
 #pragma unroll
                     for (int c = 0; c < NCOL; ++c) {
                         bf16x8_t w0, w1;
@@ -140,7 +126,7 @@ __global__ __launch_bounds__(WAVES * 64) void gemm_skinny_w8_kernel(const bf16_t
     __syncthreads();
     const float inv_k = 1.f / (float)K;
     for (int i = threadIdx.x; i < NOUT * MG * 256; i += WAVES * 64) {   // (output column group, row group, m, n)
-        const int c = i / (MG * 256), mg = (i >> 8) % MG, mm = (i >> 4) & 15, nn = i & 15;
+        SKINNY_TILE_IDX(MG, i);
         const int m = mg * 16 + mm;
         const int64_t n = n0 + c * 16 + nn;
         if (m < M && n < N) {
@@ -155,7 +141,7 @@ __global__ __launch_bounds__(WAVES * 64) void gemm_skinny_w8_kernel(const bf16_t
             v *= rstd * wscale[n];
             if (GLU) {
                 const float gt = bf2f(f2bf(v)), up = bf2f(f2bf(v2 * rstd * wscale[up_off + n]));
-                C[(int64_t)m * ldc + n] = f2bf(bf2f(f2bf(silu_w8(gt))) * up);
+                C[(int64_t)m * ldc + n] = f2bf(bf2f(f2bf(silu_f32(gt))) * up);
             } else {
                 if (bias) v += bf2f(bias[n]);
                 if (residual) v += bf2f(residual[(int64_t)m * ldr + n]);
@@ -189,7 +175,7 @@ TR1_DEV void quant16_fp8(const float (&v)[16], float mul, int (&o)[4]) {
 }
 
 // XLDS (round 3, MG = 1): the bf16 activation rows and the norm weight - 8 of the 12 vector loads of a k-step at NCOL = 2, all in the MFMA operand
-// layout that costs 64 L1 tag look-ups per KiB (see gemm.hip) - reach the lanes through ONE DMA copy into LDS per block: x as [K/128 segments][16 rows]
+// layout that costs 64 L1 tag look-ups per KiB (see gemm_skinny.hip) - reach the lanes through ONE DMA copy into LDS per block: x as [K/128 segments][16 rows]
 // [256 bytes] with chunk c of row r at c ^ r, lnw as it is.  Only the fp8 weights stay on the vector-memory path.  Same values, same order.
 template <int WAVES, int UNROLL, int NCOL, int MG, bool NORM, bool GLU, bool XLDS = false>
 __global__ __launch_bounds__(WAVES * 64) void gemm_skinny_w8a8_kernel(const bf16_t* __restrict__ X, const bf16_t* __restrict__ lnw,
@@ -218,10 +204,8 @@ __global__ __launch_bounds__(WAVES * 64) void gemm_skinny_w8a8_kernel(const bf16
 #pragma unroll
     for (int mg = 0; mg < MG; ++mg) xp[mg] = X + (int64_t)(mg * 16 + u < M ? mg * 16 + u : (M - 1)) * ldx + g * 16;
     const bf16_t* lp = NORM ? lnw + g * 16 : nullptr;
-    const int64_t nsteps = K / 128;
-    const int64_t s_per = (nsteps + WAVES - 1) / WAVES;
-    const int64_t s0 = wave * s_per;
-    int64_t s1 = s0 + s_per; if (s1 > nsteps) s1 = nsteps;
+    int64_t s0, s1;
+    skinny_wave_kslice<WAVES>(K / 128, wave, s0, s1);
     f32x4_t acc[NCOL][MG];
     float ss[MG];
 #pragma unroll
@@ -382,7 +366,7 @@ __global__ __launch_bounds__(WAVES * 64) void gemm_skinny_w8a8_kernel(const bf16
     __syncthreads();
     const float inv_k = 1.f / (float)K;
     for (int i = threadIdx.x; i < NOUT * MG * 256; i += WAVES * 64) {
-        const int c = i / (MG * 256), mg = (i >> 8) % MG, mm = (i >> 4) & 15, nn = i & 15;
+        SKINNY_TILE_IDX(MG, i);
         const int m = mg * 16 + mm;
         const int64_t n = n0 + c * 16 + nn;
         if (m < M && n < N) {
@@ -397,7 +381,7 @@ __global__ __launch_bounds__(WAVES * 64) void gemm_skinny_w8a8_kernel(const bf16
             v *= rstd * wscale[n];
             if (GLU) {
                 const float gt = bf2f(f2bf(v)), up = bf2f(f2bf(v2 * rstd * wscale[up_off + n]));
-                C[(int64_t)m * ldc + n] = f2bf(bf2f(f2bf(silu_w8(gt))) * up);
+                C[(int64_t)m * ldc + n] = f2bf(bf2f(f2bf(silu_f32(gt))) * up);
             } else {
                 if (bias) v += bf2f(bias[n]);
                 if (residual) v += bf2f(residual[(int64_t)m * ldr + n]);
@@ -408,15 +392,12 @@ __global__ __launch_bounds__(WAVES * 64) void gemm_skinny_w8a8_kernel(const bf16
 }
 
 // ------------------------------------------------------------------------------------------------ W8A8, LDS-streamed gate/up (M <= 16)
-// The fp8 twin of norm_glu_lds_kernel (gemm.hip): weights travel HBM -> LDS in full 128-byte row runs (global_load_lds, 8 rows per wave
+// The fp8 twin of norm_glu_lds_kernel (gemm_skinny.hip): weights travel HBM -> LDS in full 128-byte row runs (global_load_lds, 8 rows per wave
 // instruction) - with 1-byte codes a run is 128 k = exactly one 16x16x128 MFMA step; each of the NW waves owns a K/NW = 512-wide slice
 // (4 stages), its own ring of R stages and a counted vmcnt, no barrier in the stream.  A block is persistent over a range of 16-column
 // pairs (16 gate rows + 16 up rows): the block-quantised activation fragments x' = e4m3(x * lnw / 2^E) of the wave's k-slice and their
-// E8M0 scales are built ONCE and stay in registers (4 x (8 + 1) VGPRs), sum x^2 once per block.  Stage image, swizzle (keyA8 on the DMA's
+// E8M0 scales are built ONCE and stay in registers (4 x (8 + 1) VGPRs), sum x^2 once per block.  Stage image, swizzle (keyA on the DMA's
 // SOURCE address) and the two ds_read_b128 per operand are those of the bf16 kernel: chunk h*4 + g of row u = the lane's half h.
-typedef const __attribute__((address_space(1))) void* w8_gptr_t;
-typedef __attribute__((address_space(3))) void* w8_lptr_t;
-TR1_DEV int keyA8(int row) { return (row >> 1) & 7; }
 #define W8_BARRIER() do { asm volatile("" ::: "memory"); __builtin_amdgcn_sched_barrier(0); __builtin_amdgcn_s_barrier(); asm volatile("" ::: "memory"); __builtin_amdgcn_sched_barrier(0); } while (0)
 
 template <int NW, int R>
@@ -440,7 +421,7 @@ __global__ __launch_bounds__(NW * 64) void norm_glu_lds_f8_kernel(const bf16_t* 
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
         const int r = 8 * j + (lane >> 3);
-        pg[j] = W + (p0 * 16 + r) * ldw + kb + (((lane & 7) ^ keyA8(r)) << 4);
+        pg[j] = W + (p0 * 16 + r) * ldw + kb + (((lane & 7) ^ keyA(r)) << 4);
         pu[j] = pg[j] + up_off * ldw;
     }
     const int64_t pair_step = 16 * ldw;
@@ -448,14 +429,14 @@ __global__ __launch_bounds__(NW * 64) void norm_glu_lds_f8_kernel(const bf16_t* 
 #define G8_ISSUE(ST) do {                                                                                                \
         char* dst__ = ring + islot * STAGE - (ST) * 128;   /* the instruction offset is added to the LDS address as well */  \
         _Pragma("unroll") for (int j = 0; j < 2; ++j) {                                                                  \
-            __builtin_amdgcn_global_load_lds((w8_gptr_t)pg[j], (w8_lptr_t)(dst__ + j * 1024), 16, (ST) * 128, 2);        \
-            __builtin_amdgcn_global_load_lds((w8_gptr_t)pu[j], (w8_lptr_t)(dst__ + 2048 + j * 1024), 16, (ST) * 128, 2); \
+            __builtin_amdgcn_global_load_lds((gptr_t)pg[j], (lptr_t)(dst__ + j * 1024), 16, (ST) * 128, 2);        \
+            __builtin_amdgcn_global_load_lds((gptr_t)pu[j], (lptr_t)(dst__ + 2048 + j * 1024), 16, (ST) * 128, 2); \
         }                                                                                                                \
         islot = (islot + 1 == R) ? 0 : islot + 1;                                                                        \
     } while (0)
 #define G8_ISSUE_ST(ST) do { switch (ST) { case 0: G8_ISSUE(0); break; case 1: G8_ISSUE(1); break; case 2: G8_ISSUE(2); break; default: G8_ISSUE(3); break; } } while (0)
 #define G8_NEXT_PAIR() do { _Pragma("unroll") for (int j = 0; j < 2; ++j) { pg[j] += pair_step; pu[j] += pair_step; } } while (0)
-    // ---- block-quantised activation fragments of this wave's k-slice (once per block).  Round 3 (same finding as norm_glu_lds_kernel in gemm.hip:
+    // ---- block-quantised activation fragments of this wave's k-slice (once per block).  Round 3 (same finding as norm_glu_lds_kernel in gemm_skinny.hip:
     // 32 vector loads per lane in the MFMA operand layout = 64 L1 tag look-ups per KiB, in dependent batches, while only R-1 weight stages were in
     // flight): the wave's x slice (16 rows x 512 columns = NST stages of 16 rows x 256 bytes) and its norm-weight slice are copied by DMA - x into the
     // wave's own still empty ring (+ one 4 KiB stage behind the rings when R < NST), lnw into a private KiB - and read back from LDS; the weight
@@ -466,7 +447,7 @@ __global__ __launch_bounds__(NW * 64) void norm_glu_lds_f8_kernel(const bf16_t* 
     {
         int64_t col = kb + lane * 8;
         if (col + 8 > K) col = K - 8;
-        __builtin_amdgcn_global_load_lds((w8_gptr_t)(lnw + col), (w8_lptr_t)lnw_lds, 16, 0, 0);
+        __builtin_amdgcn_global_load_lds((gptr_t)(lnw + col), (lptr_t)lnw_lds, 16, 0, 0);
 #pragma unroll
         for (int st = 0; st < NST; ++st) {
             char* dst = st < R ? ring + st * STAGE : x_extra;
@@ -474,7 +455,7 @@ __global__ __launch_bounds__(NW * 64) void norm_glu_lds_f8_kernel(const bf16_t* 
             for (int i4 = 0; i4 < 4; ++i4) {                              // 4 rows x 256 bytes per instruction; row r keeps logical chunk c at c ^ r
                 const int r = 4 * i4 + (lane >> 4);
                 const bf16_t* src = X + (int64_t)(r < M ? r : M - 1) * ldx + kb + st * 128 + (((lane & 15) ^ r) << 3);
-                __builtin_amdgcn_global_load_lds((w8_gptr_t)src, (w8_lptr_t)(dst + i4 * 1024), 16, 0, 0);
+                __builtin_amdgcn_global_load_lds((gptr_t)src, (lptr_t)(dst + i4 * 1024), 16, 0, 0);
             }
         }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -541,7 +522,7 @@ __global__ __launch_bounds__(NW * 64) void norm_glu_lds_f8_kernel(const bf16_t* 
         rstd = rsqrtf(sq * (1.f / (float)K) + eps);
     }
     const int rd_off = u * 128;
-    const int kA = keyA8(u);
+    const int kA = keyA(u);
     int cslot = 0;
     for (int pi = 0; pi < npair; ++pi) {
         f32x4_t ag = {0.f, 0.f, 0.f, 0.f}, au = {0.f, 0.f, 0.f, 0.f};
@@ -587,7 +568,7 @@ __global__ __launch_bounds__(NW * 64) void norm_glu_lds_f8_kernel(const bf16_t* 
                 if (NW * 64 < 256) { float sq = 0.f; _Pragma("unroll") for (int w = 0; w < NW; ++w) sq += ssq[w * 16 + mm]; rs = rsqrtf(sq * (1.f / (float)K) + eps); }
                 v *= rs * wscale[n];
                 const float gt = bf2f(f2bf(v)), up = bf2f(f2bf(v2 * rs * wscale[up_off + n]));
-                C[(int64_t)mm * ldc + n] = f2bf(bf2f(f2bf(silu_w8(gt))) * up);
+                C[(int64_t)mm * ldc + n] = f2bf(bf2f(f2bf(silu_f32(gt))) * up);
             }
         }
     }
@@ -597,7 +578,7 @@ __global__ __launch_bounds__(NW * 64) void norm_glu_lds_f8_kernel(const bf16_t* 
 }
 
 // ------------------------------------------------------------------------------- W8A8, LDS-streamed split-K + fixup projection (M <= 16)
-// The fp8 twin of gemm_skinny_lds_fix_kernel (gemm.hip; decode down projection: N = 3584 columns, K = 18944): a block owns 64 output columns
+// The fp8 twin of gemm_skinny_lds_fix_kernel (gemm_skinny.hip; decode down projection: N = 3584 columns, K = 18944): a block owns 64 output columns
 // and one of gridDim.y K-slabs; its waves take the slab's 128-wide stages round-robin, each with a two-slot ring: 64 weight rows x 128 bytes
 // of fp8 (8 KiB) + the 16 activation rows x 128 k of bf16 (2 x 16 x 128 bytes, quantised per lane pair right before the MFMA).  The partial
 // tiles go through the same workspace and ticket protocol (the last-arriving slab sums the tiles in slab order); the weight's row scale is
@@ -622,22 +603,22 @@ __global__ __launch_bounds__(WAVES * 64) void gemm_skinny_lds_fix_f8_kernel(cons
     for (int j = 0; j < NWI; ++j) {
         const int r = 8 * j + (lane >> 3);
         int64_t row = n0 + r; if (row >= N) row = N - 1;
-        pw[j] = W + row * ldw + k0 + (int64_t)wave * 128 + (((lane & 7) ^ keyA8(r)) << 4);
+        pw[j] = W + row * ldw + k0 + (int64_t)wave * 128 + (((lane & 7) ^ keyA(r)) << 4);
     }
 #pragma unroll
     for (int j = 0; j < 4; ++j) {            // activation stage = 32 "rows" of 128 bytes: row rho = h * 16 + m holds x[m][k + h*64 .. +64]
         const int rho = 8 * j + (lane >> 3), m = rho & 15, h = rho >> 4;
-        px[j] = X + (int64_t)(m < M ? m : M - 1) * ldx + k0 + (int64_t)wave * 128 + h * 64 + (((lane & 7) ^ keyA8(rho)) << 3);
+        px[j] = X + (int64_t)(m < M ? m : M - 1) * ldx + k0 + (int64_t)wave * 128 + h * 64 + (((lane & 7) ^ keyA(rho)) << 3);
     }
 #define SK8_ISSUE(SLOT) do {                                                                                              \
         char* dst__ = ring + (SLOT) * STAGE;                                                                              \
-        _Pragma("unroll") for (int j = 0; j < NWI; ++j) { __builtin_amdgcn_global_load_lds((w8_gptr_t)pw[j], (w8_lptr_t)(dst__ + j * 1024), 16, 0, 2); pw[j] += WAVES * 128; } \
-        _Pragma("unroll") for (int j = 0; j < 4; ++j) { __builtin_amdgcn_global_load_lds((w8_gptr_t)px[j], (w8_lptr_t)(dst__ + NWI * 1024 + j * 1024), 16, 0, 0); px[j] += WAVES * 128; } \
+        _Pragma("unroll") for (int j = 0; j < NWI; ++j) { __builtin_amdgcn_global_load_lds((gptr_t)pw[j], (lptr_t)(dst__ + j * 1024), 16, 0, 2); pw[j] += WAVES * 128; } \
+        _Pragma("unroll") for (int j = 0; j < 4; ++j) { __builtin_amdgcn_global_load_lds((gptr_t)px[j], (lptr_t)(dst__ + NWI * 1024 + j * 1024), 16, 0, 0); px[j] += WAVES * 128; } \
     } while (0)
     f32x4_t acc[NC];
 #pragma unroll
     for (int c = 0; c < NC; ++c) acc[c] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
-    const int rd_w = u * 128, kA = keyA8(u);
+    const int rd_w = u * 128, kA = keyA(u);
     const int partner = lane ^ 16, src_lane = u + 16 * (2 * (g & 1));
     auto consume = [&](int slot) {
         const char* sb = ring + slot * STAGE;
@@ -698,41 +679,15 @@ __global__ __launch_bounds__(WAVES * 64) void gemm_skinny_lds_fix_f8_kernel(cons
 #pragma unroll
         for (int r = 0; r < 4; ++r) red[((wave * NC + c) * 16 + u) * 17 + g * 4 + r] = acc[c][r];
     __syncthreads();
-    float* mine = fix_ws + ((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * TILE;
-    for (int i = threadIdx.x; i < TILE; i += WAVES * 64) {
-        const int c = i >> 8, mm = (i >> 4) & 15, nn = i & 15;
-        float v = 0.f;
-#pragma unroll
-        for (int w = 0; w < WAVES; ++w) v += red[((w * NC + c) * 16 + mm) * 17 + nn];
-        __hip_atomic_store(mine + i, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (threadIdx.x == 0) *s_ticket = __hip_atomic_fetch_add(&fix_cnt[blockIdx.x], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __syncthreads();
-    if (*s_ticket != (int)gridDim.y - 1) return;
-    for (int i = threadIdx.x; i < TILE; i += WAVES * 64) {
-        const int c = i >> 8, mm = (i >> 4) & 15, nn = i & 15;
+    SKINNY_SPLITK_FIXUP(TILE, WAVES * 64, 1, false, red[((w * NC + c) * 16 + mm) * 17 + nn], *s_ticket, , , return, {
         const int64_t n = n0 + c * 16 + nn;
-        float v = 0.f;
-        if (gridDim.y == 4) {       // unrolled: the four device-scope loads in flight together; same sum in the same order (see gemm_skinny_lds_fix_kernel)
-            float t[4];
-#pragma unroll
-            for (int ks = 0; ks < 4; ++ks)
-                t[ks] = __hip_atomic_load(fix_ws + ((int64_t)ks * gridDim.x + blockIdx.x) * TILE + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            v = ((t[0] + t[1]) + t[2]) + t[3];
-        } else {
-            for (int ks = 0; ks < (int)gridDim.y; ++ks)
-                v += __hip_atomic_load(fix_ws + ((int64_t)ks * gridDim.x + blockIdx.x) * TILE + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
         if (mm < M && n < N && c * 16 + nn < COLS) {
             v *= wscale[n];
             if (bias) v += bf2f(bias[n]);
             if (residual) v += bf2f(residual[(int64_t)mm * ldr + n]);
             C[(int64_t)mm * ldc + n] = f2bf(v);
         }
-    }
-    if (threadIdx.x == 0) fix_cnt[blockIdx.x] = 0;
+    });
 }
 
 // Per-row symmetric quantisation: scale[n] = amax_n / 448 (1 for an all-zero row), q = fp8_e4m3(w * (448 / amax_n)), round to nearest even.
@@ -772,17 +727,22 @@ extern "C" int tr1_quantize_fp8_rows(const void* w_bf16, int64_t ldw, void* q_fp
     TR1_LAUNCH_CHECK();
 }
 
-extern "C" int tr1_gemm_skinny_w8(const void* x, const void* lnw, const void* W_fp8, const void* wscale, const void* bias, const void* residual,
-                                  void* out, int64_t M, int64_t N, int64_t K, int64_t ldx, int64_t ldw, int64_t ldc, int64_t ldr, float eps,
-                                  int glu, void* stream) {
-    TR1_CHECK_ARG(K % 128 == 0 && K >= 128, "gemm_skinny_w8: K must be a positive multiple of 128");
-    TR1_CHECK_ARG(M >= 1 && M <= 64, "gemm_skinny_w8: 1 <= M <= 64 (decode rows)");
-    TR1_CHECK_ARG(N % 8 == 0 && ldx % 8 == 0 && ldw % 16 == 0 && ldc % 8 == 0 && (!residual || ldr % 8 == 0), "gemm_skinny_w8: N%8, ldx%8, ldw%16, ldc%8");
-    TR1_CHECK_ARG(!glu || (lnw && !bias && !residual), "gemm_skinny_w8: the GLU form is norm + gate/up only");
-    hipStream_t s = (hipStream_t)stream;
+// ---- launch of the two register-fragment families.  FAM::kernel<WAVES, UNROLL, NCOL, MG, NORM, GLU> is the W8A16 or the W8A8 kernel of one shape; the argument
+// checks (W8_CHECK_ARGS, the entry point's name in the messages) and the dispatch table (launch_skinny_w8) are written once for both.
+struct W8A16Family { template <int WV, int UN, int NC, int MGR, bool NRM, bool GL> static constexpr auto kernel = gemm_skinny_w8_kernel<WV, UN, NC, MGR, NRM, GL>; };
+struct W8A8Family { template <int WV, int UN, int NC, int MGR, bool NRM, bool GL> static constexpr auto kernel = gemm_skinny_w8a8_kernel<WV, UN, NC, MGR, NRM, GL>; };
+#define W8_CHECK_ARGS(NAME)                                                                                                                          \
+    TR1_CHECK_ARG(K % 128 == 0 && K >= 128, NAME ": K must be a positive multiple of 128");                                                          \
+    TR1_CHECK_ARG(M >= 1 && M <= 64, NAME ": 1 <= M <= 64 (decode rows)");                                                                           \
+    TR1_CHECK_ARG(N % 8 == 0 && ldx % 8 == 0 && ldw % 16 == 0 && ldc % 8 == 0 && (!residual || ldr % 8 == 0), NAME ": N%8, ldx%8, ldw%16, ldc%8");   \
+    TR1_CHECK_ARG(!glu || (lnw && !bias && !residual), NAME ": the GLU form is norm + gate/up only")
+
+template <class FAM>
+static void launch_skinny_w8(const void* x, const void* lnw, const void* W_fp8, const void* wscale, const void* bias, const void* residual, void* out, int64_t M,
+                             int64_t N, int64_t K, int64_t ldx, int64_t ldw, int64_t ldc, int64_t ldr, float eps, int glu, hipStream_t s) {
     const int mg = M <= 16 ? 1 : (M <= 32 ? 2 : 4);
 #define W8(WV, UN, NC, MGR, NRM, GL)                                                                                                       \
-    hipLaunchKernelGGL((gemm_skinny_w8_kernel<WV, UN, NC, MGR, NRM, GL>), dim3((unsigned)((N + (GL ? 8 * NC : 16 * NC) - 1) / (GL ? 8 * NC : 16 * NC))), \
+    hipLaunchKernelGGL((FAM::template kernel<WV, UN, NC, MGR, NRM, GL>), dim3((unsigned)((N + (GL ? 8 * NC : 16 * NC) - 1) / (GL ? 8 * NC : 16 * NC))), \
                        dim3(WV * 64), 0, s, (const bf16_t*)x, (const bf16_t*)lnw, (const unsigned char*)W_fp8, (const float*)wscale,       \
                        (bf16_t*)out, (const bf16_t*)bias, (const bf16_t*)residual, (int)M, N, K, ldx, ldw, ldc, ldr, eps, N)
 #define W8_MG(WV, UN, NC, NRM, GL)                                                         \
@@ -796,59 +756,47 @@ extern "C" int tr1_gemm_skinny_w8(const void* x, const void* lnw, const void* W_
     else W8_MG(4, 2, 1, false, false);
 #undef W8_MG
 #undef W8
+}
+
+extern "C" int tr1_gemm_skinny_w8(const void* x, const void* lnw, const void* W_fp8, const void* wscale, const void* bias, const void* residual,
+                                  void* out, int64_t M, int64_t N, int64_t K, int64_t ldx, int64_t ldw, int64_t ldc, int64_t ldr, float eps,
+                                  int glu, void* stream) {
+    W8_CHECK_ARGS("gemm_skinny_w8");
+    launch_skinny_w8<W8A16Family>(x, lnw, W_fp8, wscale, bias, residual, out, M, N, K, ldx, ldw, ldc, ldr, eps, glu, (hipStream_t)stream);
     TR1_LAUNCH_CHECK();
 }
 
-// W8A8: the same dispatch on the fp8-MFMA kernel (activations block-quantised to e4m3 in the operand load)
+// W8A8: the same dispatch on the fp8-MFMA kernel (activations block-quantised to e4m3 in the operand load), after the forms only W8A8 has
 extern "C" int tr1_gemm_skinny_w8a8(const void* x, const void* lnw, const void* W_fp8, const void* wscale, const void* bias, const void* residual,
                                   void* out, int64_t M, int64_t N, int64_t K, int64_t ldx, int64_t ldw, int64_t ldc, int64_t ldr, float eps,
                                   int glu, void* stream) {
-    TR1_CHECK_ARG(K % 128 == 0 && K >= 128, "gemm_skinny_w8a8: K must be a positive multiple of 128");
-    TR1_CHECK_ARG(M >= 1 && M <= 64, "gemm_skinny_w8a8: 1 <= M <= 64 (decode rows)");
-    TR1_CHECK_ARG(N % 8 == 0 && ldx % 8 == 0 && ldw % 16 == 0 && ldc % 8 == 0 && (!residual || ldr % 8 == 0), "gemm_skinny_w8a8: N%8, ldx%8, ldw%16, ldc%8");
-    TR1_CHECK_ARG(!glu || (lnw && !bias && !residual), "gemm_skinny_w8a8: the GLU form is norm + gate/up only");
+    W8_CHECK_ARGS("gemm_skinny_w8a8");
     hipStream_t s = (hipStream_t)stream;
-    const int mg = M <= 16 ? 1 : (M <= 32 ? 2 : 4);
-#define W8(WV, UN, NC, MGR, NRM, GL)                                                                                                       \
-    hipLaunchKernelGGL((gemm_skinny_w8a8_kernel<WV, UN, NC, MGR, NRM, GL>), dim3((unsigned)((N + (GL ? 8 * NC : 16 * NC) - 1) / (GL ? 8 * NC : 16 * NC))), \
-                       dim3(WV * 64), 0, s, (const bf16_t*)x, (const bf16_t*)lnw, (const unsigned char*)W_fp8, (const float*)wscale,       \
-                       (bf16_t*)out, (const bf16_t*)bias, (const bf16_t*)residual, (int)M, N, K, ldx, ldw, ldc, ldr, eps, N)
-#define W8_MG(WV, UN, NC, NRM, GL)                                                         \
-    do { if (mg == 1) W8(WV, UN, NC, 1, NRM, GL); else if (mg == 2) W8(WV, UN, NC, 2, NRM, GL); else W8(WV, 1, NC, 4, NRM, GL); } while (0)
-    {   // gate/up at <= 16 rows, hidden 3584 / 2048 / 1536: the LDS-streamed form
-        const int64_t nw = K / 512;
-        if (glu && M <= 16 && K % 512 == 0 && (nw == 7 || nw == 4 || nw == 3) && N % 16 == 0) {
-            constexpr int RING = 3;
-            const size_t dyn = (size_t)nw * RING * 4096 + (2 * nw * 2 * 16 * 17 + nw * 16) * sizeof(float) + (size_t)nw * (4096 + 1024);      // + one x stage and the norm-weight KiB per wave
-            constexpr int mx = 7 * RING * 4096 + (2 * 7 * 2 * 16 * 17 + 7 * 16) * (int)sizeof(float) + 7 * (4096 + 1024);      // the 7-wave form's: one limit for the three
-            const int64_t NP = N / 16, n_cu = tr1_cu_count();
-            const unsigned grid = (unsigned)(NP < n_cu ? NP : n_cu);
-            tr1_dispatch<7, 4, 3>((int)nw, [&](auto NW) {
-                tr1_launch<norm_glu_lds_f8_kernel<decltype(NW)::value, RING>>(dim3(grid), dim3(decltype(NW)::value * 64), dyn, mx, s, (const bf16_t*)x, (const bf16_t*)lnw,
-                                                                            (const unsigned char*)W_fp8, (const float*)wscale, (bf16_t*)out, (int)M, N, K, ldx, ldw, ldc, eps, N);
-            });
-            TR1_LAUNCH_CHECK();
-        }
+    if (glu && M <= 16 && skinny_lds_stream_k(K) && N % 16 == 0) {   // gate/up at <= 16 rows, hidden 3584 / 2048 / 1536: the LDS-streamed form, one wave per 512 k
+        constexpr int RING = 3;
+        const int64_t nw = K / 512, NP = N / 16, n_cu = tr1_cu_count();
+        const unsigned grid = (unsigned)(NP < n_cu ? NP : n_cu);
+        tr1_dispatch<7, 4, 3>((int)nw, [&](auto NW) {
+            tr1_launch<norm_glu_lds_f8_kernel<decltype(NW)::value, RING>>(dim3(grid), dim3(decltype(NW)::value * 64), norm_glu_lds_f8_bytes(decltype(NW)::value, RING),
+                                                                        (int)norm_glu_lds_f8_bytes(7, RING), s, (const bf16_t*)x, (const bf16_t*)lnw,
+                                                                        (const unsigned char*)W_fp8, (const float*)wscale, (bf16_t*)out, (int)M, N, K, ldx, ldw, ldc, eps, N);
+        });
+        TR1_LAUNCH_CHECK();
     }
-    // column groups per block: the activations are re-read from L2 by every block, and with fp8 weights they are as many bytes as a
-    // 2-group weight slab - 4 groups halve that traffic (measured, M = 16: lm_head 168 -> 140 us)
-    if (glu) { if (mg == 1) W8(4, 2, 4, 1, true, true); else if (mg == 2) W8(4, 2, 4, 2, true, true); else W8(4, 1, 2, 4, true, true); }
-    else if (lnw && N >= 100000) { if (mg == 1) W8(4, 2, 4, 1, true, false); else if (mg == 2) W8(4, 2, 4, 2, true, false); else W8(4, 1, 2, 4, true, false); }
-    else {
 // x image (32 bytes per k: 16 rows of bf16) + the norm weight, which arrives in whole 1 KiB DMA instructions (the last one may run past K * 2 bytes)
 #define W8X_LDS(K_) ((int64_t)(K_) * 32 + (((int64_t)(K_) * 2 + 1023) / 1024) * 1024)
-        const bool x_ok = mg == 1 && K < 8192 && K % 128 == 0 && W8X_LDS(K) <= 128 * 1024 && (int64_t)M * ldx * 2 < 0x7fffffffLL;
+    // <= 16 rows, K < 8192, neither gate/up nor the lm_head: x and the norm weight through LDS (XLDS), where the image fits
+    if (!glu && !(lnw && N >= 100000) && M <= 16 && K < 8192 && W8X_LDS(K) <= 128 * 1024 && (int64_t)M * ldx * 2 < 0x7fffffffLL) {
 #define W8X(NC, NRM)                                                                                                                             \
-            tr1_launch<gemm_skinny_w8a8_kernel<4, 2, NC, 1, NRM, false, true>>(dim3((unsigned)((N + 16 * NC - 1) / (16 * NC))), dim3(256), (size_t)W8X_LDS(K), 128 * 1024, s, \
-                               (const bf16_t*)x, (const bf16_t*)lnw, (const unsigned char*)W_fp8, (const float*)wscale, (bf16_t*)out, (const bf16_t*)bias,  \
-                               (const bf16_t*)residual, (int)M, N, K, ldx, ldw, ldc, ldr, eps, N)
-        if (lnw) { if (x_ok) W8X(2, true); else W8_MG(4, 2, 2, true, false); }
-        else if (K >= 8192) W8_MG(8, 2, 1, false, false);
-        else { if (x_ok) W8X(1, false); else W8_MG(4, 2, 1, false, false); }
+        tr1_launch<gemm_skinny_w8a8_kernel<4, 2, NC, 1, NRM, false, true>>(dim3((unsigned)((N + 16 * NC - 1) / (16 * NC))), dim3(256), (size_t)W8X_LDS(K), 128 * 1024, s, \
+                           (const bf16_t*)x, (const bf16_t*)lnw, (const unsigned char*)W_fp8, (const float*)wscale, (bf16_t*)out, (const bf16_t*)bias,  \
+                           (const bf16_t*)residual, (int)M, N, K, ldx, ldw, ldc, ldr, eps, N)
+        if (lnw) W8X(2, true); else W8X(1, false);
 #undef W8X
+        TR1_LAUNCH_CHECK();
     }
-#undef W8_MG
-#undef W8
+#undef W8X_LDS
+    launch_skinny_w8<W8A8Family>(x, lnw, W_fp8, wscale, bias, residual, out, M, N, K, ldx, ldw, ldc, ldr, eps, glu, s);
     TR1_LAUNCH_CHECK();
 }
 

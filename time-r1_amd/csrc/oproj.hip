@@ -12,15 +12,12 @@
 //     LDS in wave order, the residual is added, done: no ticket, no partial tiles in HBM.
 #include "tr1_common.h"
 
-typedef const __attribute__((address_space(1))) void* gptr_t;
-typedef __attribute__((address_space(3))) void* lptr_t;
-
 #define OPJ_WAVES 8
 #define OPJ_MAXS 7        // weight stages per wave of the o-projection forms: K <= 8 * 7 * 64 = 3584
 #define OPJ_MAXS_LONG 18  // round 6, the long-K form (<= 8 columns per block, 1 KiB stages, 16 rows): K <= 8 * 18 * 64 = 9216 (Qwen2-VL-2B down projection: 8960)
 
 namespace {
-TR1_DEV int opj_key(int row) { return (row >> 1) & 7; }      // chunk swizzle of a 128-byte stage row (keyA of gemm.hip)
+TR1_DEV int opj_key(int row) { return (row >> 1) & 7; }      // chunk swizzle of a 128-byte stage row (keyA of tr1_common.h)
 }
 
 // MAXS = weight stages per wave; NJ = 8-row DMA instructions (KiB) per stage: 2 -> up to 16 columns per block; 1 -> up to 8 columns (the MFMA's weight rows 8..15 then

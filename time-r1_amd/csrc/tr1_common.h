@@ -86,6 +86,14 @@ TR1_DEV float block_max(float v, float* red) {
     return t;
 }
 
+// ---- what every kernel with a DMA-staged 128-byte-row LDS image shares (GEMMs, decode projections) ----
+typedef const __attribute__((address_space(1))) void* gptr_t;      // operand types of __builtin_amdgcn_global_load_lds
+typedef __attribute__((address_space(3))) void* lptr_t;
+TR1_DEV int keyA(int row) { return (row >> 1) & 7; }               // row r keeps its logical 16-byte chunk c at position c ^ keyA(r): conflict-free 16-row fragment reads
+// raw s_barrier pinned against the scheduler (no vmcnt(0) / lgkmcnt(0) drain as __syncthreads has: DMA stays in flight across it)
+#define TR1_PIN() do { asm volatile("" ::: "memory"); __builtin_amdgcn_sched_barrier(0); } while (0)
+#define TR1_BARRIER() do { TR1_PIN(); __builtin_amdgcn_s_barrier(); TR1_PIN(); } while (0)
+
 // ---- LDS DMA (global -> LDS without a register round trip): each lane's 16 (tr1_dma16) / 4 (tr1_dma4) bytes at sbase + voff land at LDS byte address
 // lds_addr (wave-uniform, it travels in m0) + lane * 16 / 4.  The instructions are written in assembly: for the builtin, hipcc tracks the asynchronous LDS
 // write and puts an s_waitcnt vmcnt(0) in front of the next LDS read it cannot prove disjoint (all of them: one dynamic LDS array) - the "prefetch" then

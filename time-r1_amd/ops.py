@@ -300,11 +300,7 @@ class HipOps:
         assert q.dtype == torch.uint8 and q.shape[1] == K and x.stride(1) == 1 and q.stride(1) == 1 and scale.dtype == F32
         out = self.empty(M, N)
         if a8 and lnw is None and not glu and M <= 16 and K >= 8192 and K % 512 == 0 and N % 64 == 0:
-            n = int(self.L.raw("tr1_gemm_skinny_fixup_workspace_floats")(M, N, K))
-            key = "skinny_fix8_%d_%d_%d" % (M, N, K)
-            ws = self._ws.get(key)
-            if ws is None:
-                ws = self._ws[key] = torch.zeros(n, dtype=F32, device=self.device)
+            ws, n = self._skinny_fix_ws("skinny_fix8", M, N, K)
             self.L.call("tr1_gemm_skinny_fixup_w8a8", _p(x), _p(q), _p(scale), _p(out), _p(bias), _p(residual), M, N, K, x.stride(0), q.stride(0), N,
                         residual.stride(0) if residual is not None else 0, _p(ws), n, self._s())
             return out
@@ -363,17 +359,23 @@ class HipOps:
         self.L.call("tr1_gemm_oproj_frag", _p(xfrag), _p(w), _p(residual), _p(c), M, N, K, _ld(w), residual.stride(0) if residual is not None else 0, _ld(c), self._s())
         return c
 
+    def _skinny_fix_ws(self, prefix, M, N, K):
+        """(workspace, floats) of the split-K + fixup decode projections: fp32 tiles + ticket counters, zero-filled ONCE per (prefix, M, N, K) - the
+        kernels re-arm the counters, so the buffer persists across launches."""
+        n = int(self.L.raw("tr1_gemm_skinny_fixup_workspace_floats")(M, N, K))
+        key = "%s_%d_%d_%d" % (prefix, M, N, K)
+        ws = self._ws.get(key)
+        if ws is None:
+            ws = self._ws[key] = torch.zeros(n, dtype=F32, device=self.device)     # ticket counters start at zero
+        return ws, n
+
     def gemm_skinny_fixup(self, a, b, bias=None, residual=None):
         """Decode rows x narrow projection (o_proj / down_proj): split-K with in-kernel fixup; bf16 [M, N]."""
         self._chk(a, b, bias, residual)
         M, K = a.shape
         N = b.shape[0]
         assert a.stride(1) == 1 and b.stride(1) == 1 and b.shape[1] == K
-        n = int(self.L.raw("tr1_gemm_skinny_fixup_workspace_floats")(M, N, K))
-        key = "skinny_fix_%d_%d_%d" % (M, N, K)
-        ws = self._ws.get(key)
-        if ws is None:
-            ws = self._ws[key] = torch.zeros(n, dtype=F32, device=self.device)     # ticket counters start at zero
+        ws, n = self._skinny_fix_ws("skinny_fix", M, N, K)
         out = self.empty(M, N)
         self.L.call("tr1_gemm_skinny_fixup", _p(a), _p(b), _p(out), _p(bias), _p(residual), M, N, K, a.stride(0), b.stride(0), N,
                     residual.stride(0) if residual is not None else 0, _p(ws), n, self._s())

@@ -1,6 +1,7 @@
 // Block-timeline probe of the decode GEMM: when does each block start / finish its k loop / exit?  Build + run on the GPU box:
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -DTR1_PROBE -I time-r1_amd/csrc tools/probe_skinny.hip -o /tmp/probe && /tmp/probe
-#include "../time-r1_amd/csrc/gemm.hip"
+#include "../time-r1_amd/csrc/gemm_skinny.hip"      // the kernel under the probe (TR1_PROBE_AT)
+#include "../time-r1_amd/csrc/gemm.hip"             // tr1_gemm_nt_bf16, which routes M <= 64 to it
 #include <algorithm>
 #include <vector>
 
