@@ -322,6 +322,17 @@ int tr1_adamw_step(void* p_f32, void* m_f32, void* v_f32, void* g_f32, void* p_b
 /* Data-parallel forms: the all-reduced gradient is consumed from its bf16 wire buffer (no copy back into the fp32 accumulator, which is only
  * zeroed).  ref: DeepSpeed's bf16 gradient all-reduce + FusedAdam (scripts/zero3.json:13-33). */
 int tr1_adamw_step_g16(void* p_f32, void* m_f32, void* v_f32, void* g_f32, const void* g_bf16, void* p_bf16, int64_t n, float lr, float beta1, float beta2, float eps, float weight_decay, int64_t step, const void* sumsq_scalar, float max_norm, float grad_mult, int zero_grad, void* stream);
+/* AdamW with bf16 moments (GRPOConfig.optimizer_state_dtype = "bf16"): m and v are read as bf16 and widened exactly; coef, gg, m', v', denom and p' are
+ * tr1_adamw_step's expressions in fp32; p' and p_bf16 = bf16_rne(p') come from the UNROUNDED m', v' (the master update of a step is the fp32-state kernel's);
+ * then m', v' are stored rounded stochastically.  The chain sumsq -> coef -> gg -> m', v' runs without fma contraction, each operation rounded once:
+ * m' = b1*m + (1-b1)*gg, v' = b2*v + ((1-b2)*gg)*gg, coef = grad_mult * fminf(1, max_norm / (sqrtf(sumsq)*grad_mult + 1e-6f)) - a host fp32 emulation gives the
+ * same bits.  Rounding of fp32 bits b with a 16-bit r: mag = b & 0x7fffffff; mag >= 0x7f800000 (inf / NaN) -> nearest-even; else s = min(mag + r, 0x7f7fffff)
+ * and the result is ((b & 0x80000000) | s) >> 16.  Random bits of the GLOBAL element e = index_base + i: Philox4x32-10, key (seed & 0xffffffff, seed >> 32),
+ * counter ((e >> 2) & 0xffffffff, (e >> 2) >> 32, step & 0xffffffff, 0x53523136), output word e & 3: its low 16 bits round m, its high 16 bits v.  index_base
+ * (>= 0, any value) is the offset of element 0 in the whole arena: splitting a range into several calls or sharding it over ranks changes no bit.
+ * g_bf16 (nullable): the gradient is read from this bf16 array (the wire buffer) and g_f32 is only zeroed.  Never synchronises; n == 0 is a no-op; step >= 1;
+ * views may start at any element. */
+int tr1_adamw_step_sr16(void* p_f32, void* m_bf16, void* v_bf16, void* g_f32, const void* g_bf16, void* p_bf16, int64_t n, float lr, float beta1, float beta2, float eps, float weight_decay, int64_t step, const void* sumsq_scalar, float max_norm, float grad_mult, int zero_grad, uint64_t seed, int64_t index_base, void* stream);
 /* Gradient norm without re-reading the large gradient matrices (ref: torch.nn.utils.clip_grad_norm_ inside HF Trainer.training_step, TF trainer.py:1785 /
  * DeepSpeed gradient_clipping, scripts/zero3.json:35).  tr1_wgrad_f32_sumsq is the weight-gradient GEMM (NT or K-major B form, bit-identical C) whose epilogue
  * also leaves one sum of squares per wave of what it stored - in the LAST micro-step of an accumulation window that is the final gradient; *n_partials (HOST)

@@ -2,6 +2,7 @@
 // Replaces DeepSpeed's FusedAdam / DeepSpeedCPUAdam on the reference path (scripts/zero3.json:13-21, zero3_offload.json:24-31);
 // update rule = torch.optim.AdamW (decoupled weight decay, bias correction), HF defaults lr/betas/eps, max_grad_norm 1.0.
 // HBM-bound: 16 B read (g, p, m, v) + 14 B written (p, m, v, bf16 copy) [+4 B when the gradient is zeroed in place] per parameter.
+// With bf16 moments (tr1_adamw_step_sr16, stochastic rounding): 12 B read + 10 B written.
 #include "tr1_common.h"
 
 // every array is streamed exactly once per step (258 GB for the 7B arena): nt loads/stores keep it from turning over L2 / the memory-side cache
@@ -124,6 +125,124 @@ extern "C" int tr1_adamw_step_g16(void* p_f32, void* m_f32, void* v_f32, void* g
     hipLaunchKernelGGL(adamw_kernel<true>, dim3(tr1_grid_1d(n / 4 + 1, 256, 4096)), dim3(256), 0, (hipStream_t)stream, (float*)p_f32, (float*)m_f32,
                        (float*)v_f32, (float*)g_f32, (bf16_t*)p_bf16, n, lr, beta1, beta2, eps, weight_decay, bc1, bc2_sqrt,
                        (const float*)sumsq_scalar, max_norm, grad_mult, zero_grad, (const bf16_t*)g_bf16);
+    TR1_LAUNCH_CHECK();
+}
+
+// ---- AdamW with bf16 moments (GRPOConfig.optimizer_state_dtype="bf16"): m and v are stored in bf16, rounded STOCHASTICALLY (nearest-even freezes them: at beta2 =
+// 0.999 a decaying v = 1.0 rounds back to 1.0 for ever).  HBM: 12 B read (g, p, m16, v16) + 10 B written (p, m16, v16, bf16 copy) [+4 B zeroing] per parameter.
+// The master update of a step is the fp32-state kernel's from the same inputs: p' and p16 come from the UNROUNDED fp32 m', v'; only what is stored is rounded.
+// Rounding of fp32 bits b with 16 random bits r: s = min((b & 0x7fffffff) + r, 0x7f7fffff), result = sign | s, upper half.  A value bf16 holds is unchanged, zero
+// stays zero, v stays >= 0, a finite value stays finite, and the mean over r is the value.  inf / NaN take the nearest-even conversion.
+TR1_DEV unsigned bf_sr(float f, unsigned r16) {
+    const unsigned b = __float_as_uint(f), mag = b & 0x7fffffffu;
+    const unsigned s = min(mag + r16, 0x7f7fffffu);
+    return mag >= 0x7f800000u ? (unsigned)f2bf(f) : ((b & 0x80000000u) | s) >> 16;      // a select, not a branch: the conversion has no side effect
+}
+// sumsq -> coef -> gg -> m', v' with every operation rounded once (no fma contraction), so a host fp32 emulation reproduces the stored moments bit for bit:
+// the random bits decide at a fixed threshold, and one ulp of fp32 moves a value across it.
+TR1_DEV float sr16_coef(const float* __restrict__ sumsq, float max_norm, float grad_mult) {
+#pragma clang fp contract(off)
+    if (!(sumsq && max_norm > 0.f)) return grad_mult;
+    const float norm = sqrtf(*sumsq) * grad_mult;
+    const float den = norm + 1e-6f;
+    return grad_mult * fminf(1.f, max_norm / den);
+}
+TR1_DEV void sr16_moments(float g, float coef, float beta1, float beta2, float m, float v, float& mn, float& vn) {
+#pragma clang fp contract(off)
+    const float gg = g * coef;
+    const float m1 = beta1 * m, m2 = (1.f - beta1) * gg;
+    mn = m1 + m2;
+    const float v1 = beta2 * v, v2 = (1.f - beta2) * gg, v3 = v2 * gg;
+    vn = v1 + v3;
+}
+#define SR16_STREAM 0x53523136u     // "SR16": the last Philox counter word (the sampler's is 0)
+#define SR16_GRID_CAP 4096          // blocks of 256 lanes x 8 elements: one grid trip covers 2^23 elements (7B arena: 30.6 / 29.8 / 29.5 ms at 1024 / 2048 / 4096)
+// Random bits of the GLOBAL element e = index_base + i: Philox block e / 4, word e % 4; its low half rounds m, its high half v.  A lane's 8 elements lie in 2
+// blocks when index_base is a multiple of 4 and in 3 otherwise: SH = index_base % 4 is a template argument, so the words are picked without indexed registers.
+template <bool G16, int SH>
+__global__ __launch_bounds__(256) void adamw_sr16_kernel(float* __restrict__ p, bf16_t* __restrict__ m, bf16_t* __restrict__ v, float* __restrict__ g,
+                                                         bf16_t* __restrict__ p16, int64_t n, float lr, float beta1, float beta2, float eps, float wd, float bc1,
+                                                         float bc2_sqrt, const float* __restrict__ sumsq, float max_norm, float grad_mult, int zero_grad,
+                                                         const bf16_t* __restrict__ g16, uint64_t seed, uint64_t index_base, unsigned step_lo) {
+    const float coef = sr16_coef(sumsq, max_norm, grad_mult);
+    const unsigned k0 = (unsigned)(seed & 0xffffffffu), k1 = (unsigned)(seed >> 32);
+    const int64_t n8 = n >> 3;
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n8; i += (int64_t)gridDim.x * blockDim.x) {
+        f32x4_t pv[2] = {OPT_LD(reinterpret_cast<f32x4_t*>(p) + 2 * i), OPT_LD(reinterpret_cast<f32x4_t*>(p) + 2 * i + 1)};
+        const u32x4_t mw = OPT_LD(reinterpret_cast<u32x4_t*>(m) + i), vw = OPT_LD(reinterpret_cast<u32x4_t*>(v) + i);
+        f32x4_t gv[2];
+        if (G16) {
+            const u32x4_t w = OPT_LD(reinterpret_cast<const u32x4_t*>(g16) + i);
+            gv[0] = (f32x4_t){bflo(w[0]), bfhi(w[0]), bflo(w[1]), bfhi(w[1])}; gv[1] = (f32x4_t){bflo(w[2]), bfhi(w[2]), bflo(w[3]), bfhi(w[3])};
+        } else { gv[0] = OPT_LD(reinterpret_cast<f32x4_t*>(g) + 2 * i); gv[1] = OPT_LD(reinterpret_cast<f32x4_t*>(g) + 2 * i + 1); }
+        constexpr int NB = SH ? 3 : 2;
+        unsigned R[4 * NB];
+        const uint64_t q = (index_base + 8 * (uint64_t)i) >> 2;
+#pragma unroll
+        for (int b = 0; b < NB; ++b) {
+            unsigned c[4] = {(unsigned)((q + b) & 0xffffffffu), (unsigned)((q + b) >> 32), step_lo, SR16_STREAM};
+            philox4x32_10(c, k0, k1);
+            R[4 * b] = c[0]; R[4 * b + 1] = c[1]; R[4 * b + 2] = c[2]; R[4 * b + 3] = c[3];
+        }
+        unsigned mh[8], vh[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const float m0 = (j & 1) ? bfhi(mw[j >> 1]) : bflo(mw[j >> 1]), v0 = (j & 1) ? bfhi(vw[j >> 1]) : bflo(vw[j >> 1]);
+            float mn, vn;
+            sr16_moments(gv[j >> 2][j & 3], coef, beta1, beta2, m0, v0, mn, vn);
+            float pj = pv[j >> 2][j & 3];
+            pj *= (1.f - lr * wd);
+            const float denom = sqrtf(vn) / bc2_sqrt + eps;
+            pj -= (lr / bc1) * (mn / denom);
+            pv[j >> 2][j & 3] = pj;
+            const unsigned r = R[SH + j];
+            mh[j] = bf_sr(mn, r & 0xffffu); vh[j] = bf_sr(vn, r >> 16);
+        }
+        OPT_ST(pv[0], reinterpret_cast<f32x4_t*>(p) + 2 * i); OPT_ST(pv[1], reinterpret_cast<f32x4_t*>(p) + 2 * i + 1);
+        const u32x4_t mo = {mh[0] | (mh[1] << 16), mh[2] | (mh[3] << 16), mh[4] | (mh[5] << 16), mh[6] | (mh[7] << 16)};
+        const u32x4_t vo = {vh[0] | (vh[1] << 16), vh[2] | (vh[3] << 16), vh[4] | (vh[5] << 16), vh[6] | (vh[7] << 16)};
+        OPT_ST(mo, reinterpret_cast<u32x4_t*>(m) + i); OPT_ST(vo, reinterpret_cast<u32x4_t*>(v) + i);
+        const u32x4_t w = {pack2bf(pv[0][0], pv[0][1]), pack2bf(pv[0][2], pv[0][3]), pack2bf(pv[1][0], pv[1][1]), pack2bf(pv[1][2], pv[1][3])};
+        OPT_ST(w, reinterpret_cast<u32x4_t*>(p16) + i);
+        if (zero_grad) {
+            OPT_ST(((f32x4_t){0.f, 0.f, 0.f, 0.f}), reinterpret_cast<f32x4_t*>(g) + 2 * i); OPT_ST(((f32x4_t){0.f, 0.f, 0.f, 0.f}), reinterpret_cast<f32x4_t*>(g) + 2 * i + 1);
+        }
+    }
+    if (blockIdx.x == 0) {
+        for (int64_t i = n8 * 8 + threadIdx.x; i < n; i += blockDim.x) {
+            float mn, vn;
+            sr16_moments(G16 ? bf2f(g16[i]) : g[i], coef, beta1, beta2, bf2f(m[i]), bf2f(v[i]), mn, vn);
+            float pj = p[i] * (1.f - lr * wd);
+            pj -= (lr / bc1) * (mn / (sqrtf(vn) / bc2_sqrt + eps));
+            const uint64_t e = index_base + (uint64_t)i;
+            unsigned c[4] = {(unsigned)((e >> 2) & 0xffffffffu), (unsigned)(e >> 34), step_lo, SR16_STREAM};
+            philox4x32_10(c, k0, k1);
+            const unsigned w = (unsigned)(e & 3), r = w == 0 ? c[0] : w == 1 ? c[1] : w == 2 ? c[2] : c[3];
+            p[i] = pj; m[i] = (bf16_t)bf_sr(mn, r & 0xffffu); v[i] = (bf16_t)bf_sr(vn, r >> 16); p16[i] = f2bf(pj);
+            if (zero_grad) g[i] = 0.f;
+        }
+    }
+}
+
+// bf16 moments, stochastic rounding keyed by (seed, step, index_base + i): index_base is the offset of element 0 in the whole arena, so a range split into several
+// calls or sharded over ranks gets the same bits.  g_bf16 (nullable): the wire-buffer form, g_f32 is then only zeroed.
+extern "C" int tr1_adamw_step_sr16(void* p_f32, void* m_bf16, void* v_bf16, void* g_f32, const void* g_bf16, void* p_bf16, int64_t n, float lr, float beta1,
+                                   float beta2, float eps, float weight_decay, int64_t step, const void* sumsq_scalar, float max_norm, float grad_mult,
+                                   int zero_grad, uint64_t seed, int64_t index_base, void* stream) {
+    TR1_CHECK_ARG(step >= 1 && index_base >= 0 && n >= 0, "adamw_sr16: step counts from 1, index_base and n are not negative");
+    if (n == 0) return 0;
+    const float bc1 = (float)(1.0 - pow((double)beta1, (double)step));
+    const float bc2_sqrt = (float)sqrt(1.0 - pow((double)beta2, (double)step));
+    const dim3 grid(tr1_grid_1d(n / 8 + 1, 256, SR16_GRID_CAP));
+    tr1_dispatch<0, 1, 2, 3>((int)(index_base & 3), [&](auto sh) {
+        constexpr int SH = decltype(sh)::value;
+        auto go = [&](auto kernel) {
+            hipLaunchKernelGGL(kernel, grid, dim3(256), 0, (hipStream_t)stream, (float*)p_f32, (bf16_t*)m_bf16, (bf16_t*)v_bf16, (float*)g_f32, (bf16_t*)p_bf16, n, lr,
+                               beta1, beta2, eps, weight_decay, bc1, bc2_sqrt, (const float*)sumsq_scalar, max_norm, grad_mult, zero_grad, (const bf16_t*)g_bf16,
+                               seed, (uint64_t)index_base, (unsigned)((uint64_t)step & 0xffffffffu));
+        };
+        if (g_bf16) go(adamw_sr16_kernel<true, SH>); else go(adamw_sr16_kernel<false, SH>);
+    });
     TR1_LAUNCH_CHECK();
 }
 

@@ -9,17 +9,6 @@
 // value kept, as HF's TopKLogitsWarper does); softmax over the kept set; inverse-CDF draw in vocabulary order with a
 // Philox4x32-10 uniform keyed by (seed, row, step).  top_k <= 0 disables the filter.
 // ---------------------------------------------------------------------------------------------------------------------
-TR1_DEV unsigned mulhi32(unsigned a, unsigned b) { return __umulhi(a, b); }
-TR1_DEV void philox4x32_10(unsigned c[4], unsigned k0, unsigned k1) {
-#pragma unroll
-    for (int i = 0; i < 10; ++i) {
-        const unsigned h0 = mulhi32(0xD2511F53u, c[0]), l0 = 0xD2511F53u * c[0];
-        const unsigned h1 = mulhi32(0xCD9E8D57u, c[2]), l1 = 0xCD9E8D57u * c[2];
-        const unsigned n0 = h1 ^ c[1] ^ k0, n1 = l1, n2 = h0 ^ c[3] ^ k1, n3 = l0;
-        c[0] = n0; c[1] = n1; c[2] = n2; c[3] = n3;
-        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-    }
-}
 // 16-bit order-preserving key of a bf16 logit (temperature > 0 does not change the order, so top-k is selected on raw logits)
 TR1_DEV unsigned bfkey(bf16_t b) { return (b & 0x8000u) ? ((~(unsigned)b) & 0xffffu) : ((unsigned)b | 0x8000u); }
 // +0.0 and -0.0 compare equal as floats, so a k-th value of +0.0 ties with every -0.0 (HF's warper keeps both); -0.0 holds the next lower key

@@ -86,6 +86,19 @@ TR1_DEV float block_max(float v, float* red) {
     return t;
 }
 
+// ---- Philox4x32-10 (Salmon et al. 2011): the one counter-based generator of the library.  The sampler keys it by (seed; row, step, 0, 0), the bf16-moment AdamW by
+// (seed; element / 4 low, element / 4 high, step, 0x53523136): the last counter word keeps the two streams apart.
+TR1_DEV void philox4x32_10(unsigned c[4], unsigned k0, unsigned k1) {
+#pragma unroll
+    for (int i = 0; i < 10; ++i) {
+        const unsigned long long p0 = 0xD2511F53ull * c[0], p1 = 0xCD9E8D57ull * c[2];      // one 32 x 32 -> 64 multiply each (v_mad_u64_u32), not a high and a low one
+        const unsigned h0 = (unsigned)(p0 >> 32), l0 = (unsigned)p0, h1 = (unsigned)(p1 >> 32), l1 = (unsigned)p1;
+        const unsigned n0 = h1 ^ c[1] ^ k0, n1 = l1, n2 = h0 ^ c[3] ^ k1, n3 = l0;
+        c[0] = n0; c[1] = n1; c[2] = n2; c[3] = n3;
+        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+    }
+}
+
 // ---- what every kernel with a DMA-staged 128-byte-row LDS image shares (GEMMs, decode projections) ----
 typedef const __attribute__((address_space(1))) void* gptr_t;      // operand types of __builtin_amdgcn_global_load_lds
 typedef __attribute__((address_space(3))) void* lptr_t;

@@ -978,3 +978,15 @@ class HipOps:
             return
         self.L.call("tr1_adamw_step", _p(p32), _p(m), _p(v), _p(g), _p(p16), n, float(lr), float(beta1), float(beta2), float(eps),
                     float(weight_decay), int(step), _p(sumsq), float(max_norm), float(grad_mult), int(zero_grad), self._s())
+
+    def adamw_step_sr16(self, p32, m16, v16, g, p16, lr, beta1, beta2, eps, weight_decay, step, seed, index_base, sumsq=None, max_norm=0.0, grad_mult=1.0,
+                        zero_grad=True, g16=None):
+        """adamw_step with bf16 moments rounded stochastically (GRPOConfig.optimizer_state_dtype="bf16").  The random bits are a function of (seed, step,
+        index_base + i): index_base is the offset of element 0 in the whole arena, so slices and shards of one arena get the bits of the whole."""
+        assert p32.dtype == F32 and m16.dtype == BF16 and v16.dtype == BF16 and g.dtype == F32 and p16.dtype == BF16
+        n = p32.numel()
+        assert m16.numel() == n and v16.numel() == n and g.numel() == n and p16.numel() == n
+        assert g16 is None or (g16.dtype == BF16 and g16.numel() == n)
+        assert int(index_base) >= 0 and 0 <= int(seed) < (1 << 64)
+        self.L.call("tr1_adamw_step_sr16", _p(p32), _p(m16), _p(v16), _p(g), _p(g16), _p(p16), n, float(lr), float(beta1), float(beta2), float(eps),
+                    float(weight_decay), int(step), _p(sumsq), float(max_norm), float(grad_mult), int(zero_grad), int(seed), int(index_base), self._s())

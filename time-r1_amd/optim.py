@@ -10,8 +10,17 @@ from .dist import DataParallel, GradSync, ShardSync
 
 class AdamWFlat:
     def __init__(self, params, ops, lr=1e-6, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, max_grad_norm=1.0, dp: DataParallel = None,
-                 grad_wire_dtype=torch.bfloat16, shard_optimizer=False):
+                 grad_wire_dtype=torch.bfloat16, shard_optimizer=False, state_dtype=None, seed=0):
         self.params, self.ops = params, ops
+        # dtype of the moments m / v: None keeps what the arena has, a value converts it (Arena.set_moment_dtype).  bf16 moments are rounded STOCHASTICALLY by
+        # adamw_step_sr16, the random bits a function of (seed, step, global arena index): the same run gives the same bits, a resume continues bit for bit and
+        # the sharded optimizer equals the replicated one.  `seed` must be the same on every rank (the replicated optimizer updates the whole arena on each).
+        if state_dtype is not None:
+            params.train.set_moment_dtype(state_dtype)
+        self.state_dtype, self.seed = params.train.moment_dtype, int(seed) & 0xFFFFFFFFFFFFFFFF
+        self.sr16 = self.state_dtype == torch.bfloat16
+        if self.sr16 and not hasattr(ops, "adamw_step_sr16"):
+            raise NotImplementedError("bf16 optimizer state: the %s op backend has no adamw_step_sr16" % type(ops).__name__)
         self.lr, self.betas, self.eps, self.weight_decay, self.max_grad_norm = lr, betas, eps, weight_decay, max_grad_norm
         self.step_count = 0
         self.dp = dp or DataParallel()
@@ -96,6 +105,13 @@ class AdamWFlat:
             small.append((pos, lz["stride"]))
         return spans, small
 
+    def _adamw(self, index_base, p32, m, v, g, p16, lr, **kw):
+        """The one fused AdamW launch on a slice that starts at element `index_base` of the whole arena: fp32 moments -> adamw_step, bf16 -> adamw_step_sr16."""
+        if self.sr16:
+            self.ops.adamw_step_sr16(p32, m, v, g, p16, lr, self.betas[0], self.betas[1], self.eps, self.weight_decay, self.step_count, self.seed, index_base, **kw)
+        else:
+            self.ops.adamw_step(p32, m, v, g, p16, lr, self.betas[0], self.betas[1], self.eps, self.weight_decay, self.step_count, **kw)
+
     def step(self, lr=None):
         """Averages grads across ranks, clips by global norm, applies AdamW, refreshes the bf16 working weights, zeroes grads.
         Returns the (pre-clip) gradient norm as a device scalar (no host sync)."""
@@ -120,8 +136,8 @@ class AdamWFlat:
         spans, small = self._zero_spans(a.numel)
         for x, y, z in spans:
             kw = {} if g16 is None else {"g16": g16[x:y]}
-            self.ops.adamw_step(a.master[x:y], a.m[x:y], a.v[x:y], a.grad[x:y], a.w16[x:y], self.lr if lr is None else lr, self.betas[0], self.betas[1], self.eps,
-                                self.weight_decay, self.step_count, sumsq=self._sumsq, max_norm=self.max_grad_norm, grad_mult=mult, zero_grad=z, **kw)
+            self._adamw(x, a.master[x:y], a.m[x:y], a.v[x:y], a.grad[x:y], a.w16[x:y], self.lr if lr is None else lr, sumsq=self._sumsq,
+                        max_norm=self.max_grad_norm, grad_mult=mult, zero_grad=z, **kw)
         if small:
             lz = self._lz()
             self.ops.zero_ranges_periodic(a.grad, lz["base"], lz["stride"], lz["count"], small)
@@ -148,9 +164,8 @@ class AdamWFlat:
             self._send = torch.empty(a.numel // W, dtype=a.w16.dtype, device=a.w16.device)       # output: no aliasing between send and receive views
         for (_, sa, sb), (ca, cb, la) in zip(a.segments, a.chunks()):
             n = cb - ca
-            ops.adamw_step(a.master[la:la + n], a.m[la:la + n], a.v[la:la + n], g[la:la + n], self._send[la:la + n], self.lr if lr is None else lr,
-                           self.betas[0], self.betas[1], self.eps, self.weight_decay, self.step_count, sumsq=self._sumsq, max_norm=self.max_grad_norm,
-                           grad_mult=mult, zero_grad=False)
+            self._adamw(ca, a.master[la:la + n], a.m[la:la + n], a.v[la:la + n], g[la:la + n], self._send[la:la + n], self.lr if lr is None else lr,
+                        sumsq=self._sumsq, max_norm=self.max_grad_norm, grad_mult=mult, zero_grad=False)      # ca: the chunk's place in the WHOLE arena
             works.append(dist.all_gather_into_tensor(a.w16[sa:sb], self._send[la:la + n], async_op=True))
         spans, small = self._zero_spans(a.numel)      # the full fp32 accumulator (the fused kernel only sees the reduced shard)
         for x, y, z in spans:
@@ -164,6 +179,8 @@ class AdamWFlat:
         return self._sumsq.sqrt() * mult
 
     def state_dict(self):
+        """The moments are saved in their own dtype (bf16 moments: 4 B per parameter less).  load_state_dict accepts the other dtype: fp32 -> bf16 rounds to
+        nearest even once, bf16 -> fp32 is exact; only a resume in the SAME dtype (and, for bf16, with the same seed) continues bit for bit."""
         a = self.params.train
         return dict(step=self.step_count, master=a.master, m=a.m, v=a.v, shard=a.shard)
 

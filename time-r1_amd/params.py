@@ -1,7 +1,7 @@
 """Parameter arenas: every weight is a view into ONE flat buffer per role, so the optimizer, the gradient all-reduce and the
 reference-model snapshot are single large operations (MI355X: few, large HBM/xGMI transfers instead of thousands of small ones).
 
-  trainable arena : bf16 working weights + fp32 master / m / v / grad   (LLM + patch-merger; reference timer1_trainer.py:272-280)
+  trainable arena : bf16 working weights + fp32 master / grad + m / v in fp32 or bf16 (moment_dtype)   (LLM + patch-merger; reference timer1_trainer.py:272-280)
   frozen arena    : bf16 only (ViT patch-embed + blocks when fix_vit=True)
 With train_vit (fix_vit=False, reference timer1_trainer.py:267-288) the ViT specs are appended to the trainable arena after the merger and
 the frozen arena is empty; `ModelParams.vit` names whichever arena holds the tower.
@@ -66,8 +66,10 @@ def _specs_vit(cfg: ModelConfig):
 
 
 class Arena:
-    def __init__(self, ops, specs, with_optimizer_state, with_grad=None):
+    def __init__(self, ops, specs, with_optimizer_state, with_grad=None, moment_dtype=torch.float32):
+        assert moment_dtype in (torch.float32, torch.bfloat16), moment_dtype
         self.ops = ops
+        self.moment_dtype = moment_dtype     # dtype of the Adam moments m / v (bf16: AdamWFlat rounds them stochastically); master stays fp32
         self.specs = specs
         self.offsets = {}
         self.segments = []               # [(key, start, end)] contiguous, covering [0, numel); every boundary is a multiple of SEG_ALIGN
@@ -96,8 +98,8 @@ class Arena:
             self.grad = ops.zeros(off, dtype=torch.float32)
         if with_optimizer_state:
             self.master = ops.zeros(off, dtype=torch.float32)
-            self.m = ops.zeros(off, dtype=torch.float32)
-            self.v = ops.zeros(off, dtype=torch.float32)
+            self.m = ops.zeros(off, dtype=moment_dtype)
+            self.v = ops.zeros(off, dtype=moment_dtype)
 
     def view(self, flat, name):
         off, shape = self.offsets[name]
@@ -156,13 +158,33 @@ class Arena:
                 self.master = self.ops.zeros(n, dtype=torch.float32)
                 self.master.copy_(self.local_of(self.w16))
             else:
-                setattr(self, name, self.ops.zeros(n, dtype=torch.float32))
+                setattr(self, name, self.ops.zeros(n, dtype=self.moment_dtype))
             del full
+
+    def set_moment_dtype(self, dtype):
+        """Convert the Adam moments to `dtype` (fp32 -> bf16 rounds to nearest even once, bf16 -> fp32 is exact); nothing happens when it already matches or the
+        arena holds no optimizer state.  Moments that are all zero (a fresh optimizer) are released before the new ones are made, so the peak is not both."""
+        assert dtype in (torch.float32, torch.bfloat16), dtype
+        if dtype == self.moment_dtype:
+            return
+        self.moment_dtype = dtype
+        for name in ("m", "v"):
+            old = getattr(self, name)
+            if old is None:
+                continue
+            if not bool(old.any()):
+                n = old.numel()
+                setattr(self, name, None)
+                del old
+                setattr(self, name, self.ops.zeros(n, dtype=dtype))
+            else:
+                setattr(self, name, old.to(dtype))
 
     def clone_weights_only(self):
         """bf16-only snapshot (the frozen reference policy, reference timer1_trainer.py:295-307)."""
         a = Arena.__new__(Arena)
         a.ops, a.specs, a.offsets, a.numel, a.segments, a.shard = self.ops, self.specs, self.offsets, self.numel, self.segments, None
+        a.moment_dtype = self.moment_dtype
         a.w16 = self.w16.clone()
         a.version = 0                    # its own counter: bumped when the snapshot is rewritten (the trainer's sync_ref_model), like the source arena's
         a.grad = a.master = a.m = a.v = None
@@ -180,12 +202,12 @@ def arena_specs(cfg: ModelConfig, train_vit=False):
 class ModelParams:
     """Qwen2-VL parameters: `train` arena (LLM + merger, + ViT with train_vit) and `frozen` arena (ViT, empty with train_vit)."""
 
-    def __init__(self, cfg: ModelConfig, ops, seed=0, init="random", optimizer_state=True, train_vit=False):
+    def __init__(self, cfg: ModelConfig, ops, seed=0, init="random", optimizer_state=True, train_vit=False, moment_dtype=torch.float32):
         self.cfg = cfg
         self.ops = ops
         self.train_vit = bool(train_vit)
         trs, fzs = arena_specs(cfg, self.train_vit)
-        self.train = Arena(ops, trs, with_optimizer_state=optimizer_state, with_grad=True)
+        self.train = Arena(ops, trs, with_optimizer_state=optimizer_state, with_grad=True, moment_dtype=moment_dtype)
         self.frozen = Arena(ops, fzs, with_optimizer_state=False)
         if init == "random":
             self.init_random(seed)
@@ -201,7 +223,8 @@ class ModelParams:
         7B two copies do not fit one card: build the layout you need directly)."""
         if bool(train_vit) == self.train_vit:
             return self
-        out = ModelParams(self.cfg, self.ops, init="none", optimizer_state=self.train.master is not None, train_vit=train_vit)
+        out = ModelParams(self.cfg, self.ops, init="none", optimizer_state=self.train.master is not None, train_vit=train_vit,
+                          moment_dtype=self.train.moment_dtype)
         for src in (self.train, self.frozen):
             for name in src.names():
                 dst = out.train if name in out.train.offsets else out.frozen

@@ -486,6 +486,22 @@ def _(p32, m, v, g, p16, lr, beta1, beta2, eps, weight_decay, step, max_norm, gr
     return p32.new_empty(1)
 
 
+@_op("adamw_step_sr16", mutates_args=("p32", "m", "v", "g", "p16"))
+def adamw_step_sr16(p32: Tensor, m: Tensor, v: Tensor, g: Tensor, p16: Tensor, lr: float, beta1: float, beta2: float, eps: float, weight_decay: float, step: int,
+                    max_norm: float, grad_mult: float, seed: int, index_base: int) -> Tensor:
+    """adamw_step with bf16 moments m / v rounded stochastically; the random bits are keyed by (seed, step, index_base + element).  Returns the pre-clip norm."""
+    o = _ops(p32)
+    ss = torch.zeros(1, dtype=F32, device=p32.device)
+    o.sumsq_accum(g, ss)
+    o.adamw_step_sr16(p32, m, v, g, p16, lr, beta1, beta2, eps, weight_decay, step, seed, index_base, sumsq=ss, max_norm=max_norm, grad_mult=grad_mult, zero_grad=True)
+    return ss.sqrt() * grad_mult
+
+
+@adamw_step_sr16.register_fake
+def _(p32, m, v, g, p16, lr, beta1, beta2, eps, weight_decay, step, max_norm, grad_mult, seed, index_base):
+    return p32.new_empty(1)
+
+
 @_op("ref_mixup", mutates_args=("ref",))
 def ref_mixup(ref: Tensor, policy: Tensor, alpha: float) -> Tensor:
     """trl.GRPOConfig.sync_ref_model's update: ref = (1 - alpha) ref + alpha policy in place on flat bf16 weights (fp32 arithmetic, one rounding to bf16).
@@ -512,7 +528,7 @@ def _(frames_u8, out_h, out_w, k_pad):
 
 OP_NAMES = ["rmsnorm_fwd", "rmsnorm_bwd", "swiglu_fwd", "swiglu_bwd", "linear_fwd", "linear_bwd", "rope_fwd", "mrope_table", "attn_fwd", "attn_bwd",
             "logp_entropy_fwd", "logp_bwd", "logp_entropy_bwd", "entropy_quantile_weight", "lmhead_logp_entropy", "grpo_loss", "grpo_loss_ratio", "grpo_policy_loss", "sample_tokens", "sample_tokens_filtered", "penalize_logits", "mark_seen_ids",
-            "mark_seen_drawn", "adamw_step", "ref_mixup", "video_preprocess"]
+            "mark_seen_drawn", "adamw_step", "adamw_step_sr16", "ref_mixup", "video_preprocess"]
 
 
 # ================================================================================================ dropping the ops into an HF model

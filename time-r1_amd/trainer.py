@@ -148,6 +148,8 @@ class GRPOConfig:
         self.ref_model_sync_steps = int(self.ref_model_sync_steps)
         if self.activation_recompute not in ("none", "mlp"):
             raise ValueError('activation_recompute must be "none" or "mlp", got %r' % (self.activation_recompute,))
+        if self.optimizer_state_dtype not in ("fp32", "bf16"):
+            raise ValueError('optimizer_state_dtype must be "fp32" or "bf16", got %r' % (self.optimizer_state_dtype,))
         if self.sync_ref_model and float(self.beta) == 0.0:
             raise ValueError("sync_ref_model needs a reference policy: beta = 0 keeps none")
         if self.sync_ref_model and self.ref_model_sync_steps % self.num_iterations != 0:
@@ -178,6 +180,10 @@ class GRPOConfig:
                                             # 29 704 B per row and layer); the backward rebuilds them layer by layer with the forward's own launches - one more gate/up GEMM
                                             # per layer, every gradient bit for bit the "none" run's.  This is what buys the memory the reference
                                             # gets from --gradient_checkpointing
+    optimizer_state_dtype: str = "fp32"     # "bf16": the Adam moments m / v are kept in bf16 and rounded stochastically (4 of the trainable arena's 18 B per parameter
+                                            # less: -30.6 GB at 7B, and 8 of the optimizer kernel's 30 B of traffic); the random bits are a function of (seed, optimizer
+                                            # step, parameter index), so a run repeats, a resume continues bit for bit and the sharded optimizer equals the replicated
+                                            # one.  Master weights, gradients and the update rule stay fp32; optimizer_rank*.pt then holds bf16 m / v
     prompt_type: str = "v1"
     fix_vit: bool = True
     stop_at_eos: bool = False               # the reference's GenerationConfig carries no eos_token_id (a6): always C tokens
@@ -350,7 +356,7 @@ def config_from_hf(hc, name="model"):
     return cfg
 
 
-def load_model_dir(path, ops, train_vit=False):
+def load_model_dir(path, ops, train_vit=False, moment_dtype=torch.float32):
     """HF checkpoint directory (config.json + *.safetensors) -> (ModelConfig, ModelParams); train_vit: the tower in the trainable arena."""
     from safetensors.torch import load_file
     cfg = config_from_hf(json.load(open(os.path.join(path, "config.json"))), name=os.path.basename(os.path.normpath(path)))
@@ -358,17 +364,17 @@ def load_model_dir(path, ops, train_vit=False):
     for f in sorted(os.listdir(path)):
         if f.endswith(".safetensors"):
             sd.update(load_file(os.path.join(path, f)))
-    params = ModelParams(cfg, ops, init="none", train_vit=train_vit)
+    params = ModelParams(cfg, ops, init="none", train_vit=train_vit, moment_dtype=moment_dtype)
     params.load_hf_state_dict(sd)
     return cfg, params
 
 
-def load_hf_module(model, ops, train_vit=False):
+def load_hf_module(model, ops, train_vit=False, moment_dtype=torch.float32):
     """A loaded transformers model (reference timer1_trainer.py:184-206, :244-262 accepts a `PreTrainedModel` instance as well as a path) ->
     (ModelConfig, ModelParams): its config and state dict are copied into the engine's arenas; the module itself is not kept."""
     hc = model.config.to_dict()
     cfg = config_from_hf(hc, name=str(getattr(model.config, "_name_or_path", "") or type(model).__name__).rstrip("/").split("/")[-1])
-    params = ModelParams(cfg, ops, init="none", train_vit=train_vit)
+    params = ModelParams(cfg, ops, init="none", train_vit=train_vit, moment_dtype=moment_dtype)
     params.load_hf_state_dict({k: v.detach() for k, v in model.state_dict().items()})
     return cfg, params
 
@@ -400,21 +406,24 @@ class TimeR1_Trainer:
         # merger all train (reference :267-288) - the tower's weights live in the trainable arena (ModelParams(train_vit=True)), so AdamW, the clipping
         # norm, the data-parallel exchange, the reference snapshot and the checkpoints cover them with the rest of the arena
         train_vit = not getattr(args, "fix_vit", True)
+        # the moments are allocated in their final dtype wherever this constructor builds the arena (fp32 moments never exist at 7B with "bf16"); a
+        # caller's ModelParams is converted in place by AdamWFlat(state_dtype=) below
+        mdt = torch.bfloat16 if getattr(args, "optimizer_state_dtype", "fp32") == "bf16" else torch.float32
         if isinstance(model, str):
             if model in PRESETS:
                 self.cfg = PRESETS[model]()
-                self.params = ModelParams(self.cfg, ops, seed=args.seed, train_vit=train_vit)
+                self.params = ModelParams(self.cfg, ops, seed=args.seed, train_vit=train_vit, moment_dtype=mdt)
             else:
-                self.cfg, self.params = load_model_dir(model, ops, train_vit=train_vit)
+                self.cfg, self.params = load_model_dir(model, ops, train_vit=train_vit, moment_dtype=mdt)
         elif isinstance(model, ModelParams):
             # a ModelParams of the other layout is copied by name into a new one (optimizer state included) while the caller's stays alive: two copies
             # of the model at once, which a 7B model does not fit on one card - there, pass a preset / checkpoint directory / ModelConfig, or build
             # ModelParams(train_vit=not fix_vit) yourself (no copy)
             self.cfg, self.params = model.cfg, model.relayout(train_vit)
         elif isinstance(model, ModelConfig):
-            self.cfg, self.params = model, ModelParams(model, ops, seed=args.seed, train_vit=train_vit)
+            self.cfg, self.params = model, ModelParams(model, ops, seed=args.seed, train_vit=train_vit, moment_dtype=mdt)
         elif hasattr(model, "state_dict") and hasattr(model, "config"):
-            self.cfg, self.params = load_hf_module(model, ops, train_vit=train_vit)      # a loaded transformers model, like the reference accepts
+            self.cfg, self.params = load_hf_module(model, ops, train_vit=train_vit, moment_dtype=mdt)      # a loaded transformers model, like the reference accepts
         else:
             raise TypeError("model must be a checkpoint path, a preset name, a ModelConfig, a ModelParams or a loaded transformers model")
         self.model = self.params
@@ -492,7 +501,7 @@ class TimeR1_Trainer:
         self.optimizer = AdamWFlat(self.params, ops, lr=args.learning_rate, betas=(args.adam_beta1, args.adam_beta2), eps=args.adam_epsilon,
                                    weight_decay=args.weight_decay, max_grad_norm=args.max_grad_norm, dp=self.dp,
                                    grad_wire_dtype=torch.bfloat16 if getattr(args, "grad_wire_dtype", "bf16") == "bf16" else torch.float32,
-                                   shard_optimizer=self._wants_shard(args, self.dp))
+                                   shard_optimizer=self._wants_shard(args, self.dp), state_dtype=mdt, seed=args.seed)
         # the decoder layers' large gradient matrices are overwritten by the first micro-step of every window: the optimizer does not zero them
         self.optimizer.lazy_zero = self.engine.lazy_zero_plan() if getattr(args, "lazy_grad_zero", True) else None
         self.engine.lazy_zero_active = self.optimizer.lazy_zero is not None
@@ -1164,6 +1173,7 @@ class TimeR1_Trainer:
                        "train_batch_size": self.args.per_device_train_batch_size}, open(os.path.join(d, "trainer_state.json"), "w"), indent=1)
         if not self.args.save_only_model:
             os.makedirs(d, exist_ok=True)
+            # (optimizer_state_dtype="bf16": m and v are saved as bf16, 4 B per parameter less; a checkpoint of the other dtype loads too - AdamWFlat.state_dict)
             sd = {k: (v.cpu() if torch.is_tensor(v) else v) for k, v in self.optimizer.state_dict().items()}
             sd["rollout_calls"] = self.core.roll.calls
             sd["micro"] = self._micro
