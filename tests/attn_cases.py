@@ -305,6 +305,9 @@ _SPECS = [
     ("long-causal", 128, 2, 2, lambda: masks_causal(448), {"v_kind": "offset"}),            # 7 key tiles
     ("long-prefix", 128, 4, 2, lambda: masks_prefix_shared(400, 3, 60), {}),                 # 6.25 prefix tiles + the groups: up to 9 tiles per row
     ("long-prefix-d64", 64, 6, 2, lambda: masks_prefix_shared(400, 2, 50), {"v_kind": "offset"}),
+    # head dim 120 in the kernels padded to 128 (d_real < D): attn_fwd_kernel<128>, attn_bwd_dq_kernel<128>, attn_bwd_dkdv_kernel<128, 8> (128 keys per block)
+    ("causal-33-d120", 120, 2, 2, lambda: masks_causal(33), {}),                              # 33 packed rows: QS == 1, the direct bf16 epilogue under d < d_real
+    ("prefix-d120", 120, 4, 2, lambda: masks_prefix_shared(70, 3, 20), {}),                   # 260 packed rows, 130 slots: QS = 5, 2 keys in the second key block
 ]
 CASE_NAMES = [s[0] for s in _SPECS]
 # split-KV / decode launches: name, head dim, n_heads, n_kv, masks, options (rot: where the 11-token family period starts - every case has two edge-weighted rows)
@@ -378,13 +381,15 @@ class Bwd:
 
 
 def dk_from_bf16_p(c):
-    """True where the dK kernel forms dS from the bf16-rounded P (attn_bwd_dkdv32_kernel: head dim 128)."""
+    """True where the dK kernel of an ordinary launch forms dS from the bf16-rounded P: attn_bwd_dkdv32_kernel, head dim exactly 128 (Q / dO within its
+    32-bit DMA range; past it the launch takes attn_bwd_dkdv_kernel<128, 8>, and ref_bwd is told so)."""
     return c.hd == 128
 
 
-def ref_bwd(c, o, lse, rope=None):
+def ref_bwd(c, o, lse, rope=None, dk_bf16_p=None):
     """fp64 flash backward OF THE INPUTS THE KERNEL IS GIVEN: bf16 q / k / v / O / dO and the fp32 lse (o: [T, nh hd], lse: [nh, T]; any dtype, used in fp64).
-    -> Bwd with dQ [T, nh hd], dK / dV [S, n_kv hd] and their bounds.  rope = (cos, sin) [T, hd / 2]: dQ / dK times the transposed rotation."""
+    -> Bwd with dQ [T, nh hd], dK / dV [S, n_kv hd] and their bounds.  rope = (cos, sin) [T, hd / 2]: dQ / dK times the transposed rotation.
+    dk_bf16_p: whether dK forms dS from the bf16 P - a property of the ROUTE the launch takes (None: dk_from_bf16_p(c), an ordinary launch of the case)."""
     q, k, v = _heads(c)
     T, S, nh, nkv, g, hd = c.T, c.S, c.nh, c.nkv, c.group, c.hd
     do = c.do.double().view(T, nh, hd).permute(1, 0, 2)
@@ -407,7 +412,7 @@ def ref_bwd(c, o, lse, rope=None):
     # head dim 128, dK only: attn_bwd_dkdv32_kernel hands P from its role-0 waves to its role-1 waves as the bf16 fragments of the dV product (the P exchange
     # buffer, make_p -> make_ds in csrc/attn_bwd.hip), so dS = bf16(bf16(P) (dP - delta)) = dS (1 + e1)(1 + e2), |e| <= u: the dS term counts twice.  The other
     # dK / dV kernels and every dQ kernel multiply the fp32 P.
-    n_ds = 2.0 if dk_from_bf16_p(c) else 1.0
+    n_ds = 2.0 if (dk_from_bf16_p(c) if dk_bf16_p is None else dk_bf16_p) else 1.0
     r.tol_dK = (1.05 * U * (n_ds * grp(c.scale * ds.abs().transpose(1, 2) @ q.abs()) + r.dK.abs()) + grp(c.scale * e.transpose(1, 2) @ q.abs())
                 + 2.0 ** -20 * mq)
     r.tol_dV = 1.05 * U * (grp(p.transpose(1, 2) @ do.abs()) + r.dV.abs()) + 2.0 ** -20 * mdo
@@ -561,7 +566,7 @@ def emulate_bwd(c, o, lse):
 def replay_bwd(c):
     """dkdv_qsplit and the qmeta tile skipping of the dK / dV kernels (csrc/attn_bwd.hip) -> (QS, (query tile, key block) visits skipped, visits made)."""
     d_pad = (c.hd + 31) // 32 * 32
-    kb = 192 if d_pad == 128 else 128 if d_pad == 64 else 64
+    kb = 192 if c.hd == 128 else 128 if d_pad in (64, 128) else 64       # by route: attn_bwd_dkdv32_kernel | the 8-wave attn_bwd_dkdv_kernel | its 4-wave form
     nR = c.T * c.group
     n_qtiles = (nR + 63) // 64
     kvblocks = ((c.S + kb - 1) // kb) * c.nkv

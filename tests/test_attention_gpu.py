@@ -95,10 +95,10 @@ def check_fwd(c, r, o, lse, what):
 
 
 # ------------------------------------------------------------------------------------------------------------ A. forward, single pass
-# attn_fwd_kernel<D, 2, 1> (V^T operand; head dims 32 / 64 / 80 / 128), attn_fwd32_kernel<8> (v_rows) and attn_fwd64_kernel (TR1_FWD64=1), each against fp64.
-# Worst share of the bound seen on MI355X over the 24 cases (tol_O | tol_lse):
+# attn_fwd_kernel<D, 2, 1> (V^T operand; head dims 32 / 64 / 80 / 120 / 128), attn_fwd32_kernel<8> (v_rows) and attn_fwd64_kernel (TR1_FWD64=1), each against fp64.
+# Worst share of the bound seen on MI355X over the 26 cases (tol_O | tol_lse):
 #   attn_fwd_kernel<32>    0.680 (clamped-d32)      | 0.023        attn_fwd_kernel<64>   0.705 (tile-edges-64-32) | 0.055 (long-prefix-d64)
-#   attn_fwd_kernel<96>    0.580 (causal-65)        | 0.027        attn_fwd_kernel<128>  0.733 (tile-edges-65-31) | 0.035
+#   attn_fwd_kernel<96>    0.580 (causal-65)        | 0.027        attn_fwd_kernel<128>  0.733 (tile-edges-65-31) | 0.035 (head dim 120, d_real < D: 0.709 | 0.027, prefix-d120)
 #   attn_fwd32_kernel<8>   0.789 (long-causal)      | 0.035        attn_fwd64_kernel     0.789 (long-causal)      | 0.035 (every figure equal to the 32-row kernel's)
 # The largest LSE error was 1.0e-5 (long-causal, rows with 60-nat scores): tol_lse is an fp32 worst case, the MFMA accumulation stays far inside it.
 @pytest.mark.parametrize("name", ac.CASE_NAMES)
@@ -239,11 +239,13 @@ def check_bwd(c, r, b, dq, dk, dv, what):
     return sh
 
 
-# tr1_attn_bwd: attn_bwd_dq_kernel + attn_bwd_dkdv_kernel in the 4-wave Q^T form (head dims 32, 80) and the 8-wave form (64), attn_bwd_dq32_kernel +
-# attn_bwd_dkdv32_kernel (128); QS == 1 (causal-1, causal-64) and QS > 1 with attn_bwd_reduce_kernel.
-# Worst share of the bound seen on MI355X over the 24 cases (tol_dQ | tol_dK | tol_dV):
+# tr1_attn_bwd: attn_bwd_dq_kernel<D> + attn_bwd_dkdv_kernel<D, 4> in the 4-wave Q^T form (head dims 32, 80) and <D, 8> in the 8-wave form (64, and 120 in
+# the kernels padded to 128: d_real < D), attn_bwd_dq32_kernel + attn_bwd_dkdv32_kernel (128); QS == 1 (causal-1, causal-64, causal-33-d120) and QS > 1 with
+# attn_bwd_reduce_kernel<false>.
+# Worst share of the bound seen on MI355X over the 26 cases (tol_dQ | tol_dK | tol_dV):
 #   head dim 32   0.784 (clamped-d32)      | 0.694 (clamped-d32) | 0.735 (causal-9)           head dim 64    0.769 (tile-edges-64-32) | 0.753 (gap-d64) | 0.638
 #   head dim 80   0.780 (segments)         | 0.751 (segments)    | 0.759 (causal-65)          head dim 128   0.872 (rows256-g2)       | 0.698 (rows257) | 0.828 (causal-64)
+#   head dim 120  0.850 (prefix-d120)      | 0.671 (prefix-d120) | 0.726 (prefix-d120)
 # (head dim 128 dK with the bf16-P term of attn_cases.ref_bwd; without it 1.04 / 0.95 / 0.92 on rows257 / rows256-g2 / causal-200.)
 @pytest.mark.parametrize("name", ac.CASE_NAMES)
 def test_backward(hip_ops, name):
@@ -253,6 +255,28 @@ def test_backward(hip_ops, name):
     pre, lo, hi = masks_dev(c)
     dq, dk, dv = hip_ops.attn_bwd(q, k, v, o, do, lse, pre, lo, hi, c.nh, c.nkv, c.S, c.hd, c.scale)
     check_bwd(c, r, b, dq, dk, dv, "bwd %s d%d" % (name, c.hd))
+    for t, h in ((q, c.q), (k, c.k), (v, c.v), (o, o16), (do, c.do)):
+        assert torch.equal(bits(t), bits(h)), "the backward wrote an input"
+
+
+# Head dim 128 with Q / dO past the 32-bit byte offsets of attn_bwd_dkdv32_kernel's LDS DMA (T * ld * 2 >= 2^32): q and dO are column views of one [T, ld] device
+# buffer of about 4.3 GB, of which only the two views are ever written or read.  The launch takes attn_delta_kernel + attn_bwd_dq32_kernel without its fused
+# prologue (K / V are ordinary) + attn_bwd_dkdv_kernel<128, 8> (64-bit addressing, fp32 P in the dK product: the dS sum of tol_dK counts ONCE) +
+# attn_bwd_reduce_kernel<false> (QS = 5).
+# Worst seen on MI355X: dQ 0.809, dK 0.670 (at the bound that counts the dS sum once), dV 0.755 of the bounds.
+def test_backward_q_and_dO_past_the_32_bit_dma_range(hip_ops):
+    c, r = ac.case("rows257"), ac.ref_fwd_of("rows257")
+    o16, lse32, (_, k, v, o, _, lse) = _bwd_inputs(c, r)
+    b = ac.ref_bwd(c, o16, lse32, dk_bf16_p=False)
+    qd = c.nh * c.hd
+    ld = -(-(1 << 32) // (2 * c.T * 8)) * 8                     # the smallest multiple of 8 with T * ld * 2 >= 2^32
+    assert c.T * ld * 2 >= 1 << 32 > c.T * (ld - 8) * 2 and ld >= 2 * qd
+    buf = torch.empty(c.T, ld, dtype=BF16, device=DEV)
+    q, do = buf[:, :qd], buf[:, qd:2 * qd]
+    q.copy_(c.q)
+    do.copy_(c.do)
+    dq, dk, dv = hip_ops.attn_bwd(q, k, v, o, do, lse, *masks_dev(c), c.nh, c.nkv, c.S, c.hd, c.scale)
+    check_bwd(c, r, b, dq, dk, dv, "bwd rows257 q / dO stride %d" % ld)
     for t, h in ((q, c.q), (k, c.k), (v, c.v), (o, o16), (do, c.do)):
         assert torch.equal(bits(t), bits(h)), "the backward wrote an input"
 

@@ -79,7 +79,7 @@ __global__ __launch_bounds__(256) void attn_delta_kernel(const bf16_t* __restric
     s += __shfl_xor(s, 1, 64);
     if (ok && sub == 0) {
         delta[(int64_t)h * T + t] = s;
-        // log2-scaled LSE for the DMA-staged dK/dV kernel (exp2 argument = s * scale_log2 - lse2); rows that saw no key carry +inf -> p = 0
+        // log2-scaled LSE for the 32x32x16 dQ and dK/dV kernels of head dim 128 (exp2 argument = s * scale_log2 - lse2); rows that saw no key carry +inf -> p = 0
         const float l0 = lse[(int64_t)h * T + t];
         lse2[(int64_t)h * T + t] = (l0 == NEG_INF) ? INFINITY : l0 * 1.4426950408889634f;
     }
@@ -267,7 +267,6 @@ struct RowMeta { float lse, dlt; int pre, lo, hi; };
 // TR (the 8-wave form): Q^T / dO^T fragments are read from the ROW-major tiles with ds_read_b64_tr_b16 (each 16-lane group reads a 4 x 16 block:
 // lane i supplies row i/4, columns 4(i%4)..+3, and receives column i of the block) - no transposed copies in LDS or in global memory, half
 // the staging traffic and registers, which pays for THREE query tiles in flight.
-
 // KT = 16-key tiles per wave.  <8, 1>: 8 waves x 16 keys; <4, 2>: 4 waves x 32 keys - every Q / dO / Q^T / dO^T fragment read from LDS then
 // feeds two MFMAs, which halves the LDS instructions per MFMA (the 16-key form reads one fragment per MFMA and is LDS-issue bound).
 template <int D, int NW, int KT = 1>
@@ -551,269 +550,6 @@ __global__ __launch_bounds__(NW * 64) void attn_bwd_dkdv_kernel(AttnParams p, in
     }
 }
 
-// -------------------------------------------------------------------------------------------------- dK/dV, LDS-DMA staged (head dim 128)
-// Same decomposition (block = KB keys of one kv head x one slice of the query tiles, K/V fragments stationary in registers, transposed
-// operands read from the row-major tiles with ds_read_b64_tr_b16), but the 64-row Q / dO tiles and their row statistics travel
-// global -> LDS with global_load_lds (no staging registers, no ds_write): a ring of NB tile buffers keeps NB-1 query tiles in flight per
-// block whatever the register budget, which is what lets a wave own 32 keys (KT = 2: every Q / dO / Q^T / dO^T fragment read from LDS
-// feeds two MFMAs - half the LDS traffic per FLOP of the 16-key form, whose LDS read time equalled its MFMA time).
-// Tile image: 64 rows x 256 bytes, no padding; row r keeps its logical 16-byte chunk c at c ^ dkey(r & 15).  dkey spreads the 16 rows of a
-// b128 fragment read over all 16 chunk positions and the 8 rows x 2 chunks of a 32-lane transposing read over 16 distinct positions:
-// both read shapes are bank-conflict free.  One DMA instruction = 4 rows (1 KiB, lane -> row lane / 16, physical chunk lane % 16).
-// Row statistics (log2-scaled LSE from attn_delta_kernel, delta, pre / lo / hi) follow as five 256-byte dword DMAs issued by wave 0.
-// Ordering: each wave counts its own DMA instructions (s_waitcnt vmcnt(n)), then ONE barrier per tile publishes the tile to the block and
-// retires the buffer consumed in the previous iteration, which is refilled right behind the barrier.
-TR1_DEV int dkey(int row) { return ((row & 7) << 1) | ((row >> 3) & 1); }
-
-template <int NW, int KT, int NB>
-__global__ __launch_bounds__(NW * 64) void attn_bwd_dkdv_dma_kernel(AttnParams p, int n_qtiles, const float* __restrict__ lse2, float* __restrict__ part_k,
-                                                                    float* __restrict__ part_v) {
-    constexpr int D = 128, KB = NW * 16 * KT;
-    constexpr int TILE = 64 * 256, META = 64 * 5 * 4, BUF = 2 * TILE + META;
-    constexpr int IPW = 16 / NW;                                      // 4-row groups per wave: IPW Q + IPW dO instructions per tile
-    constexpr int PER = 2 * IPW, PER0 = PER + 5;                      // DMA instructions per tile: waves 1.., wave 0 (+ row statistics)
-    static_assert(NB >= 3 && NB <= 5 && (NB - 2) * PER0 <= 63, "vmcnt is a 6-bit counter");
-    extern __shared__ __attribute__((aligned(16))) char dyn_lds[];   // [NB][Q rows | dO rows | lse2, delta, pre, lo, hi] + tile list
-    int* lds_tiles = reinterpret_cast<int*>(dyn_lds + NB * BUF);      // [DKDV_MAXT + 1] tile ids, then [DKDV_MAXT] their smallest prefix length
-    int* lds_minpre = lds_tiles + DKDV_MAXT + 1;
-
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, u = lane & 15, g = lane >> 4;
-    // grid = (n_kv * QS, 1, key blocks): the dispatcher walks x fastest and z slowest, so blocks leave in order of their key block.  Low key
-    // blocks are the heavy ones (every later query tile sees them; the completion keys at the end see a single group), so the long blocks
-    // start first and the short ones fill the tail (with key blocks on x the last query slice's heavy blocks started last: 34 % idle CUs)
-    const int QS = gridDim.x / p.n_kv;
-    const int kvh = blockIdx.x % p.n_kv, qz = blockIdx.x / p.n_kv;
-    const int kvb0 = blockIdx.z * KB;
-    int kv[KT]; bool kv_ok[KT];
-#pragma unroll
-    for (int kt = 0; kt < KT; ++kt) { kv[kt] = kvb0 + (wave * KT + kt) * 16 + u; kv_ok[kt] = kv[kt] < p.n_slots; }
-    const int64_t nR = (int64_t)p.T * p.group;
-
-    if (wave == 0) {      // this block's list of relevant query tiles (qi = qz, qz+QS, ...)
-        int count = 0;
-        const int n_cand = (n_qtiles - qz + QS - 1) / QS;
-        for (int base = 0; base < n_cand; base += 64) {
-            const int c = base + lane, qi = qz + c * QS;
-            bool rel = false;
-            int mnp = 0;
-            if (c < n_cand) {
-                const int mp = p.qmeta[qi * ATT_QMETA], ml = p.qmeta[qi * ATT_QMETA + 1], mh = p.qmeta[qi * ATT_QMETA + 2];
-                mnp = p.qmeta[qi * ATT_QMETA + 3];
-                rel = (kvb0 < mp) || (kvb0 + KB - 1 >= ml && kvb0 <= mh);
-            }
-            const unsigned long long mask = __ballot(rel);
-            if (rel) { const int at = count + __popcll(mask & ((1ull << lane) - 1ull)); lds_tiles[at] = qi; lds_minpre[at] = mnp; }
-            count += __popcll(mask);
-        }
-        if (lane == 0) lds_tiles[DKDV_MAXT] = count;
-    }
-    bf16x8_t kf[KT][D / 32], vf[KT][D / 32];
-#pragma unroll
-    for (int kt = 0; kt < KT; ++kt) {
-        const bf16_t* krow = p.K + (int64_t)(kv_ok[kt] ? kv[kt] : 0) * p.k_ld + (int64_t)kvh * D;
-        const bf16_t* vrow = p.V + (int64_t)(kv_ok[kt] ? kv[kt] : 0) * p.v_ld + (int64_t)kvh * D;
-#pragma unroll
-        for (int ks = 0; ks < D / 32; ++ks) {
-            kf[kt][ks] = load_row_frag(krow, ks * 32 + g * 8, D, kv_ok[kt]);
-            vf[kt][ks] = load_row_frag(vrow, ks * 32 + g * 8, D, kv_ok[kt]);
-        }
-    }
-    f32x4_t dk[KT][D / 16], dv[KT][D / 16];
-#pragma unroll
-    for (int kt = 0; kt < KT; ++kt)
-#pragma unroll
-        for (int dt = 0; dt < D / 16; ++dt) { dk[kt][dt] = (f32x4_t){0.f, 0.f, 0.f, 0.f}; dv[kt][dt] = (f32x4_t){0.f, 0.f, 0.f, 0.f}; }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                 // the K / V fragments are in registers: from here on vmcnt counts DMA only
-    __syncthreads();
-    const int n_my = lds_tiles[DKDV_MAXT];
-
-    // ---- DMA of one query tile into ring slot `slot`
-    auto issue_tile = [&](int qi, int slot) {
-        char* buf = dyn_lds + slot * BUF;
-        const int64_t Rq0 = (int64_t)qi * 64;
-#pragma unroll
-        for (int j = 0; j < IPW; ++j) {
-            const int i = wave * IPW + j;                             // rows 4i .. 4i+3
-            const int row = 4 * i + (lane >> 4);
-            int64_t R = Rq0 + row; if (R > nR - 1) R = nR - 1;
-            const unsigned ru = (unsigned)R, tu = p.group == 1 ? ru : __umulhi(ru, p.group_magic);
-            const int hq = (int)(ru - tu * (unsigned)p.group);
-            const int64_t hoff = (int64_t)(kvh * p.group + hq) * D + (((lane & 15) ^ dkey(row & 15)) << 3);
-            __builtin_amdgcn_global_load_lds((att_gptr_t)(p.Q + (int64_t)tu * p.q_ld + hoff), (att_lptr_t)(buf + i * 1024), 16, 0, 0);
-            __builtin_amdgcn_global_load_lds((att_gptr_t)(p.dO + (int64_t)tu * p.do_ld + hoff), (att_lptr_t)(buf + TILE + i * 1024), 16, 0, 0);
-        }
-        if (wave == 0) {
-            int64_t R = Rq0 + lane; if (R > nR - 1) R = nR - 1;
-            const unsigned ru = (unsigned)R, tu = p.group == 1 ? ru : __umulhi(ru, p.group_magic);
-            const int hq = (int)(ru - tu * (unsigned)p.group);
-            const int64_t si = (int64_t)(kvh * p.group + hq) * p.T + tu;
-            char* mb = buf + 2 * TILE;
-            __builtin_amdgcn_global_load_lds((att_gptr_t)(lse2 + si), (att_lptr_t)(mb), 4, 0, 0);
-            __builtin_amdgcn_global_load_lds((att_gptr_t)(p.delta + si), (att_lptr_t)(mb + 256), 4, 0, 0);
-            __builtin_amdgcn_global_load_lds((att_gptr_t)(p.pre + tu), (att_lptr_t)(mb + 512), 4, 0, 0);
-            __builtin_amdgcn_global_load_lds((att_gptr_t)(p.lo + tu), (att_lptr_t)(mb + 768), 4, 0, 0);
-            __builtin_amdgcn_global_load_lds((att_gptr_t)(p.hi + tu), (att_lptr_t)(mb + 1024), 4, 0, 0);
-        }
-    };
-#pragma unroll
-    for (int j = 0; j < NB - 1; ++j)
-        if (j < n_my) issue_tile(__builtin_amdgcn_readfirstlane(lds_tiles[j]), j);
-
-    // per-lane fragment addresses inside a tile (swizzled); qt / dt / half offsets are added in the loops
-    const int keyu = dkey(u);
-    const int trow = g * 4 + (u >> 2);                                // row (mod 16) of this lane's transposing reads
-    const int keyt = dkey(trow);
-    const int tr_lo = trow * 256 + (u & 1) * 8, tr_c = (u & 3) >> 1;  // + ((dt*2 + tr_c) ^ keyt) * 16 + qb * 256
-
-    for (int it = 0; it < n_my; ++it) {
-        // my DMA share of tile `it` has landed when at most (tiles issued after it) x (my instructions per tile) are outstanding
-        {
-            const int after = (n_my - 1 - it) < (NB - 2) ? (n_my - 1 - it) : (NB - 2);
-            if (wave == 0) {
-                if (after >= 3) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(3 * PER0 > 63 ? 63 : 3 * PER0) : "memory");
-                else if (after == 2) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * PER0) : "memory");
-                else if (after == 1) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(PER0) : "memory");
-                else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            } else {
-                if (after >= 3) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(3 * PER) : "memory");
-                else if (after == 2) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * PER) : "memory");
-                else if (after == 1) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(PER) : "memory");
-                else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            }
-        }
-        __builtin_amdgcn_s_barrier();                                 // tile `it` is complete for everybody; everybody is done with tile it-1
-        asm volatile("" ::: "memory");
-        if (it + NB - 1 < n_my) issue_tile(__builtin_amdgcn_readfirstlane(lds_tiles[it + NB - 1]), (it + NB - 1) % NB);     // = the slot of tile it-1
-
-        const int qi = __builtin_amdgcn_readfirstlane(lds_tiles[it]);
-        const int tile_minpre = __builtin_amdgcn_readfirstlane(lds_minpre[it]);
-        const char* buf = dyn_lds + (it % NB) * BUF;
-        const char* lds_q = buf;
-        const char* lds_do = buf + TILE;
-        const float* lds_lse = reinterpret_cast<const float*>(buf + 2 * TILE);
-        const float* lds_dlt = lds_lse + 64;
-        const int* lds_pre = reinterpret_cast<const int*>(lds_lse + 128);
-        const int* lds_lo = lds_pre + 64;
-        const int* lds_hi = lds_pre + 128;
-
-        f32x4_t s[KT][4], dp[KT][4];
-#pragma unroll
-        for (int kt = 0; kt < KT; ++kt)
-#pragma unroll
-            for (int qt = 0; qt < 4; ++qt) { s[kt][qt] = (f32x4_t){0.f, 0.f, 0.f, 0.f}; dp[kt][qt] = (f32x4_t){0.f, 0.f, 0.f, 0.f}; }
-#pragma unroll
-        for (int ks = 0; ks < D / 32; ++ks) {
-#pragma unroll
-            for (int qt = 0; qt < 4; ++qt) {
-                const int off = (qt * 16 + u) * 256 + (((ks * 4 + g) ^ keyu) << 4);
-                const bf16x8_t qa = *reinterpret_cast<const bf16x8_t*>(lds_q + off);
-                const bf16x8_t da = *reinterpret_cast<const bf16x8_t*>(lds_do + off);
-#pragma unroll
-                for (int kt = 0; kt < KT; ++kt) {
-                    s[kt][qt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(qa, kf[kt][ks], s[kt][qt], 0, 0, 0);
-                    dp[kt][qt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(da, vf[kt][ks], dp[kt][qt], 0, 0, 0);
-                }
-            }
-        }
-        typedef __attribute__((ext_vector_type(4))) int i32x4_t;
-        bf16x8_t pf0[KT], pf1[KT], df0[KT], df1[KT];
-        const int rows_valid = (int)((nR - (int64_t)qi * 64) < 64 ? (nR - (int64_t)qi * 64) : 64);
-        const bool full = (kvb0 + KB <= tile_minpre) && (kvb0 + KB <= p.n_slots) && rows_valid == 64;      // block-uniform
-        if (full) {
-#pragma unroll
-            for (int h = 0; h < 2; ++h) {
-                f32x4_t l4[2], d4[2];
-#pragma unroll
-                for (int q2 = 0; q2 < 2; ++q2) {
-                    l4[q2] = *reinterpret_cast<const f32x4_t*>(lds_lse + (2 * h + q2) * 16 + g * 4);
-                    d4[q2] = *reinterpret_cast<const f32x4_t*>(lds_dlt + (2 * h + q2) * 16 + g * 4);
-                }
-#pragma unroll
-                for (int kt = 0; kt < KT; ++kt) {
-                    f32x4_t pr[2], ds[2];
-#pragma unroll
-                    for (int q2 = 0; q2 < 2; ++q2)
-#pragma unroll
-                        for (int r = 0; r < 4; ++r) {
-                            const float pv = __builtin_amdgcn_exp2f(__builtin_fmaf(s[kt][2 * h + q2][r], p.scale_log2, -l4[q2][r]));
-                            pr[q2][r] = pv; ds[q2][r] = pv * (dp[kt][2 * h + q2][r] - d4[q2][r]);
-                        }
-                    if (h == 0) { pf0[kt] = pack_frag(pr[0], pr[1]); df0[kt] = pack_frag(ds[0], ds[1]); }
-                    else { pf1[kt] = pack_frag(pr[0], pr[1]); df1[kt] = pack_frag(ds[0], ds[1]); }
-                }
-            }
-        } else {
-#pragma unroll
-            for (int h = 0; h < 2; ++h) {
-                f32x4_t l4[2], d4[2];
-                i32x4_t p4[2], lo4[2], hi4[2];
-#pragma unroll
-                for (int q2 = 0; q2 < 2; ++q2) {
-                    const int o = (2 * h + q2) * 16 + g * 4;
-                    l4[q2] = *reinterpret_cast<const f32x4_t*>(lds_lse + o); d4[q2] = *reinterpret_cast<const f32x4_t*>(lds_dlt + o);
-                    p4[q2] = *reinterpret_cast<const i32x4_t*>(lds_pre + o); lo4[q2] = *reinterpret_cast<const i32x4_t*>(lds_lo + o);
-                    hi4[q2] = *reinterpret_cast<const i32x4_t*>(lds_hi + o);
-                }
-#pragma unroll
-                for (int kt = 0; kt < KT; ++kt) {
-                    f32x4_t pr[2], ds[2];
-#pragma unroll
-                    for (int q2 = 0; q2 < 2; ++q2)
-#pragma unroll
-                        for (int r = 0; r < 4; ++r) {
-                            const bool ok = kv_ok[kt] & att_visible_nb(kv[kt], p4[q2][r], lo4[q2][r], hi4[q2][r]) & ((2 * h + q2) * 16 + g * 4 + r < rows_valid);
-                            const float e = __builtin_amdgcn_exp2f(__builtin_fmaf(s[kt][2 * h + q2][r], p.scale_log2, -l4[q2][r]));
-                            const float pv = ok ? e : 0.f;
-                            pr[q2][r] = pv; ds[q2][r] = ok ? pv * (dp[kt][2 * h + q2][r] - d4[q2][r]) : 0.f;
-                        }
-                    if (h == 0) { pf0[kt] = pack_frag(pr[0], pr[1]); df0[kt] = pack_frag(ds[0], ds[1]); }
-                    else { pf1[kt] = pack_frag(pr[0], pr[1]); df1[kt] = pack_frag(ds[0], ds[1]); }
-                }
-            }
-        }
-        // transposed fragments: rows qb + trow (first 8 bytes) and qb + 16 + trow (second), feature chunk dt*2 + tr_c
-#pragma unroll
-        for (int hh = 0; hh < 2; ++hh) {
-#pragma unroll
-            for (int dt = 0; dt < D / 16; ++dt) {
-                const int off = hh * 32 * 256 + tr_lo + (((dt * 2 + tr_c) ^ keyt) << 4);
-                const bf16x8_t q0 = make_frag(att_lds_tr16(lds_q + off), att_lds_tr16(lds_q + off + 16 * 256));
-                const bf16x8_t o0 = make_frag(att_lds_tr16(lds_do + off), att_lds_tr16(lds_do + off + 16 * 256));
-                _Pragma("unroll") for (int kt = 0; kt < KT; ++kt) dv[kt][dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(o0, hh ? pf1[kt] : pf0[kt], dv[kt][dt], 0, 0, 0);
-                _Pragma("unroll") for (int kt = 0; kt < KT; ++kt) dk[kt][dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(q0, hh ? df1[kt] : df0[kt], dk[kt][dt], 0, 0, 0);
-            }
-        }
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");           // all LDS reads of this tile have returned before the barrier that frees its slot
-    }
-    // lane holds dK^T/dV^T[d = dt*16 + g*4 + r][kv]
-#pragma unroll
-    for (int kt = 0; kt < KT; ++kt)
-    if (kv_ok[kt]) {
-        if (part_k) {
-            const int64_t kvd = (int64_t)p.n_kv * D;
-            float* pk = part_k + ((int64_t)qz * p.n_slots + kv[kt]) * kvd + (int64_t)kvh * D;
-            float* pv = part_v + ((int64_t)qz * p.n_slots + kv[kt]) * kvd + (int64_t)kvh * D;
-#pragma unroll
-            for (int dt = 0; dt < D / 16; ++dt) {
-                const int d = dt * 16 + g * 4;
-                *reinterpret_cast<f32x4_t*>(pk + d) = dk[kt][dt]; *reinterpret_cast<f32x4_t*>(pv + d) = dv[kt][dt];
-            }
-        } else {
-            const float scale = p.scale_log2 * 0.6931471805599453f;
-            bf16_t* kr = p.dK + (int64_t)kv[kt] * p.dk_ld + (int64_t)kvh * D;
-            bf16_t* vr = p.dV + (int64_t)kv[kt] * p.dv_ld + (int64_t)kvh * D;
-#pragma unroll
-            for (int dt = 0; dt < D / 16; ++dt) {
-                const int d = dt * 16 + g * 4;
-                u32x2_t wk = {pack2bf(dk[kt][dt][0] * scale, dk[kt][dt][1] * scale), pack2bf(dk[kt][dt][2] * scale, dk[kt][dt][3] * scale)};
-                u32x2_t wv = {pack2bf(dv[kt][dt][0], dv[kt][dt][1]), pack2bf(dv[kt][dt][2], dv[kt][dt][3])};
-                *reinterpret_cast<u32x2_t*>(kr + d) = wk;
-                *reinterpret_cast<u32x2_t*>(vr + d) = wv;
-            }
-        }
-    }
-}
-
 // ------------------------------------------------------------------------------ dK/dV on 32x32x16 MFMA tiles, role-split wave pairs (head dim 128)
 // Round 3.  The 16x16x32 forms above read one LDS fragment per MFMA and were LDS- / issue-bound (MFMA busy 17-20 %).  Here a wave owns 32 keys
 // and works on v_mfma_f32_32x32x16_bf16 tiles: an operand fragment read from LDS feeds twice the MACs (half the LDS bytes per FLOP), and the
@@ -827,16 +563,19 @@ __global__ __launch_bounds__(NW * 64) void attn_bwd_dkdv_dma_kernel(AttnParams p
 // The C layout of a 32x32 tile (lane (n, h): rows (r&3) + 8(r>>2) + 4h) IS a legal B operand for the next product after a k-permutation:
 // registers 8c..8c+7 = the 16 query rows q = 16c + (j&3) + 8(j>>2) + 4h (j = k-slot of lane half h), and the transposed A operand
 // (dO^T / Q^T: 32 features x those 16 rows) is two ds_read_b64_tr_b16 per lane from the ROW-major tile (rows 4h..4h+3 and 8+4h..8+4h+3).
-// Tile images as in the DMA kernel above (64 rows x 256 B, unpadded, global_load_lds with the swizzle applied on the SOURCE address), but
-// keyed with skey(row) = (row&3)<<2 | (row>>2)&3: the 16 rows of a b128 service group get 16 distinct chunk positions, and the 4 rows x 4
-// chunks of a 32-lane transposing read land in 4 disjoint aligned chunk groups - both read shapes are bank-conflict free.
-
-template <int NB, int NP>
-__global__ __launch_bounds__(NP * 128) void attn_bwd_dkdv32_kernel(AttnParams p, int n_qtiles, const float* __restrict__ lse2, float* __restrict__ part_k,
-                                                              float* __restrict__ part_v) {
-    constexpr int D = 128, KB = NP * 32, SW = 2 * NP - 1;             // NP wave pairs x 32 keys; SW: the wave that also carries the row statistics
-    constexpr int TILE = 64 * 256, META = 64 * 5 * 4, BUF = 2 * TILE + META, PEX = 64 * 32 * 2;      // P exchange: bf16, one buffer per tile parity
-    static_assert(NB == 3, "ring depth (the top-of-tile wait is vmcnt(0): tile it+1 was requested one iteration ago)");
+// Tile image (attn_common.h): 64 rows x 256 B, unpadded, filled by global_load_lds (no staging registers, no ds_write; one instruction = 4 rows) with
+// logical 16-byte chunk c of row r at chunk c ^ skey(r), the swizzle applied on the SOURCE address.  skey(row) = (row&3)<<2 | (row>>2)&3: the 16 rows
+// of a b128 service group get 16 distinct chunk positions, and the 4 rows x 4 chunks of a 32-lane transposing read land in 4 disjoint aligned chunk
+// groups - both read shapes are bank-conflict free.  The row statistics (log2-scaled LSE, delta, pre / lo / hi) follow as five 256-byte dword DMAs.
+// The kernel's shape, read from HERE by the kernel, dkdv_keys_per_block, launch_bwd and tr1_attn_bwd_workspace_floats: 6 wave pairs = 12 waves = 3 per
+// SIMD, 192 keys per block (4 pairs / 128 keys measured slower in round 3); 3 ring slots (the top-of-tile wait is vmcnt(0): tile it + 1 was requested
+// one iteration ago, a deeper ring would never fill)
+constexpr int DKDV32_PAIRS = 6, DKDV32_KEYS = DKDV32_PAIRS * 32, DKDV32_THREADS = DKDV32_PAIRS * 128, DKDV32_RING = 3;
+constexpr int DKDV32_TILE = 64 * 256, DKDV32_BUF = 2 * DKDV32_TILE + 64 * 5 * 4, DKDV32_PEX = 64 * 32 * 2;      // ring slot = 2 tile images + statistics; P exchange of a pair: bf16, one per tile parity
+constexpr int DKDV32_LDS = DKDV32_RING * DKDV32_BUF + 2 * DKDV32_PAIRS * DKDV32_PEX + (2 * DKDV32_MAXT + 2) * 4;
+__global__ __launch_bounds__(DKDV32_THREADS) void attn_bwd_dkdv32_kernel(AttnParams p, int n_qtiles, const float* __restrict__ lse2, float* __restrict__ part_k, float* __restrict__ part_v) {
+    constexpr int D = 128, NB = DKDV32_RING, NP = DKDV32_PAIRS, KB = DKDV32_KEYS, TILE = DKDV32_TILE, BUF = DKDV32_BUF, PEX = DKDV32_PEX;
+    constexpr int SW = 2 * NP - 1;                                    // the wave that also carries the row statistics (not one of the 8 row-group DMA waves)
     extern __shared__ __attribute__((aligned(256))) char dyn_lds[];  // [NB][Q rows | dO rows | lse2, delta, pre, lo, hi] | [2][NP] P exchange | tile list
     char* lds_pex = dyn_lds + NB * BUF;
     int* lds_tiles = reinterpret_cast<int*>(lds_pex + 2 * NP * PEX);
@@ -967,31 +706,23 @@ __global__ __launch_bounds__(NP * 128) void attn_bwd_dkdv32_kernel(AttnParams p,
     // Operand reads run a fixed distance ahead of their MFMAs (explicit register ring + scheduling fences): left alone, hipcc hoists every
     // LDS read of the phase to its top and spills.
     auto product1 = [&](unsigned xa, f32x16_t& c) {                   // xa: tile rows + qb * 8192 + a_lane (LDS byte address)
-        // 8 waves (2 per SIMD): two accumulators (even / odd k-steps) - a single chain of 8 dependent 32x32x16 MFMAs runs at the instruction's
-        // latency (64 cycles), not its issue rate (32).  12 waves (3 per SIMD, 168 registers): one chain, the other waves fill the pipe.
-        constexpr bool TWO = NP == 4;
-        f32x16_t c1;
+        // one chain of 8 dependent 32x32x16 MFMAs: with 12 waves (3 per SIMD, 168 registers) the other waves fill the pipe
 #pragma unroll
-        for (int r = 0; r < 16; ++r) { c[r] = 0.f; if (TWO) c1[r] = 0.f; }
-        constexpr int AH = NP == 4 ? 3 : 2;                           // k-steps of lookahead
+        for (int r = 0; r < 16; ++r) c[r] = 0.f;
+        constexpr int AH = 2;                                         // k-steps of lookahead
         bf16x8_t a[AH + 1];
 #pragma unroll
         for (int ks = 0; ks < AH; ++ks) a[ks] = att_lds_b128(xa ^ (ks * 32));
 #pragma unroll
         for (int ks = 0; ks < D / 16; ++ks) {
             if (ks + AH < D / 16) a[(ks + AH) % (AH + 1)] = att_lds_b128(xa ^ ((ks + AH) * 32));
-            if (TWO && (ks & 1)) c1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[ks % (AH + 1)], sf[ks], c1, 0, 0, 0);
-            else c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[ks % (AH + 1)], sf[ks], c, 0, 0, 0);
+            c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[ks % (AH + 1)], sf[ks], c, 0, 0, 0);
             __builtin_amdgcn_sched_barrier(0);
-        }
-        if (TWO) {
-#pragma unroll
-            for (int r = 0; r < 16; ++r) c[r] += c1[r];
         }
     };
     // phase-2 product over two 16-row chunks: acc^T[feature][key] += Y^T[feature][q] * frag[q][key]
     auto product2 = [&](unsigned ya, const bf16x8_t& f0, const bf16x8_t& f1) {      // ya: tile rows + first chunk * 4096 + t_lane
-        constexpr int TH = NP == 4 ? 3 : 2;                           // MFMAs of lookahead
+        constexpr int TH = 2;                                         // MFMAs of lookahead
         bf16x8_t a[TH + 1];
 #pragma unroll
         for (int n = 0; n < TH; ++n) a[n] = att_p2_ld<4>(ya, n);
@@ -1051,9 +782,9 @@ __global__ __launch_bounds__(NP * 128) void attn_bwd_dkdv32_kernel(AttnParams p,
         }
     };
 
-    // prologue: tile 0 has landed (this wave's share; tile 1 may still be in flight: 4 instructions, wave 7 carries 5 statistics rows more)
-    if (n_my > 1) {                                                   // (NP = 4: wave 7 issues 4 + 5 instructions per tile; NP = 6: wave 11 only the 5)
-        if (wave == SW) { if (SW < 8) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(9) : "memory"); else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(5) : "memory"); }
+    // prologue: tile 0 has landed (this wave's share; tile 1 may still be in flight: 4 instructions of a row-group wave, the 5 statistics rows of wave SW)
+    if (n_my > 1) {
+        if (wave == SW) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(5) : "memory");
         else if (dma_wave) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(4) : "memory");
     } else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
@@ -1432,12 +1163,8 @@ __global__ void attn_bwd_reduce_kernel(const float* __restrict__ part_k, const f
 extern "C" int tr1_rope_apply(const void* in, int64_t ld_in, void* out, int64_t ld_out, const void* cosb, const void* sinb, int64_t T, int64_t n_heads,
                               int64_t head_dim, int backward, void* stream);
 
-// wave pairs per block of the 32x32x16 kernel: 6 pairs = 12 waves = 3 per SIMD, 192 keys per block (4 pairs / 128 keys measured slower in round 3)
-static int dkdv32_pairs() { return 6; }
-static int dkdv_keys_per_block(int d_pad) {      // 8-wave blocks where 8*D/512 is integral; head dim 128: the 32x32x16 kernel's pairs x 32
-    if (d_pad == 128) return dkdv32_pairs() * 32;
-    return (d_pad == 64 || d_pad == 128) ? 128 : 64;
-}
+// head dim 128: the 32x32x16 kernel; 8-wave blocks where 8*D/512 is integral (64, and 128 where that kernel cannot go: see the workspace size)
+static int dkdv_keys_per_block(int d_pad) { return d_pad == 128 ? DKDV32_KEYS : d_pad == 64 ? 128 : 64; }
 
 static int dkdv_qsplit(int64_t T, int group, int n_kv, int64_t n_slots, int kb) {
     const int64_t n_qtiles = (T * group + 63) / 64;
@@ -1450,11 +1177,11 @@ static int dkdv_qsplit(int64_t T, int group, int n_kv, int64_t n_slots, int kb) 
     return (int)qs;
 }
 
-// both head-dim-128 kernels on the 32x32x16 forms (32-bit DMA byte offsets fit): the dQ kernel's prologue then also does attn_delta_kernel's work (round 6)
-static bool bwd32_both(const AttnParams& p) {
-    return p.d_real == 128 && (uint64_t)p.n_slots * (uint64_t)(p.k_ld > p.v_ld ? p.k_ld : p.v_ld) * 2ull < 0xffffffffull &&
-           (uint64_t)p.T * (uint64_t)(p.q_ld > p.do_ld ? p.q_ld : p.do_ld) * 2ull < 0xffffffffull;
-}
+// do `rows` bf16 rows of either leading dim stay inside the 32-bit byte offsets of the LDS-DMA kernels?
+static bool dma32_fits(int64_t rows, int64_t ld_a, int64_t ld_b) { return (uint64_t)rows * (uint64_t)(ld_a > ld_b ? ld_a : ld_b) * 2ull < 0xffffffffull; }
+
+// both head-dim-128 kernels on the 32x32x16 forms: the dQ kernel's prologue then also does attn_delta_kernel's work (round 6)
+static bool bwd32_both(const AttnParams& p) { return p.d_real == 128 && dma32_fits(p.n_slots, p.k_ld, p.v_ld) && dma32_fits(p.T, p.q_ld, p.do_ld); }
 
 template <int D>
 static int launch_bwd(const AttnParams& p, hipStream_t s, float* ws, int64_t ws_floats, const float* lse2) {
@@ -1465,23 +1192,14 @@ static int launch_bwd(const AttnParams& p, hipStream_t s, float* ws, int64_t ws_
     constexpr int KB = NW * 16;
     const size_t dyn_dq = 2 * (2 * ATT_KV * KSTR) + 64;
     const size_t dyn_kv = 2 * (2 * 64 * KSTR + (NW == 8 ? 0 : 2 * D * 144) + 64 * 5 * 4 + 16) + (DKDV_MAXT + 1) * 4;
-    // head dim 128: the 32x32x16-MFMA dQ kernel (round 3)
+    // head dim 128 exactly: the 32x32x16-MFMA kernels (round 3), each where the operands it stages by LDS DMA fit 32-bit byte offsets - K / V for dQ,
+    // Q / dO for dK/dV.  Past that range, and for a real head dim under 128, the 16x16x32 kernels (64-bit addressing) take over.
     const size_t dyn_dq32 = 4 * (2 * 64 * 256) + 256;
-    const bool use_dq32 = D == 128 && p.d_real == 128 && lse2 != nullptr &&
-                          (uint64_t)p.n_slots * (uint64_t)(p.k_ld > p.v_ld ? p.k_ld : p.v_ld) * 2ull < 0xffffffffull;      // 32-bit DMA byte offsets
+    const bool use_dq32 = D == 128 && p.d_real == 128 && dma32_fits(p.n_slots, p.k_ld, p.v_ld);
+    const bool use_v32 = D == 128 && p.d_real == 128 && dma32_fits(p.T, p.q_ld, p.do_ld);
     if (use_dq32) tr1_launch<attn_bwd_dq32_kernel>(dim3((unsigned)((nR + 255) / 256), p.n_kv), dim3(512), dyn_dq32, (int)dyn_dq32, s, p, lse2);
     else tr1_launch<attn_bwd_dq_kernel<D>>(dim3((unsigned)((nR + 127) / 128), p.n_kv), dim3(256), dyn_dq, (int)dyn_dq, s, p);
-    // head dim 128 beyond the 32-bit DMA offsets of the 32x32x16 kernel: the LDS-DMA staged 16x16x32 form, 8 waves x 16 keys
-    constexpr int DMA_NB = 4;
-    const size_t dyn_dma = DMA_NB * (2 * 64 * 256 + 64 * 5 * 4) + (2 * DKDV_MAXT + 2) * 4;
-    // the 32x32x16-MFMA role-split kernel (round 3) for head dim 128
-    constexpr int V32_NB = 3;
-    const int v32_np = dkdv32_pairs();
-    const size_t dyn_v32 = V32_NB * (2 * 64 * 256 + 64 * 5 * 4) + 2 * v32_np * (64 * 32 * 2) + (2 * DKDV32_MAXT + 2) * 4;
-    const bool use_v32 = D == 128 && p.d_real == 128 && lse2 != nullptr &&
-                         (uint64_t)p.T * (uint64_t)(p.q_ld > p.do_ld ? p.q_ld : p.do_ld) * 2ull < 0xffffffffull;      // 32-bit DMA byte offsets
-    const bool use_dma = D == 128 && p.d_real == 128 && lse2 != nullptr;
-    const int QS = dkdv_qsplit(p.T, p.group, p.n_kv, p.n_slots, use_v32 ? v32_np * 32 : KB);
+    const int QS = dkdv_qsplit(p.T, p.group, p.n_kv, p.n_slots, use_v32 ? DKDV32_KEYS : KB);
     const int64_t kvd = (int64_t)p.n_kv * p.d_real;
     float *pk = nullptr, *pv = nullptr;
     if (QS > 1) {
@@ -1489,8 +1207,7 @@ static int launch_bwd(const AttnParams& p, hipStream_t s, float* ws, int64_t ws_
         if (!ws || ws_floats < need) { tr1_set_error_("attention bwd: workspace too small"); return 1000; }
         pk = ws; pv = ws + (int64_t)QS * p.n_slots * kvd;
     }
-    if (use_v32) tr1_launch<attn_bwd_dkdv32_kernel<V32_NB, 6>>(dim3((unsigned)(p.n_kv * QS), 1, (unsigned)((p.n_slots + 191) / 192)), dim3(768), dyn_v32, 160 * 1024, s, p, n_qtiles, lse2, pk, pv);
-    else if (use_dma) tr1_launch<attn_bwd_dkdv_dma_kernel<8, 1, DMA_NB>>(dim3((unsigned)(p.n_kv * QS), 1, (unsigned)((p.n_slots + 127) / 128)), dim3(512), dyn_dma, (int)dyn_dma, s, p, n_qtiles, lse2, pk, pv);
+    if (use_v32) tr1_launch<attn_bwd_dkdv32_kernel>(dim3((unsigned)(p.n_kv * QS), 1, (unsigned)((p.n_slots + DKDV32_KEYS - 1) / DKDV32_KEYS)), dim3(DKDV32_THREADS), DKDV32_LDS, DKDV32_LDS, s, p, n_qtiles, lse2, pk, pv);
     else tr1_launch<attn_bwd_dkdv_kernel<D, NW>>(dim3((unsigned)(p.n_kv * QS), 1, (unsigned)((p.n_slots + KB - 1) / KB)), dim3(NW * 64), dyn_kv, (int)dyn_kv, s, p, n_qtiles, pk, pv);
     const bool rope = p.rope_cos != nullptr;
     bool dk_rotated = false;
@@ -1518,7 +1235,7 @@ extern "C" int64_t tr1_attn_bwd_workspace_floats(int64_t T, int64_t n_heads, int
     const int d_pad = (int)((head_dim + 31) / 32 * 32);
     // the launch picks its key-block size (and with it the number of query slices) from the shape; size the partials for every form it may take
     int64_t need = 0;
-    for (int kb : {dkdv_keys_per_block(d_pad), d_pad == 128 ? 128 : 64}) {
+    for (int kb : {dkdv_keys_per_block(d_pad), d_pad == 128 ? 128 : 64}) {      // (128: attn_bwd_dkdv_kernel<128, 8> where the 32x32x16 kernel cannot go)
         const int QS = dkdv_qsplit(T, (int)(n_heads / n_kv), (int)n_kv, n_slots, kb);
         const int64_t n = QS > 1 ? 2 * (int64_t)QS * n_slots * n_kv * head_dim : 0;
         if (n > need) need = n;
@@ -1527,8 +1244,8 @@ extern "C" int64_t tr1_attn_bwd_workspace_floats(int64_t T, int64_t n_heads, int
 }
 
 // Scratch: qmeta_ws int32 [8*ceil(T*group/64)], delta fp32 [2*n_heads*T] (delta | log2-scaled LSE), ws_f32 of tr1_attn_bwd_workspace_floats() floats.
-static int attn_bwd_impl(const void* Q, int64_t q_ld, const void* K, int64_t k_ld, const void* V, int64_t v_ld, const void* KT,
-                            int64_t kt_ld, const void* QT, int64_t qt_ld, const void* dOT, int64_t dot_ld, const void* O, int64_t o_ld,
+static int attn_bwd_impl(const void* Q, int64_t q_ld, const void* K, int64_t k_ld, const void* V, int64_t v_ld,
+                            const void* QT, int64_t qt_ld, const void* dOT, int64_t dot_ld, const void* O, int64_t o_ld,
                             const void* dO, int64_t do_ld, const void* lse, void* delta, void* dQ, int64_t dq_ld, void* dK, int64_t dk_ld,
                             void* dV, int64_t dv_ld, const void* pre, const void* lo, const void* hi, void* qmeta_ws, void* ws_f32,
                             int64_t ws_floats, int64_t T, int64_t n_heads, int64_t n_kv, int64_t n_slots, int64_t head_dim, float scale,
@@ -1538,7 +1255,7 @@ static int attn_bwd_impl(const void* Q, int64_t q_ld, const void* K, int64_t k_l
     TR1_CHECK_ARG(!rope_cos || (rope_sin && n_slots == T && head_dim % 16 == 0), "attention bwd: rope tables need sin, n_slots == T and head_dim % 16 == 0");
     TR1_CHECK_ARG(n_kv > 0 && n_heads % n_kv == 0, "attention bwd: n_heads must be a multiple of n_kv");
     p.Q = (const bf16_t*)Q; p.q_ld = q_ld; p.K = (const bf16_t*)K; p.k_ld = k_ld; p.V = (const bf16_t*)V; p.v_ld = v_ld;
-    p.KT = (const bf16_t*)KT; p.kt_ld = kt_ld; p.QT = (const bf16_t*)QT; p.qt_ld = qt_ld; p.dOT = (const bf16_t*)dOT; p.dot_ld = dot_ld;
+    p.QT = (const bf16_t*)QT; p.qt_ld = qt_ld; p.dOT = (const bf16_t*)dOT; p.dot_ld = dot_ld;
     p.dO = (const bf16_t*)dO; p.do_ld = do_ld; p.dQ = (bf16_t*)dQ; p.dq_ld = dq_ld; p.dK = (bf16_t*)dK; p.dk_ld = dk_ld;
     p.dV = (bf16_t*)dV; p.dv_ld = dv_ld; p.lse = (float*)lse; p.delta = (float*)delta; p.pre = (const int*)pre; p.lo = (const int*)lo;
     p.hi = (const int*)hi; p.qmeta = (const int*)qmeta_ws;
@@ -1582,7 +1299,7 @@ extern "C" int tr1_attn_bwd(const void* Q, int64_t q_ld, const void* K, int64_t 
                             void* dV, int64_t dv_ld, const void* pre, const void* lo, const void* hi, void* qmeta_ws, void* ws_f32,
                             int64_t ws_floats, int64_t T, int64_t n_heads, int64_t n_kv, int64_t n_slots, int64_t head_dim, float scale,
                             void* stream) {
-    return attn_bwd_impl(Q, q_ld, K, k_ld, V, v_ld, KT, kt_ld, QT, qt_ld, dOT, dot_ld, O, o_ld, dO, do_ld, lse, delta, dQ, dq_ld, dK, dk_ld, dV, dv_ld, pre, lo,
+    return attn_bwd_impl(Q, q_ld, K, k_ld, V, v_ld, QT, qt_ld, dOT, dot_ld, O, o_ld, dO, do_ld, lse, delta, dQ, dq_ld, dK, dk_ld, dV, dv_ld, pre, lo,
                          hi, qmeta_ws, ws_f32, ws_floats, T, n_heads, n_kv, n_slots, head_dim, scale, nullptr, nullptr, stream);
 }
 
@@ -1596,6 +1313,6 @@ extern "C" int tr1_attn_bwd_rope(const void* Q, int64_t q_ld, const void* K, int
                                  int64_t ws_floats, int64_t T, int64_t n_heads, int64_t n_kv, int64_t n_slots, int64_t head_dim, float scale,
                                  const void* rope_cos, const void* rope_sin, void* stream) {
     TR1_CHECK_ARG(rope_cos && rope_sin, "attention bwd (rope): cos / sin tables required");
-    return attn_bwd_impl(Q, q_ld, K, k_ld, V, v_ld, KT, kt_ld, QT, qt_ld, dOT, dot_ld, O, o_ld, dO, do_ld, lse, delta, dQ, dq_ld, dK, dk_ld, dV, dv_ld, pre, lo,
+    return attn_bwd_impl(Q, q_ld, K, k_ld, V, v_ld, QT, qt_ld, dOT, dot_ld, O, o_ld, dO, do_ld, lse, delta, dQ, dq_ld, dK, dk_ld, dV, dv_ld, pre, lo,
                          hi, qmeta_ws, ws_f32, ws_floats, T, n_heads, n_kv, n_slots, head_dim, scale, rope_cos, rope_sin, stream);
 }

@@ -24,8 +24,8 @@ struct AttnParams {
     const bf16_t* Q;  int64_t q_ld;    // [T, n_heads*d]   (row = token)
     const bf16_t* K;  int64_t k_ld;    // [slots, n_kv*d]  (row = kv slot)
     const bf16_t* V;  int64_t v_ld;    // [slots, n_kv*d]
-    const bf16_t* KT; int64_t kt_ld;   // [n_kv*d, slots_pad]  (transposed copies, slot-contiguous)
-    const bf16_t* VT; int64_t vt_ld;
+    const bf16_t* KT; int64_t kt_ld;   // unused (no kernel reads K^T); the 16 bytes stay: without them the kernel-argument loads of attn_bwd_dkdv32_kernel regroup
+    const bf16_t* VT; int64_t vt_ld;   // [n_kv*d, slots_pad]  (transposed copy, slot-contiguous)
     const bf16_t* QT; int64_t qt_ld;   // [n_kv*d, T*group padded]  (packed-row-contiguous)
     const bf16_t* dOT; int64_t dot_ld;
     bf16_t* O;        int64_t o_ld;    // [T, n_heads*d]
@@ -100,59 +100,6 @@ TR1_DEV bf16x8_t zero_frag() { u32x4_t w = {0, 0, 0, 0}; return __builtin_bit_ca
 TR1_DEV bf16x8_t load_row_frag(const bf16_t* row_ptr, int d0, int d_real, bool valid) {
     if (valid && d0 < d_real) return *reinterpret_cast<const bf16x8_t*>(row_ptr + d0);
     return zero_frag();
-}
-
-// Stage `NROWS` rows x D columns (row-major source) into LDS with a (2*D+16)-byte row stride (conflict-free b128 column reads).
-// Row r of the tile is source row (row0 + r); rows >= nvalid and columns >= d_real are zero-filled.
-template <int D, int NROWS>
-TR1_DEV void stage_rows(char* lds, const bf16_t* src, int64_t ld, int64_t col0, int64_t row0, int64_t nvalid, int d_real) {
-    constexpr int CH = D / 8;
-    constexpr int STRIDE = 2 * D + 16;
-    for (int idx = threadIdx.x; idx < NROWS * CH; idx += 256) {
-        const int r = idx / CH, c = idx - r * CH;
-        u32x4_t v = {0, 0, 0, 0};
-        const int64_t row = row0 + r;
-        if (row < nvalid && c * 8 < d_real) v = *reinterpret_cast<const u32x4_t*>(src + row * ld + col0 + c * 8);
-        *reinterpret_cast<u32x4_t*>(lds + r * STRIDE + c * 16) = v;
-    }
-}
-// Same, but the tile rows are GQA-packed query rows R = R0 + r  ->  token R/group, head R%group.
-template <int D, int NROWS>
-TR1_DEV void stage_packed_rows(char* lds, const bf16_t* src, int64_t ld, int kvh, int group, int64_t R0, int64_t nR, int d_real) {
-    constexpr int CH = D / 8;
-    constexpr int STRIDE = 2 * D + 16;
-    for (int idx = threadIdx.x; idx < NROWS * CH; idx += 256) {
-        const int r = idx / CH, c = idx - r * CH;
-        u32x4_t v = {0, 0, 0, 0};
-        const int64_t R = R0 + r;
-        if (R < nR && c * 8 < d_real) {
-            const int64_t t = R / group; const int hq = (int)(R - t * group);
-            v = *reinterpret_cast<const u32x4_t*>(src + t * ld + (int64_t)(kvh * group + hq) * d_real + c * 8);
-        }
-        *reinterpret_cast<u32x4_t*>(lds + r * STRIDE + c * 16) = v;
-    }
-}
-// Stage a transposed tile: D rows (feature d) x 64 columns (slot / packed row), source is [n_kv*d_real, ldT] with the
-// column index contiguous. LDS row stride 144 bytes. Columns >= nvalid and rows >= d_real are zero-filled.
-template <int D>
-TR1_DEV void stage_T(char* lds, const bf16_t* srcT, int64_t ldT, int kvh, int64_t col0, int64_t nvalid, int d_real) {
-    for (int idx = threadIdx.x; idx < D * 8; idx += 256) {
-        const int d = idx >> 3, c = idx & 7;
-        u32x4_t v = {0, 0, 0, 0};
-        const int64_t col = col0 + c * 8;
-        if (d < d_real && col < nvalid) {
-            v = *reinterpret_cast<const u32x4_t*>(srcT + ((int64_t)kvh * d_real + d) * ldT + col);
-            if (col + 8 > nvalid) {  // ragged tail: keep only the valid columns (stale cache slots must not leak)
-                const int keep = (int)(nvalid - col);
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    if (2 * e >= keep) v[e] = 0;
-                    else if (2 * e + 1 >= keep) v[e] &= 0xffffu;
-                }
-            }
-        }
-        *reinterpret_cast<u32x4_t*>(lds + d * 144 + c * 16) = v;
-    }
 }
 
 // ---- split staging (issue the global loads early, write LDS late): hides HBM/L2 latency under the current tile's MFMAs.
@@ -326,7 +273,6 @@ TR1_DEV int att_tile_at(const TileRange& tr, int i) { return i < tr.pre_tiles ? 
 // a parameter between value and reference), compare `hipcc --cuda-device-only -S` of every kernel that uses it.
 typedef __attribute__((ext_vector_type(16))) float f32x16_t;       // 32x32 accumulator: lane (column n = lane & 31, half h = lane >> 5), register r -> row (r&3) + 8(r>>2) + 4h
 typedef __attribute__((ext_vector_type(4))) short s16x4_t;
-typedef const __attribute__((address_space(1))) void* att_gptr_t;
 typedef __attribute__((address_space(3))) void* att_lptr_t;
 // swizzle key of row (mod 16) of an unpadded 256-byte-row tile image: logical 16-byte chunk c of the row is stored at chunk c ^ skey(row)
 TR1_DEV int skey(int row) { return ((row & 3) << 2) | ((row >> 2) & 3); }
