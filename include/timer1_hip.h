@@ -355,6 +355,23 @@ int tr1_sumsq_accum_bf16(const void* g_bf16, int64_t n, void* out_scalar, void* 
  * Both arrays 16-byte aligned and distinct, any n.  ws_f32: >= 4096 floats of scratch. */
 int tr1_ref_mixup(void* ref_bf16, const void* policy_bf16, int64_t n, float alpha, void* sums_f32, void* ws_f32, int64_t ws_floats, void* stream);
 
+/* ---- LoRA (peft_config; csrc/lora.hip) -----------------------------------------------------------------------------------------
+ * ref: GRPOTrainer's peft_config (timer1_trainer.py:290-293, get_peft_config in main.py) -> peft.tuners.lora.Linear.  The adapters are kept MERGED: the policy's
+ * weight is W = bf16_rne(W0 + s Bt^T A), rebuilt from the frozen base copy W0 and the fp32 adapter masters after every optimizer step.
+ * tr1_lora_merge: W [out, in] bf16 (leading dimension ldw; a row slice of the fused q|k|v or gate|up matrix is a pointer offset), W0 likewise (ldw0), A fp32
+ * [r, in] and Bt fp32 [r, out] contiguous, r in {16, 32, 64}.  Arithmetic, each operation rounded to fp32 on its own (no fma): acc = 0; for j ascending:
+ * acc = fadd(acc, fmul(Bt[j, o], A[j, i])); W[o, i] = bf16_rne(fadd(W0[o, i], fmul(s, acc))).  in, ldw, ldw0 multiples of 8; W, W0, A 16-byte aligned; W != W0.
+ * tr1_lora_wgrad: G [r, Wd] fp32 (ldg) (+)= scale * thin^T wide with thin bf16 [M, r] (ldt) and wide bf16 [M, Wd] (ldw; a column slice is a pointer offset), both
+ * read as stored, once (bf16 MFMA, fp32 accumulate).  The rows are dealt to S splits of whole TR1_LORA_WGRAD_MCHUNK-row chunks, S the largest count that keeps
+ * S * ceil(Wd / TR1_LORA_WGRAD_COLS) at or below TR1_LORA_WGRAD_BLOCKS (at least 1, at most the number of chunks) - a function of (M, Wd) alone; S > 1 goes
+ * through S fp32 planes of r * Wd floats in ws_f32, added in ascending order: the same inputs give the same bits.  Wd, ldt, ldw multiples of 8; thin and wide
+ * 16-byte aligned. */
+#define TR1_LORA_WGRAD_MCHUNK 256
+#define TR1_LORA_WGRAD_COLS 64
+#define TR1_LORA_WGRAD_BLOCKS 1024
+int tr1_lora_merge(void* W_bf16, int64_t ldw, const void* W0_bf16, int64_t ldw0, const void* A_f32, const void* Bt_f32, int64_t out, int64_t in, int64_t r, float s, void* stream);
+int tr1_lora_wgrad(void* G_f32, int64_t ldg, const void* thin_bf16, int64_t ldt, const void* wide_bf16, int64_t ldw, int64_t M, int64_t Wd, int64_t r, float scale, int accumulate, void* ws_f32, int64_t ws_floats, void* stream);
+
 /* ---- Collectives (rccl_{init, allreduce, reduce_scatter, allgather}) ------------------------------------------------------------------
  * There is ONE exchange path: time-r1_amd/dist.py drives RCCL through torch.distributed's "nccl" backend (which IS librccl on ROCm): per-segment
  * all-reduce (GradSync) or reduce-scatter + all-gather (ShardSync) of the bf16 wire arena, overlapped with the backward.  The round-4/5

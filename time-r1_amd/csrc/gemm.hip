@@ -309,11 +309,6 @@ TR1_DEV float epi_silu(float x) { return x / (1.f + __expf(-x)); }
 // back TRANSPOSED with ds_read_b64_tr_b16 (a 16-lane group reads a 4 x 16 block, each lane supplying an 8-byte address and receiving one
 // column), so no W^T copy is ever built.  With 512-byte rows eight k-rows of a half-wave share their banks; the key spreads them over the
 // four translates a 16-byte-granular swizzle can reach (2-way conflicts on these reads, 8 of the 24 fragment reads of a tile).
-typedef __attribute__((ext_vector_type(4))) short gemm_s16x4_t;
-TR1_DEV u32x2_t gemm_lds_read_tr16(const char* p) {
-    const gemm_s16x4_t v = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) gemm_s16x4_t*)(p));
-    return __builtin_bit_cast(u32x2_t, v);
-}
 TR1_DEV int keyKM(int krow) { return (krow & 1) | ((krow & 2) << 2); }
 TR1_DEV void stage_round_km(const bf16_t* __restrict__ g, int64_t ld, int64_t n0, int64_t n_valid, int64_t k0, int64_t k_valid, char* lds_region,
                             int round, int wave, int lane) {
@@ -708,7 +703,7 @@ __global__ __launch_bounds__(512) void gemm_nt8p_kernel(const bf16_t* __restrict
                 for (int ks = 0; ks < 2; ++ks) {
                     const int lc = wn * 8 + (u & 3) * 2 + (j >> 1);                                    // logical 16-byte chunk of the piece
                     const char* pb = curB + (ks * 32 + bkm_row) * 512 + ((lc ^ bkm_key) << 4) + (j & 1) * 8;
-                    const u32x2_t h0 = gemm_lds_read_tr16(pb), h1 = gemm_lds_read_tr16(pb + 4 * 512);    // rows +4: same key (low two bits unchanged)
+                    const u32x2_t h0 = tr1_lds_read_tr16(pb), h1 = tr1_lds_read_tr16(pb + 4 * 512);    // rows +4: same key (low two bits unchanged)
                     u32x4_t w = {h0[0], h0[1], h1[0], h1[1]};
                     bf[j][ks] = __builtin_bit_cast(bf16x8_t, w);
                 }

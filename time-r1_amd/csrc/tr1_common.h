@@ -102,6 +102,12 @@ TR1_DEV void philox4x32_10(unsigned c[4], unsigned k0, unsigned k1) {
 // ---- what every kernel with a DMA-staged 128-byte-row LDS image shares (GEMMs, decode projections) ----
 typedef const __attribute__((address_space(1))) void* gptr_t;      // operand types of __builtin_amdgcn_global_load_lds
 typedef __attribute__((address_space(3))) void* lptr_t;
+// Transposing LDS read (ds_read_b64_tr_b16): a 16-lane group reads a 4 x 16 block of 16-bit elements, each lane supplying an 8-byte address and receiving one column.
+typedef __attribute__((ext_vector_type(4))) short tr1_s16x4_t;
+TR1_DEV u32x2_t tr1_lds_read_tr16(const char* p) {
+    const tr1_s16x4_t v = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) tr1_s16x4_t*)(p));
+    return __builtin_bit_cast(u32x2_t, v);
+}
 TR1_DEV int keyA(int row) { return (row >> 1) & 7; }               // row r keeps its logical 16-byte chunk c at position c ^ keyA(r): conflict-free 16-row fragment reads
 // raw s_barrier pinned against the scheduler (no vmcnt(0) / lgkmcnt(0) drain as __syncthreads has: DMA stays in flight across it)
 #define TR1_PIN() do { asm volatile("" ::: "memory"); __builtin_amdgcn_sched_barrier(0); } while (0)

@@ -93,7 +93,8 @@ class GRPOCore:
         if self.beta != 0.0 and with_ref:
             fl += self._llm_flops(M, pairs_all) + head                                                           # reference-policy forward (a replay reuses its log-probs)
         lin_all = self._llm_flops(M, 0.0)
-        fl += 2.0 * lin_all + 2.5 * (self._llm_flops(M, pairs_all) - lin_all) + 2.0 * head                       # backward (dgrad + wgrad; flash backward = 5 products)
+        wg = 1.0 if self.eng.lora is not None else 2.0      # LoRA mode: no full-size weight gradients (the rank-r products are below 1 % of a dgrad and not counted)
+        fl += wg * lin_all + 2.5 * (self._llm_flops(M, pairs_all) - lin_all) + wg * head                         # backward (dgrad + wgrad; flash backward = 5 products)
         self.work["train_flops"] += fl
 
     # ------------------------------------------------------------------------------------------------------- phase 1
@@ -128,7 +129,8 @@ class GRPOCore:
             pp[:, : v.patch_dim] = pix.to(pp.device).to(pp.dtype)
         st.feats, st.vis_perm = eng.vit_features(pp, grid)        # frozen blocks: once per prompt (reference: 3 x G times)
         st.pixels = pp if eng.params.train_vit else None          # fix_vit=False: the reference tower and the backward's recompute read them again
-        st.vid_embeds, st.merger_ctx = eng.merger_fwd(eng.params.train, st.feats, save=True, perm=st.vis_perm)
+        # (LoRA mode: the merger is frozen, its backward never runs - nothing of it is kept)
+        st.vid_embeds, st.merger_ctx = eng.merger_fwd(eng.params.train, st.feats, save=eng.lora is None, perm=st.vis_perm)
         return st
 
     # ------------------------------------------------------------------------------------------------------- phase 2
@@ -193,13 +195,14 @@ class GRPOCore:
         if replay:
             if eng.params.train_vit:
                 st.feats = eng.vit_features(st.pixels, st.grid)[0]
-            st.vid_embeds, st.merger_ctx = eng.merger_fwd(tr, st.feats, save=True, perm=st.vis_perm)
+            st.vid_embeds, st.merger_ctx = eng.merger_fwd(tr, st.feats, save=eng.lora is None, perm=st.vis_perm)
             st.prefill = None
         else:
             self._packed_inputs(st)
         pf = getattr(st, "prefill", None)
-        self._count_update(st, pf is not None and pf[0] is not None, with_ref=not replay)
-        if pf is not None and pf[0] is not None:
+        split = pf is not None and pf[0] is not None
+        self._count_update(st, split, with_ref=not replay)
+        if split:
             # continuation: only the G*C completion rows; the prompt rows' activations and K/V come from the rollout's prefill
             P, M = st.P, st.layout.M
             pctx, kv = pf
@@ -233,10 +236,50 @@ class GRPOCore:
             # fix_vit=False: the reference policy's features come from the INITIAL tower (its copy in the reference arena, reference :295-307)
             ref_feats = eng.vit_features(st.pixels, st.grid, arena=ra)[0] if eng.params.train_vit else st.feats
             ref_vid, _ = eng.merger_fwd(ra, ref_feats, save=False, perm=st.vis_perm)
-            h0r = eng.embed(ra, st.ids_packed, ref_vid, st.vid_rows)
-            hLr, _ = eng.llm_fwd(ra, h0r, st.cos, st.sin, st.masks, save=False, tail_from=eng.tail_rows_from(st.P, st.layout.M))
-            rlogp, _, _ = eng.head_fwd(ra, hLr, st.pred_rows, st.targets, save=False)
+            if split and eng.lora is not None:
+                hLr = self._ref_split_fwd(st, ra, ref_vid)
+            else:
+                h0r = eng.embed(ra, st.ids_packed, ref_vid, st.vid_rows)
+                hLr, _ = eng.llm_fwd(ra, h0r, st.cos, st.sin, st.masks, save=False, tail_from=eng.tail_rows_from(st.P, st.layout.M))
+            rlogp, _, _ = eng.head_fwd(ra, hLr, st.pred_rows, st.targets, save=False, **({"as_saved": True} if eng.lora is not None else {}))
             st.ref_logp = self._to_gc(st, rlogp).contiguous()
+
+    def _ref_split_fwd(self, st, ra, ref_vid):
+        """LoRA mode: the reference policy's decoder pass in the policy's own two launches - the prompt's P rows as the rollout's prefill runs them, then the
+        G*C completion rows over a K/V cache - instead of one pass over all P + G*C rows.  The work is the same; the point is the bits: a GEMM's tile and
+        its summation order follow the row count, so the one-pass form gives log-probs that differ from the policy's in a last bf16 place even on equal
+        weights (measured on tiny_test_25: 12 of 32, step-0 KL 5.6e-8).  Under peft the reference IS the policy with its adapters switched off - one code
+        path - and KL is exactly 0 until the adapters move; here the base copy takes the same path as the merged weights, launch for launch, for that.
+        The reference's cache (K, and V row-major or transposed as the attention kernel of this head dim reads it) is kept between calls: at 7B and
+        5.1k rows 0.29 GB.  Full-parameter training keeps the one-pass form: its reference is a model of its own, as the reference trainer's is."""
+        eng, ops, t, lay = self.eng, self.ops, self.cfg.text, st.layout
+        P, M = st.P, lay.M
+        kv, vc = self._ref_cache(lay.S_cap)
+        pos_p = ops.tensor(np.ascontiguousarray(st.pos3_prompt.astype(np.int32)), I32)
+        cos_p, sin_p = ops.mrope_table(pos_p, t.head_dim, t.mrope_section, t.rope_theta)
+        h = eng.embed(ra, st.prompt_ids, ref_vid, st.vid_rows)
+        hp, _ = eng.llm_fwd(ra, h, cos_p, sin_p, [ops.tensor(a, I32) for a in lay.prompt_masks()], save=False, kv_cache=kv, v_cache=vc,
+                            tail_from=eng.tail_rows_from(P, M))
+        hc = ops.gather_rows(ra.w("embed"), st.ids_packed[P:].contiguous())
+        hLc, _ = eng.llm_fwd(ra, hc, st.cos[P:].contiguous(), st.sin[P:].contiguous(), [m[P:].contiguous() for m in st.masks], save=False, kv_cache=kv,
+                             v_cache=vc, row0=P)
+        hL = ops.zeros(M, hLc.shape[1])
+        hL[P:] = hLc
+        hL[P - 1:P] = hp[P - 1:P]
+        return hL
+
+    def _ref_cache(self, s_cap):
+        """-> (per layer (K [cap, kv_dim], V^T [kv_dim, cap] or None), per layer V [cap, kv_dim] or None), cap >= s_cap, kept while it is large enough."""
+        eng, ops, t = self.eng, self.ops, self.cfg.text
+        c = getattr(self, "_ref_kv", None)
+        if c is None or c[0] < s_cap:
+            self._ref_kv = None      # release before re-allocating
+            cap = (s_cap + 511) // 512 * 512
+            rows = getattr(ops, "attn_fwd_rows_ok", lambda *a, **kw: False)(t.head_dim)
+            k = [ops.zeros(cap, t.kv_dim) for _ in range(t.n_layers)]
+            vt = [None if rows else ops.zeros(t.kv_dim, cap) for _ in range(t.n_layers)]
+            c = self._ref_kv = (cap, list(zip(k, vt)), [ops.zeros(cap, t.kv_dim) for _ in range(t.n_layers)] if rows else None)
+        return c[1], c[2]
 
     # ------------------------------------------------------------------------------------------------------- phase 4
     def loss_backward(self, st, completion_mask, advantages, grad_scale=1.0, grad_sync=None, tok_weight=None, old_logp=None, eps=(0.2, 0.2),
@@ -252,7 +295,7 @@ class GRPOCore:
         eng, ops = self.eng, self.ops
         tr = eng.params.train
         hook = None
-        if grad_sync is not None and grad_sync.active:
+        if grad_sync is not None and grad_sync.active and eng.lora is None:      # (LoRA mode: the adapters' small exchange happens in the optimizer step)
             hook = lambda i: grad_sync.ready(*tr.range_of("l%d." % i))
         if self.top_entropy_quantile < 1.0:
             # the entropy of THIS forward (a replay selects on its own, as trl recomputes the mask in every compute_loss); it multiplies with an importance cap
@@ -306,6 +349,12 @@ class GRPOCore:
             grad_sync.ready(*tr.range_of("norm"))          # final norm + untied lm_head gradients are complete after the head backward
             grad_sync.ready(*tr.range_of("lm_head"))
         dh0 = eng.llm_bwd(st.llm_ctx, dh, on_layer_done=hook)
+        if eng.lora is not None:
+            # LoRA mode: embedding, merger and vision tower are frozen (as under peft) - the backward ends at the decoder's input
+            st.llm_ctx = st.head_ctx = st.merger_ctx = None
+            if not keep_pixels:
+                st.pixels = None
+            return out3, row_len
         ids_g = st.ids_packed.clone()
         ids_g[st.vid_rows.long()] = -1
         dvid = eng.embed_bwd(dh0, ids_g, st.vid_rows)

@@ -45,6 +45,9 @@ class Engine:
         # matrices then also leave the squared norm of the final gradient (AdamWFlat.norm_sink_begin / step)
         self.norm_sink = None
         self.bwd_count = 0                   # decoder backward passes run so far: a sink is only valid if its backward was the LAST one before the step
+        # LoRA mode (lora.LoraAdapters, set by the owner of the optimizer): the base weights are frozen and params.train holds no gradient buffer.  llm_bwd then
+        # runs the adapters' rank-r gradients where the weight gradients were and head_bwd only the data gradient; None changes no call, launch or allocation
+        self.lora = None
         assert cfg.vision.variant in ("qwen2_vl", "qwen2_5_vl"), cfg.vision.variant
 
     # ================================================================================================= gradient helpers
@@ -495,12 +498,14 @@ class Engine:
             return None
         return P - 1
 
-    def llm_fwd(self, arena: Arena, h, cos, sin, masks, save, kv_cache=None, row0=0, bufs=None, tail_from=None):
+    def llm_fwd(self, arena: Arena, h, cos, sin, masks, save, kv_cache=None, row0=0, bufs=None, tail_from=None, v_cache=None):
         """Decoder stack over a packed sequence of M rows. masks = (pre, lo, hi) int32 [M] over slots == rows.
         kv_cache: optional list of (K [S_cap, kv_dim], VT [kv_dim, S_cap]) to be filled (rollout prefill).
         row0 > 0 ("continuation"): h holds only rows [row0, row0+M) of the packed sequence; their K/V are written to cache slots
         [row0, row0+M) and attention runs over slots [0, row0+M) - the prefix K/V of rows [0,row0) must already be in kv_cache.
         bufs (alloc_ctx_bufs): saved activations are written into rows [row0, row0+M) of these buffers instead of fresh tensors.
+        v_cache (with kv_cache, save=False): per layer a row-major V buffer [S_cap, kv_dim] standing where bufs' "v" stands for a saved pass - where the
+        row-major attention kernel takes the launch, V is written there, read from there, and no V^T is built (the cache's V^T entry may be None).
         tail_from (packed row index): the caller reads the stack's output only at rows >= tail_from (log-probs: the last prompt row and the completion
         rows; rollout prefill: the last prompt row).  The LAST layer's o projection and MLP then run on those rows only - the other rows' outputs feed
         nothing (their K / V, which later rows and the decode do read, come from the layer's input) - and rows < tail_from of the returned tensor and of the
@@ -541,13 +546,16 @@ class Engine:
             kc = vtc = None
             if kv_cache is not None:
                 kc, vtc = kv_cache[i]
+            vc = v_cache[i] if (v_cache is not None and kv_cache is not None and rows_ok) else None
             q, k, v = ops.gemm_qkv_rope(xn, arena.w(p + "qkv.w"), arena.w(p + "qkv.b"), cos, sin, t.n_heads, t.n_kv_heads, hd, q_out=dst(i, "q"),
-                                        k_out=kc[row0:S] if kc is not None else None, v_out=dst(i, "v"))
+                                        k_out=kc[row0:S] if kc is not None else None, v_out=vc[row0:S] if vc is not None else dst(i, "v"))
             # head dim 128: the forward kernel reads V row-major (it transposes in its LDS reads); V^T is then only built where a later decode
             # needs it in the cache (rollout prefill / continuation), not for the reference-policy and plain training forwards
             v_rows = None
             if kv_cache is not None:
-                if row0 == 0:
+                if vc is not None:
+                    v_rows, vt = vc[:S], None
+                elif row0 == 0:
                     vt = ops.pack_transpose(v, t.n_kv_heads, t.n_kv_heads, hd, out=vtc)
                     v_rows = v if rows_ok else None
                 else:
@@ -632,7 +640,8 @@ class Engine:
         # activation_recompute="mlp": the same, for another reason.  Every layer rebuilds xn / xn2 / gu / a into the ONE transient set (recompute_set) on the main
         # stream; a weight gradient still reading the layer above's xn2 or xn on the side stream would race with that.  On one stream launch order is the order.
         rc = self.recompute_mlp
-        side = None if (rc or self.ctx_bytes(dh.shape[0]) > self.CTX_STASH_GB * 1e9) else self._side_stream()
+        lora = self.lora          # LoRA mode: adapter gradients on the main stream (they accumulate into the adapter arena), no norm-weight or bias gradients
+        side = None if (rc or lora is not None or self.ctx_bytes(dh.shape[0]) > self.CTX_STASH_GB * 1e9) else self._side_stream()
         pending = None
         a_shared = not rc and t.n_layers > 1 and ctx["layers"][0]["a"].data_ptr() == ctx["layers"][1]["a"].data_ptr()
         T = self.recompute_set(dh.shape[0]) if rc else None
@@ -661,14 +670,22 @@ class Engine:
             # none 164, down + qkv 161, o or down + gate/up 174 ms).  With a_shared it has to be there: its operand is rebuilt on the main stream
             if a_shared:                  # one SwiGLU-output buffer for all layers (alloc_ctx_bufs): rebuild this layer's rows from its gate/up tensor, main stream
                 ops.swiglu_fwd(L["gu"], out=L["a"])
-            self._wgrad_async(dh, L["a"], tr.g(p + "down.w"), None, key=p + "down.w")
-            # down-projection dgrad with the SwiGLU backward in its epilogue, which also leaves dgu^T (the gate/up weight gradient's operand) from its LDS staging
-            dgu, dgut = ops.dgrad_glu_bwd(dh, tr.w(p + "down.w"), L["gu"], want_t=True)
-            self._wgrad_async(dgu, L["xn2"], tr.g(p + "gu.w"), side, key=p + "gu.w", dyt=dgut)
+            if lora is not None:
+                lora.wgrad(i, "down", dh, L["a"])
+                dgu = ops.dgrad_glu_bwd(dh, tr.w(p + "down.w"), L["gu"], want_t=False)      # (no dgu^T: no full-size gate/up weight gradient reads it)
+                lora.wgrad(i, "gu", dgu, L["xn2"])
+            else:
+                self._wgrad_async(dh, L["a"], tr.g(p + "down.w"), None, key=p + "down.w")
+                # down-projection dgrad with the SwiGLU backward in its epilogue, which also leaves dgu^T (the gate/up weight gradient's operand) from its LDS staging
+                dgu, dgut = ops.dgrad_glu_bwd(dh, tr.w(p + "down.w"), L["gu"], want_t=True)
+                self._wgrad_async(dgu, L["xn2"], tr.g(p + "gu.w"), side, key=p + "gu.w", dyt=dgut)
             dxn2 = self._dgrad(dgu, tr.w(p + "gu.w"), key=p + "gu.w")
-            dh2 = ops.rmsnorm_bwd(dxn2, L["h2"], tr.w(p + "ln2"), L["rstd2"], dres=dh, dw=tr.g(p + "ln2"))
+            dh2 = ops.rmsnorm_bwd(dxn2, L["h2"], tr.w(p + "ln2"), L["rstd2"], dres=dh, dw=None if lora is not None else tr.g(p + "ln2"))
             # h2 = o @ Wo^T + h
-            self._wgrad_async(dh2, L["o"], tr.g(p + "o.w"), side, key=p + "o.w")
+            if lora is not None:
+                lora.wgrad(i, "o", dh2, L["o"])
+            else:
+                self._wgrad_async(dh2, L["o"], tr.g(p + "o.w"), side, key=p + "o.w")
             do = self._dgrad(dh2, tr.w(p + "o.w"), key=p + "o.w")
             if tail:                                  # back to all rows for the attention backward (every row's K / V took part): zero gradient above the tail
                 L = Lf
@@ -683,9 +700,12 @@ class Engine:
                 L = dict(L, xn=T["xn"])
                 for r0, r1 in L["rows"]:
                     ops.rmsnorm_fwd(L["h"][r0:r1], tr.w(p + "ln1"), t.rms_eps, need_rstd=False, out=T["xn"][r0:r1])
-            self._wgrad_async(dqkv, L["xn"], tr.g(p + "qkv.w"), side, key=p + "qkv.w", bias_g=tr.g(p + "qkv.b"))
+            if lora is not None:
+                lora.wgrad(i, "qkv", dqkv, L["xn"])
+            else:
+                self._wgrad_async(dqkv, L["xn"], tr.g(p + "qkv.w"), side, key=p + "qkv.w", bias_g=tr.g(p + "qkv.b"))
             dxn = self._dgrad(dqkv, tr.w(p + "qkv.w"), key=p + "qkv.w")
-            dh = ops.rmsnorm_bwd(dxn, L["h"], tr.w(p + "ln1"), L["rstd1"], dres=dh2, dw=tr.g(p + "ln1"))
+            dh = ops.rmsnorm_bwd(dxn, L["h"], tr.w(p + "ln1"), L["rstd1"], dres=dh2, dw=None if lora is not None else tr.g(p + "ln1"))
             ctx["layers"][i] = None  # release this layer's activations
             if on_layer_done is not None:
                 if side is not None:
@@ -718,16 +738,18 @@ class Engine:
     # and the backward recomputes a chunk's logits with one more lm_head GEMM (~1 ms per 1024 rows at 7B) instead of holding [G*C, V].
     HEAD_CHUNK_ROWS = 4096
 
-    def head_fwd(self, arena: Arena, h_last, pred_rows, targets, save):
+    def head_fwd(self, arena: Arena, h_last, pred_rows, targets, save, as_saved=False):
         """Final norm + lm_head on the rows that predict completion tokens only, then per-token log-prob and entropy
-        (reference _get_per_token_logps materialises logits for all (G, L, V) - SURVEY 0.6)."""
+        (reference _get_per_token_logps materialises logits for all (G, L, V) - SURVEY 0.6).
+        as_saved (with save=False): take the launches a save=True call takes - up to HEAD_CHUNK_ROWS rows the logits are written and reduced by
+        logp_entropy_fwd, not in the lm_head epilogue, whose sum runs in another order (a last fp32 place) - and keep nothing."""
         ops, t = self.ops, self.cfg.text
         hp = ops.gather_rows(h_last, pred_rows)
         hn, rstd, _ = ops.rmsnorm_fwd(hp, arena.w("norm"), t.rms_eps, need_rstd=save)
         w = self.params.lm_head_w(arena)
         R, ch = hp.shape[0], self.HEAD_CHUNK_ROWS
         fused = None
-        if (not save or R > ch) and hasattr(ops, "lmhead_lse"):
+        if (not (save or as_saved) or R > ch) and hasattr(ops, "lmhead_lse"):
             # nobody reads these logits again (reference-policy forward; the large-R policy forward recomputes them chunk by chunk in the
             # backward): lm_head with the log-softmax statistics reduced in the GEMM epilogue - no [R, V] tensor in HBM at all
             fused = ops.lmhead_lse(hn, w, targets)
@@ -751,13 +773,15 @@ class Engine:
         dent (fp32 [R], pred_rows order): the gradient arriving at the entropy (an entropy term in the loss); it joins dlogp in the one pass over the logits
         (logp_entropy_bwd, with the forward's own lse and entropy).  None: the entropy is a logged number and the pass is logp_bwd."""
         ops, t, tr = self.ops, self.cfg.text, self.params.train
-        w, gw = self.params.lm_head_w(), self.params.lm_head_g()
+        frozen = self.lora is not None      # LoRA mode: lm_head and the final norm are frozen - only the data gradient runs
+        w, gw = self.params.lm_head_w(), (None if frozen else self.params.lm_head_g())
         if ctx["logits"] is not None:
             if dent is None:
                 dlogits = ops.logp_bwd(ctx["logits"], ctx["targets"], ctx["lse"], dlogp, inplace=True)
             else:
                 dlogits = ops.logp_entropy_bwd(ctx["logits"], ctx["targets"], ctx["lse"], ctx["ent"], dlogp, dent, inplace=True)
-            self._wgrad(dlogits, ctx["hn"], gw, key="lm_head.w")        # first micro-step of a window: overwrite (the optimizer left it zero: same result, no 2.2 GB read)
+            if not frozen:
+                self._wgrad(dlogits, ctx["hn"], gw, key="lm_head.w")        # first micro-step of a window: overwrite (the optimizer left it zero: same result, no 2.2 GB read)
             dhn = self._dgrad(dlogits, w, key="lm_head")
             ctx["logits"] = None
         else:           # chunked: recompute a chunk's logits, turn them into dlogits in place, feed both gradient GEMMs, drop them
@@ -771,10 +795,11 @@ class Engine:
                 else:
                     dl = ops.logp_entropy_bwd(lg, ctx["targets"][a:b].contiguous(), ctx["lse"][a:b].contiguous(), ctx["ent"][a:b].contiguous(),
                                               dlogp[a:b].contiguous(), dent[a:b].contiguous(), inplace=True)
-                self._wgrad(dl, hn[a:b], gw, key="lm_head.w")           # (only the window's first chunk overwrites; later chunks and micro-steps accumulate)
+                if not frozen:
+                    self._wgrad(dl, hn[a:b], gw, key="lm_head.w")           # (only the window's first chunk overwrites; later chunks and micro-steps accumulate)
                 dhn[a:b] = self._dgrad(dl, w, key="lm_head")
                 del lg, dl
-        dhp = ops.rmsnorm_bwd(dhn, ctx["hp"], tr.w("norm"), ctx["rstd"], dw=tr.g("norm"))
+        dhp = ops.rmsnorm_bwd(dhn, ctx["hp"], tr.w("norm"), ctx["rstd"], dw=None if frozen else tr.g("norm"))
         d = dhp.shape[1]
         dh = ops.zeros(ctx["M"], d)
         acc = ops.zeros(d, dtype=F32)

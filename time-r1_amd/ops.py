@@ -921,6 +921,63 @@ class HipOps:
         self.L.call("tr1_ref_mixup", _p(ref_w16), _p(policy_w16), ref_w16.numel(), float(alpha), _p(sums), _p(ws), 4096, self._s())
         return sums
 
+    # ---- LoRA (peft_config; csrc/lora.hip) ------------------------------------------------------------------------------
+    @classmethod
+    def lora_wgrad_splits(cls, M, Wd):
+        """(S, rows per split) tr1_lora_wgrad deals the M rows of an [M, Wd] operand to: whole LORA_WGRAD_MCHUNK-row chunks, a function of (M, Wd) alone
+        (include/timer1_hip.h states the rule; S > 1 needs S * r * Wd floats of workspace)."""
+        ch = cls.LORA_WGRAD_MCHUNK
+        ntile, nchunk = (int(Wd) + cls.LORA_WGRAD_COLS - 1) // cls.LORA_WGRAD_COLS, (int(M) + ch - 1) // ch
+        want = min(max(cls.LORA_WGRAD_BLOCKS // ntile, 1), nchunk)
+        per = (nchunk + want - 1) // want
+        return (nchunk + per - 1) // per, per * ch
+
+    def lora_merge(self, w, w0, a, bt, s):
+        """w[out, in] = bf16_rne(w0 + s * bt^T a) with a fp32 [r, in], bt fp32 [r, out] (the adapter masters; r in {16, 32, 64}) and w / w0 bf16 views of the
+        same shape (row slices of a fused matrix included).  fp32 arithmetic in a pinned order, one rounding to bf16 (tr1_lora_merge)."""
+        self._chk(w, w0)
+        self._chk(a, bt, dtype=F32)
+        out, in_ = w.shape
+        r = a.shape[0]
+        assert w0.shape == (out, in_) and a.shape == (r, in_) and bt.shape == (r, out) and a.is_contiguous() and bt.is_contiguous()
+        self.L.call("tr1_lora_merge", _p(w), _ld(w), _p(w0), _ld(w0), _p(a), _p(bt), out, in_, r, float(s), self._s())
+        return w
+
+    LORA_WGRAD_KERNEL = True      # class attribute for A/B runs (tools/bench_lora.py): False = the composition below for every shape
+
+    def lora_wgrad_covers(self, g, thin, wide):
+        """True where tr1_lora_wgrad takes the product; elsewhere lora_wgrad composes it from a transposed copy and gemm_nt.  The kernel measured 0.31 - 0.52 of
+        the composition's time on all eight operand shapes of the 7B backward at r = 16 and 64 (BASELINE 4m), so no covered shape is routed away from it."""
+        M, Wd = wide.shape
+        r = thin.shape[1]
+        return bool(self.LORA_WGRAD_KERNEL and r in (16, 32, 64) and M >= 1 and Wd >= 8 and Wd % 8 == 0 and wide.stride(1) == 1 and thin.stride(1) == 1
+                    and wide.stride(0) % 8 == 0 and thin.stride(0) % 8 == 0 and wide.data_ptr() % 16 == 0 and thin.data_ptr() % 16 == 0 and g.stride(1) == 1)
+
+    def lora_wgrad(self, g, thin, wide, scale, accumulate=True):
+        """g[r, Wd] fp32 (+)= scale * thin[M, r]^T @ wide[M, Wd] - the rank-r weight gradients of a LoRA adapter (dBt = s u^T dY, dA = s v^T x).  Both bf16
+        operands are read as stored, once; `wide` may be a column slice.  Same inputs, same bits (the split over M is a function of the shape)."""
+        self._chk(thin, wide)
+        M, Wd = wide.shape
+        r = thin.shape[1]
+        assert thin.shape[0] == M and g.dtype == F32 and g.shape == (r, Wd) and g.device.type == "cuda"
+        if not self.lora_wgrad_covers(g, thin, wide):
+            return self.lora_wgrad_composed(g, thin, wide, scale, accumulate)
+        S, _ = self.lora_wgrad_splits(M, Wd)
+        nws = S * r * Wd if S > 1 else 0
+        ws = self._workspace("lora_wgrad", nws, F32) if nws else None
+        self.L.call("tr1_lora_wgrad", _p(g), _ld(g), _p(thin), _ld(thin), _p(wide), _ld(wide), M, Wd, r, float(scale), int(bool(accumulate)), _p(ws), nws, self._s())
+        return g
+
+    def lora_wgrad_composed(self, g, thin, wide, scale, accumulate=True):
+        """The same product from the launchers that predate tr1_lora_wgrad: transposed copies of both operands (rows zero-padded to a multiple of 64), then a
+        gemm_nt with r output rows into fp32 - three passes over `wide` where the kernel makes one.  Serves the shapes the kernel does not cover."""
+        prod = self.gemm_nt(self.transpose(thin), self.transpose(wide), out_f32=True)
+        if accumulate:
+            g.add_(prod, alpha=float(scale))
+        else:
+            g.copy_(prod * float(scale))
+        return g
+
     def wgrad_sumsq(self, a, b, gw, accumulate, partials, offset, b_kmajor=False, b_rows=0, wire=None):
         """gw[N, K] fp32 (+)= a[N, Mp] @ b^T (b = X^T [K, Mp]) or a @ b (b_kmajor: b = X [>= b_rows, K] as stored), and partials[offset : offset + n] receives
         the per-wave sums of squares of the values stored (n returned; -1 when the shape is not covered and nothing was launched)."""
@@ -990,3 +1047,9 @@ class HipOps:
         assert int(index_base) >= 0 and 0 <= int(seed) < (1 << 64)
         self.L.call("tr1_adamw_step_sr16", _p(p32), _p(m16), _p(v16), _p(g), _p(g16), _p(p16), n, float(lr), float(beta1), float(beta2), float(eps),
                     float(weight_decay), int(step), _p(sumsq), float(max_norm), float(grad_mult), int(zero_grad), int(seed), int(index_base), self._s())
+
+
+# the split geometry of tr1_lora_wgrad, as include/timer1_hip.h states it (the library checks the same numbers when it is built)
+HipOps.LORA_WGRAD_MCHUNK = HipOps._header_define("TR1_LORA_WGRAD_MCHUNK")
+HipOps.LORA_WGRAD_COLS = HipOps._header_define("TR1_LORA_WGRAD_COLS")
+HipOps.LORA_WGRAD_BLOCKS = HipOps._header_define("TR1_LORA_WGRAD_BLOCKS")

@@ -202,12 +202,15 @@ def arena_specs(cfg: ModelConfig, train_vit=False):
 class ModelParams:
     """Qwen2-VL parameters: `train` arena (LLM + merger, + ViT with train_vit) and `frozen` arena (ViT, empty with train_vit)."""
 
-    def __init__(self, cfg: ModelConfig, ops, seed=0, init="random", optimizer_state=True, train_vit=False, moment_dtype=torch.float32):
+    def __init__(self, cfg: ModelConfig, ops, seed=0, init="random", optimizer_state=True, train_vit=False, moment_dtype=torch.float32, with_grad=True):
+        """with_grad=False (with optimizer_state=False): the `train` arena holds the bf16 weights only - no gradient buffer, master or moments.  LoRA
+        (lora.py) trains its own small arena and keeps the base model this way: 2 of the 18 bytes per parameter."""
         self.cfg = cfg
         self.ops = ops
         self.train_vit = bool(train_vit)
         trs, fzs = arena_specs(cfg, self.train_vit)
-        self.train = Arena(ops, trs, with_optimizer_state=optimizer_state, with_grad=True, moment_dtype=moment_dtype)
+        assert with_grad or not optimizer_state, "optimizer state without a gradient buffer"
+        self.train = Arena(ops, trs, with_optimizer_state=optimizer_state, with_grad=bool(with_grad), moment_dtype=moment_dtype)
         self.frozen = Arena(ops, fzs, with_optimizer_state=False)
         if init == "random":
             self.init_random(seed)
@@ -231,6 +234,12 @@ class ModelParams:
                 dst.w(name).copy_(src.w(name))
         out.train.sync_master_from_w16()
         return out
+
+    def drop_training_state(self):
+        """Release the `train` arena's gradient buffer, fp32 master and moments (LoRA mode: the base weights are frozen); the bf16 weights stay."""
+        a = self.train
+        a.grad = a.master = a.m = a.v = None
+        return self
 
     # lm_head is tied to the embedding for the 2B model (shared storage -> shared gradient view)
     def lm_head_w(self, arena=None):

@@ -514,6 +514,30 @@ def _(ref, policy, alpha):
     return ref.new_empty(2, dtype=F32)
 
 
+@_op("lora_merge", mutates_args=("w",))
+def lora_merge(w: Tensor, w0: Tensor, a: Tensor, bt: Tensor, s: float) -> None:
+    """peft's merged LoRA weight from the frozen base copy: w[out, in] = bf16_rne(w0 + s * bt^T a) with fp32 adapters a [r, in], bt [r, out] (lora_B stored
+    transposed), r in {16, 32, 64}; fp32 arithmetic in a pinned order, one rounding to bf16.  w / w0 may be row slices of a fused matrix."""
+    _ops(w).lora_merge(w, w0, a, bt, s)
+
+
+@lora_merge.register_fake
+def _(w, w0, a, bt, s):
+    return None
+
+
+@_op("lora_wgrad", mutates_args=("g",))
+def lora_wgrad(g: Tensor, thin: Tensor, wide: Tensor, scale: float, accumulate: bool) -> None:
+    """g[r, Wd] fp32 (+)= scale * thin[M, r]^T @ wide[M, Wd] (bf16 operands as stored; wide may be a column slice): the rank-r weight gradients of a LoRA
+    adapter.  The same inputs give the same bits."""
+    _ops(g).lora_wgrad(g, thin, wide, scale, accumulate)
+
+
+@lora_wgrad.register_fake
+def _(g, thin, wide, scale, accumulate):
+    return None
+
+
 @_op("video_preprocess")
 def video_preprocess(frames_u8: Tensor, out_h: int, out_w: int, k_pad: int) -> Tensor:
     """uint8 [T,3,H,W] -> bf16 [N_v, k_pad] normalised patches in the HF video processor's layout (resize + rescale + normalise + patchify)."""
@@ -528,7 +552,7 @@ def _(frames_u8, out_h, out_w, k_pad):
 
 OP_NAMES = ["rmsnorm_fwd", "rmsnorm_bwd", "swiglu_fwd", "swiglu_bwd", "linear_fwd", "linear_bwd", "rope_fwd", "mrope_table", "attn_fwd", "attn_bwd",
             "logp_entropy_fwd", "logp_bwd", "logp_entropy_bwd", "entropy_quantile_weight", "lmhead_logp_entropy", "grpo_loss", "grpo_loss_ratio", "grpo_policy_loss", "sample_tokens", "sample_tokens_filtered", "penalize_logits", "mark_seen_ids",
-            "mark_seen_drawn", "adamw_step", "adamw_step_sr16", "ref_mixup", "video_preprocess"]
+            "mark_seen_drawn", "adamw_step", "adamw_step_sr16", "ref_mixup", "lora_merge", "lora_wgrad", "video_preprocess"]
 
 
 # ================================================================================================ dropping the ops into an HF model

@@ -356,7 +356,7 @@ def config_from_hf(hc, name="model"):
     return cfg
 
 
-def load_model_dir(path, ops, train_vit=False, moment_dtype=torch.float32):
+def load_model_dir(path, ops, train_vit=False, moment_dtype=torch.float32, **params_kw):
     """HF checkpoint directory (config.json + *.safetensors) -> (ModelConfig, ModelParams); train_vit: the tower in the trainable arena."""
     from safetensors.torch import load_file
     cfg = config_from_hf(json.load(open(os.path.join(path, "config.json"))), name=os.path.basename(os.path.normpath(path)))
@@ -364,17 +364,17 @@ def load_model_dir(path, ops, train_vit=False, moment_dtype=torch.float32):
     for f in sorted(os.listdir(path)):
         if f.endswith(".safetensors"):
             sd.update(load_file(os.path.join(path, f)))
-    params = ModelParams(cfg, ops, init="none", train_vit=train_vit, moment_dtype=moment_dtype)
+    params = ModelParams(cfg, ops, init="none", train_vit=train_vit, moment_dtype=moment_dtype, **params_kw)
     params.load_hf_state_dict(sd)
     return cfg, params
 
 
-def load_hf_module(model, ops, train_vit=False, moment_dtype=torch.float32):
+def load_hf_module(model, ops, train_vit=False, moment_dtype=torch.float32, **params_kw):
     """A loaded transformers model (reference timer1_trainer.py:184-206, :244-262 accepts a `PreTrainedModel` instance as well as a path) ->
     (ModelConfig, ModelParams): its config and state dict are copied into the engine's arenas; the module itself is not kept."""
     hc = model.config.to_dict()
     cfg = config_from_hf(hc, name=str(getattr(model.config, "_name_or_path", "") or type(model).__name__).rstrip("/").split("/")[-1])
-    params = ModelParams(cfg, ops, init="none", train_vit=train_vit, moment_dtype=moment_dtype)
+    params = ModelParams(cfg, ops, init="none", train_vit=train_vit, moment_dtype=moment_dtype, **params_kw)
     params.load_hf_state_dict({k: v.detach() for k, v in model.state_dict().items()})
     return cfg, params
 
@@ -391,8 +391,15 @@ class TimeR1_Trainer:
             name = model if isinstance(model, str) else getattr(getattr(model, "cfg", None), "name", None) or getattr(getattr(model, "config", None), "_name_or_path", None) or "model"
             args = GRPOConfig(output_dir="%s-GRPO" % str(name).split("/")[-1])
         self.args = args
+        # peft_config (reference :264-293, main.py's get_peft_config(model_args)): LoRA on the decoder's projections, kept merged (lora.py)
+        self.lora_spec = None
         if peft_config is not None:
-            raise NotImplementedError("LoRA/peft is not part of the MI355X engine (the reference scripts train full parameters)")
+            from .lora import LoraSpec
+            self.lora_spec = LoraSpec.from_config(peft_config)
+            if getattr(args, "sync_ref_model", False):
+                raise NotImplementedError("peft_config with sync_ref_model=True: the reference policy is the frozen base copy the merge reads, it cannot move")
+            if getattr(args, "shard_optimizer", None):
+                raise ValueError("peft_config with shard_optimizer=True: the adapters' optimizer state is a few hundred MB and stays replicated")
         mik = getattr(args, "model_init_kwargs", None) or {}
         td = mik.get("torch_dtype")
         if isinstance(td, str) and td not in ("auto", "bfloat16", "float16", "float32"):   # reference :221-235
@@ -406,30 +413,48 @@ class TimeR1_Trainer:
         # merger all train (reference :267-288) - the tower's weights live in the trainable arena (ModelParams(train_vit=True)), so AdamW, the clipping
         # norm, the data-parallel exchange, the reference snapshot and the checkpoints cover them with the rest of the arena
         train_vit = not getattr(args, "fix_vit", True)
+        if self.lora_spec is not None:
+            from .lora import check_backend
+            check_backend(ops)
+            # as under peft nothing but the adapters trains: the vision tower stays frozen whatever fix_vit says (the reference's message, :285-286)
+            if int(os.environ.get("RANK", "0")) == 0:
+                print("[INFO] fix_vit=%s ignored because LoRA/PEFT is enabled." % getattr(args, "fix_vit", True), flush=True)
+            train_vit = False
+        lora_on = self.lora_spec is not None
+        base_kw = dict(optimizer_state=False, with_grad=False) if lora_on else {}      # LoRA: the base arena holds bf16 weights only
         # the moments are allocated in their final dtype wherever this constructor builds the arena (fp32 moments never exist at 7B with "bf16"); a
         # caller's ModelParams is converted in place by AdamWFlat(state_dtype=) below
         mdt = torch.bfloat16 if getattr(args, "optimizer_state_dtype", "fp32") == "bf16" else torch.float32
         if isinstance(model, str):
             if model in PRESETS:
                 self.cfg = PRESETS[model]()
-                self.params = ModelParams(self.cfg, ops, seed=args.seed, train_vit=train_vit, moment_dtype=mdt)
+                self.params = ModelParams(self.cfg, ops, seed=args.seed, train_vit=train_vit, moment_dtype=mdt, **base_kw)
             else:
-                self.cfg, self.params = load_model_dir(model, ops, train_vit=train_vit, moment_dtype=mdt)
+                self.cfg, self.params = load_model_dir(model, ops, train_vit=train_vit, moment_dtype=mdt, **base_kw)
         elif isinstance(model, ModelParams):
             # a ModelParams of the other layout is copied by name into a new one (optimizer state included) while the caller's stays alive: two copies
             # of the model at once, which a 7B model does not fit on one card - there, pass a preset / checkpoint directory / ModelConfig, or build
             # ModelParams(train_vit=not fix_vit) yourself (no copy)
             self.cfg, self.params = model.cfg, model.relayout(train_vit)
         elif isinstance(model, ModelConfig):
-            self.cfg, self.params = model, ModelParams(model, ops, seed=args.seed, train_vit=train_vit, moment_dtype=mdt)
+            self.cfg, self.params = model, ModelParams(model, ops, seed=args.seed, train_vit=train_vit, moment_dtype=mdt, **base_kw)
         elif hasattr(model, "state_dict") and hasattr(model, "config"):
-            self.cfg, self.params = load_hf_module(model, ops, train_vit=train_vit, moment_dtype=mdt)      # a loaded transformers model, like the reference accepts
+            self.cfg, self.params = load_hf_module(model, ops, train_vit=train_vit, moment_dtype=mdt, **base_kw)      # a loaded transformers model, like the reference accepts
         else:
             raise TypeError("model must be a checkpoint path, a preset name, a ModelConfig, a ModelParams or a loaded transformers model")
         self.model = self.params
         self.engine = Engine(self.cfg, ops, self.params, activation_recompute=getattr(args, "activation_recompute", "none"))
         self.beta = args.beta
-        self.ref_model = self.params.train.clone_weights_only() if self.beta != 0.0 else None    # reference :295-307
+        self.lora = None
+        if lora_on:
+            # the adapters' arena + the frozen base copy W0, which is also the reference policy (the reference keeps ref_model = None under peft and disables
+            # the adapter for the reference log-probs, :304-307); kept with beta = 0 too: the merge reads it
+            from .lora import LoraAdapters
+            self.params.drop_training_state()            # (a caller's ModelParams: its gradient buffer and optimizer state are released)
+            self.lora = self.engine.lora = LoraAdapters(self.params, self.lora_spec, seed=args.seed, moment_dtype=mdt)
+            self.ref_model = self.lora.base
+        else:
+            self.ref_model = self.params.train.clone_weights_only() if self.beta != 0.0 else None    # reference :295-307
         # ---- processor
         if processing_class is None:
             if not isinstance(model, str) or model in PRESETS:
@@ -498,12 +523,12 @@ class TimeR1_Trainer:
         self.core.roll.track_logp = bool(drift) if drift is not None else (self.core.roll.weight_dtype != "bf16" or self._is_cap is not None)
         if optimizers[0] is not None:
             raise NotImplementedError("custom torch optimizers are not supported; the engine owns a fused AdamW over its flat arena")
-        self.optimizer = AdamWFlat(self.params, ops, lr=args.learning_rate, betas=(args.adam_beta1, args.adam_beta2), eps=args.adam_epsilon,
+        self.optimizer = AdamWFlat(self.lora if lora_on else self.params, ops, lr=args.learning_rate, betas=(args.adam_beta1, args.adam_beta2), eps=args.adam_epsilon,
                                    weight_decay=args.weight_decay, max_grad_norm=args.max_grad_norm, dp=self.dp,
                                    grad_wire_dtype=torch.bfloat16 if getattr(args, "grad_wire_dtype", "bf16") == "bf16" else torch.float32,
-                                   shard_optimizer=self._wants_shard(args, self.dp), state_dtype=mdt, seed=args.seed)
+                                   shard_optimizer=False if lora_on else self._wants_shard(args, self.dp), state_dtype=mdt, seed=args.seed)
         # the decoder layers' large gradient matrices are overwritten by the first micro-step of every window: the optimizer does not zero them
-        self.optimizer.lazy_zero = self.engine.lazy_zero_plan() if getattr(args, "lazy_grad_zero", True) else None
+        self.optimizer.lazy_zero = self.engine.lazy_zero_plan() if (getattr(args, "lazy_grad_zero", True) and not lora_on) else None
         self.engine.lazy_zero_active = self.optimizer.lazy_zero is not None
         self.optimizer.lazy_zero_ok = lambda eng=self.engine: bool(eng.wgrad_overwrite_first)      # re-checked at every step (A/B attribute)
         self._metrics_store = defaultdict(list)
@@ -535,6 +560,8 @@ class TimeR1_Trainer:
         a = self.args
         if not getattr(a, "sync_ref_model", False):
             return False
+        if getattr(self, "lora_spec", None) is not None:
+            raise NotImplementedError("peft_config with sync_ref_model=True: the reference policy is the frozen base copy the merge reads, it cannot move")
         if self.ref_model is None:
             raise ValueError("sync_ref_model needs a reference policy: beta = 0 keeps none")
         if not 0.0 < float(a.ref_model_mixup_alpha) <= 1.0:
@@ -698,7 +725,7 @@ class TimeR1_Trainer:
         self._clock.mark("logps")
         scale = 1.0 / max(1, self.args.gradient_accumulation_steps)     # HF divides the loss by GA (model_accepts_loss_kwargs=False, :421-424)
         sync = None
-        if last_in_window and self.dp.enabled:
+        if last_in_window and self.dp.enabled and self.lora is None:      # (LoRA: the adapters' exchange is not overlapped, optimizer.step begins it)
             sync = self.optimizer.sync
             sync.begin()                      # overlap the gradient exchange with this (last) micro-step's backward
         mask_dev = self.ops.tensor(mask_np, torch.int32)
@@ -893,7 +920,7 @@ class TimeR1_Trainer:
             self.core.forward_logps(st, replay=True)
             clock.mark("logps")
             sync = None
-            if last and self.dp.enabled:
+            if last and self.dp.enabled and self.lora is None:
                 sync = self.optimizer.sync
                 sync.begin()
             maskf = r["mask"].to(torch.float32)
@@ -920,6 +947,8 @@ class TimeR1_Trainer:
         `save` also marks the last update on a rollout: the only place the reference policy may move (sync_ref_model), ahead of the log and the checkpoint."""
         a = self.args
         gnorm = self.optimizer.step(lr=self._lr(self.state.global_step))
+        if self.lora is not None:
+            self.lora.merge()                 # the policy's weights from the base copy and the updated adapter masters
         self.state.global_step += 1
         if save and getattr(a, "sync_ref_model", False) and self.state.global_step % int(a.ref_model_sync_steps) == 0:
             self._sync_ref_model()
@@ -1155,6 +1184,11 @@ class TimeR1_Trainer:
         os.makedirs(output_dir, exist_ok=True)
         from safetensors.torch import save_file
         save_file(self.params.export_hf_state_dict(), os.path.join(output_dir, "model.safetensors"), metadata={"format": "pt"})
+        if self.lora is not None:
+            # the merged weights above keep from_pretrained, the evaluation and the filter stages working; the adapter itself goes beside them in peft's layout
+            tensors, acfg = self.lora.export_adapter(getattr(self.cfg, "name", None))
+            save_file(tensors, os.path.join(output_dir, "adapter_model.safetensors"), metadata={"format": "pt"})
+            json.dump(acfg, open(os.path.join(output_dir, "adapter_config.json"), "w"), indent=1)
         json.dump(dataclasses.asdict(self.cfg), open(os.path.join(output_dir, "timer1_model_config.json"), "w"), indent=1)
         from .config import to_hf_config
         json.dump(to_hf_config(self.cfg), open(os.path.join(output_dir, "config.json"), "w"), indent=1)   # reference: save_pretrained via Trainer
@@ -1187,12 +1221,16 @@ class TimeR1_Trainer:
 
     def _load_checkpoint(self, d):
         from safetensors.torch import load_file
+        opt = os.path.join(d, "optimizer_rank%d.pt" % self.dp.rank)
+        if self.lora is not None and not os.path.exists(opt):
+            # model.safetensors holds the MERGED weights: without the adapter masters the first merge would overwrite them with W0 + fresh adapters
+            raise ValueError("LoRA: %s has no %s (saved with save_only_model=True?) - the adapter state is in it, and a resume without it would silently "
+                             "restart from the base model; load the merged model.safetensors as the base model instead" % (d, os.path.basename(opt)))
         self.params.load_hf_state_dict(load_file(os.path.join(d, "model.safetensors")))
         st = json.load(open(os.path.join(d, "trainer_state.json")))
         self.state.global_step = int(st["global_step"])
         self.state.log_history = st.get("log_history", [])
         self.state.epoch = float(st.get("epoch") or 0.0)
-        opt = os.path.join(d, "optimizer_rank%d.pt" % self.dp.rank)
         if os.path.exists(opt):
             sd = torch.load(opt, weights_only=False)
             self.params.train.version += 1
@@ -1204,6 +1242,8 @@ class TimeR1_Trainer:
                 self.ref_model.w16.copy_(torch.load(refp, weights_only=False)["ref_w16"].to(self.ops.device))
             elif self.ref_model is not None and "ref_w16" in sd:      # checkpoints written before round 3 embedded it per rank
                 self.ref_model.w16.copy_(sd["ref_w16"].to(self.ops.device))
+            if self.lora is not None:
+                self.lora.merge()      # W0 and the adapter masters are back: the merge gives the saved weights bit for bit
         return self.state.global_step
 
     def push_to_hub(self, *a, **k):

@@ -72,6 +72,14 @@ def main():
     ap.add_argument("--filter_max_new_tokens", type=int, default=1024)
     ap.add_argument("--filter_batch_size", type=int, default=16, help="prompts decoded together by the filter stage, 1..64 (batched greedy decoding with "
                     "early stop, the queries sharded over all ranks); 0 = one row at a time through the top_k=1 sampler on rank 0")
+    # LoRA: trl's ModelConfig flags, which the reference's main.py turns into peft_config through get_peft_config(model_args).  --lora_dropout defaults to 0
+    # here (trl: 0.05): the merged-adapter design has no dropout.  No --lora_target_modules: q_proj and v_proj, peft's default for the Qwen2 family.
+    ap.add_argument("--use_peft", type=str2bool, nargs="?", const=True, default=False)
+    ap.add_argument("--lora_r", type=int, default=16)
+    ap.add_argument("--lora_alpha", type=float, default=32)
+    ap.add_argument("--lora_dropout", type=float, default=0.0)
+    ap.add_argument("--lora_target_modules", nargs="+", default=None)
+    ap.add_argument("--use_rslora", type=str2bool, nargs="?", const=True, default=False)
     ns, _unknown = ap.parse_known_args()      # unknown reference flags (--fp16 ...) are ignored on purpose
     init_from_env("cuda")
     set_global_seed(42)
@@ -82,9 +90,14 @@ def main():
     else:
         dataset = load_json_dataset_tg(ns.train_data_path, ns.is_curriculum_learning)
         cls = TimeR1_Trainer
+    peft = {}
+    if ns.use_peft:
+        tm = ns.lora_target_modules or ["q_proj", "v_proj"]
+        peft["peft_config"] = dict(r=ns.lora_r, lora_alpha=ns.lora_alpha, lora_dropout=ns.lora_dropout, target_modules=tm[0] if tm == ["all-linear"] else tm,
+                                   use_rslora=ns.use_rslora, bias="none", task_type="CAUSAL_LM")
     trainer = cls(model=ns.model_name_or_path, reward_funcs=[reward_funcs_registry[f] for f in ns.reward_funcs],
                   metric_funcs=list(metric_funcs_registry.values()), args=args, train_dataset=dataset,
-                  callbacks=[StopAfterNEpochsCallback()] if ns.is_early_stopping else None, max_pixels=ns.max_pixels, min_pixels=ns.min_pixels)
+                  callbacks=[StopAfterNEpochsCallback()] if ns.is_early_stopping else None, max_pixels=ns.max_pixels, min_pixels=ns.min_pixels, **peft)
     # resume arithmetic of the reference (main.py:589-618): continue from checkpoint-N and EXTEND max_steps by this launch's epochs
     ckpt = args.resume_from_checkpoint
     if ckpt and os.path.isdir(ckpt):
