@@ -18,8 +18,21 @@ F32 = torch.float32
 
 
 class StepState:
-    """Per-prompt device state handed between the phases of a micro-step."""
-    pass
+    """Per-prompt device state handed between the phases of a micro-step.  Every field a phase hands over is declared here and is None until its
+    phase has run (or when its option is off); callers - bench.py, the tests - may hang further attributes on a state."""
+
+    def __init__(self):
+        # prepare(): the prompt, its rope positions and the vision features
+        self.P = self.grid = self.prompt_ids_host = self.prompt_ids = self.vid_rows = self.pos3_prompt = self.delta = None
+        self.feats = self.vis_perm = self.vid_embeds = self.merger_ctx = None
+        self.pixels = None                   # kept only while a training tower (or a replay of it) reads them again
+        # rollout() / rollout_many(): the completions; prefill = the rollout's saved prompt activations and K/V, sample_logp = log-probs under the
+        # sampling policy's logits (Rollout.track_logp), completion_ids_host = the tokens once a caller has copied them to the host
+        self.layout = self.completion_ids = self.completion_ids_host = self.prefill = self.sample_logp = None
+        # forward_logps(): the packed sequence, the saved contexts of the backward, the log-probs
+        self.ids_packed = self.pos3 = self.cos = self.sin = self.masks = self.pred_rows = self.targets = self.perm = self.inv_perm = None
+        self.llm_ctx = self.head_ctx = None
+        self.logp = self.entropy = self.ref_logp = None
 
 
 class GRPOCore:
@@ -199,7 +212,7 @@ class GRPOCore:
             st.prefill = None
         else:
             self._packed_inputs(st)
-        pf = getattr(st, "prefill", None)
+        pf = st.prefill
         split = pf is not None and pf[0] is not None
         self._count_update(st, split, with_ref=not replay)
         if split:
@@ -291,83 +304,93 @@ class GRPOCore:
         the ratio kernel's (rho = exp(logp - old_logp) clipped to [1 - eps[0], 1 + eps[1]], tok_weight inside the kernel) and out8 is returned in place of out3.
         With self.objective set, first pass and replays alike run grpo_policy_loss with the objective's clip range (`eps` is the ratio kernel's) and return out8.
         keep_pixels: further replays of this state follow (the training tower's backward reads st.pixels again).
-        Returns (out3 = [loss, mean kl, sum mask], row_len [G]) as device tensors."""
-        eng, ops = self.eng, self.ops
-        tr = eng.params.train
-        hook = None
-        if grad_sync is not None and grad_sync.active and eng.lora is None:      # (LoRA mode: the adapters' small exchange happens in the optimizer step)
-            hook = lambda i: grad_sync.ready(*tr.range_of("l%d." % i))
+        Returns (out3 = [loss, mean kl, sum mask] - or the kernel's out8, as above -, row_len [G]) as device tensors.  Three jobs, one method each: _loss_grad,
+        _entropy_bonus, _backward."""
         if self.top_entropy_quantile < 1.0:
             # the entropy of THIS forward (a replay selects on its own, as trl recomputes the mask in every compute_loss); it multiplies with an importance cap
-            sel, _ = ops.entropy_quantile_weight(st.entropy, completion_mask, self.top_entropy_quantile)
+            sel, _ = self.ops.entropy_quantile_weight(st.entropy, completion_mask, self.top_entropy_quantile)
             tok_weight = sel if tok_weight is None else tok_weight.to(torch.float32) * sel
+        dlogp, out3, row_len = self._loss_grad(st, completion_mask, advantages, grad_scale, tok_weight, old_logp, eps)
+        dent = None
+        if self.entropy_coef != 0.0:
+            out3, dent = self._entropy_bonus(st, completion_mask, out3, row_len, grad_scale)
+        self._backward(st, dlogp, dent, grad_sync, keep_pixels)
+        return out3, row_len
+
+    def _normaliser(self, st, out3, row_len):
+        """The per-token normaliser of the policy term on this path, from the kernel's own counts on the device: a live token weighs 1 / (d * k) -> (d, k).
+        Row mean (use_grpo, loss_type "grpo"): d = the row's live tokens, k = G; token mean: d = all live tokens; "dr_grpo": k = G * C.  A row (or a grid)
+        without a live token has d = 1 and no live token to weigh.  The two users divide in their own order, (m / d) / k and m / (d * k): the roundings differ."""
+        norm = self.objective["norm"] if self.objective is not None else (0 if self.use_grpo else 1)
+        if norm == 0:
+            return row_len.reshape(-1, 1).to(F32).clamp(min=1.0), float(st.layout.G)
+        if norm == 1:
+            return out3[2].to(F32).clamp(min=1.0), 1.0
+        return 1.0, float(st.layout.G) * float(st.layout.C)
+
+    def _loss_grad(self, st, completion_mask, advantages, grad_scale, tok_weight, old_logp, eps):
+        """The loss entry point of this path and what tok_weight means on it -> (dlogp [G, C], out3 or out8, row_len [G])."""
+        ops = self.ops
+        tw = None if tok_weight is None else tok_weight.to(torch.float32).contiguous()
         if self.objective is not None:
             # the objective family: first pass (old_logp None: ratio 1, tok_weight inside the kernel) and replays alike; out8 is returned in place of out3
             o = self.objective
-            tw = None if tok_weight is None else tok_weight.to(torch.float32).contiguous()
             dlogp, out3, row_len, _ = ops.grpo_policy_loss(st.logp, old_logp, st.ref_logp, completion_mask, advantages, self.beta, o["norm"], o["level"],
                                                            o["eps_low"], o["eps_high"], o["delta"], grad_scale, tok_weight=tw)
-            tok_weight = None
         elif old_logp is not None:
-            tw = None if tok_weight is None else tok_weight.to(torch.float32).contiguous()
             dlogp, out3, row_len, _ = ops.grpo_loss_ratio(st.logp, old_logp, st.ref_logp, completion_mask, advantages, self.beta, self.use_grpo,
                                                           float(eps[0]), float(eps[1]), grad_scale, tok_weight=tw)
         else:
             dlogp, out3, row_len, _ = ops.grpo_loss(st.logp, st.ref_logp, completion_mask, advantages, self.beta, self.use_grpo, grad_scale)
-        if tok_weight is not None and old_logp is None:
-            # optional truncated importance weight rho[g, t] (a constant) on the advantage term, for completions drawn from a quantised sampling
-            # policy: l = -rho * A + beta * kl = l_plain + (1 - rho) * A, same normalisation as the kernel.  None (the default) leaves the
-            # reference algebra untouched - this branch is then not executed at all.
-            m = completion_mask.to(torch.float32)
-            w = (m / row_len.reshape(-1, 1).clamp(min=1.0) / float(st.layout.G)) if self.use_grpo else (m / out3[2].clamp(min=1.0))
-            corr = (1.0 - tok_weight.to(torch.float32)) * advantages.reshape(-1, 1).to(torch.float32) * w
-            dlogp = dlogp + (corr * float(grad_scale)).to(dlogp.dtype)
-            out3 = out3.clone()
-            out3[0] = out3[0] + corr.sum().to(out3.dtype)
-        dl_pred = dlogp.reshape(-1)[st.perm].contiguous()
-        if self.entropy_coef != 0.0:
-            # loss - entropy_coef * sum n H over ALL live tokens (the selection above does not apply), n = the normaliser of the policy term on this path, built from
-            # the kernel's own counts on the device; a row (or a grid) without a live token contributes 0
-            G, C = st.layout.G, st.layout.C
-            live = completion_mask != 0
-            m = live.to(torch.float32)
-            norm = self.objective["norm"] if self.objective is not None else (0 if self.use_grpo else 1)
-            if norm == 0:
-                n = m / (row_len.reshape(-1, 1).to(torch.float32).clamp(min=1.0) * float(G))
-            elif norm == 1:
-                n = m / out3[2].to(torch.float32).clamp(min=1.0)
-            else:
-                n = m / (float(G) * float(C))
-            H = torch.where(live, st.entropy.to(torch.float32), torch.zeros_like(n))
-            dent_gc = (-self.entropy_coef * float(grad_scale)) * n
-            out3 = out3.clone()
-            out3[0] = out3[0] - (self.entropy_coef * (n * H).sum()).to(out3.dtype)
-            dh = eng.head_bwd(st.head_ctx, dl_pred, G, dent=dent_gc.reshape(-1)[st.perm].contiguous())
-        else:
-            dh = eng.head_bwd(st.head_ctx, dl_pred, st.layout.G)
+            if tw is not None:
+                # optional truncated importance weight rho[g, t] (a constant) on the advantage term, for completions drawn from a quantised sampling
+                # policy: l = -rho * A + beta * kl = l_plain + (1 - rho) * A, same normalisation as the kernel (which takes no tok_weight).  None (the
+                # default) leaves the reference algebra untouched - this branch is then not executed at all.
+                d, k = self._normaliser(st, out3, row_len)
+                corr = (1.0 - tw) * advantages.reshape(-1, 1).to(torch.float32) * (completion_mask.to(torch.float32) / d / k)
+                dlogp = dlogp + (corr * float(grad_scale)).to(dlogp.dtype)
+                out3 = out3.clone()
+                out3[0] = out3[0] + corr.sum().to(out3.dtype)
+        return dlogp, out3, row_len
+
+    def _entropy_bonus(self, st, completion_mask, out3, row_len, grad_scale):
+        """loss - entropy_coef * sum n H over ALL live tokens (the top-entropy selection does not apply), n = the normaliser of the policy term on this path; a
+        row (or a grid) without a live token contributes 0 -> (out3 with the bonus in its loss, the gradient at the entropy [G, C])."""
+        live = completion_mask != 0
+        d, k = self._normaliser(st, out3, row_len)
+        n = live.to(torch.float32) / (d * k)
+        H = torch.where(live, st.entropy.to(torch.float32), torch.zeros_like(n))
+        out3 = out3.clone()
+        out3[0] = out3[0] - (self.entropy_coef * (n * H).sum()).to(out3.dtype)
+        return out3, (-self.entropy_coef * float(grad_scale)) * n
+
+    def _backward(self, st, dlogp, dent, grad_sync, keep_pixels):
+        """The backward chain from the gradients at the log-probs (and at the entropy, or None) [G, C] into the trainable arena."""
+        eng = self.eng
+        tr = eng.params.train
+        hook = None
+        if grad_sync is not None and grad_sync.active and eng.lora is None:      # (LoRA mode: the adapters' small exchange happens in the optimizer step)
+            hook = lambda i: grad_sync.ready(*tr.range_of("l%d." % i))
+        to_pred = lambda x: x.reshape(-1)[st.perm].contiguous()
+        dh = eng.head_bwd(st.head_ctx, to_pred(dlogp), st.layout.G, dent=None if dent is None else to_pred(dent))
         if hook is not None and not self.cfg.text.tie_word_embeddings:
             grad_sync.ready(*tr.range_of("norm"))          # final norm + untied lm_head gradients are complete after the head backward
             grad_sync.ready(*tr.range_of("lm_head"))
         dh0 = eng.llm_bwd(st.llm_ctx, dh, on_layer_done=hook)
-        if eng.lora is not None:
-            # LoRA mode: embedding, merger and vision tower are frozen (as under peft) - the backward ends at the decoder's input
-            st.llm_ctx = st.head_ctx = st.merger_ctx = None
-            if not keep_pixels:
-                st.pixels = None
-            return out3, row_len
-        ids_g = st.ids_packed.clone()
-        ids_g[st.vid_rows.long()] = -1
-        dvid = eng.embed_bwd(dh0, ids_g, st.vid_rows)
-        dfeats = eng.merger_bwd(st.merger_ctx, dvid)
+        dfeats = None
+        if eng.lora is None:      # (LoRA mode: embedding, merger and vision tower are frozen, as under peft - the backward ends at the decoder's input)
+            ids_g = st.ids_packed.clone()
+            ids_g[st.vid_rows.long()] = -1
+            dvid = eng.embed_bwd(dh0, ids_g, st.vid_rows)
+            dfeats = eng.merger_bwd(st.merger_ctx, dvid)
         st.llm_ctx = st.head_ctx = st.merger_ctx = None
         if dfeats is not None:
             # fix_vit=False: the tower's activations are recomputed here, one prompt at a time (prepare() keeps none), then its backward runs.
             # Its gradient ranges are handed to the exchange by grad_sync.finish() (GradSync / ShardSync cover every range nobody announced).
             _, _, vctx = eng.vit_features(st.pixels, st.grid, save=True)
             eng.vit_bwd(vctx, dfeats)
-            if not keep_pixels:
-                st.pixels = None
-        return out3, row_len
+        if not keep_pixels:
+            st.pixels = None
 
 
 def eos_mask(completion_ids, eos_token_id):

@@ -312,6 +312,11 @@ FP8_MFMA_KEEP_BF16 = ("qkv", "o")      # default of GRPOConfig.rollout_fp8_keep_
 FP8_IMPORTANCE_CAP = 2.0      # default truncation c of the per-token importance weight for quantised sampling policies (GRPOConfig.rollout_importance_cap)
 
 
+# The device half of a micro-step's metric record: one fp32 vector with these slots, for a first pass and a replay, with and without an objective.  loss, kl and
+# entropy always carry a value; the record's has_clip / has_drift / has_kl_old say which of the others do (TimeR1_Trainer._update, _flush_metrics)
+DEV_SLOTS = ("loss", "kl", "entropy", "clip_low", "clip_high", "clip_region", "drift", "kl_old")
+
+
 def clip_ratio_metrics(logp, old_logp, advantages, mask, eps_low=0.2, eps_high=0.2):
     """Fractions of completion tokens whose probability ratio exp(logp - old_logp) left the PPO clip range on the side that matters for
     the sign of the advantage: (low, high, either), each sum(flag * mask) / sum(mask) (reference timer1_trainer_ft.py:820-829)."""
@@ -533,6 +538,7 @@ class TimeR1_Trainer:
         self.optimizer.lazy_zero_ok = lambda eng=self.engine: bool(eng.wgrad_overwrite_first)      # re-checked at every step (A/B attribute)
         self._metrics_store = defaultdict(list)
         self._pending = []                   # micro-steps whose device-side metric values have not been fetched yet (_flush_metrics)
+        self._zeros3 = None
         self._clock = _PhaseClock(ops)
         self._tok_since_log, self._micro_at_log, self._t_last_log = 0.0, 0, None
         self.generated_tokens, self.phase_ms_total = 0.0, defaultdict(float)
@@ -700,7 +706,7 @@ class TimeR1_Trainer:
         tokens = st.completion_ids
         # tokens first, THEN the log-prob forwards: a device-to-host copy waits for everything queued before it on the stream, so in this
         # order the host decodes / scores / normalises while the GPU is busy with the policy and reference forwards
-        comp_host = getattr(st, "completion_ids_host", None)
+        comp_host = st.completion_ids_host
         if comp_host is None:
             comp_host = tokens.cpu().numpy()
         self.core.forward_logps(st)
@@ -723,54 +729,64 @@ class TimeR1_Trainer:
             metric_vals = torch.stack([torch.tensor(fn(prompts=prompts_rep, completions=completions, **reward_kwargs), dtype=torch.float32)
                                        for fn in self.metric_funcs], 1)
         self._clock.mark("logps")
-        scale = 1.0 / max(1, self.args.gradient_accumulation_steps)     # HF divides the loss by GA (model_accepts_loss_kwargs=False, :421-424)
-        sync = None
-        if last_in_window and self.dp.enabled and self.lora is None:      # (LoRA: the adapters' exchange is not overlapped, optimizer.step begins it)
-            sync = self.optimizer.sync
-            sync.begin()                      # overlap the gradient exchange with this (last) micro-step's backward
         mask_dev = self.ops.tensor(mask_np, torch.int32)
         adv_dev = self.ops.tensor(advantages.numpy(), torch.float32)
         # device-side metric pieces are computed BEFORE the backward releases the step's tensors; tiny [G, C] work on the same stream
         maskf = mask_dev.to(torch.float32)
-        ent_mean = ((st.entropy.float() * maskf).sum(1) / maskf.sum(1).clamp(min=1)).mean()
         clip3 = None
         if self._is_ft and not self.use_grpo and self._objective is None:   # reference timer1_trainer_ft.py:820-842 (undefined there for use_grpo: coef_1 does not exist)
             lp = st.logp.float()
             clip3 = torch.stack(clip_ratio_metrics(lp, lp, adv_dev, maskf, self.epsilon_low, self.epsilon_high))   # old policy == policy (one update per rollout)
         drift_t, tokw = None, None
-        slp = getattr(st, "sample_logp", None)
-        if slp is not None and ctx["forced"] is None:
-            d = (st.logp.float() - slp.to(st.logp.device).float())          # log importance ratio of every drawn token: update policy / sampling policy
+        if st.sample_logp is not None and ctx["forced"] is None:
+            d = (st.logp.float() - st.sample_logp.to(st.logp.device).float())          # log importance ratio of every drawn token: update policy / sampling policy
             drift_t = (d.abs() * maskf).sum() / maskf.sum().clamp(min=1)
             if self._is_cap is not None:
                 tokw = torch.exp(d).clamp(max=float(self._is_cap))
-        if last_in_window:      # the final gradient passes through this backward's weight-gradient epilogues: they leave its squared norm (AdamWFlat.step)
-            self.engine.norm_sink = self.optimizer.norm_sink_begin(self.engine)
-        extra = {"tok_weight": tokw} if tokw is not None else {}
         if self._reuse is not None:      # num_iterations > 1: keep what the replayed updates read (the policy's log-probs are the OLD policy's from now on)
             self._reuse.append(dict(st=st, old_logp=st.logp.clone(), mask=mask_dev, adv=adv_dev, tokw=tokw))
-            extra["keep_pixels"] = True
+        # ---- metrics (reference :739-777; ft adds metrics/<fn> and clip ratios :789-842): per-sample host values + the device vector,
+        # turned into the reference's gathered means by _flush_metrics
+        rollout = dict(length=lengths, rpf=rewards_per_func.numpy().copy(), reward=rewards.numpy().copy(), std=std.numpy().copy(),
+                       mvals=None if metric_vals is None else metric_vals.numpy(), truncated=truncated)
+        self.last_completions = completions
+        self.last_rewards = rewards
+        return self._update(st, mask_dev, adv_dev, tokw=tokw, last=last_in_window, keep_pixels=self._reuse is not None,
+                            maskf=maskf, rollout=rollout, clip3=clip3, drift=drift_t)
+
+    def _update(self, st, mask_dev, adv_dev, tokw=None, old_logp=None, last=False, keep_pixels=False, maskf=None, rollout=None, clip3=None, drift=None):
+        """Loss gradient and backward of one micro-step whose log-probs are in `st`: a rollout's first update (old_logp None) or a replay against the kept
+        log-probs of the policy that drew it.  last: the window's last micro-step (the gradient exchange overlaps its backward, its weight-gradient epilogues
+        leave the clipping norm); keep_pixels: a replay of this state follows; maskf: the mask as fp32 where the caller has it already.  What only a rollout
+        has goes into its record: `rollout` (the host values _host_fields names), `clip3` (the ft trainer's own clip fractions) and `drift`.  Appends one
+        record to `_pending` and returns the loss as a device scalar."""
+        scale = 1.0 / max(1, self.args.gradient_accumulation_steps)     # HF divides the loss by GA (model_accepts_loss_kwargs=False, :421-424)
+        sync = None
+        if last and self.dp.enabled and self.lora is None:      # (LoRA: the adapters' exchange is not overlapped, optimizer.step begins it)
+            sync = self.optimizer.sync
+            sync.begin()                      # overlap the gradient exchange with this (last) micro-step's backward
+        if maskf is None:
+            maskf = mask_dev.to(torch.float32)
+        ent_mean = ((st.entropy.float() * maskf).sum(1) / maskf.sum(1).clamp(min=1)).mean()
+        extra = dict(tok_weight=tokw, old_logp=old_logp, eps=None if old_logp is None else (self.epsilon_low, self.epsilon_high), keep_pixels=keep_pixels or None)
+        extra = {k: v for k, v in extra.items() if v is not None}      # only what is set: the rest keeps loss_backward's own defaults
+        if last:      # the final gradient passes through this backward's weight-gradient epilogues: they leave its squared norm (AdamWFlat.step)
+            self.engine.norm_sink = self.optimizer.norm_sink_begin(self.engine)
         try:
-            out3, row_len = self.core.loss_backward(st, mask_dev, adv_dev, scale, grad_sync=sync, **extra)
+            out, _ = self.core.loss_backward(st, mask_dev, adv_dev, scale, grad_sync=sync, **extra)
         finally:
             self.engine.norm_sink = None
         self._clock.mark("backward")
-        out3f = out3.float()
-        z = torch.zeros(3, dtype=torch.float32, device=out3f.device)
-        if self._objective is not None:
-            clip3 = out3f[3:6]               # out8 of grpo_policy_loss: the clip fractions and the k3 distance to the old policy come from the kernel
-        dev = torch.cat([out3f[:2], ent_mean.reshape(1).float(), clip3.float() if clip3 is not None else z,
-                         drift_t.reshape(1).float() if drift_t is not None else z[:1]])      # fixed layout: loss, kl, entropy, clip x 3, drift
-        if self._objective is not None:
-            dev = torch.cat([dev, out3f[6:7]])      # ... and an eighth value on that path (first pass and replay alike): policy_kl_old
-        # ---- metrics (reference :739-777; ft adds metrics/<fn> and clip ratios :789-842): per-sample host values + the device vector,
-        # turned into the reference's gathered means by _flush_metrics
-        self._pending.append(dict(length=lengths, truncated=truncated, family=self._objective is not None, rpf=rewards_per_func.numpy().copy(), reward=rewards.numpy().copy(),
-                                  std=std.numpy().copy(), mvals=None if metric_vals is None else metric_vals.numpy(), dev=dev,
-                                  has_clip=clip3 is not None, has_drift=drift_t is not None))
-        self.last_completions = completions
-        self.last_rewards = rewards
-        return out3f[0]
+        o = out.float()
+        from_kernel = o.numel() == 8          # out8 of the ratio / policy kernels: the clip fractions and the k3 distance to the old policy come with the loss
+        clip = o[3:6] if from_kernel else clip3
+        if self._zeros3 is None:
+            self._zeros3 = torch.zeros(3, dtype=torch.float32, device=o.device)      # what a slot without a value holds
+        z = self._zeros3
+        dev = torch.cat([o[:2], ent_mean.reshape(1).float(), z if clip is None else clip.float(), z[:1] if drift is None else drift.reshape(1).float(),
+                         o[6:7] if from_kernel else z[:1]])      # DEV_SLOTS, in one launch
+        self._pending.append(dict(dev=dev, rollout=rollout, has_clip=clip is not None, has_drift=drift is not None, has_kl_old=from_kernel))
+        return o[0]
 
     # ------------------------------------------------------------------------------------------------------ deferred metrics
     @property
@@ -789,72 +805,67 @@ class TimeR1_Trainer:
         self._flush_metrics()
         return self._metrics_store
 
+    def _host_fields(self, pend):
+        """The host half of a record, per rollout: ((name, width), ...) in the order they are packed - and read back - in."""
+        G = self.num_generations
+        mvals = next((r["rollout"]["mvals"] for r in pend if r["rollout"] is not None), None)
+        return (("length", G), ("rpf", G * len(self.reward_funcs)), ("reward", G), ("std", G), ("mvals", 0 if mvals is None else G * mvals.shape[1]),
+                ("truncated", G if self.mask_truncated else 0))      # mask_truncated_completions: one more value per row, 1 = no EOS
+
     def _flush_metrics(self):
         pend, self._pending = self._pending, []
         if not pend:
             return
-        G, nf = self.num_generations, len(self.reward_funcs)
-        first = next((r for r in pend if not r.get("replay")), None)
-        nm = first["mvals"].shape[1] if first is not None and first["mvals"] is not None else 0
-        dev = torch.stack([r["dev"] for r in pend])                     # [n, nd] on the device
-        nt = G if self.mask_truncated else 0                             # mask_truncated_completions: one more host value per row, 1 = no EOS
-        blank = np.zeros(3 * G + G * nf + G * nm + nt, dtype=np.float32)      # replayed updates carry device values only
-        host = np.stack([blank if r.get("replay") else
-                         np.concatenate([r["length"], r["rpf"].reshape(-1), r["reward"], r["std"]] +
-                                        ([r["mvals"].reshape(-1)] if nm else []) + ([r["truncated"]] if nt else [])).astype(np.float32) for r in pend])
+        nf = len(self.reward_funcs)
+        fields = self._host_fields(pend)
+        names, widths = zip(*fields)
+        n_host = sum(widths)
+        dev = torch.stack([r["dev"] for r in pend])                     # [n, len(DEV_SLOTS)] on the device
+        blank = np.zeros(n_host, dtype=np.float32)                       # replayed updates carry device values only
+        host = np.stack([blank if r["rollout"] is None else
+                         np.concatenate([np.asarray(r["rollout"][name], dtype=np.float32).reshape(-1) for name, w in fields if w]) for r in pend])
         if self.dp.enabled:
             both = torch.cat([self.ops.tensor(host, torch.float32), dev], 1)
             allv = self.dp.gather(both[None]).cpu()                      # [world, n, L]
         else:
             allv = torch.cat([torch.as_tensor(host), dev.cpu()], 1)[None]
         M = self._metrics_store
-        o_rpf, o_rew, o_std, o_mv = G, G + G * nf, 2 * G + G * nf, 3 * G + G * nf
-        o_tr = o_mv + G * nm
-        o_dev = o_tr + nt
         for i, r in enumerate(pend):
             v = allv[:, i]                                               # [world, L]: rank-major, like accelerator.gather's concatenation
-            if r.get("replay"):
-                # a further update on a rollout already counted: the loss-side keys only (dev = loss, kl, entropy, low, high, either, k3 to the old policy);
-                # rewards, lengths, drift and the generated-token count belong to the rollout and were appended by its first update
-                if self.beta != 0.0:
-                    M["kl"].append(v[:, o_dev + 1].mean().item())
-                M["generation_entropy"].append(v[:, o_dev + 2].mean().item())
-                g_low, g_high, g_reg = v[:, o_dev + 3], v[:, o_dev + 4], v[:, o_dev + 5]
-                M["clip_ratio/low_mean"].append(g_low.nanmean().item())
-                M["clip_ratio/low_min"].append(g_low[~g_low.isnan()].min().item() if (~g_low.isnan()).any() else float("nan"))
-                M["clip_ratio/high_mean"].append(g_high.nanmean().item())
-                M["clip_ratio/high_max"].append(g_high[~g_high.isnan()].max().item() if (~g_high.isnan()).any() else float("nan"))
-                M["clip_ratio/region_mean"].append(g_reg.nanmean().item())
-                M["policy_kl_old"].append(v[:, o_dev + (7 if r.get("family") else 6)].mean().item())
-                continue
-            M["completion_length"].append(v[:, :G].reshape(-1).mean().item())
-            rpf = v[:, o_rpf:o_rew].reshape(-1, nf).mean(0)
-            for j, fn in enumerate(self.reward_funcs):
-                M["rewards/%s" % fn.__name__].append(rpf[j].item())
-            M["reward"].append(v[:, o_rew:o_std].reshape(-1).mean().item())
-            M["reward_std"].append(v[:, o_std:o_mv].reshape(-1).mean().item())
+            d = dict(zip(DEV_SLOTS, v[:, n_host:].unbind(1)))            # slot name -> [world]
+            h = dict(zip(names, v[:, :n_host].split(list(widths), 1))) if r["rollout"] is not None else None      # field name -> [world, width]
+            # a replay is a further update on a rollout already counted: it logs the loss-side keys only; rewards, lengths, drift and the generated-token
+            # count belong to the rollout and are appended by its first update
+            if h is not None:
+                M["completion_length"].append(h["length"].reshape(-1).mean().item())
+                rpf = h["rpf"].reshape(-1, nf).mean(0)
+                for j, fn in enumerate(self.reward_funcs):
+                    M["rewards/%s" % fn.__name__].append(rpf[j].item())
+                M["reward"].append(h["reward"].reshape(-1).mean().item())
+                M["reward_std"].append(h["std"].reshape(-1).mean().item())
             if self.beta != 0.0:
-                M["kl"].append(v[:, o_dev + 1].mean().item())
-            M["generation_entropy"].append(v[:, o_dev + 2].mean().item())
-            if nm:
-                mv = v[:, o_mv:o_tr].reshape(-1, nm)
+                M["kl"].append(d["kl"].mean().item())
+            M["generation_entropy"].append(d["entropy"].mean().item())
+            if h is not None and h["mvals"].shape[1]:
+                mv = h["mvals"].reshape(-1, len(self.metric_funcs))
                 for j, fn in enumerate(self.metric_funcs):
                     M["metrics/%s" % fn.__name__].append(mv[:, j].mean().item())
             if r["has_clip"]:
-                g_low, g_high, g_reg = v[:, o_dev + 3], v[:, o_dev + 4], v[:, o_dev + 5]
+                g_low, g_high, g_reg = d["clip_low"], d["clip_high"], d["clip_region"]
                 M["clip_ratio/low_mean"].append(g_low.nanmean().item())
                 M["clip_ratio/low_min"].append(g_low[~g_low.isnan()].min().item() if (~g_low.isnan()).any() else float("nan"))
                 M["clip_ratio/high_mean"].append(g_high.nanmean().item())
                 M["clip_ratio/high_max"].append(g_high[~g_high.isnan()].max().item() if (~g_high.isnan()).any() else float("nan"))
                 M["clip_ratio/region_mean"].append(g_reg.nanmean().item())
-            if r.get("family"):
-                M["policy_kl_old"].append(v[:, o_dev + 7].mean().item())
-            if nt:
-                M["completions/clipped_ratio"].append(v[:, o_tr:o_dev].reshape(-1).mean().item())
-            if r.get("has_drift"):
-                M["rollout_logp_drift"].append(v[:, o_dev + 6].mean().item())
-            self._tok_since_log += float(v[:, :G].sum())
-            self.generated_tokens += float(v[:, :G].sum())        # cumulative, all ranks
+            if r["has_kl_old"]:
+                M["policy_kl_old"].append(d["kl_old"].mean().item())
+            if h is not None and h["truncated"].shape[1]:
+                M["completions/clipped_ratio"].append(h["truncated"].reshape(-1).mean().item())
+            if r["has_drift"]:
+                M["rollout_logp_drift"].append(d["drift"].mean().item())
+            if h is not None:
+                self._tok_since_log += float(h["length"].sum())
+                self.generated_tokens += float(h["length"].sum())        # cumulative, all ranks
 
     def accumulation_window(self, batches):
         """All micro-steps of one optimizer step. With rollout_batching the G x len(batches) completions are decoded together
@@ -911,35 +922,13 @@ class TimeR1_Trainer:
     def _replay_window(self, recs, more):
         """One further optimizer step's micro-steps on a window already rolled out (recs: what _step_finish kept).  No decode loop, no reference-policy
         forward, no reward calls; more: another replay follows (the states keep their pixels)."""
-        clock = self._clock
-        clock.mark("start")
-        scale = 1.0 / max(1, self.args.gradient_accumulation_steps)
+        self._clock.mark("start")
         losses = []
         for i, r in enumerate(recs):
-            last, st = i == len(recs) - 1, r["st"]
-            self.core.forward_logps(st, replay=True)
-            clock.mark("logps")
-            sync = None
-            if last and self.dp.enabled and self.lora is None:
-                sync = self.optimizer.sync
-                sync.begin()
-            maskf = r["mask"].to(torch.float32)
-            ent_mean = ((st.entropy.float() * maskf).sum(1) / maskf.sum(1).clamp(min=1)).mean()
-            if last:
-                self.engine.norm_sink = self.optimizer.norm_sink_begin(self.engine)
-            try:
-                out8, _ = self.core.loss_backward(st, r["mask"], r["adv"], scale, grad_sync=sync, tok_weight=r["tokw"], old_logp=r["old_logp"],
-                                                  eps=(self.epsilon_low, self.epsilon_high), keep_pixels=more)
-            finally:
-                self.engine.norm_sink = None
-            clock.mark("backward")
-            o = out8.float()
-            if self._objective is not None:      # the first pass's eight values: the drift slot stays empty, k3 sits behind it
-                self._pending.append(dict(replay=True, family=True, dev=torch.cat([o[:2], ent_mean.reshape(1).float(), o[3:6], torch.zeros_like(o[:1]), o[6:7]])))
-            else:
-                self._pending.append(dict(replay=True, dev=torch.cat([o[:2], ent_mean.reshape(1).float(), o[3:7]])))      # loss, kl, entropy, clip x 3, k3 to the old policy
+            self.core.forward_logps(r["st"], replay=True)
+            self._clock.mark("logps")
+            losses.append(self._update(r["st"], r["mask"], r["adv"], tokw=r["tokw"], old_logp=r["old_logp"], last=(i == len(recs) - 1), keep_pixels=more))
             self._replays_since_log += 1
-            losses.append(o[0])
         return losses
 
     def _optimizer_step(self, t_start, save=True):
