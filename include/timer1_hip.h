@@ -72,7 +72,13 @@ int tr1_gemm_nn_acc_f32(const void* A, const void* B, void* C_f32, int64_t M, in
  * (ref: input_layernorm -> q/k/v_proj TF:559-580 and post_attention_layernorm -> gate/up_proj TF:600-610 inside generate).
  * glu != 0: W is [2N, K] (gate rows, then up rows) and out[M, N] = silu(gate) * up (Qwen2MLP TF:459-466) - no [M, 2N] intermediate.
  * glu == 2 (M <= 16, tr1_norm_gemm_glu_frag_ok): the same values leave FRAGMENT-MAJOR - element (m, n) at (n / 32) * 512 + m * 32 + n % 32 of `out`
- * (16 x N bf16) - the operand layout of tr1_gemm_oproj_frag, which then runs the down projection with its whole weight slice in flight (2B shapes). */
+ * (16 x N bf16) - the operand layout of tr1_gemm_oproj_frag, which then runs the down projection with its whole weight slice in flight (2B shapes).
+ * Losslessly packed 12-bit gate/up weights (csrc/gemm_pk.hip; M <= 16, N % 16 == 0, K = 512 * {7, 4, 3}): a 4-bit sign + exponent code against a per-stage base,
+ * the low byte verbatim, an exact patch list for the rest.  The IMAGE of W[2N, K] is one buffer of S * 3136 + 16 bytes, S = (N / 16) * 8 * (K / 512) stages:
+ * S records of 3072 bytes, S tails of 64 bytes, then an int flag.
+ * glu == 5: no GEMM - W[2N, K] (ldw) is packed into `out` (x, lnw, bias unused); flag = 1 when some stage needs more than 14 patches: the matrix is then NOT
+ *   representable and the caller keeps glu = 1 / 2.
+ * glu == 3 / 4: W is that image (flag 0; ldw unused); the bits glu = 1 / 2 store, 0.77x the bytes streamed. */
 int tr1_norm_gemm_glu_frag_ok(int64_t M, int64_t N, int64_t K);
 int tr1_norm_gemm_skinny(const void* x, const void* lnw, const void* W, const void* bias, void* out, int64_t M, int64_t N, int64_t K, int64_t ldx, int64_t ldw, int64_t ldc, float eps, int glu, void* stream);
 /* Decode rows: input_layernorm -> fused q/k/v projection -> M-RoPE -> KV-cache append in ONE launch (tr1_norm_gemm_skinny + tr1_decode_qkv_post):
@@ -217,7 +223,8 @@ int tr1_gemm_skinny_fixup_w8a8(const void* x, const void* W_fp8, const void* wsc
  * ref: per-token body of model.generate (timer1_trainer.py:568-573; Qwen2VLDecoderLayer TF:559-624, norm TF:839, lm_head TF:1323).
  * layer_ptrs: HOST array of 9 * n_layers DEVICE pointers {ln1, qkv.w, qkv.b, o.w, ln2, gu.w, down.w, K cache [B*s_cap, kv_dim],
  * V^T cache [kv_dim, B*s_cap]} per layer; dims: HOST int64[12] {n_layers, hidden, n_heads, n_kv, head_dim, intermediate, vocab, rows,
- * n_batch, s_cap, nsplit, fp8_mask (fp8 steps only, ignored here)}; ids int32[R]; cosb/sinb fp32 [R, head_dim/2]; slots int32[R] (absolute cache slot of each row's new token);
+ * n_batch, s_cap, nsplit, fp8_mask (fp8 steps only; here only bit 8 is read: set = 10 pointers per layer, the tenth the packed 12-bit image of gu.w -
+ * tr1_norm_gemm_skinny glu = 5 - or NULL for a layer that keeps the bf16 gate/up launch; the same logits bit for bit)}; ids int32[R]; cosb/sinb fp32 [R, head_dim/2]; slots int32[R] (absolute cache slot of each row's new token);
  * pre/lo/hi int32[R] (two-interval mask, cache-local per batch entry); work: device scratch of tr1_decode_step_workspace_bytes(dims),
  * ZERO-FILLED once by the caller before the first step (it holds self re-arming split-K ticket counters). */
 int tr1_decode_step(const void* layer_ptrs, const int64_t* dims, const void* embed, const void* final_norm, const void* lm_head, const void* ids, const void* cosb, const void* sinb, const void* slots, const void* pre, const void* lo, const void* hi, void* work, int64_t work_bytes, void* logits, float eps, float scale, void* stream);

@@ -41,7 +41,7 @@ struct Carve {
 // D_QMASK (fp8 steps only): which matrices of the SAMPLING policy are fp8 - bit 0 qkv, 1 o, 2 gate/up, 3 down, 4 lm_head; a clear bit means that slot of the
 // layer table (and the lm_head argument) holds the bf16 weight and the bf16 kernel runs (mixed-precision sampling policies: config 5's drift study)
 enum { D_LAYERS, D_HIDDEN, D_HEADS, D_KV, D_HEAD_DIM, D_INTER, D_VOCAB, D_ROWS, D_BATCH, D_SCAP, D_NSPLIT, D_QMASK, D_N };
-enum { QM_QKV = 1, QM_O = 2, QM_GU = 4, QM_DOWN = 8, QM_LM = 16, QM_ALL = 31 };
+enum { QM_QKV = 1, QM_O = 2, QM_GU = 4, QM_DOWN = 8, QM_LM = 16, QM_ALL = 31, QM_PK = 256 };
 }  // namespace
 
 static int64_t decode_ws_bytes(const int64_t* d) {
@@ -58,6 +58,8 @@ extern "C" int64_t tr1_decode_step_workspace_bytes(const int64_t* dims) { return
 
 // One decode step.  w8 = false: bf16 weights, 9 pointers per layer.  w8 = true: the four matrices are fp8 e4m3 with fp32 row scales
 // (csrc/gemm_w8.hip), 13 pointers per layer {ln1, qkv.q, qkv.b, o.q, ln2, gu.q, down.q, K cache, V^T cache, qkv.s, o.s, gu.s, down.s}.
+// bf16 steps with QM_PK set in dims[D_QMASK]: 10 pointers per layer, the tenth the packed 12-bit image of gu.w (csrc/gemm_pk.hip, tr1_norm_gemm_skinny glu = 5) or
+// null for a layer that keeps the bf16 gate/up launch.
 static int decode_step_impl(int w8, const void* layer_ptrs, const int64_t* dims, const void* embed, const void* final_norm, const void* lm_head,
                             const void* lm_head_scale, const void* ids, const void* cosb, const void* sinb, const void* slots, const void* pre,
                             const void* lo, const void* hi, void* work, int64_t work_bytes, void* logits, float eps, float scale, void* stream) {
@@ -87,7 +89,8 @@ static int decode_step_impl(int w8, const void* layer_ptrs, const int64_t* dims,
                            tr1_norm_gemm_glu_frag_ok(R, inter, hid);
     TR1_CHECK_ARG(c.ok, "decode_step: workspace too small (tr1_decode_step_workspace_bytes)");
     const void* const* lp = (const void* const*)layer_ptrs;
-    const int stride = w8 ? 13 : 9;
+    const bool pk = !w8 && (dims[D_QMASK] & QM_PK);                              // the layer table carries the packed gate/up images
+    const int stride = w8 ? 13 : (pk ? 10 : 9);
 #define CK(call) do { int e__ = (call); if (e__) return e__; } while (0)
     // w8 == 2: the fp8-MFMA (W8A8) projections; w8 == 1: W8A16 (fp8 codes converted to bf16 in registers)
     auto gemm8 = w8 == 2 ? tr1_gemm_skinny_w8a8 : tr1_gemm_skinny_w8;
@@ -123,6 +126,7 @@ static int decode_step_impl(int w8, const void* layer_ptrs, const int64_t* dims,
         {
             ProfScope ps(2, stream);
             if (qm & QM_GU) CK(gemm8(h2, w[4], w[5], w[11], nullptr, nullptr, a, R, inter, hid, hid, hid, inter, 0, eps, 1, stream));
+            else if (pk && w[9]) CK(tr1_norm_gemm_skinny(h2, w[4], w[9], nullptr, a, R, inter, hid, hid, hid, inter, eps, down_frag ? 4 : 3, stream));
             else CK(tr1_norm_gemm_skinny(h2, w[4], w[5], nullptr, a, R, inter, hid, hid, hid, inter, eps, down_frag ? 2 : 1, stream));
         }
         ProfScope ps3(3, stream);

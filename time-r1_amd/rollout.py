@@ -71,6 +71,9 @@ class Rollout:
         #                               per call; "fp8" converts the codes to bf16 in registers (W8A16), "fp8-mfma" feeds them to the fp8 matrix
         #                               instruction with block-quantised e4m3 activations (W8A8, BASELINE config "CDNA4 fp8 MFMA")
         self._w8 = None
+        self._pk_now = None           # this call's packed gate/up copies (_pack12)
+        self.pack_gate_up = True      # bf16 rollouts: the native decode step streams a losslessly packed 12-bit image of the gate/up weights (csrc/gemm_pk.hip):
+        #                               the same tokens bit for bit, 0.77x the bytes of the step's largest launch.  Repacked when the weights change (_pack12)
         self.fp8_keep_bf16 = ()       # matrices of the fp8 sampling policy that stay bf16: any of "qkv", "o", "gu", "down", "lm_head" (drift study)
         self.track_logp = False       # also record, per drawn token, its full-softmax log-prob under the logits it was SAMPLED from (one more pass
         #                               over the step's L2-resident logits): the drift of a quantised sampling policy against the bf16 policy of the
@@ -125,6 +128,36 @@ class Rollout:
         if qm & 16:
             ops.quantize_fp8_rows(w_lm, q=self._w8["lm"][0], scale=self._w8["lm"][1])
         return self._w8
+
+    PK_HEADROOM = 8 << 30     # device memory that must stay free after the packed copies are allocated
+    PK_FROM_CALL = 1          # the copies are allocated from this call of the Rollout on (0: at once - tests)
+
+    def _pack12(self, arena, rows):
+        """Packed 12-bit copies of the layers' gate/up weights for the native bf16 decode step: -> dict(layers=[image], host=flags, event, ...), or
+        None where there are none (backend, shape, memory).  The copies belong to the engine - one set, whichever Rollout decodes (training, evaluation,
+        filtering) - and are rebuilt when the bytes the decode reads have changed: another arena, another arena.version (optimizer step, checkpoint load,
+        LoRA merge) or a torch-side write into w16.  They are allocated from the SECOND call on and only where 8 GB of device memory stay free afterwards:
+        by then torch's pool holds the peak of a whole step, so the copies (5.8 GB at 7B) can neither push the run's peak over the device nor make the
+        allocator retry; a run without that room keeps the bf16 launch."""
+        ops, t = self.eng.ops, self.eng.cfg.text
+        if not (self.pack_gate_up and hasattr(ops, "pack_bf16_glu") and ops.glu_pk_ok(rows, t.intermediate, t.hidden)):
+            return None
+        pk = getattr(self.eng, "glu_pk", None)
+        if pk is None:
+            nb = ops.pack_bf16_glu_stages(t.intermediate, t.hidden) * 3136 + 16
+            if self.calls < self.PK_FROM_CALL or torch.cuda.mem_get_info(ops.device)[0] < t.n_layers * (nb + 1024) + self.PK_HEADROOM:
+                return None
+            pk = self.eng.glu_pk = dict(key=None, layers=[ops.empty(nb, dtype=torch.uint8) for _ in range(t.n_layers)], flags=ops.zeros(t.n_layers, dtype=I32),
+                                        host=torch.zeros(t.n_layers, dtype=I32, pin_memory=True), event=torch.cuda.Event())
+        key = (id(arena), arena.w16.data_ptr(), arena.w16._version, getattr(arena, "version", 0))
+        if pk["key"] != key:
+            for i, image in enumerate(pk["layers"]):
+                ops.pack_bf16_glu(arena.w("l%d.gu.w" % i), image)
+                pk["flags"][i:i + 1].copy_(ops.pack_flag(image))
+            pk["host"].copy_(pk["flags"], non_blocking=True)
+            pk["event"].record()
+            pk["key"] = key
+        return pk
 
     def generate(self, arena, prompt_ids, vid_embeds, vid_rows, prompt_pos3, delta, save_prefill=False):
         """One prompt. prompt_ids: int32 device tensor [P]; prompt_pos3: numpy [3, P]; returns (tokens int32 [G, C] on device, layout)."""
@@ -243,14 +276,15 @@ class Rollout:
         w_lm = eng.params.lm_head_w(arena)
         self._filter_kwargs(ops)      # (a backend that cannot honour top_p / min_p: refuse before anything is computed)
         buf = self._buffers(items, greedy_op, int(w_lm.shape[0]))
+        fused = B * G <= 64        # the fused decode kernels hold all rows of a step in one MFMA column block set
+        native = fused and self.native_decode and hasattr(ops, "decode_step")
+        self._pk_now = self._pack12(arena, B * G) if native and on_gpu and self.weight_dtype == "bf16" else None      # (the packers run ahead of the prefill)
         per = [self._prefill(arena, w_lm, buf, b, it, save_prefill) for b, it in enumerate(items)]
         tab = self._step_tables(per, buf.cache, int(torch.cuda.get_device_properties(dev).multi_processor_count) if on_gpu else 256)
-        fused = B * G <= 64        # the fused decode kernels hold all rows of a step in one MFMA column block set
         w8 = None
         if self.weight_dtype in ("fp8", "fp8-mfma"):
             assert fused and t.hidden % 128 == 0 and t.intermediate % 128 == 0 and t.q_dim % 128 == 0, "fp8 decode: <= 64 rows, K % 128 == 0"
             w8 = self._quantize(arena, w_lm)
-        native = fused and self.native_decode and hasattr(ops, "decode_step")
         step = (_NativeStep if native else _HostStep)(self, arena, w_lm, buf, tab, per, w8)
         if on_gpu:
             ev0 = torch.cuda.Event(enable_timing=True)
@@ -334,8 +368,12 @@ class _NativeStep(_Step):
         def layer_tensors(i):
             return [arena.w("l%d.ln1" % i), mat(i, "qkv.w"), arena.w("l%d.qkv.b" % i), mat(i, "o.w"), arena.w("l%d.ln2" % i), mat(i, "gu.w"), mat(i, "down.w"),
                     cache.k[i], cache.vt[i]] + ([w8["layers"][i][n][1] for n in self.roll.MATS] if w8 is not None else [])
+        pk, extra = self.roll._pk_now, {}
+        if pk is not None:         # packed gate/up copies; a layer whose matrix is not representable (flag 1) keeps the bf16 launch
+            pk["event"].synchronize()
+            extra["pk"] = [None if int(f) else lt for f, lt in zip(pk["host"].tolist(), pk["layers"])]
         self.plan = ops.decode_plan([layer_tensors(i) for i in range(t.n_layers)], t.hidden, t.n_heads, t.n_kv_heads, t.head_dim, t.intermediate, t.vocab_size,
-                                    self.R, self.B, cache.s_cap, tab.nsplit, a8=self.a8, qmask=qmask)
+                                    self.R, self.B, cache.s_cap, tab.nsplit, a8=self.a8, qmask=qmask, **extra)
         lm_p = self.w_lm.data_ptr() if w8 is None else ((w8["lm"][0] if qmask & 16 else self.w_lm).data_ptr(), w8["lm"][1].data_ptr())
         self.ids = ops.zeros(self.R, dtype=I32)
         self.fixed_p = (arena.w("embed").data_ptr(), arena.w("norm").data_ptr(), lm_p, self.ids.data_ptr())

@@ -550,6 +550,75 @@ def _(frames_u8, out_h, out_w, k_pad):
     return frames_u8.new_empty(T * (out_h // 14) * (out_w // 14), k_pad, dtype=BF16)
 
 
+# ================================================================================== packed 12-bit bf16 gate/up weights: the format in plain torch
+# The definition of csrc/gemm_pk.hip's format that runs on a CPU (see the note at the head of that file): any device, integer tensor ops only.  A stage = 16 gate + 16 up rows
+# of a column-group pair x 64 k, stage index (pair * 8 + wave) * NST + s; inside a stage the value of operand op (gate k-half 0 / 1, up 0 / 1), lane
+# g * 16 + u, element e is W[(op >> 1) * I + pair * 16 + u, wave * K / 8 + s * 64 + (op & 1) * 32 + g * 8 + e].
+PK_REC, PK_TAIL_DW, PK_P = 3072, 16, 14
+
+
+def _pk_stages(w: Tensor) -> Tensor:
+    """bf16 [2I, K] -> int32 bit patterns [stages, 4 operands, 64 lanes, 8 elements]."""
+    I, K = w.shape[0] // 2, w.shape[1]
+    nst = K // 512
+    assert w.dtype == BF16 and w.shape[0] == 2 * I and I % 16 == 0 and K == 512 * nst and nst in (7, 4, 3)
+    b = w.contiguous().view(torch.int16).to(torch.int32) & 0xFFFF
+    v = b.view(2, I // 16, 16, 8, nst, 2, 4, 8)                     # up, pair, u, wave, s, khalf, g, e
+    return v.permute(1, 3, 4, 0, 5, 6, 2, 7).reshape(-1, 4, 64, 8)  # pair, wave, s | up, khalf | g, u | e
+
+
+def pack_bf16_glu_ref(w: Tensor) -> Tuple[Tensor, Tensor, bool]:
+    """-> (records uint8 [stages, 3072], tails int32 [stages, 16], representable).  Byte for byte the records and tails of the image HipOps.pack_bf16_glu writes."""
+    v = _pk_stages(w)
+    n = v.shape[0]
+    e7 = (v >> 8) & 0x7F
+    flat = e7.reshape(n, 2048)
+    base = (flat.amax(dim=1) - 7).clamp_(min=0)                                            # the window under the stage's largest value ...
+    over = (((flat < base[:, None]) | (flat > base[:, None] + 7)).sum(dim=1) > PK_P).nonzero(as_tuple=True)[0]
+    if over.numel():                                                                       # ... unless that leaves more than PK_P values outside: the fullest window
+        hist = torch.zeros(over.numel(), 129, dtype=torch.int64, device=w.device)
+        hist[:, 1:].scatter_add_(1, flat[over].to(torch.int64), torch.ones(over.numel(), 2048, dtype=torch.int64, device=w.device))
+        cs = hist.cumsum(dim=1)
+        cover = cs[:, 8:] - cs[:, :121]                                                    # values inside the window [b, b + 7], b = 0 .. 120
+        base[over] = (cover * 128 + torch.arange(121, device=w.device)).argmax(dim=1).to(base.dtype)      # among equals the highest
+    off = e7 - base.view(n, 1, 1, 1)
+    inw = (off >= 0) & (off <= 7)
+    nib = torch.where(inw, ((v >> 15) << 3) | off, torch.zeros_like(off))
+    lo = (v & 0xFF).view(n, 2, 2, 64, 8).permute(0, 1, 3, 2, 4).reshape(n, 2048)            # planes A | B: [up][lane][khalf][e]
+    code = (nib[..., :4] | (nib[..., 4:] << 4)).permute(0, 2, 1, 3).reshape(n, 1024)        # plane C: [lane][op][byte]
+    rec = torch.cat([lo, code], dim=1).to(torch.uint8)
+    miss = ~inw.reshape(n, 2048)
+    cnt = miss.sum(dim=1)
+    tails = torch.zeros(n, PK_TAIL_DW, dtype=torch.int64, device=w.device)
+    tails[:, 0] = base * 0x01010101
+    tails[:, 1] = cnt.clamp(max=PK_P)
+    r, pos = miss.nonzero(as_tuple=True)                                                   # row-major: ascending position inside each stage
+    k = (miss.cumsum(dim=1) - 1)[r, pos]
+    keep = k < PK_P
+    tails[r[keep], 2 + k[keep]] = (pos[keep] << 16) | v.reshape(n, 2048)[r[keep], pos[keep]].to(torch.int64)
+    tails = torch.where(tails >= 2 ** 31, tails - 2 ** 32, tails).to(torch.int32)
+    return rec, tails, bool((cnt <= PK_P).all())
+
+
+def unpack_bf16_glu_ref(rec: Tensor, tails: Tensor, I: int, K: int) -> Tensor:
+    """The bf16 [2I, K] weight the packed gate/up kernel multiplies by: codes against the stage base, then the patches."""
+    n, nst = rec.shape[0], K // 512
+    r = rec.to(torch.int32)
+    t = tails.to(torch.int64) & 0xFFFFFFFF
+    lo = r[:, :2048].view(n, 2, 64, 2, 8).permute(0, 1, 3, 2, 4).reshape(n, 4, 64, 8)
+    c = r[:, 2048:].view(n, 64, 4, 4).permute(0, 2, 1, 3)                                  # [op][lane][byte]
+    nib = torch.cat([c & 0xF, c >> 4], dim=3)
+    base = (t[:, 0] & 0x7F).to(torch.int32).view(n, 1, 1, 1)
+    v = (((nib >> 3) << 15) | (((nib & 7) + base) << 8) | lo).reshape(n, 2048)
+    for i in range(PK_P):
+        has = (t[:, 1] > i).nonzero(as_tuple=True)[0]
+        if has.numel():
+            e = t[has, 2 + i]
+            v[has, e >> 16] = (e & 0xFFFF).to(torch.int32)
+    v = v.view(I // 16, 8, nst, 2, 2, 4, 16, 8).permute(3, 0, 6, 1, 2, 4, 5, 7).reshape(2 * I, K)
+    return torch.where(v >= 2 ** 15, v - 2 ** 16, v).to(torch.int16).view(BF16)
+
+
 OP_NAMES = ["rmsnorm_fwd", "rmsnorm_bwd", "swiglu_fwd", "swiglu_bwd", "linear_fwd", "linear_bwd", "rope_fwd", "mrope_table", "attn_fwd", "attn_bwd",
             "logp_entropy_fwd", "logp_bwd", "logp_entropy_bwd", "entropy_quantile_weight", "lmhead_logp_entropy", "grpo_loss", "grpo_loss_ratio", "grpo_policy_loss", "sample_tokens", "sample_tokens_filtered", "penalize_logits", "mark_seen_ids",
             "mark_seen_drawn", "adamw_step", "adamw_step_sr16", "ref_mixup", "lora_merge", "lora_wgrad", "video_preprocess"]
