@@ -73,14 +73,22 @@ int tr1_gemm_nn_acc_f32(const void* A, const void* B, void* C_f32, int64_t M, in
  * glu != 0: W is [2N, K] (gate rows, then up rows) and out[M, N] = silu(gate) * up (Qwen2MLP TF:459-466) - no [M, 2N] intermediate.
  * glu == 2 (M <= 16, tr1_norm_gemm_glu_frag_ok): the same values leave FRAGMENT-MAJOR - element (m, n) at (n / 32) * 512 + m * 32 + n % 32 of `out`
  * (16 x N bf16) - the operand layout of tr1_gemm_oproj_frag, which then runs the down projection with its whole weight slice in flight (2B shapes).
- * Losslessly packed 12-bit gate/up weights (csrc/gemm_pk.hip; M <= 16, N % 16 == 0, K = 512 * {7, 4, 3}): a 4-bit sign + exponent code against a per-stage base,
- * the low byte verbatim, an exact patch list for the rest.  The IMAGE of W[2N, K] is one buffer of S * 3136 + 16 bytes, S = (N / 16) * 8 * (K / 512) stages:
- * S records of 3072 bytes, S tails of 64 bytes, then an int flag.
- * glu == 5: no GEMM - W[2N, K] (ldw) is packed into `out` (x, lnw, bias unused); flag = 1 when some stage needs more than 14 patches: the matrix is then NOT
- *   representable and the caller keeps glu = 1 / 2.
- * glu == 3 / 4: W is that image (flag 0; ldw unused); the bits glu = 1 / 2 store, 0.77x the bytes streamed. */
+ * glu is 0, 1 or 2; anything else is an argument error. */
 int tr1_norm_gemm_glu_frag_ok(int64_t M, int64_t N, int64_t K);
 int tr1_norm_gemm_skinny(const void* x, const void* lnw, const void* W, const void* bias, void* out, int64_t M, int64_t N, int64_t K, int64_t ldx, int64_t ldw, int64_t ldc, float eps, int glu, void* stream);
+/* Losslessly packed 12-bit gate/up weights (csrc/gemm_pk.hip; same call site as tr1_norm_gemm_skinny(glu = 1 / 2): post_attention_layernorm -> gate/up_proj TF:600-610,
+ * Qwen2MLP TF:459-466 inside generate): a 4-bit sign + exponent code against a per-stage base, the low byte verbatim, an exact patch list for the rest.
+ * The IMAGE of W[2I, K] (gate rows, then up rows) is one buffer of tr1_glu_pk_image_bytes(I, K) bytes: S = (I / 16) * 8 * (K / 512) stages as S records of 3072 bytes,
+ * S tails of 64 bytes, then 16 bytes whose first int is the flag.
+ * tr1_glu_pk_ok: 1 where the shape is covered - 1 <= M <= 16 rows, I >= 16, I % 16 == 0, K = 512 * {7, 4, 3}.
+ * tr1_pack_bf16_glu: W[2I, K] (ldw) -> image; flag = 1 when some stage needs more than 14 patches: the matrix is then NOT representable and the caller keeps
+ *   tr1_norm_gemm_skinny(glu = 1 / 2).
+ * tr1_norm_glu_pk: out[M, I] = silu(gate) * up of rmsnorm(x; lnw, eps) against an image with flag 0 - the bits tr1_norm_gemm_skinny(glu = 1) stores, 0.77x the bytes
+ *   streamed; frag != 0 (I % 32 == 0): the fragment-major output of glu = 2. */
+int tr1_glu_pk_ok(int64_t M, int64_t I, int64_t K);
+int64_t tr1_glu_pk_image_bytes(int64_t I, int64_t K);
+int tr1_pack_bf16_glu(const void* W, int64_t I, int64_t K, int64_t ldw, void* image, void* stream);
+int tr1_norm_glu_pk(const void* x, const void* lnw, const void* image, void* out, int64_t M, int64_t I, int64_t K, int64_t ldx, int64_t ldc, float eps, int frag, void* stream);
 /* Decode rows: input_layernorm -> fused q/k/v projection -> M-RoPE -> KV-cache append in ONE launch (tr1_norm_gemm_skinny + tr1_decode_qkv_post):
  * roped q -> q_out[M, n_heads*hd]; roped k -> kcache[slots[m], :]; v -> vtcache[:, slots[m]].  Wqkv: [(n_heads + 2 n_kv)*hd, K] (q | k | v rows).
  * ref: Qwen2VLAttention.forward TF:521-556 + DynamicCache.update inside generate (timer1_trainer.py:568-573).  head_dim % 32 == 0. */
@@ -221,22 +229,22 @@ int tr1_gemm_skinny_fixup_w8a8(const void* x, const void* W_fp8, const void* wsc
 /* One call enqueues a whole rollout decode step for R <= 64 rows: embed gather -> n_layers x {norm+qkv, rope + KV append, split-KV attention,
  * o_proj + residual, norm + gate/up + SwiGLU, down_proj + residual} -> final norm + lm_head -> logits[R, vocab] (bf16).
  * ref: per-token body of model.generate (timer1_trainer.py:568-573; Qwen2VLDecoderLayer TF:559-624, norm TF:839, lm_head TF:1323).
- * layer_ptrs: HOST array of 9 * n_layers DEVICE pointers {ln1, qkv.w, qkv.b, o.w, ln2, gu.w, down.w, K cache [B*s_cap, kv_dim],
- * V^T cache [kv_dim, B*s_cap]} per layer; dims: HOST int64[12] {n_layers, hidden, n_heads, n_kv, head_dim, intermediate, vocab, rows,
- * n_batch, s_cap, nsplit, fp8_mask (fp8 steps only; here only bit 8 is read: set = 10 pointers per layer, the tenth the packed 12-bit image of gu.w -
- * tr1_norm_gemm_skinny glu = 5 - or NULL for a layer that keeps the bf16 gate/up launch; the same logits bit for bit)}; ids int32[R]; cosb/sinb fp32 [R, head_dim/2]; slots int32[R] (absolute cache slot of each row's new token);
+ * layer_ptrs: HOST array of 14 * n_layers DEVICE pointers, per layer {ln1, qkv.w, qkv.b, o.w, ln2, gu.w, down.w, K cache [B*s_cap, kv_dim], V^T cache [kv_dim, B*s_cap],
+ * qkv.scale, o.scale, gu.scale, down.scale, gu.pk}; a slot the step does not use is NULL.  dims: HOST int64[13] {n_layers, hidden, n_heads, n_kv, head_dim,
+ * intermediate, vocab, rows, n_batch, s_cap, nsplit, fp8_mask, mode}.
+ * mode 0: bf16 weights; the scale slots, lm_head_scale and fp8_mask are unused (fp8_mask must be 0).  gu.pk: the packed 12-bit image of gu.w (tr1_pack_bf16_glu, flag 0) -
+ *   the layer's gate/up launch is then tr1_norm_glu_pk, the same logits bit for bit - or NULL for a layer that keeps the bf16 gate/up launch.
+ * mode 1 (W8A16, tr1_gemm_skinny_w8) / 2 (W8A8, every fp8 projection through tr1_gemm_skinny_w8a8, the fp8 MFMA): fp8 weights of tr1_quantize_fp8_rows with their
+ *   fp32 row scales in the scale slots, lm_head / lm_head_scale likewise; embedding, norms, biases, KV cache stay bf16; gu.pk must be NULL.
+ *   fp8_mask (bits 0..4 only): bit 0 qkv, 1 o, 2 gate/up, 3 down, 4 lm_head (31 = all).  A CLEAR bit keeps that matrix of the sampling policy in bf16: its weight slot
+ *   (or `lm_head`) then holds the bf16 weight and the bf16 decode kernel runs - the mixed-precision policies of the config-5 drift study.  lm_head_scale may be NULL
+ *   unless bit 4 is set.
+ * ids int32[R]; cosb/sinb fp32 [R, head_dim/2]; slots int32[R] (absolute cache slot of each row's new token);
  * pre/lo/hi int32[R] (two-interval mask, cache-local per batch entry); work: device scratch of tr1_decode_step_workspace_bytes(dims),
- * ZERO-FILLED once by the caller before the first step (it holds self re-arming split-K ticket counters). */
-int tr1_decode_step(const void* layer_ptrs, const int64_t* dims, const void* embed, const void* final_norm, const void* lm_head, const void* ids, const void* cosb, const void* sinb, const void* slots, const void* pre, const void* lo, const void* hi, void* work, int64_t work_bytes, void* logits, float eps, float scale, void* stream);
+ * ZERO-FILLED once by the caller before the first step (it holds self re-arming split-K ticket counters); the size depends on dims[0..10] alone. */
+int tr1_decode_step(const void* layer_ptrs, const int64_t* dims, const void* embed, const void* final_norm, const void* lm_head, const void* lm_head_scale, const void* ids, const void* cosb, const void* sinb, const void* slots, const void* pre, const void* lo, const void* hi, void* work, int64_t work_bytes, void* logits, float eps, float scale, void* stream);
 int64_t tr1_decode_step_workspace_bytes(const int64_t* dims);
-/* Same step with fp8 weights (tr1_quantize_fp8_rows): 13 pointers per layer {ln1, qkv.q, qkv.b, o.q, ln2, gu.q, down.q, K cache, V^T cache,
- * qkv.scale, o.scale, gu.scale, down.scale}; lm_head_fp8 / lm_head_scale likewise.  Embedding, norms, biases, KV cache stay bf16.
- * dims[11] = fp8_mask: bit 0 qkv, 1 o, 2 gate/up, 3 down, 4 lm_head (31 = all).  A CLEAR bit keeps that matrix of the sampling policy in bf16: its slot
- * (and `lm_head_fp8`) then holds the bf16 weight and the bf16 decode kernel runs - the mixed-precision policies of the config-5 drift study. */
-int tr1_decode_step_w8(const void* layer_ptrs, const int64_t* dims, const void* embed, const void* final_norm, const void* lm_head_fp8, const void* lm_head_scale, const void* ids, const void* cosb, const void* sinb, const void* slots, const void* pre, const void* lo, const void* hi, void* work, int64_t work_bytes, void* logits, float eps, float scale, void* stream);
-/* Same step, every projection through tr1_gemm_skinny_w8a8 (fp8 MFMA). */
-int tr1_decode_step_w8a8(const void* layer_ptrs, const int64_t* dims, const void* embed, const void* final_norm, const void* lm_head_fp8, const void* lm_head_scale, const void* ids, const void* cosb, const void* sinb, const void* slots, const void* pre, const void* lo, const void* hi, void* work, int64_t work_bytes, void* logits, float eps, float scale, void* stream);
-/* Measurement helpers (bench.py `roofline`): between begin and end every tr1_decode_step* call records a pair of HIP events on its
+/* Measurement helpers (bench.py `roofline`): between begin and end every tr1_decode_step call records a pair of HIP events on its
  * stream around each projection GEMM it launches (families 0 qkv, 1 o, 2 gate/up, 3 down, 4 lm_head).  end() synchronises those events and
  * writes, per family, the summed and the minimum launch duration in ms and the number of launches (host arrays of 5).  Not thread-safe. */
 int tr1_decode_profile_begin(void);

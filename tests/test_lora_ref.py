@@ -331,7 +331,7 @@ def test_the_two_symbols_are_declared_and_exported():
     raw = ctypes.CDLL(hip.LIB_PATH)
     for name in ("tr1_lora_merge", "tr1_lora_wgrad"):
         assert name in decls and hasattr(raw, name), name
-    assert len(decls) == 101
+    assert len(decls) == 103
     from time_r1_amd.ops import HipOps
     assert HipOps.LORA_WGRAD_MCHUNK == 256 and HipOps.lora_wgrad_splits(257, 8) == (2, 256) and HipOps.lora_wgrad_splits(256, 8) == (1, 256)
     assert HipOps.lora_wgrad_splits(5074, 18944) == (3, 1792)

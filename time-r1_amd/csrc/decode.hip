@@ -38,10 +38,14 @@ struct Carve {
         void* r = p; p += bytes; left -= bytes; return r;
     }
 };
-// D_QMASK (fp8 steps only): which matrices of the SAMPLING policy are fp8 - bit 0 qkv, 1 o, 2 gate/up, 3 down, 4 lm_head; a clear bit means that slot of the
+// D_MODE: 0 bf16 weights, 1 W8A16, 2 W8A8 (fp8 e4m3 matrices with fp32 row scales, csrc/gemm_w8.hip).
+// D_QMASK (0 in mode 0): which matrices of the SAMPLING policy are fp8 - bit 0 qkv, 1 o, 2 gate/up, 3 down, 4 lm_head; a clear bit means that slot of the
 // layer table (and the lm_head argument) holds the bf16 weight and the bf16 kernel runs (mixed-precision sampling policies: config 5's drift study)
-enum { D_LAYERS, D_HIDDEN, D_HEADS, D_KV, D_HEAD_DIM, D_INTER, D_VOCAB, D_ROWS, D_BATCH, D_SCAP, D_NSPLIT, D_QMASK, D_N };
-enum { QM_QKV = 1, QM_O = 2, QM_GU = 4, QM_DOWN = 8, QM_LM = 16, QM_ALL = 31, QM_PK = 256 };
+enum { D_LAYERS, D_HIDDEN, D_HEADS, D_KV, D_HEAD_DIM, D_INTER, D_VOCAB, D_ROWS, D_BATCH, D_SCAP, D_NSPLIT, D_QMASK, D_MODE, D_N };
+enum { QM_QKV = 1, QM_O = 2, QM_GU = 4, QM_DOWN = 8, QM_LM = 16, QM_ALL = 31 };
+// The layer table: S_N pointers per layer, NULL where the step does not use the slot.  S_*_S: the fp32 row scales of an fp8 matrix; S_GU_PK (mode 0): the packed
+// 12-bit image of gu.w (csrc/gemm_pk.hip, tr1_pack_bf16_glu), NULL for a layer that keeps the bf16 gate/up launch.
+enum { S_LN1, S_QKV_W, S_QKV_B, S_O_W, S_LN2, S_GU_W, S_DOWN_W, S_KC, S_VT, S_QKV_S, S_O_S, S_GU_S, S_DOWN_S, S_GU_PK, S_N };
 }  // namespace
 
 static int64_t decode_ws_bytes(const int64_t* d) {
@@ -56,18 +60,22 @@ static int64_t decode_ws_bytes(const int64_t* d) {
 
 extern "C" int64_t tr1_decode_step_workspace_bytes(const int64_t* dims) { return decode_ws_bytes(dims); }
 
-// One decode step.  w8 = false: bf16 weights, 9 pointers per layer.  w8 = true: the four matrices are fp8 e4m3 with fp32 row scales
-// (csrc/gemm_w8.hip), 13 pointers per layer {ln1, qkv.q, qkv.b, o.q, ln2, gu.q, down.q, K cache, V^T cache, qkv.s, o.s, gu.s, down.s}.
-// bf16 steps with QM_PK set in dims[D_QMASK]: 10 pointers per layer, the tenth the packed 12-bit image of gu.w (csrc/gemm_pk.hip, tr1_norm_gemm_skinny glu = 5) or
-// null for a layer that keeps the bf16 gate/up launch.
-static int decode_step_impl(int w8, const void* layer_ptrs, const int64_t* dims, const void* embed, const void* final_norm, const void* lm_head,
-                            const void* lm_head_scale, const void* ids, const void* cosb, const void* sinb, const void* slots, const void* pre,
-                            const void* lo, const void* hi, void* work, int64_t work_bytes, void* logits, float eps, float scale, void* stream) {
+// One decode step; the layer table, dims and the three weight modes are described at tr1_decode_step in include/timer1_hip.h.
+extern "C" int tr1_decode_step(const void* layer_ptrs, const int64_t* dims, const void* embed, const void* final_norm, const void* lm_head,
+                               const void* lm_head_scale, const void* ids, const void* cosb, const void* sinb, const void* slots, const void* pre,
+                               const void* lo, const void* hi, void* work, int64_t work_bytes, void* logits, float eps, float scale, void* stream) {
+    // the checks of the table's shape come first: nothing is launched, and no HIP call made, for a step that names its mode, mask or slots wrongly
+    TR1_CHECK_ARG(layer_ptrs && dims && work && logits, "decode_step: null argument");
+    TR1_CHECK_ARG(dims[D_MODE] >= 0 && dims[D_MODE] <= 2, "decode_step: mode (dims[12]) must be 0 (bf16), 1 (W8A16) or 2 (W8A8)");
+    const int w8 = (int)dims[D_MODE];
+    const void* const* lp = (const void* const*)layer_ptrs;
+    TR1_CHECK_ARG(!(dims[D_QMASK] & ~(int64_t)QM_ALL) && (w8 || !dims[D_QMASK]), "decode_step: fp8_mask (dims[11]) has bits 0..4 only and is 0 in mode 0");
+    for (int64_t i = 0; w8 && i < dims[D_LAYERS]; ++i)
+        TR1_CHECK_ARG(!lp[i * S_N + S_GU_PK], "decode_step: a packed gate/up image (gu.pk) needs mode 0");
     const int64_t L = dims[D_LAYERS], hid = dims[D_HIDDEN], nh = dims[D_HEADS], nkv = dims[D_KV], hd = dims[D_HEAD_DIM], inter = dims[D_INTER];
     const int64_t V = dims[D_VOCAB], R = dims[D_ROWS], B = dims[D_BATCH], scap = dims[D_SCAP], nsplit = dims[D_NSPLIT];
     TR1_CHECK_ARG(R >= 1 && R <= 64 && B >= 1 && R % B == 0, "decode_step: 1 <= rows <= 64, rows % n_batch == 0");
-    TR1_CHECK_ARG(layer_ptrs && dims && work && logits, "decode_step: null argument");
-    TR1_CHECK_ARG(!w8 || !(dims[D_QMASK] & QM_LM) || lm_head_scale, "decode_step_w8: lm_head scale missing");
+    TR1_CHECK_ARG(!(dims[D_QMASK] & QM_LM) || lm_head_scale, "decode_step: lm_head scale missing");
     const int64_t qd = nh * hd, kvd = nkv * hd, qkvd = qd + 2 * kvd, T = R / B;
     const int64_t att_floats = B * tr1_attn_fwd_workspace_floats(T, nh, nkv, hd, nsplit);
     Carve c{(char*)work, (size_t)work_bytes};
@@ -80,7 +88,7 @@ static int decode_step_impl(int w8, const void* layer_ptrs, const int64_t* dims,
     void* fix = c.take(fix_floats * 4);
     // relevant-tile lists of this step's split-KV attention: written by layer 0's launch, read by the others
     void* plan = c.take(tr1_attn_plan_ints(T, nh, nkv, B) * 4);
-    const int qm = w8 ? (int)(dims[D_QMASK] & QM_ALL) : 0;                     // fp8 matrices of this step
+    const int qm = (int)dims[D_QMASK];                                         // fp8 matrices of this step
     const bool planned = nsplit > 1 && L > 1;
     const bool down_fixup = !(qm & QM_DOWN) && R >= 16 && inter >= 8192;
     const bool down_fixup8 = w8 == 2 && (qm & QM_DOWN) && R <= 16 && inter >= 8192 && inter % 512 == 0 && hid % 64 == 0;      // fp8 MFMA: LDS-streamed split-K form
@@ -88,53 +96,50 @@ static int decode_step_impl(int w8, const void* layer_ptrs, const int64_t* dims,
     const bool down_frag = !(qm & (QM_DOWN | QM_GU)) && R <= 16 && inter > 3584 && tr1_gemm_oproj_frag_ok(R, hid, inter) &&
                            tr1_norm_gemm_glu_frag_ok(R, inter, hid);
     TR1_CHECK_ARG(c.ok, "decode_step: workspace too small (tr1_decode_step_workspace_bytes)");
-    const void* const* lp = (const void* const*)layer_ptrs;
-    const bool pk = !w8 && (dims[D_QMASK] & QM_PK);                              // the layer table carries the packed gate/up images
-    const int stride = w8 ? 13 : (pk ? 10 : 9);
 #define CK(call) do { int e__ = (call); if (e__) return e__; } while (0)
     // w8 == 2: the fp8-MFMA (W8A8) projections; w8 == 1: W8A16 (fp8 codes converted to bf16 in registers)
     auto gemm8 = w8 == 2 ? tr1_gemm_skinny_w8a8 : tr1_gemm_skinny_w8;
     CK(tr1_gather_rows(embed, ids, hA, R, hid, stream));
     void* h = hA; void* h2 = hB;
     for (int64_t i = 0; i < L; ++i) {
-        const void* const* w = lp + i * stride;
+        const void* const* w = lp + i * S_N;
         if (qm & QM_QKV) {
-            CK(gemm8(h, w[0], w[1], w[9], w[2], nullptr, qkv, R, qkvd, hid, hid, hid, qkvd, 0, eps, 0, stream));
-            CK(tr1_decode_qkv_post(qkv, qkvd, cosb, sinb, q, qd, (void*)w[7], kvd, (void*)w[8], B * scap, slots, R, nh, nkv, hd, stream));
+            CK(gemm8(h, w[S_LN1], w[S_QKV_W], w[S_QKV_S], w[S_QKV_B], nullptr, qkv, R, qkvd, hid, hid, hid, qkvd, 0, eps, 0, stream));
+            CK(tr1_decode_qkv_post(qkv, qkvd, cosb, sinb, q, qd, (void*)w[S_KC], kvd, (void*)w[S_VT], B * scap, slots, R, nh, nkv, hd, stream));
         } else if (hd % 32 == 0) {      // norm + q/k/v projection + M-RoPE + KV append in one launch
             ProfScope ps(0, stream);
-            CK(tr1_norm_gemm_qkv(h, w[0], w[1], w[2], cosb, sinb, q, qd, (void*)w[7], kvd, (void*)w[8], B * scap, slots, R, nh, nkv, hd, hid, hid, hid,
+            CK(tr1_norm_gemm_qkv(h, w[S_LN1], w[S_QKV_W], w[S_QKV_B], cosb, sinb, q, qd, (void*)w[S_KC], kvd, (void*)w[S_VT], B * scap, slots, R, nh, nkv, hd, hid, hid, hid,
                                  eps, stream));
         } else {
-            CK(tr1_norm_gemm_skinny(h, w[0], w[1], w[2], qkv, R, qkvd, hid, hid, hid, qkvd, eps, 0, stream));
-            CK(tr1_decode_qkv_post(qkv, qkvd, cosb, sinb, q, qd, (void*)w[7], kvd, (void*)w[8], B * scap, slots, R, nh, nkv, hd, stream));
+            CK(tr1_norm_gemm_skinny(h, w[S_LN1], w[S_QKV_W], w[S_QKV_B], qkv, R, qkvd, hid, hid, hid, qkvd, eps, 0, stream));
+            CK(tr1_decode_qkv_post(qkv, qkvd, cosb, sinb, q, qd, (void*)w[S_KC], kvd, (void*)w[S_VT], B * scap, slots, R, nh, nkv, hd, stream));
         }
         // bf16 o projection on the all-stages-in-flight kernel (csrc/oproj.hip) where the shape is covered: the split-KV merge then writes its rows fragment-major
         const bool o_frag = !(qm & QM_O) && nsplit > 1 && hd == 128 && tr1_gemm_oproj_frag_ok(R, hid, qd);
         if (o_frag)
-            CK(tr1_attn_fwd_planned_frag(q, qd, w[7], kvd, w[8], B * scap, o, pre, lo, hi, T, nh, nkv, scap, hd, scale, nsplit, att, att_floats, B, scap,
+            CK(tr1_attn_fwd_planned_frag(q, qd, w[S_KC], kvd, w[S_VT], B * scap, o, pre, lo, hi, T, nh, nkv, scap, hd, scale, nsplit, att, att_floats, B, scap,
                                          planned ? plan : nullptr, planned ? (i == 0 ? 1 : 2) : 0, stream));
         else
-            CK(tr1_attn_fwd_planned(q, qd, w[7], kvd, w[8], B * scap, o, qd, nullptr, pre, lo, hi, T, nh, nkv, scap, hd, scale, nsplit, att, att_floats, B,
+            CK(tr1_attn_fwd_planned(q, qd, w[S_KC], kvd, w[S_VT], B * scap, o, qd, nullptr, pre, lo, hi, T, nh, nkv, scap, hd, scale, nsplit, att, att_floats, B,
                                     scap, planned ? plan : nullptr, planned ? (i == 0 ? 1 : 2) : 0, stream));
         {
             ProfScope ps(1, stream);
-            if (o_frag) CK(tr1_gemm_oproj_frag(o, w[3], h, h2, R, hid, qd, qd, hid, hid, stream));
-            else if (qm & QM_O) CK(gemm8(o, nullptr, w[3], w[10], nullptr, h, h2, R, hid, qd, qd, qd, hid, hid, eps, 0, stream));
-            else CK(tr1_gemm_nt_bf16(o, w[3], h2, nullptr, h, R, hid, qd, qd, qd, hid, hid, 0, 0, stream));          // h2 = o Wo^T + h
+            if (o_frag) CK(tr1_gemm_oproj_frag(o, w[S_O_W], h, h2, R, hid, qd, qd, hid, hid, stream));
+            else if (qm & QM_O) CK(gemm8(o, nullptr, w[S_O_W], w[S_O_S], nullptr, h, h2, R, hid, qd, qd, qd, hid, hid, eps, 0, stream));
+            else CK(tr1_gemm_nt_bf16(o, w[S_O_W], h2, nullptr, h, R, hid, qd, qd, qd, hid, hid, 0, 0, stream));          // h2 = o Wo^T + h
         }
         {
             ProfScope ps(2, stream);
-            if (qm & QM_GU) CK(gemm8(h2, w[4], w[5], w[11], nullptr, nullptr, a, R, inter, hid, hid, hid, inter, 0, eps, 1, stream));
-            else if (pk && w[9]) CK(tr1_norm_gemm_skinny(h2, w[4], w[9], nullptr, a, R, inter, hid, hid, hid, inter, eps, down_frag ? 4 : 3, stream));
-            else CK(tr1_norm_gemm_skinny(h2, w[4], w[5], nullptr, a, R, inter, hid, hid, hid, inter, eps, down_frag ? 2 : 1, stream));
+            if (qm & QM_GU) CK(gemm8(h2, w[S_LN2], w[S_GU_W], w[S_GU_S], nullptr, nullptr, a, R, inter, hid, hid, hid, inter, 0, eps, 1, stream));
+            else if (w[S_GU_PK]) CK(tr1_norm_glu_pk(h2, w[S_LN2], w[S_GU_PK], a, R, inter, hid, hid, inter, eps, down_frag, stream));
+            else CK(tr1_norm_gemm_skinny(h2, w[S_LN2], w[S_GU_W], nullptr, a, R, inter, hid, hid, hid, inter, eps, down_frag ? 2 : 1, stream));
         }
         ProfScope ps3(3, stream);
-        if (w8 == 2 && down_fixup8) CK(tr1_gemm_skinny_fixup_w8a8(a, w[6], w[12], h, nullptr, h2, R, hid, inter, inter, inter, hid, hid, fix, fix_floats, stream));
-        else if (qm & QM_DOWN) CK(gemm8(a, nullptr, w[6], w[12], nullptr, h2, h, R, hid, inter, inter, inter, hid, hid, eps, 0, stream));
-        else if (down_frag) CK(tr1_gemm_oproj_frag(a, w[6], h2, h, R, hid, inter, inter, hid, hid, stream));         // h = a Wd^T + h2
-        else if (down_fixup) CK(tr1_gemm_skinny_fixup(a, w[6], h, nullptr, h2, R, hid, inter, inter, inter, hid, hid, fix, fix_floats, stream));
-        else CK(tr1_gemm_nt_bf16(a, w[6], h, nullptr, h2, R, hid, inter, inter, inter, hid, hid, 0, 0, stream));  // h = a Wd^T + h2
+        if (w8 == 2 && down_fixup8) CK(tr1_gemm_skinny_fixup_w8a8(a, w[S_DOWN_W], w[S_DOWN_S], h, nullptr, h2, R, hid, inter, inter, inter, hid, hid, fix, fix_floats, stream));
+        else if (qm & QM_DOWN) CK(gemm8(a, nullptr, w[S_DOWN_W], w[S_DOWN_S], nullptr, h2, h, R, hid, inter, inter, inter, hid, hid, eps, 0, stream));
+        else if (down_frag) CK(tr1_gemm_oproj_frag(a, w[S_DOWN_W], h2, h, R, hid, inter, inter, hid, hid, stream));         // h = a Wd^T + h2
+        else if (down_fixup) CK(tr1_gemm_skinny_fixup(a, w[S_DOWN_W], h, nullptr, h2, R, hid, inter, inter, inter, hid, hid, fix, fix_floats, stream));
+        else CK(tr1_gemm_nt_bf16(a, w[S_DOWN_W], h, nullptr, h2, R, hid, inter, inter, inter, hid, hid, 0, 0, stream));  // h = a Wd^T + h2
     }
     {
         ProfScope ps(4, stream);
@@ -171,25 +176,4 @@ extern "C" int tr1_decode_profile_end(double* ms_by_family, double* min_ms_by_fa
         v.clear();
     }
     return 0;
-}
-
-extern "C" int tr1_decode_step(const void* layer_ptrs, const int64_t* dims, const void* embed, const void* final_norm, const void* lm_head,
-                               const void* ids, const void* cosb, const void* sinb, const void* slots, const void* pre, const void* lo,
-                               const void* hi, void* work, int64_t work_bytes, void* logits, float eps, float scale, void* stream) {
-    return decode_step_impl(0, layer_ptrs, dims, embed, final_norm, lm_head, nullptr, ids, cosb, sinb, slots, pre, lo, hi, work, work_bytes, logits,
-                            eps, scale, stream);
-}
-
-extern "C" int tr1_decode_step_w8(const void* layer_ptrs, const int64_t* dims, const void* embed, const void* final_norm, const void* lm_head_fp8,
-                                  const void* lm_head_scale, const void* ids, const void* cosb, const void* sinb, const void* slots, const void* pre,
-                                  const void* lo, const void* hi, void* work, int64_t work_bytes, void* logits, float eps, float scale, void* stream) {
-    return decode_step_impl(1, layer_ptrs, dims, embed, final_norm, lm_head_fp8, lm_head_scale, ids, cosb, sinb, slots, pre, lo, hi, work, work_bytes,
-                            logits, eps, scale, stream);
-}
-
-extern "C" int tr1_decode_step_w8a8(const void* layer_ptrs, const int64_t* dims, const void* embed, const void* final_norm, const void* lm_head_fp8,
-                                    const void* lm_head_scale, const void* ids, const void* cosb, const void* sinb, const void* slots, const void* pre,
-                                    const void* lo, const void* hi, void* work, int64_t work_bytes, void* logits, float eps, float scale, void* stream) {
-    return decode_step_impl(2, layer_ptrs, dims, embed, final_norm, lm_head_fp8, lm_head_scale, ids, cosb, sinb, slots, pre, lo, hi, work, work_bytes,
-                            logits, eps, scale, stream);
 }

@@ -22,6 +22,7 @@
 //     loads: the stage keeps the four vector-memory operations the hand-counted vmcnt waits of the bf16 kernel assume, base and count arrive with the data they
 //     describe, and no load with a register destination sits in the stream (hipcc drains the DMA queue in front of the first use of one).
 #include "skinny_common.h"
+#include "../../include/timer1_hip.h"
 
 namespace {
 constexpr int PK_REC = 3072;                 // bytes of a record
@@ -327,16 +328,22 @@ __global__ __launch_bounds__(256) void pack_bf16_glu_kernel(const bf16_t* __rest
     else if (t < PK_REC / 16 + PK_TAIL_DW / 4) reinterpret_cast<u32x4_t*>(tails + r * PK_TAIL_DW)[t - PK_REC / 16] = src[t];
 }
 
-// ---- host side.  No entry points of their own: the C ABI reaches both through tr1_norm_gemm_skinny (glu = 3 / 4: the packed launch, glu = 5: the packer) and
-// the decode driver calls them directly.  The packed IMAGE of a [2I, K] weight is one buffer: skinny_glu_pk_stages(I, K) records of 3072 bytes, then as many
-// tails of 64 bytes, then 16 bytes whose first int is the flag (1: some stage needs more than PK_P patches - the matrix is not representable, keep the bf16 kernel).
-int64_t skinny_glu_pk_image_bytes(int64_t I, int64_t K) { return skinny_glu_pk_stages(I, K) * (PK_REC + PK_TAIL_DW * 4) + 16; }
+// ---- host side: the four entry points of the packed path (include/timer1_hip.h); the decode driver calls tr1_norm_glu_pk per layer.  The packed IMAGE of a
+// [2I, K] weight is one buffer: pk_stages(I, K) records of 3072 bytes, then as many tails of 64 bytes, then 16 bytes whose first int is the flag (1: some stage
+// needs more than PK_P patches - the matrix is not representable, keep the bf16 kernel).
+static int64_t pk_stages(int64_t I, int64_t K) { return (I / 16) * 8 * (K / 512); }
 
-int launch_pack_bf16_glu(const void* W, int64_t I, int64_t K, int64_t ldw, void* image, hipStream_t s) {
-    TR1_CHECK_ARG(skinny_glu_pk_ok(1, I, K), "pack_bf16_glu: I % 16 == 0 and K = 512 * {7, 4, 3} required");
+// <= 16 rows, whole column-group pairs, K = 512 * {7, 4, 3}
+extern "C" int tr1_glu_pk_ok(int64_t M, int64_t I, int64_t K) { return M >= 1 && M <= 16 && I >= 16 && I % 16 == 0 && skinny_lds_stream_k(K); }
+
+extern "C" int64_t tr1_glu_pk_image_bytes(int64_t I, int64_t K) { return pk_stages(I, K) * (PK_REC + PK_TAIL_DW * 4) + 16; }
+
+extern "C" int tr1_pack_bf16_glu(const void* W, int64_t I, int64_t K, int64_t ldw, void* image, void* stream) {
+    TR1_CHECK_ARG(tr1_glu_pk_ok(1, I, K), "pack_bf16_glu: I % 16 == 0 and K = 512 * {7, 4, 3} required");
     TR1_CHECK_ARG(W && image && ldw % 8 == 0 && ldw >= K, "pack_bf16_glu: null argument or ldw % 8");
     TR1_CHECK_ARG(((uintptr_t)W | (uintptr_t)image) % 16 == 0, "pack_bf16_glu: 16-byte aligned buffers required");
-    const int64_t nrec = skinny_glu_pk_stages(I, K);
+    hipStream_t s = (hipStream_t)stream;
+    const int64_t nrec = pk_stages(I, K);
     char* rec = (char*)image;
     unsigned* tails = (unsigned*)(rec + nrec * PK_REC);
     int* flag = (int*)(rec + nrec * (PK_REC + PK_TAIL_DW * 4));
@@ -347,20 +354,20 @@ int launch_pack_bf16_glu(const void* W, int64_t I, int64_t K, int64_t ldw, void*
     TR1_LAUNCH_CHECK();
 }
 
-// out = silu(gate) * up of rmsnorm(x; lnw) against the packed image (flag 0): the bits the bf16 launch stores.  frag: fragment-major output (skinny_glu_frag_ok)
-int launch_norm_glu_pk(const void* x, const void* lnw, const void* image, void* out, int64_t M, int64_t I, int64_t K, int64_t ldx, int64_t ldc, float eps,
-                       bool frag, hipStream_t s) {
-    TR1_CHECK_ARG(skinny_glu_pk_ok(M, I, K), "norm_gemm_skinny: packed gate/up needs M <= 16, N % 16 == 0, K = 512 * {7, 4, 3}");
-    TR1_CHECK_ARG(x && lnw && image && out && ldx % 8 == 0 && ldc % 8 == 0, "norm_gemm_skinny: packed gate/up: null argument or ldx % 8, ldc % 8");
-    TR1_CHECK_ARG(!frag || I % 32 == 0, "norm_gemm_skinny: fragment-major packed gate/up needs N % 32 == 0");
-    const int64_t NP = I / 16, n_cu = tr1_cu_count(), nrec = skinny_glu_pk_stages(I, K);
+// out = silu(gate) * up of rmsnorm(x; lnw) against the packed image (flag 0): the bits the bf16 launch stores.  frag: fragment-major output (tr1_norm_gemm_glu_frag_ok)
+extern "C" int tr1_norm_glu_pk(const void* x, const void* lnw, const void* image, void* out, int64_t M, int64_t I, int64_t K, int64_t ldx, int64_t ldc, float eps,
+                               int frag, void* stream) {
+    TR1_CHECK_ARG(tr1_glu_pk_ok(M, I, K), "norm_glu_pk: M <= 16, I % 16 == 0, K = 512 * {7, 4, 3} required");
+    TR1_CHECK_ARG(x && lnw && image && out && ldx % 8 == 0 && ldc % 8 == 0, "norm_glu_pk: null argument or ldx % 8, ldc % 8");
+    TR1_CHECK_ARG(!frag || I % 32 == 0, "norm_glu_pk: fragment-major output needs I % 32 == 0");
+    const int64_t NP = I / 16, n_cu = tr1_cu_count(), nrec = pk_stages(I, K);
     const unsigned grid = (unsigned)(NP < n_cu ? NP : n_cu);
     constexpr size_t dyn = pk_lds_bytes(PK_RING);
     const char* rec = (const char*)image;
     tr1_dispatch<7, 4, 3>((int)(K / 512), [&](auto NST) {
-        tr1_launch<norm_glu_lds_pk_kernel<decltype(NST)::value, PK_RING>>(dim3(grid), dim3(512), dyn, (int)dyn, s, (const bf16_t*)x, (const bf16_t*)lnw, rec,
-                                                                         (const unsigned*)(rec + nrec * PK_REC), (bf16_t*)out, (int)M, I, K, ldx, ldc, eps,
-                                                                         frag ? 1 : 0);
+        tr1_launch<norm_glu_lds_pk_kernel<decltype(NST)::value, PK_RING>>(dim3(grid), dim3(512), dyn, (int)dyn, (hipStream_t)stream, (const bf16_t*)x,
+                                                                         (const bf16_t*)lnw, rec, (const unsigned*)(rec + nrec * PK_REC), (bf16_t*)out, (int)M, I, K,
+                                                                         ldx, ldc, eps, frag ? 1 : 0);
     });
     TR1_LAUNCH_CHECK();
 }

@@ -639,9 +639,7 @@ static void launch_norm_glu_lds(int64_t nst, unsigned grid, size_t dyn, hipStrea
 
 extern "C" int tr1_norm_gemm_skinny(const void* x, const void* lnw, const void* W, const void* bias, void* out, int64_t M, int64_t N, int64_t K,
                                     int64_t ldx, int64_t ldw, int64_t ldc, float eps, int glu, void* stream) {
-    // glu = 3 / 4: W is the packed 12-bit image of the gate/up weight (row-major / fragment-major output); glu = 5: no GEMM, W [2N, K] is packed into `out` (gemm_pk.hip)
-    if (glu == 5) return launch_pack_bf16_glu(W, N, K, ldw, out, (hipStream_t)stream);
-    if (glu == 3 || glu == 4) return launch_norm_glu_pk(x, lnw, W, out, M, N, K, ldx, ldc, eps, glu == 4, (hipStream_t)stream);
+    TR1_CHECK_ARG(glu >= 0 && glu <= 2, "norm_gemm_skinny: glu must be 0, 1 or 2 (packed gate/up weights: tr1_norm_glu_pk)");
     TR1_CHECK_ARG(K % BK == 0 && K >= BK, "norm_gemm_skinny: K must be a positive multiple of 64");
     TR1_CHECK_ARG(M >= 1 && M <= 64, "norm_gemm_skinny: 1 <= M <= 64 (decode rows)");
     TR1_CHECK_ARG(N % 8 == 0 && ldx % 8 == 0 && ldw % 8 == 0 && ldc % 8 == 0, "norm_gemm_skinny: N%8, ldx%8, ldw%8, ldc%8 required");

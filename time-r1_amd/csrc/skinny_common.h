@@ -13,14 +13,6 @@
 void launch_skinny(const void* A, const void* B, void* C, const void* bias, const void* residual, int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldb,
                    int64_t ldc, int64_t ldr, int out_f32, int ksplit, hipStream_t s);
 
-// The packed 12-bit gate/up path (gemm_pk.hip): shapes it covers (<= 16 rows, whole column-group pairs, K = 512 * {7, 4, 3}), stages of an image, the launches.
-inline bool skinny_glu_pk_ok(int64_t M, int64_t I, int64_t K) { return M >= 1 && M <= 16 && I >= 16 && I % 16 == 0 && K % 512 == 0 && (K / 512 == 7 || K / 512 == 4 || K / 512 == 3); }
-inline int64_t skinny_glu_pk_stages(int64_t I, int64_t K) { return (I / 16) * 8 * (K / 512); }
-int64_t skinny_glu_pk_image_bytes(int64_t I, int64_t K);
-int launch_pack_bf16_glu(const void* W, int64_t I, int64_t K, int64_t ldw, void* image, hipStream_t s);
-int launch_norm_glu_pk(const void* x, const void* lnw, const void* image, void* out, int64_t M, int64_t I, int64_t K, int64_t ldx, int64_t ldc, float eps, bool frag,
-                       hipStream_t s);
-
 TR1_DEV float silu_f32(float x) { return x / (1.f + __expf(-x)); }
 // x' = bf16(x * w) of one MFMA fragment (the rmsnorm weight folded into the operand) while ss accumulates sum x^2
 TR1_DEV bf16x8_t scale_frag_sumsq(bf16x8_t x, bf16x8_t w, float& ss) {

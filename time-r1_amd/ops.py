@@ -266,26 +266,24 @@ class HipOps:
         self.L.call("tr1_norm_gemm_skinny", _p(x), _p(lnw), _p(w), _p(bias), _p(out), M, N, K, x.stride(0), w.stride(0), N, float(eps), int(glu), self._s())
         return out
 
-    # ---- losslessly packed 12-bit gate/up weights (decode rows; csrc/gemm_pk.hip through tr1_norm_gemm_skinny glu = 3 / 4 / 5) -------------------------
-    @staticmethod
-    def glu_pk_ok(M, I, K):
-        """The shapes the packed gate/up kernel covers (the launcher checks the same rule)."""
-        return 1 <= M <= 16 and I >= 16 and I % 16 == 0 and K in (3584, 2048, 1536)
+    # ---- losslessly packed 12-bit gate/up weights (decode rows; csrc/gemm_pk.hip: tr1_glu_pk_ok, tr1_glu_pk_image_bytes, tr1_pack_bf16_glu, tr1_norm_glu_pk) ------
+    def glu_pk_ok(self, M, I, K):
+        """The shapes the packed gate/up kernel covers."""
+        return bool(self.L.raw("tr1_glu_pk_ok")(M, I, K))
 
-    @staticmethod
-    def pack_bf16_glu_stages(I, K):
-        return (I // 16) * 8 * (K // 512)
+    def pack_bf16_glu_image_bytes(self, I, K):
+        return int(self.L.raw("tr1_glu_pk_image_bytes")(I, K))
 
     def pack_bf16_glu(self, w, image=None):
-        """bf16 [2I, K] -> the packed image, uint8 [stages * 3136 + 16]: records (3072 bytes a stage), tails (64), an int32 flag; flag = 1: some stage
+        """bf16 [2I, K] -> the packed image, uint8 [pack_bf16_glu_image_bytes(I, K)]: records (3072 bytes a stage), tails (64), an int32 flag; flag = 1: some stage
         overflows its patch list, the matrix is not representable (pack_flag(image)).  image may be preallocated.  No host synchronisation."""
         self._chk(w)
         I, K = w.shape[0] // 2, w.shape[1]
         assert w.stride(1) == 1 and self.glu_pk_ok(1, I, K)
-        nb = self.pack_bf16_glu_stages(I, K) * 3136 + 16
+        nb = self.pack_bf16_glu_image_bytes(I, K)
         image = self.empty(nb, dtype=torch.uint8) if image is None else image
         assert image.dtype == torch.uint8 and image.numel() == nb and image.is_contiguous()
-        self.L.call("tr1_norm_gemm_skinny", 0, 0, _p(w), 0, _p(image), 1, I, K, 0, w.stride(0), 0, 0.0, 5, self._s())
+        self.L.call("tr1_pack_bf16_glu", _p(w), I, K, w.stride(0), _p(image), self._s())
         return image
 
     @staticmethod
@@ -296,9 +294,9 @@ class HipOps:
         """norm_gemm(..., glu) against the packed image of the weight: the same bits, 0.77x the bytes streamed."""
         self._chk(x, lnw)
         M, K = x.shape
-        assert x.stride(1) == 1 and lnw.numel() == K and self.glu_pk_ok(M, I, K) and image.numel() == self.pack_bf16_glu_stages(I, K) * 3136 + 16
+        assert x.stride(1) == 1 and lnw.numel() == K and self.glu_pk_ok(M, I, K) and image.numel() == self.pack_bf16_glu_image_bytes(I, K)
         out = self.zeros(16 * I) if int(glu) == 2 else self.empty(M, I)
-        self.L.call("tr1_norm_gemm_skinny", _p(x), _p(lnw), _p(image), 0, _p(out), M, I, K, x.stride(0), K, I, float(eps), 4 if int(glu) == 2 else 3, self._s())
+        self.L.call("tr1_norm_glu_pk", _p(x), _p(lnw), _p(image), _p(out), M, I, K, x.stride(0), I, float(eps), int(int(glu) == 2), self._s())
         return out
 
     def norm_gemm_qkv(self, x, lnw, eps, wqkv, bias, cos, sin, kcache, vtcache, slots, n_heads, n_kv, head_dim):
@@ -344,40 +342,31 @@ class HipOps:
         return out
 
     # ---- native decode-step driver ------------------------------------------------------------------------------------
-    def decode_plan(self, layers, hidden, n_heads, n_kv, head_dim, inter, vocab, rows, n_batch, s_cap, nsplit, a8=False, qmask=31, pk=None):
-        """layers: per decoder layer the 9 tensors (ln1, qkv.w, qkv.b, o.w, ln2, gu.w, down.w, K cache, V^T cache).  Builds the host
-        pointer table + device scratch once per rollout; decode_step then costs one C call per generated token.
-        pk (bf16 steps): per layer the image pack_bf16_glu(gu.w), or None for a layer that keeps the bf16 gate/up launch."""
+    DECODE_LAYER_SLOTS = ("ln1", "qkv.w", "qkv.b", "o.w", "ln2", "gu.w", "down.w", "k", "vt", "qkv.scale", "o.scale", "gu.scale", "down.scale", "gu.pk")
+    DECODE_MODES = {"bf16": 0, "fp8": 1, "fp8-mfma": 2}
+
+    def decode_plan(self, layers, hidden, n_heads, n_kv, head_dim, inter, vocab, rows, n_batch, s_cap, nsplit, weights="bf16", qmask=0):
+        """layers: per decoder layer a dict of tensors keyed by DECODE_LAYER_SLOTS (the layer table of tr1_decode_step; k / vt: the layer's K and V^T cache); a
+        missing key is a NULL slot.  weights "fp8" / "fp8-mfma": the matrices whose bit of qmask is set are fp8 codes with their row scales in the *.scale slots.
+        "gu.pk" (bf16 only): the image pack_bf16_glu(gu.w) - absent for a layer that keeps the bf16 gate/up launch.  Builds the host pointer table + device scratch
+        once per rollout; decode_step then costs one C call per generated token."""
         import ctypes
-        flat = [t for L in layers for t in L]
-        per = len(flat) // max(len(layers), 1)
-        assert per in (9, 13) and len(flat) == per * len(layers)      # 13 = fp8 matrices + their row scales (decode_step_w8)
-        use_pk = pk is not None and per == 9 and any(p is not None for p in pk)
-        if use_pk:         # a tenth pointer per layer and bit 8 of the mask word say so to the driver
-            assert len(pk) == len(layers)
-            tab = [a for L, p in zip(layers, pk) for a in [t.data_ptr() for t in L] + [p.data_ptr() if p is not None else None]]
-            flat = flat + [p for p in pk if p is not None]
-            qmask = int(qmask) | 256
-        else:
-            tab = [t.data_ptr() for t in flat]
+        assert all(set(L) <= set(self.DECODE_LAYER_SLOTS) for L in layers)
+        tab = [L[n].data_ptr() if n in L else None for L in layers for n in self.DECODE_LAYER_SLOTS]
         ptrs = (ctypes.c_void_p * len(tab))(*tab)
-        dims = (ctypes.c_int64 * 12)(len(layers), hidden, n_heads, n_kv, head_dim, inter, vocab, rows, n_batch, s_cap, nsplit, int(qmask))   # qmask: fp8 steps (+ bit 8)
+        dims = (ctypes.c_int64 * 13)(len(layers), hidden, n_heads, n_kv, head_dim, inter, vocab, rows, n_batch, s_cap, nsplit, int(qmask), self.DECODE_MODES[weights])
         nbytes = int(self.L.raw("tr1_decode_step_workspace_bytes")(dims))
         work = torch.zeros(nbytes, dtype=torch.uint8, device=self.device)     # zero: the split-K ticket counters inside start disarmed
         logits = self.empty(rows, vocab)
-        return dict(pk=[p is not None for p in pk] if use_pk else None, ptrs=ptrs, ptrs_p=ctypes.cast(ptrs, ctypes.c_void_p), dims=dims, work=work, work_p=work.data_ptr(), nbytes=nbytes,
-                    logits=logits, logits_p=logits.data_ptr(), keep=flat, stream=self._s(), w8=per == 13, a8=bool(a8))
+        pk = ["gu.pk" in L for L in layers]
+        return dict(pk=pk if any(pk) else None, ptrs=ptrs, ptrs_p=ctypes.cast(ptrs, ctypes.c_void_p), dims=dims, work=work, work_p=work.data_ptr(), nbytes=nbytes,
+                    logits=logits, logits_p=logits.data_ptr(), keep=layers, stream=self._s())
 
-    def decode_step(self, plan, embed_p, norm_p, lm_head_p, ids_p, cos_p, sin_p, slots_p, pre_p, lo_p, hi_p, eps, scale):
-        """All arguments after `plan` are raw device addresses (ints): the caller precomputes row pointers into its step tables.
-        Returns plan["logits"] [rows, vocab] (overwritten every step)."""
-        if plan["w8"]:
-            lm_q, lm_s = lm_head_p                  # (fp8 codes address, row scales address)
-            self.L.call("tr1_decode_step_w8a8" if plan.get("a8") else "tr1_decode_step_w8", plan["ptrs_p"], plan["dims"], embed_p, norm_p, lm_q, lm_s, ids_p, cos_p, sin_p, slots_p, pre_p, lo_p,
-                        hi_p, plan["work_p"], plan["nbytes"], plan["logits_p"], float(eps), float(scale), plan["stream"])
-        else:
-            self.L.call("tr1_decode_step", plan["ptrs_p"], plan["dims"], embed_p, norm_p, lm_head_p, ids_p, cos_p, sin_p, slots_p, pre_p, lo_p, hi_p,
-                        plan["work_p"], plan["nbytes"], plan["logits_p"], float(eps), float(scale), plan["stream"])
+    def decode_step(self, plan, embed_p, norm_p, lm_head_p, lm_scale_p, ids_p, cos_p, sin_p, slots_p, pre_p, lo_p, hi_p, eps, scale):
+        """All arguments after `plan` are raw device addresses (ints; lm_scale_p: 0 unless the lm_head is fp8): the caller precomputes row pointers into its step
+        tables.  Returns plan["logits"] [rows, vocab] (overwritten every step)."""
+        self.L.call("tr1_decode_step", plan["ptrs_p"], plan["dims"], embed_p, norm_p, lm_head_p, lm_scale_p, ids_p, cos_p, sin_p, slots_p, pre_p, lo_p, hi_p,
+                    plan["work_p"], plan["nbytes"], plan["logits_p"], float(eps), float(scale), plan["stream"])
         return plan["logits"]
 
     def attn_fwd_frag(self, q, k, vt, pre, lo, hi, n_heads, n_kv, n_slots, head_dim, scale, nsplit, n_batch=1, kv_batch_slots=0, plan=None, plan_mode=0):

@@ -144,7 +144,7 @@ class Rollout:
             return None
         pk = getattr(self.eng, "glu_pk", None)
         if pk is None:
-            nb = ops.pack_bf16_glu_stages(t.intermediate, t.hidden) * 3136 + 16
+            nb = ops.pack_bf16_glu_image_bytes(t.intermediate, t.hidden)
             if self.calls < self.PK_FROM_CALL or torch.cuda.mem_get_info(ops.device)[0] < t.n_layers * (nb + 1024) + self.PK_HEADROOM:
                 return None
             pk = self.eng.glu_pk = dict(key=None, layers=[ops.empty(nb, dtype=torch.uint8) for _ in range(t.n_layers)], flags=ops.zeros(t.n_layers, dtype=I32),
@@ -365,18 +365,25 @@ class _NativeStep(_Step):
         def mat(i, n):      # fp8 codes, or the bf16 weight itself where there is no fp8 copy or the mask keeps this matrix in bf16
             return w8["layers"][i][n][0] if w8 is not None and qmask & self.roll.QBITS[n[:-2]] else arena.w("l%d.%s" % (i, n))
 
-        def layer_tensors(i):
-            return [arena.w("l%d.ln1" % i), mat(i, "qkv.w"), arena.w("l%d.qkv.b" % i), mat(i, "o.w"), arena.w("l%d.ln2" % i), mat(i, "gu.w"), mat(i, "down.w"),
-                    cache.k[i], cache.vt[i]] + ([w8["layers"][i][n][1] for n in self.roll.MATS] if w8 is not None else [])
-        pk, extra = self.roll._pk_now, {}
+        pk, images = self.roll._pk_now, {}
         if pk is not None:         # packed gate/up copies; a layer whose matrix is not representable (flag 1) keeps the bf16 launch
             pk["event"].synchronize()
-            extra["pk"] = [None if int(f) else lt for f, lt in zip(pk["host"].tolist(), pk["layers"])]
+            images = {i: image for i, (f, image) in enumerate(zip(pk["host"].tolist(), pk["layers"])) if not int(f)}
+
+        def layer_tensors(i):      # the slots of HipOps.DECODE_LAYER_SLOTS this step uses
+            L = {n: arena.w("l%d.%s" % (i, n)) for n in ("ln1", "qkv.b", "ln2")}
+            L.update({n: mat(i, n) for n in self.roll.MATS}, k=cache.k[i], vt=cache.vt[i])
+            if w8 is not None:
+                L.update({n[:-1] + "scale": w8["layers"][i][n][1] for n in self.roll.MATS})
+            if i in images:
+                L["gu.pk"] = images[i]
+            return L
+        fp8 = w8 is not None
         self.plan = ops.decode_plan([layer_tensors(i) for i in range(t.n_layers)], t.hidden, t.n_heads, t.n_kv_heads, t.head_dim, t.intermediate, t.vocab_size,
-                                    self.R, self.B, cache.s_cap, tab.nsplit, a8=self.a8, qmask=qmask, **extra)
-        lm_p = self.w_lm.data_ptr() if w8 is None else ((w8["lm"][0] if qmask & 16 else self.w_lm).data_ptr(), w8["lm"][1].data_ptr())
+                                    self.R, self.B, cache.s_cap, tab.nsplit, weights=self.roll.weight_dtype if fp8 else "bf16", qmask=qmask if fp8 else 0)
+        lm_p, lm_scale_p = (w8["lm"][0].data_ptr(), w8["lm"][1].data_ptr()) if fp8 and qmask & 16 else (self.w_lm.data_ptr(), 0)
         self.ids = ops.zeros(self.R, dtype=I32)
-        self.fixed_p = (arena.w("embed").data_ptr(), arena.w("norm").data_ptr(), lm_p, self.ids.data_ptr())
+        self.fixed_p = (arena.w("embed").data_ptr(), arena.w("norm").data_ptr(), lm_p, lm_scale_p, self.ids.data_ptr())
         self.cos_p, self.sin_p, self.slot_p, self.hi_p = tab.cos.data_ptr(), tab.sin.data_ptr(), tab.slots.data_ptr(), tab.hi.data_ptr()
         self.pre_p, self.lo_p = tab.pre.data_ptr(), tab.lo.data_ptr()
         self.row_bytes, self.rope_bytes = self.R * 4, self.R * (t.head_dim // 2) * 4      # one step's row of the int32 [C, R] / fp32 [C, R, half] tables
