@@ -296,12 +296,17 @@ int tr1_grpo_loss_ratio(const void* logp, const void* old_logp, const void* ref_
 int tr1_grpo_policy_loss(const void* logp, const void* old_logp /*may be null*/, const void* ref_logp /*may be null*/, const void* tok_weight /*may be null*/, const void* mask, const void* adv, void* dlogp, void* out8, void* row_len, void* row_kl, void* ws, int64_t G, int64_t C, float beta, int norm_mode, int seq_level, float eps_low, float eps_high, float delta, float grad_scale, void* stream);
 /* ref: model.generate(do_sample=True, temperature, top_k) at timer1_trainer.py:568-573.  tokens[row*tok_ld + *step_ptr] = draw.
  * group_rows > 0: rows [b*group_rows, (b+1)*group_rows) belong to prompt b and draw from the stream (seed + b*seed_stride, row % group_rows, step),
- * so several prompts sampled in one launch get exactly the tokens of one launch per prompt. */
-int tr1_sample_tokens(const void* logits, int64_t ld, int64_t rows, int64_t V, float temperature, int64_t top_k, uint64_t seed, int64_t group_rows, uint64_t seed_stride, const void* step_ptr, void* tokens, int64_t tok_ld, void* finished, int64_t eos_id, int64_t pad_id, int stop_at_eos, void* u_out, void* ws_u32, int64_t ws_words, void* stream);
+ * so several prompts sampled in one launch get exactly the tokens of one launch per prompt.
+ * done_count (last argument of the four tr1_sample_tokens* entry points; int32 [1], null = off, needs finished): a rollout that ends when every row has drawn
+ * its EOS (ref: scripts/finetune/run_activitynet.sh sets --max_completion_length 1024 for answers of one or two hundred tokens).  The lane that writes a row's
+ * token adds 1 with an ordinary atomicAdd when finished[row] goes 0 -> 1: once per row; a second EOS of a row that runs on (stop_at_eos = 0) and rows skipped
+ * as finished do not count - tr1_greedy_tokens_step keeps the same counter - so the host polls one word instead of summing the flags.  It is declared behind
+ * `stream` so that the argument list of the earlier declaration is a prefix of this one. */
+int tr1_sample_tokens(const void* logits, int64_t ld, int64_t rows, int64_t V, float temperature, int64_t top_k, uint64_t seed, int64_t group_rows, uint64_t seed_stride, const void* step_ptr, void* tokens, int64_t tok_ld, void* finished, int64_t eos_id, int64_t pad_id, int stop_at_eos, void* u_out, void* ws_u32, int64_t ws_words, void* stream, void* done_count /*may be null*/);
 /* The decode loop's form (model.generate's per-token sampling, timer1_trainer.py:568-573): next_ids[row] (optional) receives the drawn token as well - the
  * buffer the next step's embedding gather reads - and ws_zeroed != 0 promises a workspace zero-filled ONCE and only used through this entry point (the pick
  * kernel re-zeroes it), so neither a copy kernel nor a memset runs between two decode steps. */
-int tr1_sample_tokens_step(const void* logits, int64_t ld, int64_t rows, int64_t V, float temperature, int64_t top_k, uint64_t seed, int64_t group_rows, uint64_t seed_stride, const void* step_ptr, void* tokens, int64_t tok_ld, void* finished, int64_t eos_id, int64_t pad_id, int stop_at_eos, void* u_out, void* ws_u32, int64_t ws_words, void* next_ids, int ws_zeroed, void* stream);
+int tr1_sample_tokens_step(const void* logits, int64_t ld, int64_t rows, int64_t V, float temperature, int64_t top_k, uint64_t seed, int64_t group_rows, uint64_t seed_stride, const void* step_ptr, void* tokens, int64_t tok_ld, void* finished, int64_t eos_id, int64_t pad_id, int stop_at_eos, void* u_out, void* ws_u32, int64_t ws_words, void* next_ids, int ws_zeroed, void* stream, void* done_count /*may be null*/);
 int64_t tr1_sample_workspace_words(int64_t rows);
 /* TF: TopPLogitsWarper and MinPLogitsWarper behind TemperatureLogitsWarper and TopKLogitsWarper (transformers generation/logits_process.py; the order of
  * GenerationMixin._get_logits_processor), and SamplingParams(top_p=...) of ref: src/vllm_inference/vllm_infer.py:106-111.  The arguments of tr1_sample_tokens /
@@ -310,8 +315,8 @@ int64_t tr1_sample_workspace_words(int64_t rows);
  * (deterministic where the warper's unstable sort is not; identical on rows without ties), the maximum always stays.  min-p keeps x iff
  * exp((x - max)/T) >= min_p.  The kept set is the intersection of the three; the draw is the inverse CDF of tr1_sample_tokens with the same Philox stream.
  * With top_p = 1 and min_p = 0 the launches and the tokens are those of tr1_sample_tokens / tr1_sample_tokens_step. */
-int tr1_sample_tokens_filtered(const void* logits, int64_t ld, int64_t rows, int64_t V, float temperature, int64_t top_k, float top_p, float min_p, uint64_t seed, int64_t group_rows, uint64_t seed_stride, const void* step_ptr, void* tokens, int64_t tok_ld, void* finished, int64_t eos_id, int64_t pad_id, int stop_at_eos, void* u_out, void* ws_u32, int64_t ws_words, void* stream);
-int tr1_sample_tokens_filtered_step(const void* logits, int64_t ld, int64_t rows, int64_t V, float temperature, int64_t top_k, float top_p, float min_p, uint64_t seed, int64_t group_rows, uint64_t seed_stride, const void* step_ptr, void* tokens, int64_t tok_ld, void* finished, int64_t eos_id, int64_t pad_id, int stop_at_eos, void* u_out, void* ws_u32, int64_t ws_words, void* next_ids, int ws_zeroed, void* stream);
+int tr1_sample_tokens_filtered(const void* logits, int64_t ld, int64_t rows, int64_t V, float temperature, int64_t top_k, float top_p, float min_p, uint64_t seed, int64_t group_rows, uint64_t seed_stride, const void* step_ptr, void* tokens, int64_t tok_ld, void* finished, int64_t eos_id, int64_t pad_id, int stop_at_eos, void* u_out, void* ws_u32, int64_t ws_words, void* stream, void* done_count /*may be null*/);
+int tr1_sample_tokens_filtered_step(const void* logits, int64_t ld, int64_t rows, int64_t V, float temperature, int64_t top_k, float top_p, float min_p, uint64_t seed, int64_t group_rows, uint64_t seed_stride, const void* step_ptr, void* tokens, int64_t tok_ld, void* finished, int64_t eos_id, int64_t pad_id, int stop_at_eos, void* u_out, void* ws_u32, int64_t ws_words, void* next_ids, int ws_zeroed, void* stream, void* done_count /*may be null*/);
 int64_t tr1_sample_filtered_workspace_words(int64_t rows);
 /* TF: RepetitionPenaltyLogitsProcessor (transformers generation/logits_process.py), SamplingParams(repetition_penalty=...) of ref:
  * src/vllm_inference/vllm_infer.py:106-111.  out[r, v] = logits[r, v] where bit v of seen[r] is clear, else x * penalty (x < 0) or x / penalty, computed in

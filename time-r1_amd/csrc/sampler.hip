@@ -31,6 +31,7 @@ struct SampleArgs {
     int* finished; int eos_id, pad_id, stop_at_eos; float* u_out; unsigned* ws;
     int* next_ids;      // optional [rows]: the drawn token once more, where the next decode step's embedding gather reads it (no copy kernel in between)
     int ws_clean;       // the caller zero-filled ws once: the fused pick kernel re-zeroes what the histogram kernels dirtied (no memset per call)
+    int* done_count;    // optional [1]: += 1 when a row's finished flag goes 0 -> 1 (the early-stop poll of a sampled rollout reads it); NULL = off
 };
 // The launches of the top-p / min-p path carry three more arguments; without those filters the kernels receive SampleArgs and run the code they always ran.
 struct SampleArgsF : SampleArgs {
@@ -39,6 +40,13 @@ struct SampleArgsF : SampleArgs {
 };
 
 TR1_DEV bool samp_row_done(const SampleArgs& a, int r) { return a.finished && a.stop_at_eos && a.finished[r]; }
+// The one lane that wrote the row's token: EOS raises finished[r]; done_count counts the 0 -> 1 transition only (a second EOS of a row that runs on with
+// stop_at_eos = 0 finds the flag set; rows skipped as done never get here).  finished[r] is written by this lane alone, so the read needs no atomic.
+TR1_DEV void samp_mark_eos(const SampleArgs& a, int r, int tok) {
+    if (!a.finished || tok != a.eos_id) return;
+    if (a.done_count && !a.finished[r]) atomicAdd(a.done_count, 1);
+    a.finished[r] = 1;
+}
 
 // threshold search over a 256-bin histogram: largest bin b with (count of keys in bins > b) < need <= (count in bins >= b)
 TR1_DEV void samp_find_bin(const unsigned* hist, int need, int& bin, int& rem) {
@@ -194,7 +202,7 @@ template <bool EXT> TR1_DEV void samp_pick_body(const SampleArgs& a, unsigned* e
         }
         *tok_out = tok;
         if (a.next_ids) a.next_ids[r] = tok;
-        if (a.finished && tok == a.eos_id) a.finished[r] = 1;
+        samp_mark_eos(a, r, tok);
     }
 }
 __global__ __launch_bounds__(256) void samp_pick_kernel(SampleArgs a) { samp_pick_body<false>(a, nullptr); }
@@ -324,7 +332,7 @@ template <bool EXT> TR1_DEV void samp_sum_pick_body(const SampleArgs& a, unsigne
     }
     *tok_out = tok;
     if (a.next_ids) a.next_ids[r] = tok;
-    if (a.finished && tok == a.eos_id) a.finished[r] = 1;
+    samp_mark_eos(a, r, tok);
 }
 __global__ __launch_bounds__(1024) void samp_sum_pick_kernel(SampleArgs a) { samp_sum_pick_body<false>(a, nullptr); }
 __global__ __launch_bounds__(1024) void samp_sum_pick_ext_kernel(SampleArgsF a) { samp_sum_pick_body<true>(a, a.ext); }
@@ -589,8 +597,9 @@ extern "C" int64_t tr1_sample_workspace_words(int64_t rows) { return rows * SAMP
 static int sample_tokens_impl(const void* logits, int64_t ld, int64_t rows, int64_t V, float temperature, int64_t top_k, float top_p, float min_p,
                                  uint64_t seed, int64_t group_rows, uint64_t seed_stride, const void* step_ptr, void* tokens, int64_t tok_ld,
                                  void* finished, int64_t eos_id, int64_t pad_id, int stop_at_eos, void* u_out, void* ws_u32, int64_t ws_words,
-                                 void* next_ids, int ws_zeroed, bool filtered, void* stream) {
+                                 void* next_ids, int ws_zeroed, bool filtered, void* done_count, void* stream) {
     TR1_CHECK_ARG(temperature > 0.f, "sample: temperature must be > 0");
+    TR1_CHECK_ARG(!done_count || finished, "sample: done_count counts the rows whose finished flag rises: finished must not be null");
     const int64_t row_words = filtered ? SAMP_WS_WORDS + SAMP_EXT_WORDS : SAMP_WS_WORDS;
     TR1_CHECK_ARG(ws_u32 && ws_words >= rows * row_words, "sample: workspace too small (tr1_sample_workspace_words / tr1_sample_filtered_workspace_words)");
     TR1_CHECK_ARG(!filtered || (top_p > 0.f && top_p <= 1.f && min_p >= 0.f && min_p <= 1.f), "sample: need 0 < top_p <= 1 and 0 <= min_p <= 1");
@@ -602,7 +611,7 @@ static int sample_tokens_impl(const void* logits, int64_t ld, int64_t rows, int6
     a.logits = (const bf16_t*)logits; a.ld = ld; a.V = (int)V; a.inv_temp = 1.0f / temperature; a.top_k = (int)top_k; a.seed = seed; a.group_rows = (int)group_rows; a.seed_stride = seed_stride;
     a.step_ptr = (const int*)step_ptr; a.tokens = (int*)tokens; a.tok_ld = tok_ld; a.finished = (int*)finished; a.eos_id = (int)eos_id;
     a.pad_id = (int)pad_id; a.stop_at_eos = stop_at_eos; a.u_out = (float*)u_out; a.ws = (unsigned*)ws_u32;
-    a.next_ids = (int*)next_ids;
+    a.next_ids = (int*)next_ids; a.done_count = (int*)done_count;
     // top_p = 1 and min_p = 0 keep everything: exactly the launches of the unfiltered entry points
     const bool use_p = filtered && top_p < 1.f, use_m = filtered && min_p > 0.f;
     a.ext = (use_p || use_m) ? (unsigned*)ws_u32 + rows * SAMP_WS_WORDS : nullptr;
@@ -636,12 +645,15 @@ static int sample_tokens_impl(const void* logits, int64_t ld, int64_t rows, int6
     TR1_LAUNCH_CHECK();
 }
 
+// done_count (the last argument of the four sampling entry points; int32 [1], may be NULL = off, needs finished): the lane that writes a row's token adds 1
+// with an ordinary atomicAdd when finished[row] goes 0 -> 1 - once per row, as tr1_greedy_tokens_step counts - so the early stop of a sampled rollout
+// (Rollout.early_stop) polls one word.  It stands behind `stream`: a caller of the earlier declaration that passes NULL there is a caller of this one.
 extern "C" int tr1_sample_tokens(const void* logits, int64_t ld, int64_t rows, int64_t V, float temperature, int64_t top_k,
                                  uint64_t seed, int64_t group_rows, uint64_t seed_stride, const void* step_ptr, void* tokens, int64_t tok_ld,
                                  void* finished, int64_t eos_id, int64_t pad_id, int stop_at_eos, void* u_out, void* ws_u32, int64_t ws_words,
-                                 void* stream) {
+                                 void* stream, void* done_count) {
     return sample_tokens_impl(logits, ld, rows, V, temperature, top_k, 1.f, 0.f, seed, group_rows, seed_stride, step_ptr, tokens, tok_ld, finished, eos_id, pad_id,
-                              stop_at_eos, u_out, ws_u32, ws_words, nullptr, 0, false, stream);
+                              stop_at_eos, u_out, ws_u32, ws_words, nullptr, 0, false, done_count, stream);
 }
 
 // The decode loop's form: next_ids[row] (optional) receives the drawn token as well - the buffer the next step's embedding gather reads, so no copy
@@ -650,9 +662,9 @@ extern "C" int tr1_sample_tokens(const void* logits, int64_t ld, int64_t rows, i
 extern "C" int tr1_sample_tokens_step(const void* logits, int64_t ld, int64_t rows, int64_t V, float temperature, int64_t top_k,
                                       uint64_t seed, int64_t group_rows, uint64_t seed_stride, const void* step_ptr, void* tokens, int64_t tok_ld,
                                       void* finished, int64_t eos_id, int64_t pad_id, int stop_at_eos, void* u_out, void* ws_u32, int64_t ws_words,
-                                      void* next_ids, int ws_zeroed, void* stream) {
+                                      void* next_ids, int ws_zeroed, void* stream, void* done_count) {
     return sample_tokens_impl(logits, ld, rows, V, temperature, top_k, 1.f, 0.f, seed, group_rows, seed_stride, step_ptr, tokens, tok_ld, finished, eos_id, pad_id,
-                              stop_at_eos, u_out, ws_u32, ws_words, next_ids, ws_zeroed, false, stream);
+                              stop_at_eos, u_out, ws_u32, ws_words, next_ids, ws_zeroed, false, done_count, stream);
 }
 
 // ---- sampler with top-p and min-p (HF TopPLogitsWarper / MinPLogitsWarper behind temperature and top-k; vLLM SamplingParams(top_p, min_p)) -----------
@@ -663,17 +675,17 @@ extern "C" int64_t tr1_sample_filtered_workspace_words(int64_t rows) { return ro
 extern "C" int tr1_sample_tokens_filtered(const void* logits, int64_t ld, int64_t rows, int64_t V, float temperature, int64_t top_k, float top_p, float min_p,
                                           uint64_t seed, int64_t group_rows, uint64_t seed_stride, const void* step_ptr, void* tokens, int64_t tok_ld,
                                           void* finished, int64_t eos_id, int64_t pad_id, int stop_at_eos, void* u_out, void* ws_u32, int64_t ws_words,
-                                          void* stream) {
+                                          void* stream, void* done_count) {
     return sample_tokens_impl(logits, ld, rows, V, temperature, top_k, top_p, min_p, seed, group_rows, seed_stride, step_ptr, tokens, tok_ld, finished, eos_id,
-                              pad_id, stop_at_eos, u_out, ws_u32, ws_words, nullptr, 0, true, stream);
+                              pad_id, stop_at_eos, u_out, ws_u32, ws_words, nullptr, 0, true, done_count, stream);
 }
 
 extern "C" int tr1_sample_tokens_filtered_step(const void* logits, int64_t ld, int64_t rows, int64_t V, float temperature, int64_t top_k, float top_p,
                                                float min_p, uint64_t seed, int64_t group_rows, uint64_t seed_stride, const void* step_ptr, void* tokens,
                                                int64_t tok_ld, void* finished, int64_t eos_id, int64_t pad_id, int stop_at_eos, void* u_out, void* ws_u32,
-                                               int64_t ws_words, void* next_ids, int ws_zeroed, void* stream) {
+                                               int64_t ws_words, void* next_ids, int ws_zeroed, void* stream, void* done_count) {
     return sample_tokens_impl(logits, ld, rows, V, temperature, top_k, top_p, min_p, seed, group_rows, seed_stride, step_ptr, tokens, tok_ld, finished, eos_id,
-                              pad_id, stop_at_eos, u_out, ws_u32, ws_words, next_ids, ws_zeroed, true, stream);
+                              pad_id, stop_at_eos, u_out, ws_u32, ws_words, next_ids, ws_zeroed, true, done_count, stream);
 }
 
 extern "C" int tr1_penalize_logits(const void* logits, int64_t ld, void* out, int64_t out_ld, const void* seen, int64_t seen_ld, int64_t rows, int64_t V,

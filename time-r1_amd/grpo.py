@@ -33,13 +33,21 @@ class StepState:
         self.ids_packed = self.pos3 = self.cos = self.sin = self.masks = self.pred_rows = self.targets = self.perm = self.inv_perm = None
         self.llm_ctx = self.head_ctx = None
         self.logp = self.entropy = self.ref_logp = None
+        # trim_completions: decode_steps = the decode steps the rollout enqueued for this prompt's batch; prefill_tail_from = the tail_from the rollout's prefill
+        # ran with (it was decided on the untrimmed row count; the passes that repeat that prefill launch for launch read it here)
+        # full_C = the configured completion length of a state that trim() has cut (None: not cut) - the width everything [G, C]-shaped keeps
+        self.decode_steps = self.prefill_tail_from = self.full_C = None
 
 
 class GRPOCore:
     def __init__(self, engine: Engine, ref_arena=None, num_generations=8, max_completion_length=200, beta=0.04, use_grpo=False,
                  temperature=1.0, top_k=50, seed=1234, rope_index_mode="hf4", stop_at_eos=False, reuse_prefill=True, greedy=False,
-                 top_p=1.0, min_p=None, repetition_penalty=1.0, objective=None, entropy_coef=0.0, top_entropy_quantile=1.0, activation_recompute=None):
+                 top_p=1.0, min_p=None, repetition_penalty=1.0, objective=None, entropy_coef=0.0, top_entropy_quantile=1.0, activation_recompute=None,
+                 trim_completions=False):
         self.eng = engine
+        # trim_completions (GRPOConfig.trim_completions): the sampled rollout ends once every row has drawn its EOS (Rollout.early_stop), and trim() cuts an
+        # update's packed sequence to the columns some row still lives in.  False: neither exists for any call below.
+        self.trim_completions = bool(trim_completions)
         # "none" | "mlp" (Engine.activation_recompute): what the update's forwards save for the backward; None keeps the engine's own setting
         if activation_recompute is not None:
             engine.set_activation_recompute(activation_recompute)
@@ -70,6 +78,8 @@ class GRPOCore:
         self.reuse_prefill = bool(reuse_prefill)
         self.roll = Rollout(engine, self.G, self.C, temperature, top_k, seed, stop_at_eos, greedy=greedy, top_p=top_p, min_p=min_p,
                             repetition_penalty=repetition_penalty)      # greedy: evaluation (argmax tokens, early stop)
+        if self.trim_completions:
+            self.roll.stop_at_eos = self.roll.early_stop = True
         if self.beta != 0.0 and ref_arena is None:
             raise ValueError("beta != 0 needs a reference-policy arena (reference timer1_trainer.py:295-307)")
         # algorithmic work of what was run since the trainer last read it (TimeR1_Trainer.log -> perf/* keys): bytes the decode steps must
@@ -83,13 +93,14 @@ class GRPOCore:
         att = 4.0 * pairs * t.head_dim * t.n_heads
         return t.n_layers * (lin + att)
 
-    def _count_decode(self, states):      # states: the prompt lengths P of one batched rollout
+    def _count_decode(self, states, steps=None):      # states: the prompt lengths P of one batched rollout; steps: the decode steps it enqueued (None: all C - 1)
         t = self.cfg.text
         wb = 1.0 if self.roll.weight_dtype in ("fp8", "fp8-mfma") else 2.0
         w_bytes = wb * (t.n_layers * (t.hidden * t.qkv_dim + t.q_dim * t.hidden + 3 * t.hidden * t.intermediate) + t.vocab_size * t.hidden)
         G, C = self.G, self.C
-        kv = sum(sum(P + G * s for s in range(1, C)) for P in states) * t.kv_dim * 2 * 2.0 * t.n_layers   # prefix once per prompt + every group's suffix
-        self.work["decode_bytes"] += (C - 1) * w_bytes + kv
+        n = C - 1 if steps is None else int(steps)
+        kv = sum(sum(P + G * s for s in range(1, n + 1)) for P in states) * t.kv_dim * 2 * 2.0 * t.n_layers   # prefix once per prompt + every group's suffix
+        self.work["decode_bytes"] += n * w_bytes + kv
         for e0, e1 in self.roll.decode_events:
             e1.synchronize()
             self.work["decode_ms_events"] += e0.elapsed_time(e1)
@@ -97,7 +108,7 @@ class GRPOCore:
 
     def _count_update(self, st, reused_prefill, with_ref=True):
         t = self.cfg.text
-        P, G, C = st.P, self.G, self.C
+        P, G, C = st.P, self.G, st.layout.C      # the rows actually run (trim())
         M = P + G * C
         pairs_c = G * (C * P + C * (C + 1) / 2.0)
         pairs_all = P * (P + 1) / 2.0 + pairs_c
@@ -154,7 +165,8 @@ class GRPOCore:
         st.completion_ids = tokens        # int32 [G, C] on device
         st.prefill = self.roll.last_prefill[0] if self.reuse_prefill else None
         st.sample_logp = self.roll.last_sample_logp[0] if self.roll.last_sample_logp is not None else None
-        self._pending_decode = (getattr(self, "_pending_decode", []) + [[st.P]])[-64:]
+        st.decode_steps = self.roll.last_steps_run
+        self._pending_decode = (getattr(self, "_pending_decode", []) + [([st.P], st.decode_steps)])[-64:]
         return tokens
 
     def rollout_many(self, states):
@@ -166,18 +178,40 @@ class GRPOCore:
             st.layout, st.completion_ids = lay, tokens
             st.prefill = self.roll.last_prefill[b] if self.reuse_prefill else None
             st.sample_logp = self.roll.last_sample_logp[b] if self.roll.last_sample_logp is not None else None
-        self._pending_decode = (getattr(self, "_pending_decode", []) + [[st.P for st in states]])[-64:]
+            st.decode_steps = self.roll.last_steps_run
+        self._pending_decode = (getattr(self, "_pending_decode", []) + [([st.P for st in states], self.roll.last_steps_run)])[-64:]
         return [st.completion_ids for st in states]
 
     def drain_work(self):
         """-> the work counters since the last call (decode events are resolved here, i.e. when the trainer logs - never inside a step)."""
-        for states in getattr(self, "_pending_decode", []):
-            self._count_decode(states)
+        for states, steps in getattr(self, "_pending_decode", []):
+            self._count_decode(states, steps)
         self._pending_decode = []
         w, self.work = self.work, dict.fromkeys(self.work, 0.0)
         return w
 
     # ------------------------------------------------------------------------------------------------------- phase 3
+    TRIM_FLOOR = 8      # no update runs on fewer completion columns than this (the shapes the kernels are tested on)
+
+    def trim(self, st, completion_ids_host, eos_token_id):
+        """trim_completions: cut the state to the live columns, ahead of forward_logps.  L = the largest (first EOS index + 1) over the rows (C for a row
+        without EOS), Ct = min(C, max(TRIM_FLOOR, L)).  Ct < C: the layout becomes PackedLayout(P, G, Ct) and completion_ids the contiguous [:, :Ct], so every
+        pass that runs the model - policy and reference forward, head, backward, every replay - sees P + G*Ct rows.  The columns that leave lie behind every
+        row's EOS: their mask is 0 (eos_mask).  What is [G, C]-shaped stays so (_to_gc pads with 0), the loss kernels and their normalisers with it; only
+        dlogp[:, :Ct] enters the backward.  The rollout's saved prefill belongs to the untrimmed layout: its buffers, stash and K/V cache are used as
+        [: P + G*Ct] views and its tail_from travels in the saved context (forward_logps).  Callers keep the host's full [G, C] rows for rewards and
+        decoding - the reference decodes what follows the EOS too.  -> Ct"""
+        ids = np.asarray(completion_ids_host)
+        G, C = ids.shape
+        is_eos = ids == eos_token_id
+        L = int(np.where(is_eos.any(1), is_eos.argmax(1) + 1, C).max())
+        Ct = min(C, max(self.TRIM_FLOOR, L))
+        if Ct < C:
+            st.full_C = C
+            st.layout = PackedLayout(st.P, G, Ct)
+            st.completion_ids = st.completion_ids[:, :Ct].contiguous()
+        return Ct
+
     def _packed_inputs(self, st):
         ops, lay = self.ops, st.layout
         comp = st.completion_ids
@@ -196,7 +230,13 @@ class GRPOCore:
         st.inv_perm[st.perm] = torch.arange(G * C, device=comp.device)
 
     def _to_gc(self, st, x_pred_order):
-        return x_pred_order[st.inv_perm].view(st.layout.G, st.layout.C)
+        """pred_rows order -> [G, C]; a trimmed state keeps its configured C: the columns >= layout.C hold 0 (their mask is 0)."""
+        x = x_pred_order[st.inv_perm].view(st.layout.G, st.layout.C)
+        if st.full_C is None:
+            return x
+        out = torch.zeros(st.layout.G, st.full_C, dtype=x.dtype, device=x.device)
+        out[:, :st.layout.C] = x
+        return out
 
     def forward_logps(self, st, replay=False):
         """Policy log-probs / entropy (activations saved for backward) and reference log-probs (no grad).
@@ -219,6 +259,7 @@ class GRPOCore:
             # continuation: only the G*C completion rows; the prompt rows' activations and K/V come from the rollout's prefill
             P, M = st.P, st.layout.M
             pctx, kv = pf
+            st.prefill_tail_from = int(pctx.get("tail_from", 0) or 0) or None      # (= Engine.tail_rows_from(P, the rollout's M): None or P - 1)
             if pctx.get("stash"):            # large sequences: this prompt's prefill rows were parked; the one full buffer set is free now
                 pctx = eng.unstash_ctx(pctx, P, M)
             hc = ops.gather_rows(tr.w("embed"), st.ids_packed[P:].contiguous())
@@ -271,8 +312,9 @@ class GRPOCore:
         pos_p = ops.tensor(np.ascontiguousarray(st.pos3_prompt.astype(np.int32)), I32)
         cos_p, sin_p = ops.mrope_table(pos_p, t.head_dim, t.mrope_section, t.rope_theta)
         h = eng.embed(ra, st.prompt_ids, ref_vid, st.vid_rows)
+        # tail_from: the decision the rollout's prefill took (on its own, untrimmed row count), not a new one on this layout's M
         hp, _ = eng.llm_fwd(ra, h, cos_p, sin_p, [ops.tensor(a, I32) for a in lay.prompt_masks()], save=False, kv_cache=kv, v_cache=vc,
-                            tail_from=eng.tail_rows_from(P, M))
+                            tail_from=st.prefill_tail_from)
         hc = ops.gather_rows(ra.w("embed"), st.ids_packed[P:].contiguous())
         hLc, _ = eng.llm_fwd(ra, hc, st.cos[P:].contiguous(), st.sin[P:].contiguous(), [m[P:].contiguous() for m in st.masks], save=False, kv_cache=kv,
                              v_cache=vc, row0=P)
@@ -326,7 +368,7 @@ class GRPOCore:
             return row_len.reshape(-1, 1).to(F32).clamp(min=1.0), float(st.layout.G)
         if norm == 1:
             return out3[2].to(F32).clamp(min=1.0), 1.0
-        return 1.0, float(st.layout.G) * float(st.layout.C)
+        return 1.0, float(st.layout.G) * float(st.full_C or st.layout.C)      # (the configured C, as loss.hip divides: a trimmed layout's C is smaller)
 
     def _loss_grad(self, st, completion_mask, advantages, grad_scale, tok_weight, old_logp, eps):
         """The loss entry point of this path and what tok_weight means on it -> (dlogp [G, C], out3 or out8, row_len [G])."""
@@ -371,7 +413,8 @@ class GRPOCore:
         hook = None
         if grad_sync is not None and grad_sync.active and eng.lora is None:      # (LoRA mode: the adapters' small exchange happens in the optimizer step)
             hook = lambda i: grad_sync.ready(*tr.range_of("l%d." % i))
-        to_pred = lambda x: x.reshape(-1)[st.perm].contiguous()
+        Cr = st.layout.C      # the columns the model ran on (trim()): gradients behind them are zero and stay out
+        to_pred = lambda x: (x if x.shape[1] == Cr else x[:, :Cr]).reshape(-1)[st.perm].contiguous()
         dh = eng.head_bwd(st.head_ctx, to_pred(dlogp), st.layout.G, dent=None if dent is None else to_pred(dent))
         if hook is not None and not self.cfg.text.tie_word_embeddings:
             grad_sync.ready(*tr.range_of("norm"))          # final norm + untied lm_head gradients are complete after the head backward

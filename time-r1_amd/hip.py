@@ -56,8 +56,16 @@ class _Lib:
             fn.restype = _CT[ret]
         self.cdll.tr1_last_error.restype = ctypes.c_char_p
 
+    # Entry points whose declaration grew by optional trailing arguments (NULL = off) behind the list older callers pass: name -> how many.  A call that
+    # stops short by at most that many is completed with NULL, so it means what it meant; any other short call stays the TypeError it always was.
+    TRAILING_OPTIONAL = {"tr1_sample_tokens": 1, "tr1_sample_tokens_step": 1, "tr1_sample_tokens_filtered": 1, "tr1_sample_tokens_filtered_step": 1}
+
     def call(self, name, *args):
-        rc = getattr(self.cdll, name)(*args)
+        fn = getattr(self.cdll, name)
+        short = len(fn.argtypes or ()) - len(args)
+        if 0 < short <= self.TRAILING_OPTIONAL.get(name, 0):
+            args = args + (None,) * short
+        rc = fn(*args)
         if rc != 0:
             raise HipError("%s failed (code %d): %s" % (name, rc, (self.cdll.tr1_last_error() or b"").decode()))
 

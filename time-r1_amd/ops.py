@@ -860,9 +860,11 @@ class HipOps:
                                    float(eps_high), float(delta) if delta else 0.0, float(grad_scale))
 
     def sample_tokens(self, logits, temperature, top_k, seed, step_dev, tokens, finished, eos_id, pad_id, stop_at_eos, u_out=None, group_rows=0,
-                      seed_stride=0, next_ids=None, top_p=1.0, min_p=0.0):
+                      seed_stride=0, next_ids=None, top_p=1.0, min_p=0.0, done_count=None):
         """next_ids (int32 [rows], optional): also receives the drawn tokens (the next decode step's embedding gather reads it: no copy kernel).
-        top_p / min_p: nucleus and min-p filters behind top-k (HF order); at the defaults (1.0, 0.0) the call is the unfiltered entry point's."""
+        top_p / min_p: nucleus and min-p filters behind top-k (HF order); at the defaults (1.0, 0.0) the call is the unfiltered entry point's.
+        done_count (int32 [1], optional; needs finished): += 1 for every row whose finished flag this call raises (the entry points' last argument;
+        None = NULL: nothing is counted)."""
         self._chk(logits)
         assert tokens.dtype == I32 and (step_dev is None or step_dev.dtype == I32)
         rows, V = logits.shape
@@ -874,16 +876,18 @@ class HipOps:
         nws = self.L.raw("tr1_sample_filtered_workspace_words" if filt else "tr1_sample_workspace_words")(rows)
         head = (_p(logits), _ld(logits), rows, V, float(temperature), int(top_k or 0)) + extra + (int(seed) & (2**64 - 1), int(group_rows),
                 int(seed_stride) & (2**64 - 1), _p(step_dev), _p(tokens), tokens.stride(0), _p(finished), int(eos_id), int(pad_id), int(bool(stop_at_eos)), _p(u_out))
+        if done_count is not None:
+            assert finished is not None and done_count.dtype == I32 and done_count.numel() == 1 and done_count.device == logits.device
         if next_ids is not None:
             assert next_ids.dtype == I32 and next_ids.numel() == rows and next_ids.is_contiguous()
             key = ("sampler_step" + sfx, rows)
             ws = self._ws.get(key)
             if ws is None:
                 ws = self._ws[key] = torch.zeros(nws, dtype=I32, device=self.device)      # zero ONCE: the kernels leave it zero after every call
-            self.L.call("tr1_sample_tokens%s_step" % sfx, *head, _p(ws), nws, _p(next_ids), 1, self._s())
+            self.L.call("tr1_sample_tokens%s_step" % sfx, *head, _p(ws), nws, _p(next_ids), 1, self._s(), _p(done_count))
             return
         ws = self._workspace("sampler" + sfx, nws, I32)
-        self.L.call("tr1_sample_tokens" + sfx, *head, _p(ws), nws, self._s())
+        self.L.call("tr1_sample_tokens" + sfx, *head, _p(ws), nws, self._s(), _p(done_count))
 
     @staticmethod
     def seen_words(V):

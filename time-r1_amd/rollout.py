@@ -39,7 +39,11 @@ class Rollout:
     step is enqueued the host reads only a copy recorded at least `poll_every` steps earlier - it never waits on the step it has just enqueued, the queue
     never drains, and no per-step .item() / synchronize() exists.  Up to 2 * poll_every padding-only steps may therefore run after the last row has
     finished; the result equals running all C - 1 steps, because finished rows only ever receive pad_token_id (tokens start as pad_token_id in this mode).
-    poll_every=0 switches the early stop off.  last_steps_run = decode steps enqueued by the last call.  greedy=False: nothing of this is executed.
+    poll_every=0 switches the early stop off.  last_steps_run = decode steps enqueued by the last call.  greedy=False: nothing of this is executed, unless
+    the attribute early_stop is set (GRPOConfig.trim_completions): with stop_at_eos and poll_every > 0 the sampled loop then runs the same poller, native
+    step and op-by-op step alike.  Its tokens start as pad_token_id too, and the sampler kernels count the rows they finish on the device (done_count of
+    ops.sample_tokens) as the greedy kernel does; a backend whose sample_tokens has no done_count argument is polled through finished.sum().  Steps that
+    were not enqueued leave track_logp's log-probs at 0 behind the last EOS (a full run writes the pad token's there); both lie outside the completion mask.
 
     top_p / min_p / repetition_penalty (HF generate's order: penalty, temperature, top-k, top-p, min-p; defaults 1 / 0 / 1 = off, and then no call differs
     from a Rollout without them).  A token is seen by a row when it is in the row's prompt or was drawn for the row before (padding of finished rows
@@ -61,6 +65,7 @@ class Rollout:
         self.G, self.C = int(num_generations), int(max_completion_length)
         self.temperature, self.top_k, self.seed, self.stop_at_eos = float(temperature), int(top_k or 0), int(seed), bool(stop_at_eos)
         self.greedy, self.poll_every = bool(greedy), int(poll_every or 0)
+        self.early_stop = False       # sampled mode: end the decode loop once every row has drawn its EOS (needs stop_at_eos and poll_every > 0)
         if self.greedy:
             self.top_k, self.stop_at_eos = 1, True
         self.last_steps_run = 0
@@ -173,6 +178,16 @@ class Rollout:
                                       % (self.top_p, self.min_p, getattr(ops, "name", type(ops).__name__)))
         return dict(top_p=self.top_p, min_p=self.min_p)
 
+    def _stops_early(self):
+        """The decode loop runs the early-stop poller: always in greedy mode, in sampled mode when early_stop asks for it and rows do stop at EOS."""
+        return self.poll_every > 0 and (self.greedy or (self.early_stop and self.stop_at_eos))
+
+    def _count_kwargs(self, ops, buf):
+        """done_count for ops.sample_tokens where this call keeps a counter and the backend's sampler takes it (else none: the poller sums the flags)."""
+        if buf.greedy_op or buf.done_count is None:
+            return {}
+        return dict(done_count=buf.done_count)
+
     def _penalized(self, buf, logits, r0=0):
         """The logits the selection reads: `logits` itself without a penalty, else their penalised copy in buf.pen[r0 : r0 + rows]."""
         if buf.seen is None:
@@ -193,9 +208,14 @@ class Rollout:
         (one bit per token of the V-token vocabulary and row) and the buffer of penalised logits."""
         ops, G, C, R = self.eng.ops, self.G, self.C, len(items) * self.G
         steps = ops.tensor(np.arange(C, dtype=np.int32), I32)
-        tokens = torch.full((R, C), int(self.eng.cfg.pad_token_id), dtype=I32, device=steps.device) if self.greedy else ops.zeros(R, C, dtype=I32)
+        sampled_stop = not self.greedy and self._stops_early()
+        tokens = torch.full((R, C), int(self.eng.cfg.pad_token_id), dtype=I32, device=steps.device) if (self.greedy or sampled_stop) else ops.zeros(R, C, dtype=I32)
         finished = ops.zeros(R, dtype=I32)
-        done_count = ops.zeros(1, dtype=I32) if greedy_op else None      # rows that selected EOS; zeroed here, once per call
+        counted = greedy_op
+        if sampled_stop:
+            pars = inspect.signature(ops.sample_tokens).parameters
+            counted = "done_count" in pars or any(p.kind == p.VAR_KEYWORD for p in pars.values())
+        done_count = ops.zeros(1, dtype=I32) if counted else None      # rows that selected EOS; zeroed here, once per call
         slogp = ops.zeros(R, C, dtype=torch.float32) if self.track_logp else None
         lays = [PackedLayout(int(it[0].shape[0]), G, C) for it in items]
         seen = pen = None
@@ -238,7 +258,7 @@ class Rollout:
                               cfg.pad_token_id, done_count=buf.done_count)
         else:
             ops.sample_tokens(sel.expand(G, sel.shape[1]), self.temperature, self.top_k, seed, buf.steps[0:1], tokens, finished,
-                              cfg.eos_token_id, cfg.pad_token_id, self.stop_at_eos, **self._filter_kwargs(ops))
+                              cfg.eos_token_id, cfg.pad_token_id, self.stop_at_eos, **self._filter_kwargs(ops), **self._count_kwargs(ops, buf))
         self._mark_drawn(buf, 0, b * G, G)
         if buf.slogp is not None:      # (the first token is drawn from the bf16 prefill's logits in every mode)
             buf.slogp[b * G:(b + 1) * G, 0] = ops.logp_entropy_fwd(logits.expand(G, logits.shape[1]).contiguous(), tokens[:, 0].contiguous())[0]
@@ -289,7 +309,7 @@ class Rollout:
         if on_gpu:
             ev0 = torch.cuda.Event(enable_timing=True)
             ev0.record()
-        stop = _EarlyStop(buf, B * G, C, self.poll_every) if self.greedy and self.poll_every > 0 else None
+        stop = _EarlyStop(buf, B * G, C, self.poll_every) if self._stops_early() else None
         self.last_steps_run = 0
         for s in range(C - 1):
             if stop is not None and stop.before(s):
@@ -308,7 +328,8 @@ class Rollout:
         return [(st["tokens"], st["lay"]) for st in per]
 
 
-# One call's allocations: tokens / slogp [B*G, C], finished [B*G], done_count [1] (greedy_op only), steps = arange(C), one layout per prompt, the KV cache
+# One call's allocations: tokens / slogp [B*G, C], finished [B*G], done_count [1] (greedy_op, or a sampled early stop whose backend counts; else None),
+# steps = arange(C), one layout per prompt, the KV cache
 # seen int32 [B*G, ceil(seen_vocab / 32)] / pen [B*G, seen_vocab]: only with a repetition penalty (else None)
 _Buffers = namedtuple("_Buffers", "greedy_op steps tokens finished done_count slogp lays cache seen pen seen_vocab")
 # cos / sin [C, B*G, half]; slots [C, B*G] into the unified cache; hi [C, B*G]: hi of step s = the slot just appended (cache-local); pre / lo [B*G]
@@ -316,7 +337,8 @@ _StepTables = namedtuple("_StepTables", "cos sin slots hi pre lo nsplit")
 
 
 class _EarlyStop:
-    """The poller of greedy mode (Rollout's docstring): counts of finished rows copied to pinned host memory, read poll_every steps later."""
+    """The poller of greedy mode and of a sampled early stop (Rollout's docstring): counts of finished rows copied to pinned host memory, read poll_every
+    steps later.  The count is the kernels' own counter where the call keeps one, else the sum of the finished flags."""
 
     def __init__(self, buf, rows, C, poll_every):
         self.buf, self.rows, self.pe = buf, rows, poll_every
@@ -335,7 +357,7 @@ class _EarlyStop:
                 return True
         if s > 0 and s % pe == 0:
             slot = s // pe
-            self.host_counts[slot:slot + 1].copy_(buf.done_count if buf.greedy_op else buf.finished.sum(dtype=I32).reshape(1), non_blocking=True)
+            self.host_counts[slot:slot + 1].copy_(buf.done_count if buf.done_count is not None else buf.finished.sum(dtype=I32).reshape(1), non_blocking=True)
             ev = None
             if self.on_dev:
                 ev = torch.cuda.Event()
@@ -352,6 +374,7 @@ class _Step:
         self.ops, self.cfg, self.t = roll.eng.ops, roll.eng.cfg, roll.eng.cfg.text
         self.qmask, self.a8 = roll.fp8_mask(), roll.weight_dtype == "fp8-mfma"
         self.R, self.B, self.scale = tab.hi.shape[1], len(per), self.t.head_dim ** -0.5
+        self.count_kw = roll._count_kwargs(self.ops, buf)      # looked at once per call, not per step
 
 
 class _NativeStep(_Step):
@@ -403,7 +426,8 @@ class _NativeStep(_Step):
         else:
             # all prompts of the window in ONE sampler launch set; every prompt keeps its own Philox stream (seed_b = seed_0 + 7919 b)
             ops.sample_tokens(logits, roll.temperature, roll.top_k, self.per[0]["seed"], buf.steps[s + 1:s + 2], buf.tokens, buf.finished, cfg.eos_token_id,
-                              cfg.pad_token_id, roll.stop_at_eos, group_rows=roll.G, seed_stride=7919, next_ids=self.ids, **roll._filter_kwargs(ops))
+                              cfg.pad_token_id, roll.stop_at_eos, group_rows=roll.G, seed_stride=7919, next_ids=self.ids, **roll._filter_kwargs(ops),
+                              **self.count_kw)
         roll._mark_drawn(buf, s + 1)
 
 
@@ -478,5 +502,5 @@ class _HostStep(_Step):
             ops.greedy_tokens(logits, buf.steps[s + 1:s + 2], buf.tokens, buf.finished, cfg.eos_token_id, cfg.pad_token_id, done_count=buf.done_count)
         for b, st in enumerate(() if buf.greedy_op else self.per):      # every prompt with its own seed and row slices
             ops.sample_tokens(logits[b * G:(b + 1) * G], roll.temperature, roll.top_k, st["seed"], buf.steps[s + 1:s + 2], st["tokens"],
-                              st["finished"], cfg.eos_token_id, cfg.pad_token_id, roll.stop_at_eos, **roll._filter_kwargs(ops))
+                              st["finished"], cfg.eos_token_id, cfg.pad_token_id, roll.stop_at_eos, **roll._filter_kwargs(ops), **self.count_kw)
         roll._mark_drawn(buf, s + 1)

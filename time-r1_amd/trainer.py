@@ -94,6 +94,9 @@ class GRPOConfig:
         self.repetition_penalty = 1.0 if self.repetition_penalty is None else float(self.repetition_penalty)
         if not 0.0 < self.top_p <= 1.0:
             raise ValueError("top_p must be in (0, 1], got %r" % (self.top_p,))
+        self.trim_completions = bool(self.trim_completions)
+        if self.trim_completions:
+            self.stop_at_eos = True      # trimming is about rows that END: a finished row is padded, and the rollout stops once every row is
         if self.min_p is not None and not 0.0 <= self.min_p <= 1.0:
             raise ValueError("min_p must be None or in [0, 1], got %r" % (self.min_p,))
         if not 0.0 < self.repetition_penalty < float("inf"):
@@ -187,6 +190,10 @@ class GRPOConfig:
     prompt_type: str = "v1"
     fix_vit: bool = True
     stop_at_eos: bool = False               # the reference's GenerationConfig carries no eos_token_id (a6): always C tokens
+    trim_completions: bool = False          # rollouts end at EOS: sets stop_at_eos=True; the sampled decode loop stops once every row has drawn its EOS (polled, never a
+                                            # per-step wait), and the update - policy and reference forward, head, backward, every replay - runs on the columns up to
+                                            # the last row's EOS only (at least 8), P + G*Ct rows instead of P + G*C.  Masks, normalisers (dr_grpo keeps 1 / (G*C)),
+                                            # rewards and metrics see the full [G, C]; one more metric key, completions/trimmed_length.  DESIGN.md section 7t
     rollout_batching: bool = True           # decode the prompts of one accumulation window together (same weights, same results)
     grad_wire_dtype: str = "bf16"           # data-parallel gradient exchange wire format ("bf16" | "fp32")
     shard_optimizer: Optional[bool] = None  # ZeRO-style: master/m/v on 1/world of every arena segment, reduce-scatter grads, all-gather bf16 weights.
@@ -514,7 +521,7 @@ class TimeR1_Trainer:
                              rope_index_mode=args.rope_index_mode, stop_at_eos=args.stop_at_eos, top_p=getattr(args, "top_p", 1.0),
                              min_p=getattr(args, "min_p", None), repetition_penalty=getattr(args, "repetition_penalty", 1.0), objective=self._objective,
                              entropy_coef=getattr(args, "entropy_coef", 0.0), top_entropy_quantile=getattr(args, "top_entropy_quantile", 1.0),
-                             activation_recompute=getattr(args, "activation_recompute", "none"))
+                             activation_recompute=getattr(args, "activation_recompute", "none"), trim_completions=getattr(args, "trim_completions", False))
         self.core.roll.weight_dtype = getattr(args, "rollout_weight_dtype", "bf16")
         keep = getattr(args, "rollout_fp8_keep_bf16", None)
         if keep is None:
@@ -709,6 +716,9 @@ class TimeR1_Trainer:
         comp_host = st.completion_ids_host
         if comp_host is None:
             comp_host = tokens.cpu().numpy()
+        # trim_completions: the model runs on the columns up to the last row's EOS; comp_host keeps the full [G, C] rows for the mask, the rewards and the decoded
+        # completions (the reference decodes what follows the EOS too)
+        trimmed = self.core.trim(st, comp_host, self.processing_class.eos_token_id) if self.core.trim_completions else None
         self.core.forward_logps(st)
         mask_np = eos_mask(comp_host, self.processing_class.eos_token_id)
         lengths, truncated = mask_np.sum(1).astype(np.float32), None      # completion_length and the token counts keep the rollout's lengths
@@ -748,7 +758,7 @@ class TimeR1_Trainer:
         # ---- metrics (reference :739-777; ft adds metrics/<fn> and clip ratios :789-842): per-sample host values + the device vector,
         # turned into the reference's gathered means by _flush_metrics
         rollout = dict(length=lengths, rpf=rewards_per_func.numpy().copy(), reward=rewards.numpy().copy(), std=std.numpy().copy(),
-                       mvals=None if metric_vals is None else metric_vals.numpy(), truncated=truncated)
+                       mvals=None if metric_vals is None else metric_vals.numpy(), truncated=truncated, trimmed=trimmed)
         self.last_completions = completions
         self.last_rewards = rewards
         return self._update(st, mask_dev, adv_dev, tokw=tokw, last=last_in_window, keep_pixels=self._reuse is not None,
@@ -810,7 +820,8 @@ class TimeR1_Trainer:
         G = self.num_generations
         mvals = next((r["rollout"]["mvals"] for r in pend if r["rollout"] is not None), None)
         return (("length", G), ("rpf", G * len(self.reward_funcs)), ("reward", G), ("std", G), ("mvals", 0 if mvals is None else G * mvals.shape[1]),
-                ("truncated", G if self.mask_truncated else 0))      # mask_truncated_completions: one more value per row, 1 = no EOS
+                ("truncated", G if self.mask_truncated else 0),      # mask_truncated_completions: one more value per row, 1 = no EOS
+                ("trimmed", 1 if self.core.trim_completions else 0))  # trim_completions: the completion columns the update ran on
 
     def _flush_metrics(self):
         pend, self._pending = self._pending, []
@@ -861,6 +872,8 @@ class TimeR1_Trainer:
                 M["policy_kl_old"].append(d["kl_old"].mean().item())
             if h is not None and h["truncated"].shape[1]:
                 M["completions/clipped_ratio"].append(h["truncated"].reshape(-1).mean().item())
+            if h is not None and h["trimmed"].shape[1]:
+                M["completions/trimmed_length"].append(h["trimmed"].reshape(-1).mean().item())
             if r["has_drift"]:
                 M["rollout_logp_drift"].append(d["drift"].mean().item())
             if h is not None:

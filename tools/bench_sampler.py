@@ -62,14 +62,14 @@ def main():
         c = ctypes
         L.tr1_sample_tokens_step.restype = c.c_int
         L.tr1_sample_tokens_step.argtypes = [c.c_void_p, c.c_int64, c.c_int64, c.c_int64, c.c_float, c.c_int64, c.c_uint64, c.c_int64, c.c_uint64, c.c_void_p, c.c_void_p,
-                                             c.c_int64, c.c_void_p, c.c_int64, c.c_int64, c.c_int, c.c_void_p, c.c_void_p, c.c_int64, c.c_void_p, c.c_int, c.c_void_p]
+                                             c.c_int64, c.c_void_p, c.c_int64, c.c_int64, c.c_int, c.c_void_p, c.c_void_p, c.c_int64, c.c_void_p, c.c_int, c.c_void_p, c.c_void_p]      # (the last: done_count, NULL - a build from before that argument ignores it)
         nws = int(L.tr1_sample_workspace_words(rows))
         ws = torch.zeros(nws, dtype=I32, device=dev)
         stream = torch.cuda.current_stream(dev).cuda_stream
 
         def base():
             rc = L.tr1_sample_tokens_step(logits.data_ptr(), V, rows, V, a.temperature, a.top_k, 1234, 0, 0, step.data_ptr(), tokens.data_ptr(), tokens.stride(0),
-                                          None, -1, 0, 0, None, ws.data_ptr(), nws, nid.data_ptr(), 1, stream)
+                                          None, -1, 0, 0, None, ws.data_ptr(), nws, nid.data_ptr(), 1, stream, None)
             assert rc == 0
         res["lib"] = a.lib
         res["defaults"] = timed(base, a.calls, a.warmup, a.repeats)
