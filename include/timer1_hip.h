@@ -38,7 +38,8 @@ int tr1_gemm_nt_bf16(const void* A, const void* B, void* C, const void* bias, co
 /* The same product (b_kmajor = 0: B = [N, K]; 1: B = [K, N] as stored, e.g. the weight itself in a dgrad) for THIN outputs over a long K - the continuation
  * forward's down / o projections (1600 x 3584 x 18944 / 3584), the lm_head's data gradient (1600 x 3584 over K = 152064): the K tiles are dealt to S <= 8 shares
  * that run as blocks of ONE launch into fp32 planes of ws_f32 (>= 2*M*N floats; 8*M*N lets the cost model pick any S), a second launch adds the planes in a
- * fixed order (+bias, +residual): deterministic split-K.  K % 64 == 0; bf16 output. */
+ * fixed order (+bias, +residual): deterministic split-K.  K % 64 == 0 and K >= 128 (at least two k tiles: S >= 2 and every share owns at least one tile,
+ * S <= K / 64; a smaller K is rejected before any launch); bf16 output. */
 int tr1_gemm_splitk_bf16(const void* A, const void* B, void* C, const void* bias, const void* residual, int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldb, int64_t ldc, int64_t ldr, int b_kmajor, void* ws_f32, int64_t ws_floats, void* stream);
 int64_t tr1_gemm_splitk_max_splits(void);
 /* C[M,N] = A[M,K] * B[K,N], B K-major ("NN").  The dgrad of a Linear (dX = dY * W; reference: autograd of F.linear under accelerator.backward,

@@ -973,6 +973,8 @@ extern "C" int tr1_gemm_nn_glubwd_bf16(const void* dh, const void* Wd, const voi
 // lm_head's data gradient (1600 x 3584 over K = 152064, which used to pay a 2.2 GB transpose of the lm_head weight in front of a 128 x 128-tile GEMM).
 // All S shares of the reduction run as blocks of ONE launch into fp32 planes of ws_f32, a second launch adds the planes in a fixed order.  (RT, S) by the
 // cost model below: rounds of 256 blocks x tile rows x k tiles per share.  b_kmajor: B = [K, N] as stored (the weight itself in a dgrad).
+// K must hold at least two k tiles (K >= 2 * 64) and S never exceeds the number of k tiles: every share owns at least one tile.  (A share of no tiles
+// would still run the kernel's prologue, which stages tile 0 of its share - 128 bytes past the end of every row of A and B.)
 __global__ __launch_bounds__(256) void splitk_reduce_kernel(const float* __restrict__ planes, int S, int64_t plane, const bf16_t* __restrict__ bias,
                                                             const bf16_t* __restrict__ residual, int64_t ldr, bf16_t* __restrict__ C, int64_t ldc, int64_t M, int64_t N) {
     const int64_t nch = N >> 3, total = M * nch;
@@ -1019,12 +1021,14 @@ extern "C" int tr1_gemm_splitk_bf16(const void* A, const void* B, void* C, const
                                     int64_t lda, int64_t ldb, int64_t ldc, int64_t ldr, int b_kmajor, void* ws_f32, int64_t ws_floats, void* stream) {
     TR1_CHECK_ARG(K % BK == 0 && N % 8 == 0 && lda % 8 == 0 && ldb % 8 == 0 && ldc % 8 == 0 && (!residual || ldr % 8 == 0), "gemm_splitk: K%64, N%8, ld%8 required");
     TR1_CHECK_ARG(ws_f32 && ws_floats >= 2 * M * N, "gemm_splitk: workspace of at least 2*M*N floats required (8*M*N for every split count)");
+    TR1_CHECK_ARG(K >= 2 * BK, "gemm_splitk: K >= 128 required (two k tiles: one per share of the smallest split)");
     if (M == 0 || N == 0) return 0;
     hipStream_t s = (hipStream_t)stream;
     int rt, S;
     const int64_t max_s = ws_floats / (M * N);
     splitk_pick(M, N, K, (int)(max_s < 8 ? max_s : 8), &rt, &S);
-    if (S < 2) S = 2;        // (the caller asked for the split form: thin outputs; S = 1 would be the plain GEMM)
+    if (S < 2) S = 2;        // (the caller asked for the split form: thin outputs; S = 1 would be the plain GEMM); K >= 2 * BK above keeps S <= nk
+    TR1_CHECK_ARG(S <= K / BK, "gemm_splitk: more shares than k tiles");
     const int64_t t2n = (N + BN2 - 1) / BN2;
     const Nt8pTile t(rt, M);
     GemmEpi ep{}; ep.ld0 = M * N; ep.i0 = S;
