@@ -1,5 +1,7 @@
-"""ORACLE - TEST INFRASTRUCTURE ONLY.  CPU restatement (plain PyTorch, fp32 math) of every op behind the C ABI in
-include/timer1_hip.h, with the same Python interface as time-r1_amd/ops.py:HipOps.
+"""ORACLE - TEST INFRASTRUCTURE ONLY.  CPU restatement (plain PyTorch, fp32 math) of the ops behind the C ABI in
+include/timer1_hip.h, with the same Python interface as time-r1_amd/ops.py:HipOps (tests/test_backend_contract.py compares the two:
+same names, same parameters bar a few HIP-only keywords).  RefOps has every op the engine's plain path and its optional features ask
+for, and none of the ops whose mere presence turns a fast path on (greedy_tokens, decode_step, attn_plan, wgrad_nn, ...).
 
 Only tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg may import this package; the product path
 (time-r1_amd/) never does and fails loudly when libtimer1_hip.so is missing.
@@ -14,7 +16,11 @@ import math
 import numpy as np
 import torch
 
+from . import sampler_filter as SF
+from . import sr16
+
 F32 = torch.float32
+BF16 = torch.bfloat16
 I32 = torch.int32
 
 
@@ -43,6 +49,36 @@ def visible_mask(pre, lo, hi, n_slots):
     kv = torch.arange(n_slots)[None, :]
     pre, lo, hi = pre.long()[:, None], lo.long()[:, None], hi.long()[:, None]
     return (kv < pre) | ((kv >= lo) & (kv <= hi))
+
+
+def grpo_modes(norm, level):
+    """grpo_policy_loss's norm / level as the C ABI's ints, from either their names ("row" | "token" | "fixed", "token" | "sequence") or the ints."""
+    from time_r1_amd.ops import GRPO_LEVELS, GRPO_NORM_MODES
+    return GRPO_NORM_MODES.get(norm, norm), GRPO_LEVELS.get(level, level)
+
+
+def mixup_composite(r, p, alpha):
+    """((1 - a) r + a p) as three separate fp32 torch ops, rounded once to r's dtype (bf16: the contract of tr1_ref_mixup, csrc/optim.hip, which must match this
+    bit for bit; the fp32 arenas of the CPU backend: no rounding)."""
+    a = torch.tensor(alpha, dtype=F32)
+    keep = torch.tensor(1.0, dtype=F32) - a
+    t1 = keep * r.float()
+    t2 = a * p.float()
+    return (t1 + t2).to(r.dtype)
+
+
+def merge_acc(a, bt):
+    """The fp32 chain over j of the LoRA merge (csrc/lora.hip), one multiplication and one addition per step, each its own torch op (no contraction on the CPU)."""
+    acc = torch.zeros(bt.shape[1], a.shape[1], dtype=F32)
+    for j in range(a.shape[0]):
+        acc = acc + bt[j].float()[:, None] * a[j].float()[None, :]
+    return acc
+
+
+def merge_composite(w0, a, bt, s):
+    """W0 + s * (Bt^T A) one fp32 op at a time, rounded once to w0's dtype: tr1_lora_merge must match it bit for bit."""
+    t = torch.tensor(s, dtype=F32) * merge_acc(a, bt)
+    return (w0.float() + t).to(w0.dtype)
 
 
 class RefOps:
@@ -164,7 +200,7 @@ class RefOps:
         return qq, sc
 
     @staticmethod
-    def mx_quant_e4m3(x, block=32):
+    def _mx_quant_e4m3(x, block=32):
         """OCP-microscaling style activation quantisation of the W8A8 decode GEMM: per row and per `block` consecutive k one power-of-two
         scale 2^E, E = floor(log2(amax)) - 7 (values land in [128, 256) of e4m3's 448 range), elements rounded to e4m3 (nearest even);
         blocks with amax < 2^-119 are zero.  Returns the dequantised fp32 tensor."""
@@ -182,12 +218,12 @@ class RefOps:
         if lnw is not None and a8:        # the fp8-MFMA kernel quantises x * lnw and applies the row's rstd to the accumulator
             xf = x.float()
             rstd = torch.rsqrt((xf * xf).mean(-1, keepdim=True) + eps)
-            y = (self.mx_quant_e4m3(xf * lnw.float()[None, :]) @ wd.t()) * rstd * scale.float()[None, :]
+            y = (self._mx_quant_e4m3(xf * lnw.float()[None, :]) @ wd.t()) * rstd * scale.float()[None, :]
         elif lnw is not None:
             x, _, _ = self.rmsnorm_fwd(x, lnw, eps, need_rstd=False)
             y = (x.float() @ wd.t()) * scale.float()[None, :]
         else:
-            y = ((self.mx_quant_e4m3(x) if a8 else x.float()) @ wd.t()) * scale.float()[None, :]
+            y = ((self._mx_quant_e4m3(x) if a8 else x.float()) @ wd.t()) * scale.float()[None, :]
         if bias is not None:
             y = y + bias.float()
         if residual is not None:
@@ -252,6 +288,12 @@ class RefOps:
     def quickgelu_fwd(self, x):
         v = x.float()
         return self._a(v * torch.sigmoid(1.702 * v))
+
+    def quickgelu_bwd(self, x, dy):
+        """The fp32 formula, rounded once like the HIP kernel (a training vision tower, fix_vit = false)."""
+        v = x.float()
+        s = torch.sigmoid(1.702 * v)
+        return self._a(dy.float() * (s + 1.702 * v * s * (1.0 - s)))
 
     def add(self, a, b):
         return self._a(a.float() + b.float())
@@ -436,6 +478,33 @@ class RefOps:
             return logits
         return d
 
+    def logp_entropy_bwd(self, logits, targets, lse, ent, dlogp, dent, inplace=True):
+        """logp_bwd with a gradient at the entropy (GRPOConfig.entropy_coef): dlogits = dlogp (1[v == t] - p) - dent p ((x - lse) + H)."""
+        if dent is None:
+            return self.logp_bwd(logits, targets, lse, dlogp, inplace=inplace)
+        lp = logits.float() - lse[:, None]
+        p = torch.exp(lp)
+        onehot = torch.zeros_like(p)
+        onehot.scatter_(1, targets.long()[:, None], 1.0)
+        d = self._a(dlogp[:, None] * (onehot - p) - dent[:, None] * p * (lp + ent[:, None]))
+        if inplace:
+            logits.copy_(d)
+            return logits
+        return d
+
+    def entropy_quantile_weight(self, ent, mask, rho):
+        """GRPOConfig.top_entropy_quantile: weight = live and H >= the quantile of order 1 - rho of the live entropies (fp32 torch.quantile)
+        -> (weight, [threshold, tokens kept, live tokens])."""
+        live = mask != 0
+        vals = ent[live].float()
+        n = int(vals.numel())
+        w = torch.zeros(ent.shape, dtype=torch.float32)
+        if n == 0:
+            return w, torch.zeros(3)
+        thr = torch.quantile(vals, 1.0 - float(rho))
+        w[live] = (vals >= thr).float()
+        return w, torch.stack([thr, w.sum(), torch.tensor(float(n))])
+
     def grpo_loss(self, logp, ref_logp, mask, adv, beta, use_grpo, grad_scale=1.0):
         G, C = logp.shape
         m = mask.float()
@@ -458,32 +527,152 @@ class RefOps:
         out3 = torch.stack([loss, klm, m.sum()])
         return dlogp, out3, lens, (kl * m).sum(1)
 
+    def grpo_loss_ratio(self, logp, old_logp, ref_logp, mask, adv, beta, use_grpo, eps_low, eps_high, grad_scale=1.0, tok_weight=None):
+        """The GRPO loss against an OLD policy (tr1_grpo_loss_ratio; tests/ratio_cases.py states it) and its gradient in closed form, fp32
+        -> (dlogp, out8, row_len, row_kl)."""
+        G, C = logp.shape
+        f = torch.float32
+        live = mask != 0
+        m = live.to(f)
+        A = adv.to(f).reshape(-1, 1)
+        zero = torch.zeros_like(logp, dtype=f)
+        d = torch.where(live, logp.to(f) - old_logp.to(f), zero)
+        rho = torch.exp(d)
+        kl, dkl = zero, zero
+        if ref_logp is not None:
+            r = torch.where(live, ref_logp.to(f) - logp.to(f), zero)
+            e = torch.exp(r)
+            kl, dkl = e - r - 1, 1 - e
+        w = tok_weight.to(f) if tok_weight is not None else torch.ones_like(zero)
+        lo, hi = 1 - eps_low, 1 + eps_high
+        is_low = (rho < lo) & (A < 0)
+        is_high = (rho > hi) & (A > 0)
+        lens, tot = m.sum(1), m.sum()
+        if use_grpo:
+            l = -w * rho * A + beta * kl
+            dl = -w * rho * A + beta * dkl
+            loss = ((l * m).sum(1) / lens).mean()
+            norm = m / lens[:, None] / G
+        else:
+            l = -w * torch.minimum(rho * A, torch.clamp(rho, lo, hi) * A) + beta * kl
+            dl = torch.where(is_low | is_high, zero, -w * rho * A) + beta * dkl
+            loss = (l * m).sum() / tot
+            norm = m / tot
+        dlogp = torch.where(live, dl * norm * grad_scale, zero)
+        out8 = torch.stack([loss, ((kl * m).sum(1) / lens).mean(), tot, (is_low * m).sum() / tot, (is_high * m).sum() / tot, ((is_low | is_high) * m).sum() / tot,
+                            ((torch.expm1(d) - d) * m).sum() / tot, torch.where(live, rho, zero).max()])
+        return dlogp, out8, lens, (kl * m).sum(1)
+
+    def grpo_policy_loss(self, logp, old_logp, ref_logp, mask, adv, beta, norm, level, eps_low, eps_high, delta=None, grad_scale=1.0, tok_weight=None):
+        """The GRPO objective family (tr1_grpo_policy_loss; tests/loss_family_cases.py states it) and its gradient in closed form.  Like the kernel it forms the
+        row sums behind s_g (log-ratios, weights) in fp64 and everything else in fp32."""
+        norm, level = grpo_modes(norm, level)
+        G, C = logp.shape
+        f = torch.float32
+        delta = float(delta) if delta else 0.0
+        live = mask != 0
+        m = live.to(f)
+        A = adv.to(f).reshape(-1, 1)
+        zero = torch.zeros_like(logp, dtype=f)
+        lens, tot = m.sum(1), m.sum()
+        len1, tot1 = lens.clamp(min=1), tot.clamp(min=1)
+        n = (1 / (len1[:, None] * G), (1 / tot1).expand(G, 1), torch.full((G, 1), 1.0 / (float(G) * float(C)), dtype=f))[norm]
+        w = tok_weight.to(f) if tok_weight is not None else torch.ones_like(zero)
+        if level == 1:
+            dd = torch.where(live, logp.double() - old_logp.double(), zero.double()) if old_logp is not None else zero.double()
+            dbar = dd.sum(1) / len1.double()
+            c = torch.exp(dbar).to(f)[:, None].expand(G, C)
+            k3 = (torch.expm1(dbar) - dbar).to(f)[:, None].expand(G, C)
+            wbar = (torch.where(live, w.double(), zero.double()).sum(1) / len1.double()).to(f)[:, None]
+        else:
+            d = torch.where(live, logp.to(f) - old_logp.to(f), zero) if old_logp is not None else zero
+            c = torch.exp(d)
+            k3 = torch.expm1(d) - d
+        kl, dkl = zero, zero
+        if ref_logp is not None:
+            r = torch.where(live, ref_logp.to(f) - logp.to(f), zero)
+            e = torch.exp(r)
+            kl, dkl = e - r - 1, 1 - e
+        lo, hi = 1 - eps_low, 1 + eps_high
+        is_low = (c < lo) & (A < 0)
+        is_high = (c > hi) & (A > 0)
+        stuck = is_low | is_high
+        capped = c
+        if delta > 0:
+            capped = torch.clamp(c, max=delta)
+            stuck = stuck | ((c > delta) & (A < 0))
+        l = -w * torch.minimum(capped * A, torch.clamp(c, lo, hi) * A) + beta * kl
+        if level == 1:
+            dl = (torch.where(stuck, zero, -A * c * wbar) + beta * dkl) * n
+        else:
+            dl = (torch.where(stuck, zero, -w * A * c) + beta * dkl) * n
+        dlogp = torch.where(live, dl * grad_scale, zero)
+        lm = torch.where(live, l, zero)
+        loss = ((lm.sum(1) / len1).sum() / G, lm.sum() / tot1, lm.sum() / (float(G) * float(C)))[norm]
+        klm = torch.where(live, kl, zero)
+        out8 = torch.stack([loss, (klm.sum(1) / len1).mean(), tot, (is_low * m).sum() / tot1, (is_high * m).sum() / tot1, ((is_low | is_high) * m).sum() / tot1,
+                            torch.where(live, k3, zero).sum() / tot1, torch.where(live, c, zero).max()])
+        return dlogp, out8, lens, klm.sum(1)
+
     def sample_tokens(self, logits, temperature, top_k, seed, step_dev, tokens, finished, eos_id, pad_id, stop_at_eos, u_out=None, group_rows=0,
-                      seed_stride=0):
+                      seed_stride=0, top_p=1.0, min_p=0.0):
+        """A non-default top_p / min_p draws from sampler_filter.ref_filter's fp64 kept set and CDF; the defaults run the float32 scaling and the float64
+        CDF below, as they did before the filters existed.  No next_ids and no done_count: the rollout's poller sums the finished flags."""
         rows, V = logits.shape
         step = int(step_dev.item()) if step_dev is not None else 0
-        x = logits.float().numpy().astype(np.float32) * np.float32(1.0 / temperature)
+        filtered = not (top_p == 1.0 and min_p == 0.0)
+        x = None if filtered else logits.float().numpy().astype(np.float32) * np.float32(1.0 / temperature)
         for r in range(rows):
             if finished is not None and finished[r] and stop_at_eos:
                 tokens[r, step] = pad_id
                 continue
-            xr = x[r]
-            thr = -np.inf
-            if top_k and 0 < top_k < V:
-                thr = np.partition(xr, V - top_k)[V - top_k]
-            keep = xr >= thr
-            e = np.where(keep, np.exp((xr - xr.max()).astype(np.float64)), 0.0)
             u = philox_uniform(int(seed) + (r // group_rows) * int(seed_stride), r % group_rows, step) if group_rows else philox_uniform(int(seed), r, step)
             if u_out is not None:
                 u_out[r] = u
-            cdf = np.cumsum(e)
-            tok = int(np.searchsorted(cdf, u * cdf[-1], side="left"))
+            if filtered:
+                keep, cdf, _ = SF.ref_filter(logits[r], temperature, top_k, top_p, min_p)
+                tok = int(torch.searchsorted(cdf, torch.tensor(u, dtype=torch.float64)))
+            else:
+                xr = x[r]
+                thr = -np.inf
+                if top_k and 0 < top_k < V:
+                    thr = np.partition(xr, V - top_k)[V - top_k]
+                keep = xr >= thr
+                e = np.where(keep, np.exp((xr - xr.max()).astype(np.float64)), 0.0)
+                cdf = np.cumsum(e)
+                tok = int(np.searchsorted(cdf, u * cdf[-1], side="left"))
             tok = min(tok, V - 1)
             while not keep[tok]:
                 tok -= 1
             tokens[r, step] = tok
             if finished is not None and tok == eos_id:
                 finished[r] = 1
+
+    def penalize_logits(self, logits, seen, penalty, out=None):
+        """Repetition penalty on the tokens whose bit is set in the seen bitmap: fp32, one rounding to bf16.  Writes `out` (never the input)."""
+        rows, V = logits.shape
+        sets = [sorted(SF.bitmap_tokens(seen[r], V)) for r in range(rows)]
+        res = SF.ref_penalize(logits.to(BF16), sets, penalty).to(logits.dtype)
+        if out is None:
+            return res
+        out.copy_(res)
+        return out
+
+    def mark_seen(self, seen, V, ids=None, tokens=None, step_dev=None, finished=None):
+        """ids: every id into EVERY row of the bitmap.  tokens ([rows], or [rows, C] with step_dev): row r's token into row r, finished rows skipped."""
+        rows = seen.shape[0]
+        if ids is not None:
+            for r in range(rows):
+                for v in ids.tolist():
+                    if 0 <= v < V:
+                        SF.set_bit(seen, r, v)
+            return
+        col = tokens[:, int(step_dev.item())] if tokens.dim() == 2 else tokens
+        for r in range(rows):
+            if finished is not None and finished[r]:
+                continue
+            if 0 <= int(col[r]) < V:
+                SF.set_bit(seen, r, int(col[r]))
 
     # ---- optimizer (ref: torch.optim.AdamW semantics = DeepSpeed FusedAdam adam_w_mode; clip = clip_grad_norm_)
     def sumsq_ranges_periodic(self, g, base, stride, count, rel_ranges, out_scalar):
@@ -519,3 +708,38 @@ class RefOps:
         p16.copy_(p32.to(p16.dtype))
         if zero_grad:
             g_acc.zero_()
+
+    def adamw_step_sr16(self, p32, m16, v16, g, p16, lr, beta1, beta2, eps, weight_decay, step, seed, index_base, sumsq=None, max_norm=0.0, grad_mult=1.0,
+                        zero_grad=True, g16=None):
+        """AdamW with bf16 moments and stochastic rounding (GRPOConfig.optimizer_state_dtype="bf16"): the master update is adamw_step's on the widened moments
+        (what the fp32-state path gives from the same inputs), the stored moments are the emulation's (oracle/sr16.py)."""
+        assert p32.dtype == F32 and m16.dtype == BF16 and v16.dtype == BF16 and g.dtype == F32 and step >= 1
+        n = p32.numel()
+        assert m16.numel() == n and v16.numel() == n and g.numel() == n and p16.numel() == n and (g16 is None or (g16.dtype == BF16 and g16.numel() == n))
+        used = g16.float() if g16 is not None else g
+        mb, vb, _, _ = sr16.emu_step(m16, v16, used, beta1, beta2, step, seed, index_base, None if sumsq is None else float(sumsq), max_norm, grad_mult)
+        self.adamw_step(p32, m16.float(), v16.float(), g, p16, lr, beta1, beta2, eps, weight_decay, step, sumsq=sumsq, max_norm=max_norm, grad_mult=grad_mult,
+                        zero_grad=zero_grad, g16=g16)
+        m16.copy_(sr16.bits_to_bf16(mb).view(m16.shape))
+        v16.copy_(sr16.bits_to_bf16(vb).view(v16.shape))
+
+    def ref_mixup(self, ref_w16, policy_w16, alpha):
+        """GRPOConfig.sync_ref_model: ref = (1 - alpha) ref + alpha policy in place (mixup_composite on the backend's arenas)
+        -> fp32 [sum (policy - ref)^2, sum ref^2] of the values before the mix."""
+        r, p = ref_w16.float(), policy_w16.float()
+        sums = torch.stack([((p - r) ** 2).sum(), (r ** 2).sum()]).to(F32)
+        ref_w16.copy_(mixup_composite(ref_w16, policy_w16, alpha))
+        return sums
+
+    # ---- LoRA (time-r1_amd/lora.py, csrc/lora.hip): the merge as the fp32 chain of merge_composite, the rank-r weight gradient as a plain fp32 matmul
+    def lora_merge(self, w, w0, a, bt, s):
+        w.copy_(merge_composite(w0, a, bt, s).to(w.dtype))
+        return w
+
+    def lora_wgrad(self, g, thin, wide, scale, accumulate=True):
+        prod = float(scale) * (thin.float().t() @ wide.float())
+        if accumulate:
+            g += prod
+        else:
+            g.copy_(prod)
+        return g

@@ -1,6 +1,6 @@
-"""Cases, fp64 references and a CPU stand-in for the two entropy options of the GRPO objective (GRPOConfig.entropy_coef, GRPOConfig.top_entropy_quantile):
-tr1_logp_entropy_bwd and tr1_entropy_quantile_weight (csrc/loss.hip).  Shared by tests/test_entropy_objective_ref.py (CPU) and
-tests/test_entropy_objective_gpu.py (the HIP kernels, the head, GRPOCore and the trainer on the same cases).
+"""Cases and fp64 references for the two entropy options of the GRPO objective (GRPOConfig.entropy_coef, GRPOConfig.top_entropy_quantile):
+tr1_logp_entropy_bwd and tr1_entropy_quantile_weight (csrc/loss.hip; the fp32 CPU stand-ins are RefOps' methods of the same names).  Shared by
+tests/test_entropy_objective_ref.py (CPU) and tests/test_entropy_objective_gpu.py (the HIP kernels, the head, GRPOCore and the trainer on the same cases).
 
   H = -sum_v p log p,  d H / d x_v = -p_v (log p_v + H)
   dlogits[r, v] = dlogp[r] (1[v == t_r] - p) - dent[r] p ((x - lse[r]) + H[r]),   p = exp(x - lse[r])
@@ -8,7 +8,6 @@ tests/test_entropy_objective_gpu.py (the HIP kernels, the head, GRPOCore and the
 """
 import torch
 
-import loss_family_cases as lfc
 import vocab_cases as vc
 
 RHOS = (0.2, 0.5, 0.8, 1.0)
@@ -94,34 +93,6 @@ def compare_quantile(got_w, got_stats, ent, mask, rho, what):
     if rho == 1.0:
         assert torch.equal(w, live.float()), what
     return left
-
-
-class EntropyRefOps(lfc.FamilyRefOps):
-    """FamilyRefOps plus the two entropy ops in fp32 torch (oracle/ has neither)."""
-
-    def logp_entropy_bwd(self, logits, targets, lse, ent, dlogp, dent, inplace=True):
-        if dent is None:
-            return self.logp_bwd(logits, targets, lse, dlogp, inplace=inplace)
-        lp = logits.float() - lse[:, None]
-        p = torch.exp(lp)
-        onehot = torch.zeros_like(p)
-        onehot.scatter_(1, targets.long()[:, None], 1.0)
-        d = self._a(dlogp[:, None] * (onehot - p) - dent[:, None] * p * (lp + ent[:, None]))
-        if inplace:
-            logits.copy_(d)
-            return logits
-        return d
-
-    def entropy_quantile_weight(self, ent, mask, rho):
-        live = mask != 0
-        vals = ent[live].float()
-        n = int(vals.numel())
-        w = torch.zeros(ent.shape, dtype=torch.float32)
-        if n == 0:
-            return w, torch.zeros(3)
-        thr = torch.quantile(vals, 1.0 - float(rho))
-        w[live] = (vals >= thr).float()
-        return w, torch.stack([thr, w.sum(), torch.tensor(float(n))])
 
 
 # ------------------------------------------------------------------------------------------------------ the tiny trainer with the two options

@@ -39,6 +39,18 @@ def golden_params(ops, fx):
     return cfg, pol, ref
 
 
+def ref_ops_without(*names, **kw):
+    """RefOps(**kw) of a subclass that lacks the named ops - a backend from before a feature, for the tests of the product's "backend has no ..." refusals.
+    Each name is a property that raises AttributeError, so hasattr() is false; `name` stays "ref"."""
+    from oracle.ref_ops import RefOps
+
+    def missing(n):
+        def get(self):
+            raise AttributeError("%s has no %s" % (type(self).__name__, n))
+        return property(get)
+    return type("RefOpsWithout", (RefOps,), {n: missing(n) for n in names})(**kw)
+
+
 def golden_inputs(fx):
     pv, grid = VP.patchify(frames_for(fx))
     return pv, [grid]

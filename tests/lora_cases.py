@@ -1,11 +1,11 @@
-"""Cases, references and the CPU stand-in for LoRA (time-r1_amd/lora.py, csrc/lora.hip).  Shared by tests/test_lora_ref.py (CPU) and
-tests/test_lora_gpu.py (the HIP kernels and the HIP trainer on the same cases).
+"""Cases and references for LoRA (time-r1_amd/lora.py, csrc/lora.hip; the CPU stand-ins are RefOps.lora_merge / lora_wgrad).
+Shared by tests/test_lora_ref.py (CPU) and tests/test_lora_gpu.py (the HIP kernels and the HIP trainer on the same cases).
 
 The merge, per element of a targeted matrix, with s = fp32(scale):
 
     acc = 0;  for j ascending: acc = fadd(acc, fmul(Bt[j, o], A[j, i]));   W[o, i] = bf16_rne(fadd(W0[o, i], fmul(s, acc)))
 
-`merge_composite` is that text in torch, one fp32 op at a time: the kernel must match it bit for bit.  `merge64` is the fp64 value.
+`merge_composite` (oracle.ref_ops) is that text in torch, one fp32 op at a time: the kernel must match it bit for bit.  `merge64` is the fp64 value.
 
 What the composite may differ from RNE(fp64 value) by: the r products round once each (2^-24 |p_j|), the r - 1 non-trivial additions of the chain round once each
 (at most 2^-24 sum |p|), s * acc rounds once and the last addition once - together at most 2^-24 ((r + 1) |s| sum_j |p_j| + |y|) <= (r + 3) 2^-24 c |y| with
@@ -20,7 +20,7 @@ import math
 import torch
 
 import optim_cases as oc
-import ref_sync_cases as sc
+from oracle.ref_ops import merge_acc, merge_composite  # noqa: F401  (the kernel's contract; RefOps.lora_merge is built from them)
 
 BF16, F32, F64 = torch.bfloat16, torch.float32, torch.float64
 
@@ -58,19 +58,6 @@ def merge_data(out, in_, r, seed=0, big=False):
         bad |= (w0.double().abs() + sf * dabs) > MAX_CANCELLATION * (w0.double() + sf * d).abs()
     fixed = torch.copysign(torch.maximum(w0.double().abs(), 0.25 * dabs), d).to(BF16)
     return torch.where(bad, fixed, w0), a, bt
-
-
-def merge_acc(a, bt):
-    """The fp32 chain over j, one multiplication and one addition per step, each its own torch op (no contraction on the CPU)."""
-    acc = torch.zeros(bt.shape[1], a.shape[1], dtype=F32)
-    for j in range(a.shape[0]):
-        acc = acc + bt[j].float()[:, None] * a[j].float()[None, :]
-    return acc
-
-
-def merge_composite(w0, a, bt, s):
-    t = torch.tensor(s, dtype=F32) * merge_acc(a, bt)
-    return (w0.float() + t).to(w0.dtype)
 
 
 def merge_fused_variant(w0, a, bt, s):
@@ -123,24 +110,6 @@ def wgrad64(thin, wide, scale, g0=None):
     if g0 is not None:
         prod = prod + g0.double()
     return prod, bound
-
-
-# ---------------------------------------------------------------------------------------------------------------------- the CPU stand-in
-class LoraRefOps(sc.SyncRefOps):
-    """The CPU op backend of the trainer tests plus the two LoRA ops in torch (oracle/ has none): the merge as the fp32 chain above, the rank-r weight gradient as
-    a plain fp32 matmul."""
-
-    def lora_merge(self, w, w0, a, bt, s):
-        w.copy_(merge_composite(w0, a, bt, s).to(w.dtype))
-        return w
-
-    def lora_wgrad(self, g, thin, wide, scale, accumulate=True):
-        prod = float(scale) * (thin.float().t() @ wide.float())
-        if accumulate:
-            g += prod
-        else:
-            g.copy_(prod)
-        return g
 
 
 # ---------------------------------------------------------------------------------------------------------------------- engine: adapter gradients against fp64 autograd

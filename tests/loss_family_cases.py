@@ -1,4 +1,5 @@
-"""Cases, fp64 reference and a CPU stand-in for the GRPO objective family (tr1_grpo_policy_loss, csrc/loss.hip): the clipped loss with a choice of
+"""Cases and fp64 reference for the GRPO objective family (tr1_grpo_policy_loss, csrc/loss.hip; its fp32 CPU stand-in is
+oracle.ref_ops.RefOps.grpo_policy_loss): the clipped loss with a choice of
 normaliser (GRPOConfig.loss_type), a token- or sequence-level importance coefficient (importance_sampling_level) and an upper cap on it (delta), and with
 rows that hold no live token (mask_truncated_completions).  Shared by tests/test_loss_family_ref.py (CPU) and tests/test_loss_family_gpu.py.
 
@@ -15,7 +16,7 @@ import torch
 
 import ratio_cases as rc
 import vocab_cases as vc
-from time_r1_amd.ops import GRPO_LEVELS, GRPO_NORM_MODES
+from oracle.ref_ops import grpo_modes
 
 DELTA = 1.5
 NORMS = (0, 1, 2)
@@ -117,14 +118,10 @@ def family_case(G, C, eps, seed=0):
     return out
 
 
-def _modes(norm, level):
-    return GRPO_NORM_MODES.get(norm, norm), GRPO_LEVELS.get(level, level)
-
-
 def ref_policy_loss(logp, old_logp, ref_logp, tok_weight, mask, adv, beta, norm, level, eps_low, eps_high, delta, grad_scale):
     """fp64 + autograd -> (dlogp = grad_scale * d loss / d logp, out8, row_len, row_kl).  out8 = [loss, mean_g(sum_t kl m / max(len_g, 1)), sum mask, low / high /
     either clip fraction over max(sum mask, 1), masked mean of c - 1 - log c, largest c over the live tokens (0 when there is none)]."""
-    norm, level = _modes(norm, level)
+    norm, level = grpo_modes(norm, level)
     G, C = logp.shape
     lp = logp.double().clone().requires_grad_(True)
     live = mask.bool()
@@ -153,65 +150,6 @@ def ref_policy_loss(logp, old_logp, ref_logp, tok_weight, mask, adv, beta, norm,
     out8 = torch.stack([loss.detach(), ((kl * m).sum(1) / len1).mean(), tot, (is_low * m).sum() / tot1, (is_high * m).sum() / tot1,
                         ((is_low | is_high) * m).sum() / tot1, ((c - 1 - logc) * m).sum() / tot1, torch.where(live, c, zero).max()])
     return grad * grad_scale, out8, lens, (kl * m).sum(1)
-
-
-def fp32_policy_loss(logp, old_logp, ref_logp, mask, adv, beta, norm, level, eps_low, eps_high, delta=None, grad_scale=1.0, tok_weight=None):
-    """The same loss and its gradient in closed form, fp32 torch on the CPU (what FamilyRefOps serves to the CPU trainer tests).  Like the kernel it forms the
-    row sums behind s_g (log-ratios, weights) in fp64 and everything else in fp32."""
-    norm, level = _modes(norm, level)
-    G, C = logp.shape
-    f = torch.float32
-    delta = float(delta) if delta else 0.0
-    live = mask != 0
-    m = live.to(f)
-    A = adv.to(f).reshape(-1, 1)
-    zero = torch.zeros_like(logp, dtype=f)
-    lens, tot = m.sum(1), m.sum()
-    len1, tot1 = lens.clamp(min=1), tot.clamp(min=1)
-    n = (1 / (len1[:, None] * G), (1 / tot1).expand(G, 1), torch.full((G, 1), 1.0 / (float(G) * float(C)), dtype=f))[norm]
-    w = tok_weight.to(f) if tok_weight is not None else torch.ones_like(zero)
-    if level == 1:
-        dd = torch.where(live, logp.double() - old_logp.double(), zero.double()) if old_logp is not None else zero.double()
-        dbar = dd.sum(1) / len1.double()
-        c = torch.exp(dbar).to(f)[:, None].expand(G, C)
-        k3 = (torch.expm1(dbar) - dbar).to(f)[:, None].expand(G, C)
-        wbar = (torch.where(live, w.double(), zero.double()).sum(1) / len1.double()).to(f)[:, None]
-    else:
-        d = torch.where(live, logp.to(f) - old_logp.to(f), zero) if old_logp is not None else zero
-        c = torch.exp(d)
-        k3 = torch.expm1(d) - d
-    kl, dkl = zero, zero
-    if ref_logp is not None:
-        r = torch.where(live, ref_logp.to(f) - logp.to(f), zero)
-        e = torch.exp(r)
-        kl, dkl = e - r - 1, 1 - e
-    lo, hi = 1 - eps_low, 1 + eps_high
-    is_low = (c < lo) & (A < 0)
-    is_high = (c > hi) & (A > 0)
-    stuck = is_low | is_high
-    capped = c
-    if delta > 0:
-        capped = torch.clamp(c, max=delta)
-        stuck = stuck | ((c > delta) & (A < 0))
-    l = -w * torch.minimum(capped * A, torch.clamp(c, lo, hi) * A) + beta * kl
-    if level == 1:
-        dl = (torch.where(stuck, zero, -A * c * wbar) + beta * dkl) * n
-    else:
-        dl = (torch.where(stuck, zero, -w * A * c) + beta * dkl) * n
-    dlogp = torch.where(live, dl * grad_scale, zero)
-    lm = torch.where(live, l, zero)
-    loss = ((lm.sum(1) / len1).sum() / G, lm.sum() / tot1, lm.sum() / (float(G) * float(C)))[norm]
-    klm = torch.where(live, kl, zero)
-    out8 = torch.stack([loss, (klm.sum(1) / len1).mean(), tot, (is_low * m).sum() / tot1, (is_high * m).sum() / tot1, ((is_low | is_high) * m).sum() / tot1,
-                        torch.where(live, k3, zero).sum() / tot1, torch.where(live, c, zero).max()])
-    return dlogp, out8, lens, klm.sum(1)
-
-
-class FamilyRefOps(rc.RatioRefOps):
-    """RatioRefOps plus the objective family (oracle/ has no such op)."""
-
-    def grpo_policy_loss(self, logp, old_logp, ref_logp, mask, adv, beta, norm, level, eps_low, eps_high, delta=None, grad_scale=1.0, tok_weight=None):
-        return fp32_policy_loss(logp, old_logp, ref_logp, mask, adv, beta, norm, level, eps_low, eps_high, delta, grad_scale, tok_weight)
 
 
 def settings():

@@ -1,5 +1,6 @@
-"""Emulation, cases and a CPU stand-in for AdamW with bf16 moments and stochastic rounding (GRPOConfig.optimizer_state_dtype="bf16"; tr1_adamw_step_sr16,
-csrc/optim.hip).  Shared by tests/test_optim_state_ref.py (CPU) and tests/test_optim_state_gpu.py (the HIP kernel against the same emulation, bit for bit).
+"""Cases and checks for AdamW with bf16 moments and stochastic rounding (GRPOConfig.optimizer_state_dtype="bf16"; tr1_adamw_step_sr16, csrc/optim.hip).
+Shared by tests/test_optim_state_ref.py (CPU) and tests/test_optim_state_gpu.py (the HIP kernel against the same emulation, bit for bit).  The emulation
+itself lives in oracle/sr16.py (RefOps.adamw_step_sr16, the CPU stand-in, stores its moments) and is re-exported here.
 
 The step, from bf16 moments m, v (widened exactly) and fp32 p, g, with EVERY fp32 operation rounded once (numpy float32, no fused multiply-add):
 
@@ -15,7 +16,7 @@ So the value goes AWAY from zero exactly when r >= 65536 - (b & 0xffff) (and the
 over r is the value.
 
 Random word of the GLOBAL element e = index_base + i: Philox4x32-10, key (seed & 0xffffffff, seed >> 32), counter ((e >> 2) & 0xffffffff, (e >> 2) >> 32,
-step & 0xffffffff, 0x53523136), output word e & 3.  philox4x32_10 below is a vectorised copy of oracle.ref_ops.philox4x32_10, checked against it.
+step & 0xffffffff, 0x53523136), output word e & 3.  oracle.sr16.philox4x32_10 is a vectorised copy of oracle.ref_ops.philox4x32_10, checked against it.
 
 m16' and v16' are compared BIT FOR BIT with the kernel; p' against the fp64 reference optim_cases.ref_adamw applied to the bf16-valued moments, within
 optim_cases.adamw_bounds (the moments' widening is exact, so the bounds of the fp32-state kernel hold unchanged).
@@ -24,126 +25,17 @@ import numpy as np
 import torch
 
 import optim_cases as oc
-import ref_sync_cases as sc
+from oracle.ref_ops import RefOps
+from oracle.sr16 import (STREAM, MASK, philox4x32_10, random_words, f32_bits, bf16_rne_bits, sr_round, bf16_to_np, bits_to_bf16,  # noqa: F401
+                         emu_coef, emu_moments, emu_step)
 
 BF16, F32, F64 = torch.bfloat16, torch.float32, torch.float64
-STREAM = 0x53523136
-MASK = np.uint64(0xFFFFFFFF)
 SR16_GRID_CAP = 4096                    # blocks of adamw_sr16_kernel's capped grid (csrc/optim.hip, pinned by test_optim_state_ref.py)
 SR16_PASS = SR16_GRID_CAP * 256 * 8     # elements one grid trip covers: 2^23 = 2 * oc.GRID_PASS, so oc.GRID_PASS + 3 elements are ONE partial trip and a tail
 TWO_TRIPS_N = SR16_PASS + 8 * 256 * 3 + 5   # the one case beyond it: a full trip, three blocks' worth of a second one, a 5-element tail
 
 
-# ---------------------------------------------------------------------------------------------------------------- random bits
-def philox4x32_10(c0, c1, c2, c3, k0, k1):
-    """Vectorised over the counters (uint64 arrays that hold 32-bit words); k0, k1 Python ints.  -> four uint64 arrays of 32-bit words."""
-    c0, c1, c2, c3 = (np.asarray(c, dtype=np.uint64) & MASK for c in (c0, c1, c2, c3))
-    M0, M1, W0, W1 = np.uint64(0xD2511F53), np.uint64(0xCD9E8D57), 0x9E3779B9, 0xBB67AE85
-    k0, k1 = int(k0) & 0xFFFFFFFF, int(k1) & 0xFFFFFFFF
-    sh = np.uint64(32)
-    for _ in range(10):
-        p0, p1 = M0 * c0, M1 * c2                     # 32 x 32 bit products: exact in uint64
-        h0, l0, h1, l1 = p0 >> sh, p0 & MASK, p1 >> sh, p1 & MASK
-        c0, c1, c2, c3 = h1 ^ c1 ^ np.uint64(k0), l1, h0 ^ c3 ^ np.uint64(k1), l0
-        k0, k1 = (k0 + W0) & 0xFFFFFFFF, (k1 + W1) & 0xFFFFFFFF
-    return c0, c1, c2, c3
-
-
-def random_words(n, seed, step, index_base=0):
-    """-> uint32 [n]: the random word of elements index_base .. index_base + n."""
-    if n == 0:
-        return np.zeros(0, dtype=np.uint32)
-    q0, q1 = int(index_base) >> 2, (int(index_base) + n - 1) >> 2
-    q = np.arange(q0, q1 + 1, dtype=np.uint64)
-    w = philox4x32_10(q & MASK, q >> np.uint64(32), np.full(q.shape, int(step) & 0xFFFFFFFF, dtype=np.uint64), np.full(q.shape, STREAM, dtype=np.uint64),
-                      int(seed) & 0xFFFFFFFF, (int(seed) >> 32) & 0xFFFFFFFF)
-    flat = np.stack(w, axis=1).reshape(-1).astype(np.uint32)
-    lo = int(index_base) - 4 * q0
-    return flat[lo: lo + n]
-
-
-# ---------------------------------------------------------------------------------------------------------------- the rounding rule
-def f32_bits(x):
-    return np.ascontiguousarray(x, dtype=np.float32).view(np.uint32)
-
-
-def bf16_rne_bits(x):
-    """torch's nearest-even fp32 -> bf16 conversion, as uint16 bit patterns."""
-    t = torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32)).to(BF16)
-    return t.view(torch.int16).numpy().astype(np.uint16)
-
-
-def sr_round(x, r16):
-    """fp32 array x, 16-bit random values r16 (any unsigned dtype) -> uint16 bf16 bit patterns by the rule in the header."""
-    b = f32_bits(x).astype(np.uint64)
-    mag = b & np.uint64(0x7FFFFFFF)
-    s = np.minimum(mag + np.asarray(r16, dtype=np.uint64), np.uint64(0x7F7FFFFF))
-    out = (((b & np.uint64(0x80000000)) | s) >> np.uint64(16)).astype(np.uint16)
-    special = mag >= np.uint64(0x7F800000)
-    if special.any():
-        out = np.where(special, bf16_rne_bits(x), out)
-    return out
-
-
-def bf16_to_np(t):
-    """bf16 tensor -> the float32 numpy array of the same values (exact)."""
-    return (t.detach().cpu().contiguous().view(torch.int16).numpy().astype(np.uint16).astype(np.uint32) << np.uint32(16)).view(np.float32)
-
-
-def bits_to_bf16(bits):
-    """uint16 bit patterns -> bf16 tensor."""
-    return torch.from_numpy(np.ascontiguousarray(bits, dtype=np.uint16).view(np.int16).copy()).view(BF16)
-
-
-# ---------------------------------------------------------------------------------------------------------------- the step
-def emu_coef(sumsq, max_norm, grad_mult):
-    f = np.float32
-    gm = f(grad_mult)
-    if sumsq is None or not max_norm > 0:
-        return gm
-    norm = f(np.sqrt(f(sumsq)) * gm)
-    den = f(norm + f(1e-6))
-    return f(gm * min(f(1.0), f(f(max_norm) / den)))
-
-
-def emu_moments(m, v, g, beta1, beta2, sumsq=None, max_norm=0.0, grad_mult=1.0):
-    """float32 numpy arrays m, v, g -> the unrounded fp32 m', v' (every operation rounded once)."""
-    f = np.float32
-    b1, b2 = f(beta1), f(beta2)
-    gg = g * emu_coef(sumsq, max_norm, grad_mult)
-    mn = b1 * m + (f(1.0) - b1) * gg
-    vn = b2 * v + ((f(1.0) - b2) * gg) * gg
-    assert mn.dtype == np.float32 and vn.dtype == np.float32
-    return mn, vn
-
-
-def emu_step(m16, v16, g, beta1, beta2, step, seed, index_base, sumsq=None, max_norm=0.0, grad_mult=1.0):
-    """bf16 tensors m16, v16 and the fp32 gradient the kernel reads (tensor) -> uint16 bit patterns of the stored m16', v16' and the unrounded fp32 m', v'."""
-    with np.errstate(over="ignore", under="ignore", invalid="ignore"):
-        mn, vn = emu_moments(bf16_to_np(m16), bf16_to_np(v16), g.detach().cpu().float().contiguous().numpy(), beta1, beta2,
-                             None if sumsq is None else float(sumsq), max_norm, grad_mult)
-    w = random_words(mn.size, seed, step, index_base)
-    return sr_round(mn, w & np.uint32(0xFFFF)), sr_round(vn, w >> np.uint32(16)), mn, vn
-
-
-class SROps(sc.SyncRefOps):
-    """The CPU op backend of the trainer tests plus adamw_step_sr16 (oracle/ has no such op): the master update is RefOps.adamw_step's on the widened moments
-    (what the fp32-state path gives from the same inputs), the stored moments are the emulation's."""
-
-    def adamw_step_sr16(self, p32, m16, v16, g, p16, lr, beta1, beta2, eps, weight_decay, step, seed, index_base, sumsq=None, max_norm=0.0, grad_mult=1.0,
-                        zero_grad=True, g16=None):
-        assert p32.dtype == F32 and m16.dtype == BF16 and v16.dtype == BF16 and g.dtype == F32 and step >= 1
-        n = p32.numel()
-        assert m16.numel() == n and v16.numel() == n and g.numel() == n and p16.numel() == n and (g16 is None or (g16.dtype == BF16 and g16.numel() == n))
-        used = g16.float() if g16 is not None else g
-        mb, vb, _, _ = emu_step(m16, v16, used, beta1, beta2, step, seed, index_base, None if sumsq is None else float(sumsq), max_norm, grad_mult)
-        self.adamw_step(p32, m16.float(), v16.float(), g, p16, lr, beta1, beta2, eps, weight_decay, step, sumsq=sumsq, max_norm=max_norm, grad_mult=grad_mult,
-                        zero_grad=zero_grad, g16=g16)
-        m16.copy_(bits_to_bf16(mb).view(m16.shape))
-        v16.copy_(bits_to_bf16(vb).view(v16.shape))
-
-
-class RneOps(SROps):
+class RneOps(RefOps):
     """The same step with the moments rounded to NEAREST EVEN: what the feature is not (a decaying v never leaves 1.0)."""
 
     def adamw_step_sr16(self, p32, m16, v16, g, p16, lr, beta1, beta2, eps, weight_decay, step, seed, index_base, sumsq=None, max_norm=0.0, grad_mult=1.0,

@@ -1,5 +1,5 @@
-"""Cases, fp64 reference and a CPU stand-in for the GRPO loss against an OLD policy (tr1_grpo_loss_ratio, csrc/loss.hip), and the tiny-trainer
-scenario for several updates per rollout (GRPOConfig.num_iterations).  Shared by tests/test_policy_reuse_ref.py (CPU) and
+"""Cases and fp64 reference for the GRPO loss against an OLD policy (tr1_grpo_loss_ratio, csrc/loss.hip; its fp32 CPU stand-in is
+oracle.ref_ops.RefOps.grpo_loss_ratio), and the tiny-trainer scenario for several updates per rollout (GRPOConfig.num_iterations).  Shared by tests/test_policy_reuse_ref.py (CPU) and
 tests/test_policy_reuse_gpu.py (the HIP kernel and the HIP trainer on the same cases).
 
 The loss, per live token (mask != 0), with rho = exp(logp - old_logp), kl = exp(ref - logp) - (ref - logp) - 1, w = tok_weight or 1 (a constant):
@@ -13,7 +13,6 @@ token of every case is compared.  Masked positions hold old_logp = -300 against 
 import torch
 
 import vocab_cases as vc
-from oracle.ref_ops import RefOps
 
 EPS_PAIRS = ((0.2, 0.2), (0.2, 0.28))
 MAX_DELTA = 0.6
@@ -75,55 +74,6 @@ def ref_grpo_ratio(logp, old_logp, ref_logp, tok_weight, mask, adv, beta, use_gr
     out8 = torch.stack([loss.detach(), ((kl * m).sum(1) / lens).mean(), tot, (is_low * m).sum() / tot, (is_high * m).sum() / tot,
                         ((is_low | is_high) * m).sum() / tot, ((rho - 1 - d) * m).sum() / tot, rho[live].max()])
     return grad * grad_scale, out8, lens, (kl * m).sum(1)
-
-
-def fp32_grpo_ratio(logp, old_logp, ref_logp, mask, adv, beta, use_grpo, eps_low, eps_high, grad_scale=1.0, tok_weight=None):
-    """The same loss and its gradient in closed form, fp32 torch on the CPU (what RatioRefOps serves to the CPU trainer tests)."""
-    G, C = logp.shape
-    f = torch.float32
-    live = mask != 0
-    m = live.to(f)
-    A = adv.to(f).reshape(-1, 1)
-    zero = torch.zeros_like(logp, dtype=f)
-    d = torch.where(live, logp.to(f) - old_logp.to(f), zero)
-    rho = torch.exp(d)
-    kl, dkl = zero, zero
-    if ref_logp is not None:
-        r = torch.where(live, ref_logp.to(f) - logp.to(f), zero)
-        e = torch.exp(r)
-        kl, dkl = e - r - 1, 1 - e
-    w = tok_weight.to(f) if tok_weight is not None else torch.ones_like(zero)
-    lo, hi = 1 - eps_low, 1 + eps_high
-    is_low = (rho < lo) & (A < 0)
-    is_high = (rho > hi) & (A > 0)
-    lens, tot = m.sum(1), m.sum()
-    if use_grpo:
-        l = -w * rho * A + beta * kl
-        dl = -w * rho * A + beta * dkl
-        loss = ((l * m).sum(1) / lens).mean()
-        norm = m / lens[:, None] / G
-    else:
-        l = -w * torch.minimum(rho * A, torch.clamp(rho, lo, hi) * A) + beta * kl
-        dl = torch.where(is_low | is_high, zero, -w * rho * A) + beta * dkl
-        loss = (l * m).sum() / tot
-        norm = m / tot
-    dlogp = torch.where(live, dl * norm * grad_scale, zero)
-    out8 = torch.stack([loss, ((kl * m).sum(1) / lens).mean(), tot, (is_low * m).sum() / tot, (is_high * m).sum() / tot, ((is_low | is_high) * m).sum() / tot,
-                        ((torch.expm1(d) - d) * m).sum() / tot, torch.where(live, rho, zero).max()])
-    return dlogp, out8, lens, (kl * m).sum(1)
-
-
-class RatioRefOps(RefOps):
-    """The CPU op backend of the trainer tests plus the ratio loss (oracle/ itself has no such op) and the QuickGELU backward of a training tower
-    (the fp32 formula of test_vit_train_host.TowerRefOps, rounded once like the HIP kernel)."""
-
-    def quickgelu_bwd(self, x, dy):
-        v = x.float()
-        s = torch.sigmoid(1.702 * v)
-        return self._a(dy.float() * (s + 1.702 * v * s * (1.0 - s)))
-
-    def grpo_loss_ratio(self, logp, old_logp, ref_logp, mask, adv, beta, use_grpo, eps_low, eps_high, grad_scale=1.0, tok_weight=None):
-        return fp32_grpo_ratio(logp, old_logp, ref_logp, mask, adv, beta, use_grpo, eps_low, eps_high, grad_scale, tok_weight)
 
 
 # ------------------------------------------------------------------------------------------------------ several updates per rollout: the tiny trainer

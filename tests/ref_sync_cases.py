@@ -1,4 +1,4 @@
-"""Cases, references and a CPU stand-in for the reference-policy sync (GRPOConfig.sync_ref_model; tr1_ref_mixup, csrc/optim.hip).  Shared by
+"""Cases and references for the reference-policy sync (GRPOConfig.sync_ref_model; tr1_ref_mixup, csrc/optim.hip).  Shared by
 tests/test_ref_sync_ref.py (CPU) and tests/test_ref_sync_gpu.py (the HIP kernel and the HIP trainer on the same cases).
 
 The kernel, in place on ref, with a = fp32(alpha) and keep = fp32(1 - a) (exact for every alpha below: Sterbenz for 0.5 <= a <= 1, a power of two otherwise):
@@ -6,7 +6,8 @@ The kernel, in place on ref, with a = fp32(alpha) and keep = fp32(1 - a) (exact 
   ref[i] = bf16_rne(fadd(fmul(keep, ref[i]), fmul(a, policy[i])))        three separately rounded fp32 operations, one rounding to bf16
   sums   = [sum (policy - ref)^2, sum ref^2] of the values before the mix, fp32
 
-`composite` is that text in torch, three separate fp32 ops: the kernel must match it bit for bit (a NaN by position: its payload is not part of the contract).
+`composite` (oracle.ref_ops.mixup_composite, which RefOps.ref_mixup applies to its arenas) is that text in torch, three separate fp32 ops: the kernel must match
+it bit for bit (a NaN by position: its payload is not part of the contract).
 `mix64` / `sums64` are the fp64 references.
 
 What the composite may differ from RNE(fp64 mix) by: the three fp32 roundings move the sum by at most 2^-24 (|t1| + |t2| + |mix|) = 2^-24 (c + 1) |mix| with
@@ -21,7 +22,7 @@ import numpy as np
 import torch
 
 import optim_cases as oc
-import ratio_cases as rc
+from oracle.ref_ops import mixup_composite as composite  # noqa: F401  (the kernel's contract; RefOps.ref_mixup is built from it)
 
 BF16, F32, F64 = torch.bfloat16, torch.float32, torch.float64
 PAD, TOL_SUMSQ_RTOL = oc.PAD, oc.TOL_SUMSQ_RTOL
@@ -81,15 +82,6 @@ def make_data(n, wild, seed=0):
         a, b = sp[(start + j) % len(sp)]
         r[i], p[i] = a, b
     return r, p
-
-
-def composite(r, p, alpha):
-    """((1 - a) r + a p) as three separate fp32 torch ops, rounded once to r's dtype (bf16: the kernel's contract; the fp32 arenas of the CPU backend: no rounding)."""
-    a = torch.tensor(alpha, dtype=F32)
-    keep = torch.tensor(1.0, dtype=F32) - a
-    t1 = keep * r.float()
-    t2 = a * p.float()
-    return (t1 + t2).to(r.dtype)
 
 
 def fused_variant(r, p, alpha):
@@ -171,16 +163,6 @@ def framed(r, p, off, dev="cpu"):
 def frames_intact(rb, pb, p, off):
     n = p.numel()
     return oc.sentinels_intact(rb, off, n) and oc.sentinels_intact(pb, off, n) and same_bits(pb[PAD + off: PAD + off + n], p)
-
-
-class SyncRefOps(rc.RatioRefOps):
-    """The CPU op backend of the trainer tests plus ref_mixup in torch (oracle/ has no such op): the composite on the backend's arenas, the two sums in fp32."""
-
-    def ref_mixup(self, ref_w16, policy_w16, alpha):
-        r, p = ref_w16.float(), policy_w16.float()
-        sums = torch.stack([((p - r) ** 2).sum(), (r ** 2).sum()]).to(F32)
-        ref_w16.copy_(composite(ref_w16, policy_w16, alpha))
-        return sums
 
 
 def metric_keys(log):

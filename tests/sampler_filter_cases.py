@@ -1,7 +1,8 @@
-"""fp64 reference and cases for the sampler's top-p / min-p filters and the repetition penalty (csrc/sampler.hip).
+"""Cases for the sampler's top-p / min-p filters and the repetition penalty (csrc/sampler.hip).  The fp64 reference (ref_filter, ref_penalize, bitmap_tokens)
+lives in oracle/sampler_filter.py, where RefOps' sampler, penalty and seen bitmap use it too, and is re-exported here.
 
-Shared by tests/test_sampler_filter_ref.py (CPU: this reference against the transformers warpers, and the host plumbing) and
-tests/test_sampler_filter_gpu.py (the HIP kernels against this reference).  Plain torch on the CPU, written from the rules:
+Shared by tests/test_sampler_filter_ref.py (CPU: the reference against the transformers warpers, and the host plumbing) and
+tests/test_sampler_filter_gpu.py (the HIP kernels against the reference).  Plain torch on the CPU, written from the rules:
 
   order            : repetition penalty, temperature, top-k, top-p, min-p (HF generate)
   K (top-k)        : x >= k-th largest x (ties kept; every token when top-k is off)
@@ -11,47 +12,16 @@ tests/test_sampler_filter_gpu.py (the HIP kernels against this reference).  Plai
   kept set         : K, top-p and min-p intersected; the draw is the inverse CDF over it in vocabulary order (vc.draw_error judges it)
   repetition penalty: seen token: x * penalty if x < 0 else x / penalty, fp32, then one rounding to bf16
 """
-import math
-
 import torch
 
 import vocab_cases as vc
+from oracle.sampler_filter import ref_filter, bitmap_tokens, ref_penalize  # noqa: F401
 
 BF16, I32 = vc.BF16, vc.I32
 
 # (top_k, T, top_p, min_p) of the full-vocabulary sweep
 SWEEP_CONFIGS = ((0, 1.0, 0.9, 0.0), (50, 0.7, 0.9, 0.0), (0, 1.0, 1.0, 0.05), (50, 1.0, 0.95, 0.02), (0, 0.7, 0.5, 0.0))
 SWEEP_ROWS, SWEEP_STEPS, SWEEP_SEEDS, SWEEP_ROW_SEED = 16, 8, (4321, 5330 + (1 << 33), 6339 + (2 << 33)), 1
-
-
-def ref_filter(row, temperature, top_k, top_p=1.0, min_p=0.0):
-    """fp64 (keep mask, inclusive CDF over the kept set in vocabulary order, boundary margin) of one logits row.
-
-    margin: how far the row is from a different kept set.  top-p: min over the value classes of K of |mass above the class - top_p| (masses as
-    shares of K's mass); min-p: min over the tokens of |exp((x - max) / T) - min_p| / min_p.  inf for a filter that is off."""
-    x = row.double()
-    V = x.numel()
-    keep_k, _ = vc.token_cdf(row, temperature, top_k)
-    z = x / temperature
-    e = torch.where(keep_k, (z - z.max()).exp(), torch.zeros_like(z))
-    keep = keep_k.clone()
-    margin = math.inf
-    if top_p < 1.0:
-        vals, inv = torch.unique(x, return_inverse=True)                  # ascending; float equality, so +0.0 and -0.0 are one class
-        n = vals.numel()
-        cls_mass = torch.zeros(n, dtype=torch.float64).scatter_add_(0, inv, e)
-        cls_in_k = torch.zeros(n, dtype=torch.bool).scatter_(0, inv[keep_k], True)
-        desc = cls_mass.flip(0)
-        above = (torch.cumsum(desc, 0) - desc).flip(0) / e.sum()           # share of K's mass on strictly larger logits, per class
-        keep &= (above < top_p)[inv]
-        margin = min(margin, float((above[cls_in_k] - top_p).abs().min()))
-    if min_p > 0.0:
-        ratio = (z - z.max()).exp()
-        keep &= ratio >= min_p
-        margin = min(margin, float(((ratio - min_p).abs() / min_p).min()))
-    assert bool(keep[int(x.argmax())]), "the row maximum is always kept"
-    p = torch.where(keep, e, torch.zeros_like(e))
-    return keep, torch.cumsum(p, 0) / p.sum(), margin
 
 
 def sweep_refs(cfg, rows=SWEEP_ROWS, V=vc.V_FULL, seed=SWEEP_ROW_SEED):
@@ -120,26 +90,6 @@ def seen_bitmap(rows, V, seen_lists):
         for v in toks:
             bm[r, v >> 5] |= 1 << (v & 31)
     return torch.where(bm >= 2 ** 31, bm - 2 ** 32, bm).to(I32)
-
-
-def bitmap_tokens(bm_row, V):
-    """The set a bitmap row holds."""
-    w = bm_row.to(torch.int64) & 0xFFFFFFFF
-    bits = (w[:, None] >> torch.arange(32)[None, :]) & 1
-    return set(torch.nonzero(bits.reshape(-1)[:V])[:, 0].tolist())
-
-
-def ref_penalize(logits, seen_lists, penalty):
-    """torch on the CPU: fp32 ops of RepetitionPenaltyLogitsProcessor on the seen tokens, then .to(bfloat16).  logits bf16 [rows, V]."""
-    x = logits.float()
-    out = x.clone()
-    pen = torch.tensor(penalty, dtype=torch.float32)
-    for r, toks in enumerate(seen_lists):
-        if toks:
-            idx = torch.tensor(sorted(toks), dtype=torch.long)
-            s = x[r, idx]
-            out[r, idx] = torch.where(s < 0, s * pen, s / pen)
-    return out.to(BF16)
 
 
 def penalty_seen_sets(V):

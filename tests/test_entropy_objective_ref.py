@@ -1,12 +1,13 @@
 """The entropy options of the GRPO objective (GRPOConfig.entropy_coef, GRPOConfig.top_entropy_quantile), CPU side: the fp64 references of
 tests/entropy_cases.py against autograd and against their fp32 stand-ins, config validation, the command line, the dispatcher registration, and the trainer on
-the oracle op backend (EntropyRefOps).  tests/test_entropy_objective_gpu.py runs the HIP kernels and the HIP trainer against the same references."""
+the oracle op backend (RefOps).  tests/test_entropy_objective_gpu.py runs the HIP kernels and the HIP trainer against the same references."""
 import pytest
 import torch
 
 import entropy_cases as ec
-import loss_family_cases as lfc
 import vocab_cases as vc
+from helpers import ref_ops_without
+from oracle.ref_ops import RefOps
 from time_r1_amd.trainer import GRPOConfig
 
 
@@ -29,8 +30,8 @@ def test_reference_formula_is_the_autograd_gradient():
 
 @pytest.mark.parametrize("name,kw", [c for c in vc.bwd_cases() if c[1]["V"] <= 5008], ids=[c[0] for c in vc.bwd_cases() if c[1]["V"] <= 5008])
 def test_fp32_standin_dlogits(name, kw):
-    """EntropyRefOps.logp_entropy_bwd (fp32 arithmetic, one rounding to bf16) within TOL_DLOGITS of the fp64 reference; a null dent is logp_bwd."""
-    ops = ec.EntropyRefOps()
+    """RefOps.logp_entropy_bwd (fp32 arithmetic, one rounding to bf16) within TOL_DLOGITS of the fp64 reference; a null dent is logp_bwd."""
+    ops = RefOps()
     _, x, tg, _ = vc.stat_rows(**kw)
     R = kw["R"]
     dlogp, dent = vc.bwd_dlogp(R, kw["seed"]), ec.bwd_dent(R, kw["seed"])
@@ -47,8 +48,8 @@ def test_fp32_standin_dlogits(name, kw):
 
 @pytest.mark.parametrize("G,C", ec.QUANTILE_SHAPES)
 def test_fp32_standin_selection(G, C):
-    """EntropyRefOps.entropy_quantile_weight (fp32 torch.quantile) against the fp64 reference on every mask, both entropy sets, every rho."""
-    ops = ec.EntropyRefOps()
+    """RefOps.entropy_quantile_weight (fp32 torch.quantile) against the fp64 reference on every mask, both entropy sets, every rho."""
+    ops = RefOps()
     left = 0
     for mname, mask in ec.quantile_masks(G, C).items():
         for kind in ("uniform", "zeros"):
@@ -151,7 +152,7 @@ def test_header_states_the_two_entry_points():
 
 # ------------------------------------------------------------------------------------------------------------ trainer (oracle backend)
 def test_defaults_are_the_parent_run_and_need_neither_op(tmp_path):
-    ec.check_defaults_are_the_parent_run(ec.EntropyRefOps(), tmp_path, plain_ops=lfc.FamilyRefOps())
+    ec.check_defaults_are_the_parent_run(RefOps(), tmp_path, plain_ops=ref_ops_without("logp_entropy_bwd", "entropy_quantile_weight"))
 
 
 def test_a_backend_without_the_ops_refuses_the_options(tmp_path):
@@ -159,23 +160,23 @@ def test_a_backend_without_the_ops_refuses_the_options(tmp_path):
     import ratio_cases as rc
     for over in (dict(entropy_coef=0.01), dict(top_entropy_quantile=0.5)):
         with pytest.raises(NotImplementedError, match="ref"):
-            rc.tiny_trainer(lfc.FamilyRefOps(), load_case("clip_beta"), tmp_path, mu=1, **over)
+            rc.tiny_trainer(ref_ops_without("logp_entropy_bwd", "entropy_quantile_weight"), load_case("clip_beta"), tmp_path, mu=1, **over)
 
 
 def test_entropy_bonus_in_the_logged_loss(tmp_path):
-    ec.check_entropy_bonus_in_the_logged_loss(ec.EntropyRefOps(), tmp_path)
+    ec.check_entropy_bonus_in_the_logged_loss(RefOps(), tmp_path)
 
 
 def test_top_entropy_quantile_changes_the_step(tmp_path):
-    ec.check_top_entropy_quantile_changes_the_step(ec.EntropyRefOps(), tmp_path)
+    ec.check_top_entropy_quantile_changes_the_step(RefOps(), tmp_path)
 
 
 def test_two_iterations_with_both_options(tmp_path):
-    ec.check_two_iterations_with_both_options(ec.EntropyRefOps(), tmp_path)
+    ec.check_two_iterations_with_both_options(RefOps(), tmp_path)
 
 
 def test_all_truncated_completions_leave_the_weights_bit_unchanged(tmp_path):
-    ec.check_all_truncated_leaves_the_weights_alone(ec.EntropyRefOps(), tmp_path)
+    ec.check_all_truncated_leaves_the_weights_alone(RefOps(), tmp_path)
 
 
 def test_selection_and_bonus_reach_the_loss_calls(tmp_path):
@@ -183,7 +184,7 @@ def test_selection_and_bonus_reach_the_loss_calls(tmp_path):
     masked positions, and the bonus covers every live token (not only the selected ones)."""
     from helpers import load_case
     import ratio_cases as rc
-    ops = ec.EntropyRefOps()
+    ops = RefOps()
     seen = dict(tw=[], dent=[])
     tr = rc.tiny_trainer(ops, load_case("clip_beta"), tmp_path, mu=1, ga=1, n_rows=1, loss_type="dr_grpo", entropy_coef=0.5, top_entropy_quantile=0.5)
     o_loss, o_head = ops.grpo_policy_loss, tr.engine.head_bwd

@@ -8,6 +8,7 @@ import lora_cases as lc
 import optim_cases as oc
 import ref_sync_cases as sc
 from helpers import golden_params, load_case
+from oracle.ref_ops import RefOps
 
 pytestmark = pytest.mark.gpu
 BF16, F32 = torch.bfloat16, torch.float32
@@ -154,7 +155,7 @@ CASES = {"qwen2_vl": "clip_beta", "qwen2_5_vl": "q25_clip_beta_ragged"}
 def _pair(hip_ops, fx, tmp_path, peft, **over):
     """The HIP trainer and the CPU stand-in trainer on the same (bf16-representable) weights."""
     _, pol_h, _ = golden_params(hip_ops, fx)
-    cpu = lc.LoraRefOps()
+    cpu = RefOps()
     _, pol_c, _ = golden_params(cpu, fx)
     pol_c.train.w16.copy_(pol_h.train.w16.float().cpu())
     pol_c.frozen.w16.copy_(pol_h.frozen.w16.float().cpu())

@@ -1,5 +1,5 @@
 """LoRA (TimeR1_Trainer's peft_config), CPU side: the fp32 merge chain of tests/lora_cases.py against fp64, the engine's adapter gradients against fp64 autograd on
-the UNMERGED form, and the trainer on the stand-in op backend (lora_cases.LoraRefOps): construction, the step-0 equalities, what stays frozen, resume, replays,
+the UNMERGED form, and the trainer on the oracle op backend (RefOps): construction, the step-0 equalities, what stays frozen, resume, replays,
 two ranks over gloo, the adapter file, the refusals, the command line.  tests/test_lora_gpu.py runs the HIP kernels and the HIP trainer on the same cases."""
 import json
 import os
@@ -10,7 +10,8 @@ import torch
 
 import lora_cases as lc
 import ref_sync_cases as sc
-from helpers import load_case
+from helpers import load_case, ref_ops_without
+from oracle.ref_ops import RefOps
 from time_r1_amd.lora import LoraSpec, TARGET_MODULES
 from time_r1_amd.trainer import GRPOConfig
 
@@ -84,17 +85,16 @@ def test_spec_refusals(bad, exc):
 
 
 def test_trainer_refusals(tmp_path):
-    import ratio_cases as rc
     fx = load_case("clip_beta")
     with pytest.raises(NotImplementedError, match="sync_ref_model"):
-        lc.tiny_lora_trainer(lc.LoraRefOps(), fx, tmp_path, lc.QV, sync_ref_model=True, ref_model_sync_steps=2)
+        lc.tiny_lora_trainer(RefOps(), fx, tmp_path, lc.QV, sync_ref_model=True, ref_model_sync_steps=2)
     with pytest.raises(ValueError, match="shard_optimizer"):
-        lc.tiny_lora_trainer(lc.LoraRefOps(), fx, tmp_path, lc.QV, shard_optimizer=True)
+        lc.tiny_lora_trainer(RefOps(), fx, tmp_path, lc.QV, shard_optimizer=True)
     with pytest.raises(NotImplementedError, match="lora_merge / lora_wgrad"):
-        lc.tiny_lora_trainer(rc.RatioRefOps(), fx, tmp_path, lc.QV)                 # the ref_mixup convention: a backend without the ops is named
+        lc.tiny_lora_trainer(ref_ops_without("lora_merge", "lora_wgrad"), fx, tmp_path, lc.QV)      # the ref_mixup convention: a backend without the ops is named
     with pytest.raises(NotImplementedError, match="lora_dropout"):
-        lc.tiny_lora_trainer(lc.LoraRefOps(), fx, tmp_path, dict(lc.QV, lora_dropout=0.1))
-    tr = lc.tiny_lora_trainer(lc.LoraRefOps(), fx, tmp_path, lc.QV, deepspeed="scripts/zero3.json")      # a deepspeed path resolves to the replicated optimizer
+        lc.tiny_lora_trainer(RefOps(), fx, tmp_path, dict(lc.QV, lora_dropout=0.1))
+    tr = lc.tiny_lora_trainer(RefOps(), fx, tmp_path, lc.QV, deepspeed="scripts/zero3.json")      # a deepspeed path resolves to the replicated optimizer
     assert not tr.optimizer.sharded and tr.optimizer.lazy_zero is None
     tr.args.sync_ref_model = True                      # settings changed after construction are checked again when train() starts
     with pytest.raises(NotImplementedError, match="sync_ref_model"):
@@ -120,7 +120,7 @@ def test_model_params_can_be_built_without_training_state():
 @pytest.mark.parametrize("targets,r", [("all-linear", 16), ("all-linear", 8), (["q_proj", "v_proj"], 16), (["q_proj", "v_proj"], 8)], ids=["all-r16", "all-r8", "qv-r16", "qv-r8"])
 def test_adapter_gradients_against_fp64_autograd_on_the_unmerged_form(targets, r, reuse_prefill, recompute):
     """Bt random (with Bt = 0 every dA is zero).  Tolerance: the CPU engine-gradient tests' (tests/test_trainer_host_logic.py)."""
-    lora, res = lc.engine_adapter_grads(lc.LoraRefOps(), targets, r, recompute, reuse_prefill)
+    lora, res = lc.engine_adapter_grads(RefOps(), targets, r, recompute, reuse_prefill)
     assert len(res) == 2 * lora.cfg.text.n_layers * len(lora.spec.targets)
     for name, (mine, gold) in res.items():
         gold = gold.float()
@@ -134,7 +134,7 @@ def test_adapter_gradients_against_fp64_autograd_on_the_unmerged_form(targets, r
 def test_construction_step_zero_and_what_stays_frozen(tmp_path):
     fx = load_case("clip_beta")
     from helpers import golden_params
-    ops = lc.LoraRefOps()
+    ops = RefOps()
     _, pol, _ = golden_params(ops, fx)
     loaded = pol.train.w16.clone()
     tr = lc.tiny_lora_trainer(ops, fx, tmp_path / "lora", lc.QV, pol=pol)
@@ -156,7 +156,7 @@ def test_construction_step_zero_and_what_stays_frozen(tmp_path):
             setattr(trn.ops, n, lambda *x, _o=orig, _k=(tag, n), **k: (calls.__setitem__(_k, calls.get(_k, 0) + 1), _o(*x, **k))[1])
     spy(tr, "lora")
     snaps, first = lc.run_snapshots(tr)
-    full = lc.tiny_lora_trainer(lc.LoraRefOps(), fx, tmp_path / "full", None)
+    full = lc.tiny_lora_trainer(RefOps(), fx, tmp_path / "full", None)
     spy(full, "full")
     _, first_full = lc.run_snapshots(full)
     assert all(calls.get(("full", n), 0) > 0 for n in spied) and not any(calls.get(("lora", n), 0) for n in spied), calls
@@ -178,7 +178,7 @@ def test_merged_weights_are_the_fp32_merge_of_the_saved_adapter(tmp_path):
     adapter in fp32 onto the base weights and casting once gives the saved weights."""
     from safetensors.torch import load_file
     fx = load_case("clip_beta")
-    tr = lc.tiny_lora_trainer(lc.LoraRefOps(), fx, tmp_path, lc.QV, n_rows=2)
+    tr = lc.tiny_lora_trainer(RefOps(), fx, tmp_path, lc.QV, n_rows=2)
     lc.run_snapshots(tr)
     tr.save_model(str(tmp_path / "out"))
     ad = load_file(str(tmp_path / "out" / "adapter_model.safetensors"))
@@ -202,7 +202,7 @@ def test_merged_weights_are_the_fp32_merge_of_the_saved_adapter(tmp_path):
 
 def test_resume_continues_bit_for_bit(tmp_path):
     fx = load_case("clip_beta")
-    ops = lc.LoraRefOps()
+    ops = RefOps()
     tr = lc.tiny_lora_trainer(ops, fx, tmp_path / "a", lc.ALL_LINEAR, n_rows=4, save_steps=2)
     snaps, _ = lc.run_snapshots(tr)
     d = tmp_path / "a" / "checkpoint-2"
@@ -224,7 +224,7 @@ def test_resume_from_a_model_only_checkpoint_is_refused(tmp_path):
     """save_only_model=True writes no optimizer_rank*.pt, which under LoRA is the adapter state: resuming from it would load the merged weights and then merge
     them away with W0 + fresh adapters at the first step.  It raises before anything is loaded."""
     fx = load_case("clip_beta")
-    ops = lc.LoraRefOps()
+    ops = RefOps()
     tr = lc.tiny_lora_trainer(ops, fx, tmp_path / "a", lc.QV, n_rows=1, save_steps=1, save_only_model=True)
     lc.run_snapshots(tr)
     d = tmp_path / "a" / "checkpoint-1"
@@ -238,7 +238,7 @@ def test_resume_from_a_model_only_checkpoint_is_refused(tmp_path):
 
 def test_two_updates_per_rollout_merge_between_the_replays(tmp_path):
     fx = load_case("clip_beta")
-    tr = lc.tiny_lora_trainer(lc.LoraRefOps(), fx, tmp_path, lc.ALL_LINEAR, mu=2, ga=1, n_rows=2)
+    tr = lc.tiny_lora_trainer(RefOps(), fx, tmp_path, lc.ALL_LINEAR, mu=2, ga=1, n_rows=2)
     merges, versions = [], []
     orig = tr.lora.merge
     tr.lora.merge = lambda *a, **k: (orig(*a, **k), merges.append(tr.state.global_step), versions.append(tr.params.train.version))[0]
@@ -258,7 +258,7 @@ def _worker(rank, world, port, q, out):
     dist.init_process_group("gloo", rank=rank, world_size=world)
     import lora_cases as lc
     from helpers import load_case
-    tr = lc.tiny_lora_trainer(lc.LoraRefOps(), load_case("clip_beta"), os.path.join(out, "r%d" % rank), lc.ALL_LINEAR, n_rows=2)
+    tr = lc.tiny_lora_trainer(RefOps(), load_case("clip_beta"), os.path.join(out, "r%d" % rank), lc.ALL_LINEAR, n_rows=2)
     assert tr.dp.enabled and tr.dp.world == 2 and not tr.optimizer.sharded and tr.lora.train.shard is None
     snaps, _ = lc.run_snapshots(tr)                # 2 rows over 2 ranks: one optimizer step, each rank on its own row
     assert [s["step"] for s in snaps] == [1]
@@ -289,7 +289,7 @@ def test_two_ranks_hold_identical_adapters_and_merged_weights(tmp_path):
 
 def test_ft_trainer_accepts_a_peft_config_too(tmp_path):
     from time_r1_amd.trainer import TimeR1_Trainer_ft
-    tr = lc.tiny_lora_trainer(lc.LoraRefOps(), load_case("clip_beta"), tmp_path, lc.QV, cls=TimeR1_Trainer_ft)
+    tr = lc.tiny_lora_trainer(RefOps(), load_case("clip_beta"), tmp_path, lc.QV, cls=TimeR1_Trainer_ft)
     assert tr.lora is not None and tr.engine.lora is tr.lora and tr.params.train.grad is None
 
 

@@ -1,6 +1,6 @@
 """The GRPO objective family (GRPOConfig.loss_type / importance_sampling_level / delta / scale_rewards / mask_truncated_completions), CPU side: the fp64
 reference of tests/loss_family_cases.py against its fp32 stand-in and against the references it must coincide with, the conditions on the cases, config
-validation, the host-side pieces, and the trainer on the oracle op backend (FamilyRefOps).  tests/test_loss_family_gpu.py runs the HIP kernel and the HIP
+validation, the host-side pieces, and the trainer on the oracle op backend (RefOps).  tests/test_loss_family_gpu.py runs the HIP kernel and the HIP
 trainer against the same references."""
 import math
 
@@ -11,6 +11,7 @@ import torch
 import loss_family_cases as fc
 import ratio_cases as rc
 import vocab_cases as vc
+from oracle.ref_ops import RefOps
 from test_policy_reuse_ref import STANDIN_SHARE
 from time_r1_amd.grpo import eos_mask, group_advantages, policy_objective, truncation_mask
 from time_r1_amd.trainer import GRPOConfig
@@ -31,7 +32,7 @@ def test_fp32_standin_against_fp64_reference(G, C):
             for norm, level, delta, beta, with_w in fc.settings():
                 logp, old, ref_lp, w, mask, adv = _args(cc, with_w)
                 ref = fc.ref_policy_loss(logp, old, ref_lp, w, mask, adv, beta, norm, level, eps[0], eps[1], delta, 0.5)
-                got = fc.fp32_policy_loss(logp, old, ref_lp, mask, adv, beta, norm, level, eps[0], eps[1], delta, 0.5, tok_weight=w)
+                got = RefOps().grpo_policy_loss(logp, old, ref_lp, mask, adv, beta, norm, level, eps[0], eps[1], delta, 0.5, tok_weight=w)
                 worst = max(worst, fc.compare(got, ref, dead, (eps, norm, level, delta, beta, with_w)))
     print("G=%d C=%d: worst share of TOL_GRPO %.4f, %d boundary tokens / rows moved" % (G, C, worst, moved))
     assert worst <= STANDIN_SHARE, worst
@@ -91,7 +92,7 @@ def test_empty_rows_and_an_empty_grid_give_zeros_not_nan():
                     if fn == "ref":
                         out = fc.ref_policy_loss(logp, old, ref_lp, w, mask, adv, beta, norm, level, 0.2, 0.2, delta, 1.0)
                     else:
-                        out = fc.fp32_policy_loss(logp, old, ref_lp, mask, adv, beta, norm, level, 0.2, 0.2, delta, 1.0, tok_weight=w)
+                        out = RefOps().grpo_policy_loss(logp, old, ref_lp, mask, adv, beta, norm, level, 0.2, 0.2, delta, 1.0, tok_weight=w)
                     assert all(torch.isfinite(t).all() for t in out)
                     assert bool((out[0][mask == 0] == 0).all())
                     assert float(out[2][1]) == 0 and float(out[3][1]) == 0 and float(out[2][G - 1]) == 0 and float(out[3][G - 1]) == 0
@@ -215,16 +216,16 @@ def test_torch_op_is_registered_with_a_fake_kernel_and_no_cpu_fallback():
 
 
 def test_bnpo_and_the_sequence_level_reach_the_legacy_first_step(tmp_path):
-    fc.check_first_step_equals_legacy(fc.FamilyRefOps(), tmp_path, fc.STEP1_ATOL)
+    fc.check_first_step_equals_legacy(RefOps(), tmp_path, fc.STEP1_ATOL)
 
 
 def test_all_truncated_completions_leave_the_weights_bit_unchanged(tmp_path):
-    fc.check_all_truncated_leaves_the_weights_alone(fc.FamilyRefOps(), tmp_path)
+    fc.check_all_truncated_leaves_the_weights_alone(RefOps(), tmp_path)
 
 
 def test_use_grpo_with_the_truncation_mask_takes_the_general_path(tmp_path):
     from helpers import load_case
-    ops = fc.FamilyRefOps()
+    ops = RefOps()
     calls = []
     orig = ops.grpo_policy_loss
     ops.grpo_policy_loss = lambda *a, **k: (calls.append(a[6:11]), orig(*a, **k))[1]
@@ -238,7 +239,7 @@ def test_use_grpo_with_the_truncation_mask_takes_the_general_path(tmp_path):
 
 def test_two_updates_at_sequence_level_with_a_cap_log_finite_replay_keys(tmp_path):
     from helpers import load_case
-    tr = rc.tiny_trainer(fc.FamilyRefOps(), load_case("clip_beta"), tmp_path, mu=2, ga=2, n_rows=2, importance_sampling_level="sequence", delta=1.5)
+    tr = rc.tiny_trainer(RefOps(), load_case("clip_beta"), tmp_path, mu=2, ga=2, n_rows=2, importance_sampling_level="sequence", delta=1.5)
     rec = rc.run_recorded(tr)
     assert tr.state.global_step == 2 and rec["rollouts"] == 1 and len(rec["replay_old"]) == 2
     logs = tr.state.log_history

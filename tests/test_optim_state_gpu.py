@@ -13,6 +13,7 @@ import torch
 
 import optim_cases as oc
 import optim_state_cases as osc
+from oracle.ref_ops import RefOps
 
 pytestmark = pytest.mark.gpu
 
@@ -58,7 +59,7 @@ def test_sr16_rounding_patterns(hip_ops):
 
 def test_sr16_keying_and_split_calls(hip_ops):
     got = osc.check_keying(hip_ops, DEV)
-    want = osc.check_keying(osc.SROps())
+    want = osc.check_keying(RefOps())
     assert torch.equal(got[1], want[1]) and torch.equal(got[2], want[2]), "the kernel's stored moments are the CPU stand-in's"
 
 
@@ -67,7 +68,7 @@ def test_sr16_decay_is_unbiased_and_equals_the_cpu_bits(hip_ops):
     mean, want = float(v.double().mean()), osc.decay_want()
     print("OBS sr16 v decay: mean %.6f, exact %.6f, |diff| %.2e (bound %.0e)" % (mean, want, abs(mean - want), osc.DECAY_BOUND))
     assert abs(mean - want) <= osc.DECAY_BOUND, (mean, want)
-    assert torch.equal(oc.bits16(v), oc.bits16(osc.run_decay(osc.SROps()))), "the emulation is exact: the same bits as on the CPU"
+    assert torch.equal(oc.bits16(v), oc.bits16(osc.run_decay(RefOps()))), "the emulation is exact: the same bits as on the CPU"
 
 
 def test_sr16_argument_checks_and_empty_call(hip_ops):
@@ -143,7 +144,7 @@ def test_adamw_flat_bf16_state_memory_and_resume(hip_ops):
     grads = [osc.exact_grad(n, k) for k in range(3)]
     osc.flat_steps(o16, grads, DEV)
     straight = osc.state_bits(a)
-    cpu_p = osc.tiny_params(osc.SROps(act_dtype=BF16), moment_dtype=BF16)
+    cpu_p = osc.tiny_params(RefOps(act_dtype=BF16), moment_dtype=BF16)
     cpu_o = AdamWFlat(cpu_p, cpu_p.ops, lr=1e-3, weight_decay=0.01, seed=3)
     osc.flat_steps(cpu_o, grads)
     cpu = osc.state_bits(cpu_p.train)

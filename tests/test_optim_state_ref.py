@@ -11,7 +11,7 @@ import torch
 
 import optim_cases as oc
 import optim_state_cases as osc
-from helpers import load_case
+from helpers import load_case, ref_ops_without
 from oracle.ref_ops import RefOps, philox4x32_10
 from time_r1_amd.optim import AdamWFlat
 from time_r1_amd.trainer import GRPOConfig
@@ -44,11 +44,11 @@ def test_kernel_source_pins_the_grid_cap_and_the_stream_word():
 
 
 def test_rounding_patterns_through_an_exact_step():
-    osc.check_patterns(osc.SROps())
+    osc.check_patterns(RefOps())
 
 
 def test_unbiased_where_nearest_even_freezes():
-    v = osc.run_decay(osc.SROps())
+    v = osc.run_decay(RefOps())
     mean, want = float(v.double().mean()), osc.decay_want()
     print("OBS v decay: mean %.6f, exact %.6f, |diff| %.2e (bound %.0e)" % (mean, want, abs(mean - want), osc.DECAY_BOUND))
     assert abs(want - 0.904793) < 1e-6
@@ -59,7 +59,7 @@ def test_unbiased_where_nearest_even_freezes():
 
 # ------------------------------------------------------------------------------------------------------------------ keying
 def test_keying_by_seed_step_and_global_index():
-    osc.check_keying(osc.SROps())
+    osc.check_keying(RefOps())
 
 
 def test_masters_follow_the_fp32_path_on_the_first_step(ref_ops):
@@ -69,7 +69,7 @@ def test_masters_follow_the_fp32_path_on_the_first_step(ref_ops):
     a = [p.clone(), torch.zeros(n), torch.zeros(n), g.clone(), torch.zeros(n, dtype=BF16)]
     ref_ops.adamw_step(*a, 1e-3, oc.B1, oc.B2, oc.EPS, 0.01, 1, sumsq=ss, max_norm=1.0, grad_mult=0.5)
     b = [p.clone(), torch.zeros(n, dtype=BF16), torch.zeros(n, dtype=BF16), g.clone(), torch.zeros(n, dtype=BF16)]
-    osc.SROps().adamw_step_sr16(*b, 1e-3, oc.B1, oc.B2, oc.EPS, 0.01, 1, 9, 0, sumsq=ss, max_norm=1.0, grad_mult=0.5)
+    RefOps().adamw_step_sr16(*b, 1e-3, oc.B1, oc.B2, oc.EPS, 0.01, 1, 9, 0, sumsq=ss, max_norm=1.0, grad_mult=0.5)
     assert torch.equal(oc.bits32(a[0]), oc.bits32(b[0])) and torch.equal(oc.bits16(a[4]), oc.bits16(b[4]))
     assert float((b[1].float() - a[1]).abs().max()) <= float(a[1].abs().max()) * 2.0 ** -7 and bool((b[2].float() >= 0).all())
 
@@ -80,7 +80,7 @@ def test_oracle_step_on_the_shared_cases_holds_the_bounds():
         if case["n"] > 200000:
             continue
         for use_g16 in (False, True):
-            out = osc.run_sr16(osc.SROps(), case, use_g16=use_g16)
+            out = osc.run_sr16(RefOps(), case, use_g16=use_g16)
             osc.check_sr16(out, case, limit=oc.ORACLE_SHARE)
             assert bool((out["g"] == 0).all())
 
@@ -97,7 +97,7 @@ def _flat(ops, state_dtype, lazy=False, moment_dtype=F32, seed=3, **kw):
 
 
 def test_adamw_flat_dtypes_spans_and_resume():
-    ops = osc.SROps()
+    ops = RefOps()
     params, opt = _flat(ops, BF16)
     a = params.train
     assert a.m.dtype == BF16 and a.v.dtype == BF16 and a.master.dtype == F32 and a.m.element_size() == 2 and a.moment_dtype == BF16 and opt.sr16
@@ -141,7 +141,7 @@ def test_adamw_flat_dtypes_spans_and_resume():
 
 
 def test_set_moment_dtype_converts_in_place_and_set_shard_keeps_it():
-    ops = osc.SROps()
+    ops = RefOps()
     params = osc.tiny_params(ops)
     a = params.train
     a.set_moment_dtype(F32)
@@ -173,7 +173,7 @@ def _worker(rank, world, port, q, shard, wire):
     import optim_state_cases as osc
     from time_r1_amd.dist import DataParallel
     from time_r1_amd.optim import AdamWFlat
-    ops = osc.SROps()
+    ops = RefOps()
     params = osc.tiny_params(ops)
     opt = AdamWFlat(params, ops, lr=1e-3, weight_decay=0.01, dp=DataParallel(), shard_optimizer=shard, state_dtype=torch.bfloat16, seed=3,
                     grad_wire_dtype=torch.bfloat16 if wire == "bf16" else torch.float32)
@@ -251,11 +251,11 @@ def test_backend_without_the_op_is_refused_and_the_default_never_asks(tmp_path):
     import ratio_cases as rc
     fx = load_case("clip_beta")
     with pytest.raises(NotImplementedError, match="adamw_step_sr16"):
-        AdamWFlat(osc.tiny_params(RefOps()), RefOps(), state_dtype=BF16)
+        AdamWFlat(osc.tiny_params(RefOps()), ref_ops_without("adamw_step_sr16"), state_dtype=BF16)
     with pytest.raises(NotImplementedError, match="adamw_step_sr16"):
-        rc.tiny_trainer(rc.RatioRefOps(), fx, tmp_path / "x", mu=1, optimizer_state_dtype="bf16")
+        rc.tiny_trainer(ref_ops_without("adamw_step_sr16"), fx, tmp_path / "x", mu=1, optimizer_state_dtype="bf16")
     # the default: only adamw_step, with fp32 moments
-    ops = osc.SROps()
+    ops = RefOps()
     calls = []
     orig = ops.adamw_step
     ops.adamw_step = lambda p32, m, v, *a, **k: (calls.append((m.dtype, v.dtype)), orig(p32, m, v, *a, **k))[1]
@@ -269,14 +269,14 @@ def test_backend_without_the_op_is_refused_and_the_default_never_asks(tmp_path):
 def test_trainer_with_bf16_state_trains_saves_and_resumes_exactly(tmp_path):
     import ratio_cases as rc
     fx = load_case("clip_beta")
-    tr = rc.tiny_trainer(osc.SROps(), fx, tmp_path / "a", mu=1, ga=1, n_rows=4, save_steps=2, optimizer_state_dtype="bf16")
+    tr = rc.tiny_trainer(RefOps(), fx, tmp_path / "a", mu=1, ga=1, n_rows=4, save_steps=2, optimizer_state_dtype="bf16")
     a = tr.params.train
     assert a.m.dtype == BF16 and a.v.dtype == BF16 and tr.optimizer.sr16 and tr.optimizer.seed == tr.args.seed, "a caller's ModelParams is converted in place"
     tr.train()
     assert tr.state.global_step == 4 and all(np.isfinite(l["loss"]) for l in tr.state.log_history if "loss" in l)
     sd = torch.load(tmp_path / "a" / "checkpoint-2" / "optimizer_rank0.pt", weights_only=False)
     assert sd["m"].dtype == BF16 and sd["v"].dtype == BF16 and sd["master"].dtype == F32 and bool(sd["m"].float().abs().max() > 0)
-    tr2 = rc.tiny_trainer(osc.SROps(), fx, tmp_path / "b", mu=1, ga=1, n_rows=4, optimizer_state_dtype="bf16")
+    tr2 = rc.tiny_trainer(RefOps(), fx, tmp_path / "b", mu=1, ga=1, n_rows=4, optimizer_state_dtype="bf16")
     tr2.train(resume_from_checkpoint=str(tmp_path / "a" / "checkpoint-2"))
     assert tr2.state.global_step == 4
     b = tr2.params.train
@@ -287,5 +287,5 @@ def test_trainer_with_bf16_state_trains_saves_and_resumes_exactly(tmp_path):
     from time_r1_amd.config import tiny_test
     from time_r1_amd.trainer import TimeR1_Trainer
     tr3 = TimeR1_Trainer(tiny_test(), [rc.varied_reward], [], args=GRPOConfig(output_dir=str(tmp_path / "c"), optimizer_state_dtype="bf16"),
-                         processing_class=FakeProcessor(tiny_test()), ops=osc.SROps())
+                         processing_class=FakeProcessor(tiny_test()), ops=RefOps())
     assert tr3.params.train.m.dtype == BF16 and tr3.params.train.moment_dtype == BF16

@@ -1,5 +1,5 @@
 """Several clipped policy updates per rollout (GRPOConfig.num_iterations), CPU side: the fp64 reference of the ratio loss against vocab_cases.ref_grpo and
-against its fp32 stand-in, config validation, and the trainer's step arithmetic / replay path / resume on the oracle op backend (ratio_cases.RatioRefOps).
+against its fp32 stand-in, config validation, and the trainer's step arithmetic / replay path / resume on the oracle op backend (RefOps).
 tests/test_policy_reuse_gpu.py runs the HIP kernel and the HIP trainer against the same references."""
 import itertools
 
@@ -9,6 +9,7 @@ import torch
 import ratio_cases as rc
 import vocab_cases as vc
 from helpers import load_case
+from oracle.ref_ops import RefOps
 from time_r1_amd.trainer import GRPOConfig
 
 STANDIN_SHARE = 0.25            # the fp32 stand-in must sit within this share of TOL_GRPO of the fp64 reference
@@ -22,7 +23,7 @@ def test_fp32_standin_against_fp64_reference(G, C):
         moved += c["moved"]
         w = c["tok_weight"] if with_w else None
         ref = rc.ref_grpo_ratio(c["logp"], c["old_logp"], c["ref_logp"], w, c["mask"], c["adv"], beta, use_grpo, eps[0], eps[1], gs)
-        got = rc.fp32_grpo_ratio(c["logp"], c["old_logp"], c["ref_logp"], c["mask"], c["adv"], beta, use_grpo, eps[0], eps[1], gs, tok_weight=w)
+        got = RefOps().grpo_loss_ratio(c["logp"], c["old_logp"], c["ref_logp"], c["mask"], c["adv"], beta, use_grpo, eps[0], eps[1], gs, tok_weight=w)
         for a, b in zip(got, ref):
             assert torch.isfinite(a).all()
             worst = max(worst, vc.worst(a, b, vc.TOL_GRPO)[0])
@@ -57,7 +58,7 @@ def test_config_validation():
 
 
 def test_trainer_rejects_unbounded_and_misaligned_settings(tmp_path):
-    ops = rc.RatioRefOps()
+    ops = RefOps()
     with pytest.raises(ValueError, match="use_grpo"):
         rc.tiny_trainer(ops, load_case("grpo_beta"), tmp_path, mu=2)                 # this fixture has use_grpo=True
     fx = load_case("clip_beta")
@@ -76,13 +77,13 @@ def test_two_updates_per_rollout_and_resume_on_the_oracle_backend(tmp_path):
     """GA = 2, 4 rows, num_iterations = 2: 2 rollouts, 4 optimizer steps; step 1 is the mu = 1 run's step 1, step 2 is not its step 2; the replays run no
     rollout and no reference-policy forward, are handed the first pass's log-probs, count no tokens twice, and log the clip / old-policy keys.
     (Reference-policy forwards are counted per micro-step: 4 first-pass micro-steps, 4 forwards - not 8.)  Then checkpoint-2 resumed to step 4."""
-    ops = rc.RatioRefOps()
+    ops = RefOps()
     fx, tr2, _ = rc.check_reuse_scenario(ops, tmp_path, atol_step1=0.0)
     rc.check_resume(ops, tmp_path, fx, tr2, atol=2e-6)
 
 
 def test_three_updates_hand_every_replay_the_same_old_policy(tmp_path):
-    ops = rc.RatioRefOps()
+    ops = RefOps()
     tr = rc.tiny_trainer(ops, load_case("clip_beta"), tmp_path, mu=3, ga=1, n_rows=1)
     rec = rc.run_recorded(tr)
     assert tr.state.global_step == 3 and rec["rollouts"] == 1 and rec["ref_forwards"] == 1
@@ -113,14 +114,14 @@ def test_torch_op_is_registered_with_a_fake_kernel_and_no_cpu_fallback():
 def test_replay_on_unchanged_weights_reproduces_the_first_pass_gradient(tmp_path, fix_vit):
     """fp32 on the CPU: the two passes differ in summation order only (one decoder forward over P + G C rows against prefill + continuation), the bound the
     window tests of test_trainer_resume_and_windows.py use for the same kind of difference."""
-    g1, g2, m = rc.first_pass_and_replay_grads(rc.RatioRefOps(), tmp_path, fix_vit)
+    g1, g2, m = rc.first_pass_and_replay_grads(RefOps(), tmp_path, fix_vit)
     assert float(g1.abs().max()) > 0
     assert torch.allclose(g1, g2, atol=1e-6 * max(1.0, float(g1.abs().max())), rtol=1e-4), float((g1 - g2).abs().max())
     assert m["clip_ratio/region_mean"] == 0.0 and abs(m["policy_kl_old"]) < 1e-9
 
 
 def test_two_updates_with_a_training_tower(tmp_path):
-    tr = rc.tiny_trainer(rc.RatioRefOps(), load_case("clip_beta"), tmp_path, mu=2, ga=2, n_rows=2, fix_vit=False)
+    tr = rc.tiny_trainer(RefOps(), load_case("clip_beta"), tmp_path, mu=2, ga=2, n_rows=2, fix_vit=False)
     a = tr.params.train
     lo, hi = a.offsets["patch.w"][0], a.master.numel()          # the tower's specs sit at the end of the trainable arena (params.arena_specs)
     rec = rc.run_recorded(tr)

@@ -9,7 +9,6 @@ import sys
 import pytest
 import torch
 
-import entropy_cases as ec
 import ratio_cases as rc
 import recompute_cases as rcc
 from helpers import GOLDEN, load_case
@@ -27,7 +26,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 @pytest.mark.parametrize("reuse_prefill", [True, False], ids=["prefill+continuation", "full-sequence"])
 @pytest.mark.parametrize("shape", list(rcc.SHAPES))
 def test_gradients_and_outputs_equal_the_none_run_bit_for_bit(shape, reuse_prefill, variant):
-    ops = ec.EntropyRefOps()
+    ops = RefOps()
     for beta, fix_vit in itertools.product((0.0, 0.04), (True, False)):
         kw = dict(variant=variant, beta=beta, fix_vit=fix_vit, reuse_prefill=reuse_prefill)
         none = rcc.micro_steps(ops, rcc.SHAPES[shape], "none", **kw)
@@ -39,7 +38,7 @@ def test_gradients_and_outputs_equal_the_none_run_bit_for_bit(shape, reuse_prefi
 def test_a_replayed_update_with_an_entropy_bonus_is_exact_too(fix_vit):
     """num_iterations = 2 at the core: the first pass (prefill + continuation), the weights move, then forward_logps(replay=True) - the full-sequence path into the
     pooled slot-0 buffers - and the ratio loss, with entropy_coef != 0 in both passes."""
-    ops = ec.EntropyRefOps()
+    ops = RefOps()
     kw = dict(beta=0.04, fix_vit=fix_vit, replay=True, entropy_coef=0.01)
     none = rcc.micro_steps(ops, rcc.SHAPES["tail"], "none", **kw)
     mlp = rcc.micro_steps(ops, rcc.SHAPES["tail"], "mlp", **kw)
@@ -80,7 +79,7 @@ def test_the_context_holds_exactly_ctx_bytes(shape, mode, reuse_prefill):
                     held[v.data_ptr()] = v.numel() * v.element_size()
         seen.append((sum(held.values()), eng.ctx_bytes(M), M))
     P, G, C = rcc.SHAPES[shape]
-    rcc.micro_steps(rc.RatioRefOps(torch.bfloat16), (P, G, C), mode, reuse_prefill=reuse_prefill, replay=True, on_ctx=on_ctx)
+    rcc.micro_steps(RefOps(torch.bfloat16), (P, G, C), mode, reuse_prefill=reuse_prefill, replay=True, on_ctx=on_ctx)
     assert len(seen) == 2
     t = rcc.CONFIGS["qwen2_vl"]().text
     per_row = {"none": 2 * (4 * t.hidden + t.kv_dim + 2 * t.q_dim + 3 * t.intermediate) + 8, "mlp": 2 * (2 * t.hidden + t.kv_dim + 2 * t.q_dim) + 8}[mode]
@@ -118,7 +117,7 @@ def test_stash_and_unstash_work_on_the_keys_that_exist(monkeypatch):
 # ------------------------------------------------------------------------------------------------------------ row ranges
 def _glu_rows(shape, mode, reuse_prefill):
     """-> ({layer: [rows of each forward gemm_glu call]}, the same of the backward) of one micro-step on the policy's weights."""
-    ops = ec.EntropyRefOps()
+    ops = RefOps()
     P, G, C = rcc.SHAPES[shape]
     cfg, pol, eng, core = rcc.build(ops, mode, G=G, C=C, reuse_prefill=reuse_prefill)
     layer_of = {pol.train.w("l%d.gu.w" % i).data_ptr(): i for i in range(cfg.text.n_layers)}
@@ -187,7 +186,7 @@ def test_validation_names_the_two_values():
 
 
 def _op_calls(mode, reuse_prefill):
-    spy = rcc.Spy(ec.EntropyRefOps())
+    spy = rcc.Spy(RefOps())
     rcc.micro_steps(spy, rcc.SHAPES["tail"], mode, beta=0.04, reuse_prefill=reuse_prefill)
     return [list(c) for c in spy.calls]
 
@@ -210,7 +209,7 @@ def test_gradient_checkpointing_alone_changes_nothing(tmp_path):
     fx = load_case("clip_beta")
     runs = {}
     for name, over in (("plain", {}), ("flag", dict(gradient_checkpointing=True)), ("mlp", dict(gradient_checkpointing=True, activation_recompute="mlp"))):
-        tr = rc.tiny_trainer(rc.RatioRefOps(), fx, tmp_path / name, mu=1, ga=2, n_rows=2, **over)
+        tr = rc.tiny_trainer(RefOps(), fx, tmp_path / name, mu=1, ga=2, n_rows=2, **over)
         assert tr.engine.activation_recompute == ("mlp" if name == "mlp" else "none")
         rec = rc.run_recorded(tr)
         runs[name] = (rec["masters"], tr.state.log_history)
@@ -226,15 +225,15 @@ def test_trainer_steps_and_resume_match_none_bit_for_bit(tmp_path):
     fx = load_case("clip_beta")
     masters = {}
     for mode in ("none", "mlp"):
-        tr = rc.tiny_trainer(rc.RatioRefOps(), fx, tmp_path / mode, mu=2, save_steps=2, activation_recompute=mode)
+        tr = rc.tiny_trainer(RefOps(), fx, tmp_path / mode, mu=2, save_steps=2, activation_recompute=mode)
         masters[mode] = rc.run_recorded(tr)["masters"]
         assert tr.state.global_step == 4
     for a, b in zip(masters["mlp"], masters["none"]):
         assert torch.equal(rcc.bits(a), rcc.bits(b))
-    tr = rc.tiny_trainer(rc.RatioRefOps(), fx, tmp_path / "resumed", mu=2, activation_recompute="mlp")
+    tr = rc.tiny_trainer(RefOps(), fx, tmp_path / "resumed", mu=2, activation_recompute="mlp")
     rec = rc.run_recorded(tr, ckpt=str(tmp_path / "mlp" / "checkpoint-2"))
     assert tr.state.global_step == 4 and len(rec["masters"]) == 2
-    tr0 = rc.tiny_trainer(rc.RatioRefOps(), fx, tmp_path / "resumed-none", mu=2)
+    tr0 = rc.tiny_trainer(RefOps(), fx, tmp_path / "resumed-none", mu=2)
     rec0 = rc.run_recorded(tr0, ckpt=str(tmp_path / "none" / "checkpoint-2"))
     assert torch.equal(rcc.bits(rec["masters"][-1]), rcc.bits(rec0["masters"][-1]))
 
@@ -275,7 +274,7 @@ def _gloo_worker(rank, world, port, q, mode):
     import ratio_cases
     from helpers import load_case as load
     fx = load("clip_beta")
-    tr = ratio_cases.tiny_trainer(ratio_cases.RatioRefOps(), fx, "/tmp/tr1_recompute_gloo_%s_%d" % (mode, rank), mu=1, ga=1, n_rows=2, activation_recompute=mode,
+    tr = ratio_cases.tiny_trainer(RefOps(), fx, "/tmp/tr1_recompute_gloo_%s_%d" % (mode, rank), mu=1, ga=1, n_rows=2, activation_recompute=mode,
                                   grad_wire_dtype="fp32", shard_optimizer=False)
     assert tr.dp.enabled and tr.dp.world == 2 and tr.engine.activation_recompute == mode
     tr.args.learning_rate = 1e-3

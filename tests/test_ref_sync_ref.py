@@ -1,5 +1,5 @@
 """Reference-policy sync (GRPOConfig.sync_ref_model), CPU side: the fp32 composite of tests/ref_sync_cases.py against the fp64 mix, config validation, and the
-trainer's step rule / metric / checkpoint order on the stand-in op backend (ref_sync_cases.SyncRefOps), on one process and on two ranks over gloo.
+trainer's step rule / metric / checkpoint order on the oracle op backend (RefOps), on one process and on two ranks over gloo.
 tests/test_ref_sync_gpu.py runs the HIP kernel and the HIP trainer against the same composite."""
 import os
 import sys
@@ -8,7 +8,8 @@ import pytest
 import torch
 
 import ref_sync_cases as sc
-from helpers import load_case
+from helpers import load_case, ref_ops_without
+from oracle.ref_ops import RefOps
 from time_r1_amd.trainer import GRPOConfig
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -92,9 +93,9 @@ def test_trainer_checks_again_at_train_and_names_a_backend_without_the_op(tmp_pa
     import ratio_cases as rc
     fx = load_case("clip_beta")
     with pytest.raises(NotImplementedError, match="ref_mixup"):
-        rc.tiny_trainer(rc.RatioRefOps(), fx, tmp_path, mu=1, sync_ref_model=True, ref_model_sync_steps=2)
-    rc.tiny_trainer(rc.RatioRefOps(), fx, tmp_path, mu=1)                      # off: the backend is never asked
-    tr = rc.tiny_trainer(sc.SyncRefOps(), fx, tmp_path, mu=2, sync_ref_model=True, ref_model_sync_steps=2)
+        rc.tiny_trainer(ref_ops_without("ref_mixup"), fx, tmp_path, mu=1, sync_ref_model=True, ref_model_sync_steps=2)
+    rc.tiny_trainer(ref_ops_without("ref_mixup"), fx, tmp_path, mu=1)  # off: the backend is never asked
+    tr = rc.tiny_trainer(RefOps(), fx, tmp_path, mu=2, sync_ref_model=True, ref_model_sync_steps=2)
     tr.args.ref_model_sync_steps = 3               # settings changed after construction are checked again when train() starts
     with pytest.raises(ValueError, match="ref_model_sync_steps"):
         tr.train()
@@ -131,7 +132,7 @@ def test_the_three_settings_parse_from_the_command_line(monkeypatch):
 def _trainer(tmp_path, name, mu=1, ga=1, n_rows=3, **over):
     import ratio_cases as rc
     over = {**dict(sync_ref_model=True, ref_model_sync_steps=2), **over}
-    return rc.tiny_trainer(sc.SyncRefOps(), load_case("clip_beta"), tmp_path / name, mu=mu, ga=ga, n_rows=n_rows, **over)
+    return rc.tiny_trainer(RefOps(), load_case("clip_beta"), tmp_path / name, mu=mu, ga=ga, n_rows=n_rows, **over)
 
 
 def test_reference_moves_on_the_sync_step_only_and_by_the_composite(tmp_path):
@@ -219,7 +220,7 @@ def _worker(rank, world, port, q, shard, out):
     import ratio_cases as rc
     import ref_sync_cases as sc
     from helpers import load_case
-    tr = rc.tiny_trainer(sc.SyncRefOps(), load_case("clip_beta"), os.path.join(out, "r%d" % rank), mu=1, ga=1, n_rows=4, sync_ref_model=True, ref_model_sync_steps=2,
+    tr = rc.tiny_trainer(RefOps(), load_case("clip_beta"), os.path.join(out, "r%d" % rank), mu=1, ga=1, n_rows=4, sync_ref_model=True, ref_model_sync_steps=2,
                          ref_model_mixup_alpha=0.6, shard_optimizer=shard)
     assert tr.dp.enabled and tr.dp.world == 2 and (tr.params.train.shard is not None) == shard
     ref0 = tr.ref_model.w16.clone()

@@ -11,8 +11,8 @@ import sampler_filter_cases as fc
 import vocab_cases as vc
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-from helpers import load_case, golden_params, frames_for  # noqa: E402
-from oracle.ref_ops import RefOps, philox_uniform  # noqa: E402
+from helpers import load_case, golden_params, frames_for, ref_ops_without  # noqa: E402
+from oracle.ref_ops import RefOps  # noqa: E402
 from oracle.text import FakeProcessor  # noqa: E402
 from time_r1_amd import rewards as R  # noqa: E402
 from time_r1_amd.trainer import TimeR1_Trainer, GRPOConfig, generation_config_dict  # noqa: E402
@@ -110,13 +110,8 @@ def test_rollout_range_errors():
             Rollout(None, 2, 4, **bad)
 
 
-def _set_bit(seen, r, v):
-    w = (int(seen[r, v >> 5]) & 0xFFFFFFFF) | (1 << (v & 31))
-    seen[r, v >> 5] = w - (1 << 32) if w >= (1 << 31) else w
-
-
 class FilterRefOps(RefOps):
-    """RefOps + the three new ops, written from tests/sampler_filter_cases.py; records what the rollout asks for."""
+    """RefOps that records what the rollout asks of the sampler, the penalty and the seen bitmap."""
 
     def __init__(self):
         super().__init__()
@@ -124,51 +119,28 @@ class FilterRefOps(RefOps):
 
     def sample_tokens(self, logits, temperature, top_k, seed, step_dev, tokens, finished, eos_id, pad_id, stop_at_eos, u_out=None, group_rows=0,
                       seed_stride=0, top_p=1.0, min_p=0.0):
-        rows, V = logits.shape
-        step = int(step_dev.item())
-        self.calls.append(("sample", step, top_p, min_p, logits.clone()))
-        for r in range(rows):
-            if finished is not None and finished[r] and stop_at_eos:
-                tokens[r, step] = pad_id
-                continue
-            keep, cdf, _ = fc.ref_filter(logits[r], temperature, top_k, top_p, min_p)
-            u = philox_uniform(int(seed) + (r // group_rows) * int(seed_stride), r % group_rows, step) if group_rows else philox_uniform(int(seed), r, step)
-            tok = min(int(torch.searchsorted(cdf, torch.tensor(u, dtype=torch.float64))), V - 1)
-            while not keep[tok]:
-                tok -= 1
-            tokens[r, step] = tok
-            if finished is not None and tok == eos_id:
-                finished[r] = 1
+        self.calls.append(("sample", int(step_dev.item()), top_p, min_p, logits.clone()))
+        return super().sample_tokens(logits, temperature, top_k, seed, step_dev, tokens, finished, eos_id, pad_id, stop_at_eos, u_out, group_rows, seed_stride,
+                                     top_p, min_p)
 
     def penalize_logits(self, logits, seen, penalty, out=None):
-        rows, V = logits.shape
-        sets = [sorted(fc.bitmap_tokens(seen[r], V)) for r in range(rows)]
+        sets = [sorted(fc.bitmap_tokens(seen[r], logits.shape[1])) for r in range(logits.shape[0])]
         self.calls.append(("penalize", penalty, logits.clone(), sets))
-        res = fc.ref_penalize(logits.to(vc.BF16), sets, penalty).to(logits.dtype)
         assert out is not None and out.data_ptr() != logits.data_ptr(), "the penalised logits go to a buffer of their own"
-        out.copy_(res)
-        return out
+        return super().penalize_logits(logits, seen, penalty, out=out)
 
     def mark_seen(self, seen, V, ids=None, tokens=None, step_dev=None, finished=None):
-        rows = seen.shape[0]
         if ids is not None:
             self.calls.append(("mark_ids", seen, ids.tolist()))
-            for r in range(rows):
-                for v in ids.tolist():
-                    if 0 <= v < V:
-                        _set_bit(seen, r, v)
-            return
-        col = tokens[:, int(step_dev.item())] if tokens.dim() == 2 else tokens
-        self.calls.append(("mark_drawn", int(step_dev.item()) if step_dev is not None else None, col.tolist(), None if finished is None else finished.tolist()))
-        for r in range(rows):
-            if finished is not None and finished[r]:
-                continue
-            if 0 <= int(col[r]) < V:
-                _set_bit(seen, r, int(col[r]))
+        else:
+            col = tokens[:, int(step_dev.item())] if tokens.dim() == 2 else tokens
+            self.calls.append(("mark_drawn", int(step_dev.item()) if step_dev is not None else None, col.tolist(), None if finished is None else finished.tolist()))
+        return super().mark_seen(seen, V, ids=ids, tokens=tokens, step_dev=step_dev, finished=finished)
 
 
-class RecordingRefOps(RefOps):
-    """Plain RefOps (no new arguments, no new ops) that records how sample_tokens is called."""
+class RecordingRefOps(type(ref_ops_without("penalize_logits", "mark_seen"))):
+    """An oracle backend from before the feature (sample_tokens without the new arguments, no penalize_logits / mark_seen) that records how sample_tokens is
+    called."""
 
     def __init__(self):
         super().__init__()

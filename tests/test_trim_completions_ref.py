@@ -75,13 +75,11 @@ def test_option_on_equals_option_off_when_a_row_has_no_eos(case):
 def test_replay_runs_on_the_trimmed_rows():
     """num_iterations = 2: first pass, one optimizer step, then the replay - with the option on it runs on P + 4 * 9 rows and gives the option-off replay's loss
     and gradients at the tolerances of the golden test."""
-    import ratio_cases as rc
     fx = load_case(tc.SHORT)
     P, G = len(fx["prompt_ids"]), fx["G"]
     out = {}
     for on in (True, False):
         cfg, tr = make_trainer(fx, num_iterations=2, learning_rate=1e-3, disable_log_print=True, **({"trim_completions": True} if on else {}))
-        tr.ops.grpo_loss_ratio = rc.RatioRefOps().grpo_loss_ratio      # (the oracle backend itself has no ratio loss)
         tr._video_inputs = lambda ex: ([frames_for(fx)], [2.0])
         calls = tc.spy_rows(tr)
         tr._reuse = []

@@ -1,6 +1,6 @@
 """fix_vit=False (the reference's default, main.py:44-49): the patch embedding, every vision block and the merger train (reference
-timer1_trainer.py:267-288).  CPU, oracle ops injected through `ops=`; the one kernel the oracle backend lacks (the QuickGELU backward) comes
-from a RefOps subclass defined here.  The golden captures hold the reference's gradient norms of every tower tensor (the generator built the
+timer1_trainer.py:267-288).  CPU, oracle ops injected through `ops=` (RefOps.quickgelu_bwd is the one op only a training tower asks
+for).  The golden captures hold the reference's gradient norms of every tower tensor (the generator built the
 trainer without freezing anything, and the captured reference tower equals the policy tower, which is what fix_vit=False gives at step 0)."""
 import os
 import sys
@@ -20,15 +20,6 @@ from time_r1_amd.trainer import TimeR1_Trainer, TimeR1_Trainer_ft, GRPOConfig
 from time_r1_amd import rewards as R
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-class TowerRefOps(RefOps):
-    """RefOps + the QuickGELU backward (fp32 formula, rounded once like the HIP kernel)."""
-
-    def quickgelu_bwd(self, x, dy):
-        v = x.float()
-        s = torch.sigmoid(1.702 * v)
-        return self._a(dy.float() * (s + 1.702 * v * s * (1.0 - s)))
 
 
 def tower_hf_grads(cfg, get):
@@ -168,7 +159,7 @@ def test_train_vit_layout_at_7b_from_specs(name):
 
 # ------------------------------------------------------------------------------------------------------------ the trainer
 def make_vit_trainer(fx, fix_vit=False, cls=TimeR1_Trainer, ops=None, **over):
-    ops = ops or TowerRefOps()
+    ops = ops or RefOps()
     cfg, pol, ref = golden_params(ops, fx)
     args = GRPOConfig(output_dir="/tmp/tr1_vit_test", num_generations=fx["G"], max_completion_length=fx["C"], beta=fx["beta"], use_grpo=fx["use_grpo"],
                       rope_index_mode="hf5", temperature=1.0, logging_steps=1, save_strategy="no", fix_vit=fix_vit, **over)
@@ -238,7 +229,7 @@ def test_ft_trainer_and_every_model_form_build_the_training_layout(tmp_path):
     fx = load_case("q25_grpo_beta")
     cfg, tr = make_vit_trainer(fx, cls=TimeR1_Trainer_ft)
     assert tr.params.train_vit and tr.ref_model.numel == tr.params.train.numel
-    ops = TowerRefOps()
+    ops = RefOps()
     args = GRPOConfig(output_dir=str(tmp_path), fix_vit=False, save_strategy="no")
     assert TimeR1_Trainer(cfg, [R.format_reward], [], args=args, processing_class=FakeProcessor(cfg), ops=ops).params.train_vit
     tr.save_model(str(tmp_path / "m"))
@@ -250,7 +241,7 @@ def test_preset_and_loaded_hf_module_build_the_training_layout(tmp_path):
     """The two model forms the test above leaves out: a preset name and a loaded transformers module (reference timer1_trainer.py:184-206)."""
     transformers = pytest.importorskip("transformers")
     from safetensors.torch import load_file
-    ops = TowerRefOps()
+    ops = RefOps()
     args = GRPOConfig(output_dir=str(tmp_path), fix_vit=False, save_strategy="no", seed=3)
     cfg = PRESETS["tiny25"]()
     tr = TimeR1_Trainer("tiny25", [R.format_reward], [], args=args, processing_class=FakeProcessor(cfg), ops=ops)

@@ -18,6 +18,8 @@ import math
 import numpy as np
 import torch
 
+from oracle.sampler_filter import token_cdf  # noqa: F401  (the sampler's fp64 kept set and CDF; RefOps' filtered sampler draws from the same function)
+
 BF16 = torch.bfloat16
 I32 = torch.int32
 
@@ -329,20 +331,6 @@ def philox_u(seed, row, step):
     seed &= (1 << 64) - 1
     c = _philox4x32_10((row & 0xFFFFFFFF, step & 0xFFFFFFFF, 0, 0), seed & 0xFFFFFFFF, seed >> 32)
     return float(np.float32(float(c[0] >> 8) + 0.5) * np.float32(1.0 / 16777216.0))
-
-
-def token_cdf(row, temperature, top_k):
-    """fp64 (keep mask, inclusive CDF over the kept set in vocabulary order) of one logits row.  Ties with the k-th largest value are kept (float
-    comparison, so +0.0 and -0.0 tie)."""
-    x = row.double()
-    V = x.numel()
-    if top_k and 0 < top_k < V:
-        keep = x >= torch.topk(x, top_k).values[-1]
-    else:
-        keep = torch.ones(V, dtype=torch.bool)
-    z = x / temperature
-    p = torch.where(keep, (z - z.max()).exp(), torch.zeros_like(z))
-    return keep, torch.cumsum(p, 0) / p.sum()
 
 
 def draw_error(keep, cdf, tok, u):
