@@ -121,6 +121,14 @@ class GRPOCore:
         fl += wg * lin_all + 2.5 * (self._llm_flops(M, pairs_all) - lin_all) + wg * head                         # backward (dgrad + wgrad; flash backward = 5 products)
         self.work["train_flops"] += fl
 
+    def _count_score(self, st):
+        """forward_logps(score=True): the policy's and the reference's full-sequence forwards, no backward."""
+        t = self.cfg.text
+        P, G, C = st.P, self.G, st.layout.C
+        pairs_all = P * (P + 1) / 2.0 + G * (C * P + C * (C + 1) / 2.0)
+        one = self._llm_flops(P + G * C, pairs_all) + 2.0 * G * C * t.vocab_size * t.hidden
+        self.work["train_flops"] += one * (2.0 if self.beta != 0.0 else 1.0)
+
     # ------------------------------------------------------------------------------------------------------- phase 1
     def prepare(self, input_ids, pixel_values_videos, video_grid_thw):
         """input_ids: 1-D ints (prompt with <|video_pad|> expanded); pixel_values_videos: float [N_v, patch_dim] as produced by
@@ -169,14 +177,17 @@ class GRPOCore:
         self._pending_decode = (getattr(self, "_pending_decode", []) + [([st.P], st.decode_steps)])[-64:]
         return tokens
 
-    def rollout_many(self, states):
+    def rollout_many(self, states, save_prefill=None, slot0=0):
         """Decode the prompts of one accumulation window together (weights are constant inside it): every weight byte streamed
-        from HBM serves len(states)*G rows. Sampling streams stay per prompt, so tokens equal the one-by-one rollout's."""
-        outs = self.roll.generate_many(self.eng.params.train, [(st.prompt_ids, st.vid_embeds, st.vid_rows, st.pos3_prompt, st.delta) for st in states],
-                                       save_prefill=self.reuse_prefill)
+        from HBM serves len(states)*G rows. Sampling streams stay per prompt, so tokens equal the one-by-one rollout's.
+        save_prefill: one flag per state - a generation cycle keeps the prefill of its first window's prompts only - with slot0 the number of prefills the
+        cycle's earlier groups saved (Rollout.generate_many); None = every state's, where reuse_prefill is on."""
+        saves = [self.reuse_prefill] * len(states) if save_prefill is None else [bool(x) for x in save_prefill]
+        kw = dict(save_prefill=self.reuse_prefill) if save_prefill is None else dict(save_prefill=saves, slot0=slot0)
+        outs = self.roll.generate_many(self.eng.params.train, [(st.prompt_ids, st.vid_embeds, st.vid_rows, st.pos3_prompt, st.delta) for st in states], **kw)
         for b, (st, (tokens, lay)) in enumerate(zip(states, outs)):
             st.layout, st.completion_ids = lay, tokens
-            st.prefill = self.roll.last_prefill[b] if self.reuse_prefill else None
+            st.prefill = self.roll.last_prefill[b] if saves[b] else None
             st.sample_logp = self.roll.last_sample_logp[b] if self.roll.last_sample_logp is not None else None
             st.decode_steps = self.roll.last_steps_run
         self._pending_decode = (getattr(self, "_pending_decode", []) + [([st.P for st in states], self.roll.last_steps_run)])[-64:]
@@ -238,13 +249,19 @@ class GRPOCore:
         out[:, :st.layout.C] = x
         return out
 
-    def forward_logps(self, st, replay=False):
+    def forward_logps(self, st, replay=False, score=False):
         """Policy log-probs / entropy (activations saved for backward) and reference log-probs (no grad).
+        score=True: the scoring form for a window whose update comes after the weights have moved (GRPOConfig.steps_per_generation): the policy forward
+        saves nothing and no backward follows it.  It takes the launches the replay's forward takes - the whole packed sequence in one decoder pass, the head
+        in its saved form - so on unmoved weights st.logp agrees with a replay's as closely as a replay agrees with a first pass; the reference forward is
+        the first pass's.  The vision embeddings are prepare()'s (same weights); what only a backward would read is released.
         replay=True: a further update on the SAME rollout after the weights have moved (GRPOConfig.num_iterations > 1).  The vision merger (and the tower,
         when it trains) runs again on the kept features / pixels, the decoder takes the full-sequence path - the rollout's saved prefill belongs to the old
         weights - and the reference-policy forward is skipped: its weights are frozen, so st.ref_logp of the first pass still holds."""
         eng, ops = self.eng, self.ops
         tr = eng.params.train
+        if score:
+            return self._score_logps(st)
         if replay:
             if eng.params.train_vit:
                 st.feats = eng.vit_features(st.pixels, st.grid)[0]
@@ -284,6 +301,11 @@ class GRPOCore:
         st.entropy = self._to_gc(st, ent).contiguous()
         if replay:
             return
+        self._ref_logps(st, split)
+
+    def _ref_logps(self, st, split):
+        """The reference policy's log-probs of the state's packed sequence (no grad); split: the policy forward ran as prefill + continuation."""
+        eng = self.eng
         st.ref_logp = None
         if self.beta != 0.0:
             ra = self.ref_arena
@@ -297,6 +319,20 @@ class GRPOCore:
                 hLr, _ = eng.llm_fwd(ra, h0r, st.cos, st.sin, st.masks, save=False, tail_from=eng.tail_rows_from(st.P, st.layout.M))
             rlogp, _, _ = eng.head_fwd(ra, hLr, st.pred_rows, st.targets, save=False, **({"as_saved": True} if eng.lora is not None else {}))
             st.ref_logp = self._to_gc(st, rlogp).contiguous()
+
+    def _score_logps(self, st):
+        """forward_logps(score=True)."""
+        eng = self.eng
+        tr = eng.params.train
+        self._packed_inputs(st)
+        self._count_score(st)
+        h0 = eng.embed(tr, st.ids_packed, st.vid_embeds, st.vid_rows)
+        hL, _ = eng.llm_fwd(tr, h0, st.cos, st.sin, st.masks, save=False, tail_from=eng.tail_rows_from(st.P, st.layout.M))
+        logp, ent, _ = eng.head_fwd(tr, hL, st.pred_rows, st.targets, save=False, as_saved=True)
+        st.logp = self._to_gc(st, logp).contiguous()
+        st.entropy = self._to_gc(st, ent).contiguous()
+        st.vid_embeds = st.merger_ctx = st.prefill = None      # the replay runs the merger again, on the weights of its own step
+        self._ref_logps(st, False)
 
     def _ref_split_fwd(self, st, ra, ref_vid):
         """LoRA mode: the reference policy's decoder pass in the policy's own two launches - the prompt's P rows as the rollout's prefill runs them, then the

@@ -227,8 +227,14 @@ class Rollout:
             seen, pen = ops.zeros(R, (V + 31) // 32, dtype=I32), ops.empty(R, V)
         return _Buffers(greedy_op, steps, tokens, finished, done_count, slogp, lays, self._kv(len(items), max(l.S_cap for l in lays)), seen, pen, V)
 
-    def _prefill(self, arena, w_lm, buf, b, item, save_prefill):
-        """Prompt b: prefill into its cache slots, first token (and its log-prob), and this prompt's decode tables."""
+    def release_cache(self):
+        """Let go of the KV cache: the next call allocates its own.  For a caller that decodes again while a saved prefill of the last call - which holds
+        views of that call's cache - is still to be read."""
+        self._cache = None
+
+    def _prefill(self, arena, w_lm, buf, b, item, save_prefill, slot=None):
+        """Prompt b: prefill into its cache slots, first token (and its log-prob), and this prompt's decode tables.  slot: the engine's activation buffer set
+        a saved prefill goes to (default b)."""
         prompt_ids, vid_embeds, vid_rows, prompt_pos3, delta = item
         eng, ops, cfg, t = self.eng, self.eng.ops, self.eng.cfg, self.eng.cfg.text
         G, C, half = self.G, self.C, t.head_dim // 2
@@ -241,7 +247,7 @@ class Rollout:
         masks = [ops.tensor(a, I32) for a in lay.prompt_masks()]
         h = eng.embed(arena, prompt_ids, vid_embeds, vid_rows)
         # save_prefill: the prompt rows' activations go straight into [P + G*C, .] buffers that the update's continuation forward completes
-        bufs, is_stash = eng.alloc_ctx_bufs(lay.M, slot=b, prefill_rows=P) if save_prefill else (None, False)
+        bufs, is_stash = eng.alloc_ctx_bufs(lay.M, slot=b if slot is None else slot, prefill_rows=P) if save_prefill else (None, False)
         # (only the last prompt row's output is read: first-token logits here, the first prediction row of the update later)
         hL, pctx = eng.llm_fwd(arena, h, cos, sin, masks, save=save_prefill, kv_cache=kv_views, bufs=bufs, tail_from=eng.tail_rows_from(P, lay.M))
         if is_stash:
@@ -284,9 +290,11 @@ class Rollout:
         slots = torch.cat([st["slots"] + b * cache.s_cap for b, st in enumerate(per)], 1).contiguous()
         return _StepTables(cat("cos", 1), cat("sin", 1), slots, cat("slots", 1), cat("pre", 0), cat("lo", 0), nsplit)
 
-    def generate_many(self, arena, items, save_prefill=False):
+    def generate_many(self, arena, items, save_prefill=False, slot0=0):
         """items: list of (prompt_ids, vid_embeds, vid_rows, prompt_pos3, delta), decoded together. Returns [(tokens [G, C], layout)].
-        save_prefill: keep the prompt rows' activations so the policy forward of the update can skip the prompt (same weights).
+        save_prefill: keep the prompt rows' activations so the policy forward of the update can skip the prompt (same weights).  One flag for all items, or
+        one per item: the saved ones take the engine's buffer sets slot0, slot0 + 1, ... in item order (slot0 > 0: an earlier call's saved prefills are
+        still to be read), and last_prefill holds (None, cache views) for the others.
         Each prompt keeps its own sampling stream (seed advances per prompt), so results do not depend on how prompts are batched."""
         eng, ops, t = self.eng, self.eng.ops, self.eng.cfg.text
         G, C, B = self.G, self.C, len(items)
@@ -299,7 +307,12 @@ class Rollout:
         fused = B * G <= 64        # the fused decode kernels hold all rows of a step in one MFMA column block set
         native = fused and self.native_decode and hasattr(ops, "decode_step")
         self._pk_now = self._pack12(arena, B * G) if native and on_gpu and self.weight_dtype == "bf16" else None      # (the packers run ahead of the prefill)
-        per = [self._prefill(arena, w_lm, buf, b, it, save_prefill) for b, it in enumerate(items)]
+        if isinstance(save_prefill, (list, tuple)):
+            assert len(save_prefill) == B, "save_prefill: one flag per item"
+            saves = [bool(x) for x in save_prefill]
+            per = [self._prefill(arena, w_lm, buf, b, it, saves[b], slot=int(slot0) + sum(saves[:b])) for b, it in enumerate(items)]
+        else:
+            per = [self._prefill(arena, w_lm, buf, b, it, save_prefill) for b, it in enumerate(items)]
         tab = self._step_tables(per, buf.cache, int(torch.cuda.get_device_properties(dev).multi_processor_count) if on_gpu else 256)
         w8 = None
         if self.weight_dtype in ("fp8", "fp8-mfma"):

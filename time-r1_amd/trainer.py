@@ -74,6 +74,44 @@ def generation_config_dict(cfg, args):
     return d
 
 
+def generation_windows(a, num_iterations=None, loader_windows=None):
+    """steps_per_generation of the arguments `a` against the settings it cannot work with -> k, the accumulation windows one rollout serves (1 for None).
+    Every rule raises ValueError with the values it objects to.  num_iterations: the trainer's own (default: the arguments'); loader_windows: the windows
+    of one epoch, once train() knows them."""
+    spg = getattr(a, "steps_per_generation", None)
+    if spg is None:
+        return 1
+    try:
+        whole = not isinstance(spg, bool) and int(spg) == float(spg) and int(spg) >= 1
+    except (TypeError, ValueError, OverflowError):
+        whole = False
+    if not whole:
+        raise ValueError("steps_per_generation must be None or an integer >= 1, got %r" % (spg,))
+    spg, ga = int(spg), max(1, int(a.gradient_accumulation_steps))
+    if spg % ga != 0:
+        raise ValueError("steps_per_generation (%d) must be a multiple of gradient_accumulation_steps (%d): a rollout serves whole accumulation windows, and "
+                         "generating more than once per window is not offered" % (spg, ga))
+    k = spg // ga
+    if k == 1:
+        return 1
+    mu = int(getattr(a, "num_iterations", 1) if num_iterations is None else num_iterations)
+    if getattr(a, "use_grpo", False):
+        raise ValueError("steps_per_generation = %d with gradient_accumulation_steps = %d updates %d window(s) on completions of an older policy, and use_grpo=True "
+                         "has no clip on the probability ratio: it needs use_grpo=False" % (spg, ga, k - 1))
+    if not getattr(a, "rollout_batching", True):
+        raise ValueError("steps_per_generation = %d with gradient_accumulation_steps = %d decodes %d windows together: it needs rollout_batching=True" % (spg, ga, k))
+    if getattr(a, "save_strategy", "no") == "steps" and a.save_steps and int(a.save_steps) % (k * mu) != 0:
+        raise ValueError("save_steps (%d) must be a multiple of steps_per_generation / gradient_accumulation_steps x num_iterations = %d x %d = %d: checkpoints "
+                         "are written at the end of a generation cycle only" % (a.save_steps, k, mu, k * mu))
+    if getattr(a, "sync_ref_model", False) and int(a.ref_model_sync_steps) % (k * mu) != 0:
+        raise ValueError("ref_model_sync_steps (%d) must be a multiple of steps_per_generation / gradient_accumulation_steps x num_iterations = %d x %d = %d: the "
+                         "reference moves at the end of a generation cycle only" % (a.ref_model_sync_steps, k, mu, k * mu))
+    if loader_windows is not None and k > loader_windows:
+        raise ValueError("steps_per_generation = %d is %d accumulation windows of %d micro-steps, and an epoch holds %d: an epoch shorter than a generation cycle"
+                         % (spg, k, ga, loader_windows))
+    return k
+
+
 @dataclasses.dataclass
 class GRPOConfig:
     """The training arguments the reference reads (trl.GRPOConfig + main.py:44-70 MY_GRPOConfig), as a plain dataclass."""
@@ -158,11 +196,17 @@ class GRPOConfig:
         if self.sync_ref_model and self.ref_model_sync_steps % self.num_iterations != 0:
             raise ValueError("ref_model_sync_steps (%d) must be a multiple of num_iterations (%d): the reference moves after the last update on a rollout "
                              "(the replayed updates reuse the reference log-probs of the first)" % (self.ref_model_sync_steps, self.num_iterations))
+        if self.steps_per_generation is not None:
+            self.steps_per_generation = generation_windows(self) * max(1, int(self.gradient_accumulation_steps))
 
     beta: float = 0.04
     use_grpo: bool = False
     num_iterations: int = 1                 # mu of the GRPO paper (trl.GRPOConfig.num_iterations): optimizer steps per rollout.  Steps 2 .. mu replay the window's
                                             # completions against the log-probs of the policy that drew them (PPO clip); 1 = one update per rollout, as the reference runs
+    steps_per_generation: Optional[int] = None   # trl.GRPOConfig.steps_per_generation, in micro-steps: one rollout serves this many of them.  None = gradient_accumulation_steps
+                                            # (every optimizer step draws its own window).  A multiple k * GA: the prompts of k windows are decoded together with the
+                                            # current weights - wider decode batches - and windows 2 .. k are updated, one optimizer step each, against log-probs scored
+                                            # by a no-grad forward at generation time (the clipped objective on completions one .. k - 1 steps old)
     epsilon_low: float = 0.2                # clip range of the probability ratio: [1 - epsilon_low, 1 + epsilon_high] (the reference hard-codes 0.2 / 0.2, :388-393)
     epsilon_high: Optional[float] = None    # None = same as epsilon_low
     loss_type: Optional[str] = None         # trl.GRPOConfig.loss_type: "grpo" = clip + mean over each completion, then over completions; "bnpo" = clip + mean over all
@@ -284,7 +328,8 @@ def _call(cb, name, *a, **k):
 class _PhaseClock:
     """Phase boundaries of the micro-steps (preprocess | vision | rollout | logps | backward | optimizer) as HIP events on the stream the
     kernels run on - recording costs ~2 us and never waits; the durations are read when `log()` builds the throughput keys.
-    On a CPU op backend (tests) it falls back to the host clock."""
+    On a CPU op backend (tests) it falls back to the host clock.  A generation cycle of several windows (steps_per_generation) adds the phase `score`: the
+    no-grad policy and reference forwards of the deferred windows."""
 
     def __init__(self, ops):
         dev = getattr(ops, "device", None)
@@ -507,6 +552,7 @@ class TimeR1_Trainer:
                                            getattr(args, "delta", None), self.mask_truncated, self.epsilon_low, self.epsilon_high)
         self._check_reuse_args()
         self._check_ref_sync_args()
+        self._check_generation_args()
         self._ref_sync_sums = []             # sync_ref_model: the [2] device sums of the syncs since the last log (ref_sync/weight_distance)
         self._reuse = None                   # num_iterations > 1: what the window's micro-steps keep for the replayed updates (optimizer_window)
         self._replays_since_log = 0
@@ -567,6 +613,11 @@ class TimeR1_Trainer:
         if getattr(a, "save_strategy", "no") == "steps" and a.save_steps and int(a.save_steps) % mu != 0:
             raise ValueError("save_steps (%d) must be a multiple of num_iterations (%d): checkpoints are written after the last update on a rollout"
                              % (a.save_steps, mu))
+
+    def _check_generation_args(self, loader_windows=None):
+        """steps_per_generation against the settings it cannot work with (at construction and again when train() starts: args is mutable; train() adds the
+        windows of an epoch) -> k, the accumulation windows of one generation cycle."""
+        return generation_windows(self.args, self.num_iterations, loader_windows)
 
     def _check_ref_sync_args(self):
         """sync_ref_model against the settings it cannot work with (at construction and again when train() starts: args is mutable) -> the option is on."""
@@ -704,10 +755,22 @@ class TimeR1_Trainer:
         return dict(inputs=inputs, st=st, prompts=prompts, forced=forced)
 
     def _step_finish(self, ctx, last_in_window=False):
-        """Log-probs, rewards, loss gradient and backward of one prompt.  Returns the micro-step loss as a DEVICE scalar (HF's compute_loss
-        returns a device tensor too): nothing in here waits for the GPU after the backward is enqueued - the metric values that live on the
+        """Log-probs, rewards, loss gradient and backward of one prompt: `_step_score`, then `_update`.  Returns the micro-step loss as a DEVICE scalar (HF's
+        compute_loss returns a device tensor too): nothing in here waits for the GPU after the backward is enqueued - the metric values that live on the
         device (loss, KL, entropy, clip ratios) are packed into one small vector per micro-step and fetched with ONE copy when `log()` (or
         anybody reading `self._metrics`) asks for them, so the host prepares the next micro-step while this one's backward runs."""
+        s = self._step_score(ctx)
+        st = s["st"]
+        if self._reuse is not None:      # num_iterations > 1: keep what the replayed updates read (the policy's log-probs are the OLD policy's from now on)
+            self._reuse.append(dict(st=st, old_logp=st.logp.clone(), mask=s["mask"], adv=s["adv"], tokw=s["tokw"]))
+        return self._update(st, s["mask"], s["adv"], tokw=s["tokw"], last=last_in_window, keep_pixels=self._reuse is not None,
+                            maskf=s["maskf"], rollout=s["rollout"], clip3=s["clip3"], drift=s["drift"])
+
+    def _step_score(self, ctx, deferred=False):
+        """The half of a micro-step that belongs to the rollout: the policy's and the reference's log-probs of the completions, rewards, advantages, masks, the
+        truncated importance weights and the rollout's metric values -> dict(st, mask, adv, maskf, tokw, clip3, drift, rollout).
+        deferred: a window of a generation cycle whose update comes after an optimizer step (steps_per_generation).  Its policy forward saves nothing
+        (GRPOCore.forward_logps(score=True)): st.logp is the OLD policy's from the start, and the update is a replay against it."""
         inputs, st, prompts = ctx["inputs"], ctx["st"], ctx["prompts"]
         G = self.num_generations
         tokens = st.completion_ids
@@ -719,7 +782,7 @@ class TimeR1_Trainer:
         # trim_completions: the model runs on the columns up to the last row's EOS; comp_host keeps the full [G, C] rows for the mask, the rewards and the decoded
         # completions (the reference decodes what follows the EOS too)
         trimmed = self.core.trim(st, comp_host, self.processing_class.eos_token_id) if self.core.trim_completions else None
-        self.core.forward_logps(st)
+        self.core.forward_logps(st, **({"score": True} if deferred else {}))
         mask_np = eos_mask(comp_host, self.processing_class.eos_token_id)
         lengths, truncated = mask_np.sum(1).astype(np.float32), None      # completion_length and the token counts keep the rollout's lengths
         if self.mask_truncated:
@@ -738,13 +801,13 @@ class TimeR1_Trainer:
         if self._is_ft and self.metric_funcs:
             metric_vals = torch.stack([torch.tensor(fn(prompts=prompts_rep, completions=completions, **reward_kwargs), dtype=torch.float32)
                                        for fn in self.metric_funcs], 1)
-        self._clock.mark("logps")
+        self._clock.mark("score" if deferred else "logps")
         mask_dev = self.ops.tensor(mask_np, torch.int32)
         adv_dev = self.ops.tensor(advantages.numpy(), torch.float32)
         # device-side metric pieces are computed BEFORE the backward releases the step's tensors; tiny [G, C] work on the same stream
         maskf = mask_dev.to(torch.float32)
         clip3 = None
-        if self._is_ft and not self.use_grpo and self._objective is None:   # reference timer1_trainer_ft.py:820-842 (undefined there for use_grpo: coef_1 does not exist)
+        if self._is_ft and not self.use_grpo and self._objective is None and not deferred:   # reference timer1_trainer_ft.py:820-842 (undefined there for use_grpo: coef_1 does not exist)
             lp = st.logp.float()
             clip3 = torch.stack(clip_ratio_metrics(lp, lp, adv_dev, maskf, self.epsilon_low, self.epsilon_high))   # old policy == policy (one update per rollout)
         drift_t, tokw = None, None
@@ -753,16 +816,13 @@ class TimeR1_Trainer:
             drift_t = (d.abs() * maskf).sum() / maskf.sum().clamp(min=1)
             if self._is_cap is not None:
                 tokw = torch.exp(d).clamp(max=float(self._is_cap))
-        if self._reuse is not None:      # num_iterations > 1: keep what the replayed updates read (the policy's log-probs are the OLD policy's from now on)
-            self._reuse.append(dict(st=st, old_logp=st.logp.clone(), mask=mask_dev, adv=adv_dev, tokw=tokw))
         # ---- metrics (reference :739-777; ft adds metrics/<fn> and clip ratios :789-842): per-sample host values + the device vector,
         # turned into the reference's gathered means by _flush_metrics
         rollout = dict(length=lengths, rpf=rewards_per_func.numpy().copy(), reward=rewards.numpy().copy(), std=std.numpy().copy(),
                        mvals=None if metric_vals is None else metric_vals.numpy(), truncated=truncated, trimmed=trimmed)
         self.last_completions = completions
         self.last_rewards = rewards
-        return self._update(st, mask_dev, adv_dev, tokw=tokw, last=last_in_window, keep_pixels=self._reuse is not None,
-                            maskf=maskf, rollout=rollout, clip3=clip3, drift=drift_t)
+        return dict(st=st, mask=mask_dev, adv=adv_dev, maskf=maskf, tokw=tokw, clip3=clip3, drift=drift_t, rollout=rollout)
 
     def _update(self, st, mask_dev, adv_dev, tokw=None, old_logp=None, last=False, keep_pixels=False, maskf=None, rollout=None, clip3=None, drift=None):
         """Loss gradient and backward of one micro-step whose log-probs are in `st`: a rollout's first update (old_logp None) or a replay against the kept
@@ -932,17 +992,101 @@ class TimeR1_Trainer:
             gnorm = self._optimizer_step(t_start, save=(it == mu - 1))
         return gnorm
 
-    def _replay_window(self, recs, more):
+    def _replay_window(self, recs, more, first=False):
         """One further optimizer step's micro-steps on a window already rolled out (recs: what _step_finish kept).  No decode loop, no reference-policy
-        forward, no reward calls; more: another replay follows (the states keep their pixels)."""
+        forward, no reward calls; more: another replay follows (the states keep their pixels).
+        first: the FIRST update of a deferred window of a generation cycle (recs: what _score_window kept) - the same update against the log-probs scored at
+        generation time; its records carry the rollout's host metrics and drift, and its micro-steps count as the window's own, not as replays."""
         self._clock.mark("start")
         losses = []
         for i, r in enumerate(recs):
             self.core.forward_logps(r["st"], replay=True)
             self._clock.mark("logps")
-            losses.append(self._update(r["st"], r["mask"], r["adv"], tokw=r["tokw"], old_logp=r["old_logp"], last=(i == len(recs) - 1), keep_pixels=more))
-            self._replays_since_log += 1
+            own = dict(rollout=r["rollout"], drift=r["drift"]) if first else {}
+            losses.append(self._update(r["st"], r["mask"], r["adv"], tokw=r["tokw"], old_logp=r["old_logp"], last=(i == len(recs) - 1), keep_pixels=more, **own))
+            if not first:
+                self._replays_since_log += 1
         return losses
+
+    # ------------------------------------------------------------------------------------------------------ several windows per rollout
+    rollout_group_rows = 32      # a generation cycle decodes in groups of whole prompts of at most this many rows: the LDS-resident skinny decode kernels end at 32
+    #                              rows, and the generic ones above them were slower per sample (DESIGN.md section 7j: 64 rows 11.19 ms a step against 4.83 at 32)
+
+    def _rollout_cycle(self, todo):
+        """Decode the prompts of a generation cycle with the current weights.  todo: (state, save its prefill) in prompt order; the groups follow that order, so
+        the sampling streams (seed + 7919 x calls, one call per prompt) are those of any other grouping.  A saved prefill keeps views of its group's K/V
+        cache and one of the engine's activation buffer sets: the next group gets a cache of its own, and the saved sets are numbered across the groups."""
+        core = self.core
+        per = max(1, int(self.rollout_group_rows) // self.num_generations)
+        groups = [todo[i:i + per] for i in range(0, len(todo), per)]
+        slot0 = 0
+        for gi, grp in enumerate(groups):
+            saves = [bool(save) and core.reuse_prefill for _, save in grp]
+            core.rollout_many([st for st, _ in grp], save_prefill=saves, slot0=slot0)
+            slot0 += sum(saves)
+            if any(saves) and gi < len(groups) - 1:
+                core.roll.release_cache()
+        for st, _ in todo:
+            st.completion_ids_host = st.completion_ids.cpu().numpy()        # one wait per decode loop, ahead of every update
+
+    def _score_window(self, ctxs):
+        """A deferred window of a generation cycle, before the cycle's first optimizer step: what `_step_finish` computes ahead of its update, with a policy
+        forward that saves nothing -> records of the `_reuse` shape (st, old_logp, mask, adv, tokw) plus the rollout's host metrics and drift, which are
+        logged with the window's first update."""
+        recs = []
+        for c in ctxs:
+            s = self._step_score(c, deferred=True)
+            st = s["st"]
+            recs.append(dict(st=st, old_logp=st.logp, mask=s["mask"], adv=s["adv"], tokw=s["tokw"], rollout=s["rollout"], drift=s["drift"]))
+            st.logp = st.entropy = st.sample_logp = None      # the replay's forward writes its own; the record holds the old policy's
+        return recs
+
+    def generation_cycle(self, windows, t_start=None):
+        """k = steps_per_generation / gradient_accumulation_steps accumulation windows on ONE rollout (windows: k lists of GA batches): k x num_iterations
+        optimizer steps; returns the last one's gradient norm.  k = 1 is `optimizer_window`.  Otherwise every prompt of the cycle is prepared and decoded with
+        the current weights, in groups of at most `rollout_group_rows` rows.  Window 1 is updated as ever (saved-prefill continuation, ratio 1).  Windows
+        2 .. k are scored before the first optimizer step - a no-grad policy forward in the replay's launches, the reference forward, rewards, advantages, masks,
+        importance weights - and each is then updated like a replay, against those log-probs, one optimizer step per window.  With num_iterations = mu the order
+        is trl's, iteration-major: (1,1) .. (k,1), (1,2) .. (k,mu), and iterations 2 .. mu replay every window.  Checkpoints and the reference sync wait for the
+        cycle's last step.  max_steps or a callback stop inside a cycle ends it after that optimizer step; the rest of its rollouts is dropped."""
+        k, mu = len(windows), self.num_iterations
+        if k != self._check_generation_args():
+            raise ValueError("generation_cycle got %d window(s); steps_per_generation = %r with gradient_accumulation_steps = %d makes %d"
+                             % (k, self.args.steps_per_generation, self.args.gradient_accumulation_steps, self._check_generation_args()))
+        if k == 1:
+            return self.optimizer_window(windows[0], t_start)
+        if self._t_last_log is None:         # driven without train(): the throughput keys count from the first cycle
+            self._t_last_log, self._micro_at_log = time.perf_counter(), self._micro
+        clock = self._clock
+        clock.mark("start")
+        ctxs = [[self._step_prepare(b) for b in w] for w in windows]
+        # only window 1 saves its prefill for the backward: a deferred window's would belong to weights that have moved by then, and it is large
+        self._rollout_cycle([(c["st"], wi == 0) for wi, w in enumerate(ctxs) for c in w if c["forced"] is None])
+        clock.mark("rollout")
+        for w in ctxs[1:]:
+            for c in w:
+                c["st"].merger_ctx = None      # no backward follows prepare()'s merger pass of a deferred window: 0.10 GB per prompt at 7B, ahead of the step's peak
+        self._reuse = [] if mu > 1 else None
+        try:
+            self._loss_acc.extend(self._step_finish(c, last_in_window=(i == len(ctxs[0]) - 1)) for i, c in enumerate(ctxs[0]))
+        finally:
+            first, self._reuse = self._reuse, None
+        recs = [first] + [self._score_window(w) for w in ctxs[1:]]
+        del ctxs
+        stopped = lambda: self.control.should_training_stop or (self.state.max_steps > 0 and self.state.global_step >= self.state.max_steps)
+        gnorm = None
+        for it in range(mu):
+            for wi in range(k):
+                if gnorm is not None and stopped():
+                    return gnorm
+                if it == 0:
+                    self._micro += len(windows[wi])
+                if it > 0 or wi > 0:
+                    self._loss_acc.extend(self._replay_window(recs[wi], more=(it < mu - 1), first=(it == 0)))
+                if it == mu - 1:
+                    recs[wi] = None          # the window's last update is enqueued: its states, features and [G, C] tensors go
+                gnorm = self._optimizer_step(t_start, save=(it == mu - 1 and wi == k - 1))
+        return gnorm
 
     def _optimizer_step(self, t_start, save=True):
         """AdamW step + schedule + callbacks + logging (+ step-based checkpoint when `save`: with num_iterations > 1 only after a rollout's last update).
@@ -1064,14 +1208,17 @@ class TimeR1_Trainer:
         micro-steps, optimizer step + LR schedule, callbacks, checkpoints, and HF's resume arithmetic: a checkpoint at global step s
         restarts in epoch s // steps_per_epoch after skipping the (s % steps_per_epoch) * GA batches that epoch already consumed (with
         num_iterations = mu > 1 a loader window yields mu optimizer steps: steps_per_epoch = windows_per_epoch * mu, ((s // mu) % windows_per_epoch) * GA batches); the
-        run ends at state.max_steps (main.py sets max_steps = global_step + epochs * steps_per_epoch before resuming, :600-618)."""
+        run ends at state.max_steps (main.py sets max_steps = global_step + epochs * steps_per_epoch before resuming, :600-618).
+        steps_per_generation = k * GA groups the windows into generation cycles of k (`generation_cycle`): a cycle never spans an epoch, the windows that do
+        not fill one are dropped, steps_per_epoch = (windows_per_epoch // k) * k * mu, and a checkpoint sits at a cycle's end - so does a resume."""
         a = self.args
         loader = self.get_train_dataloader()
         ga = max(1, a.gradient_accumulation_steps)
         self._check_reuse_args()
         self._check_ref_sync_args()
+        k = self._check_generation_args(len(loader) // ga)
         mu = self.num_iterations
-        windows_per_epoch = max(len(loader) // ga, 1)
+        windows_per_epoch = max(len(loader) // ga, 1) // k * k      # (k = 1: every window; else the windows of the epoch's whole cycles)
         steps_per_epoch = windows_per_epoch * mu              # optimizer steps: one loader window yields num_iterations of them
         self._steps_per_epoch = steps_per_epoch
         if self.state.max_steps <= 0:
@@ -1082,6 +1229,9 @@ class TimeR1_Trainer:
         ckpt = resume_from_checkpoint if resume_from_checkpoint is not None else a.resume_from_checkpoint
         if ckpt:
             start_step = self._load_checkpoint(ckpt)
+        if k > 1 and (start_step % steps_per_epoch) % (k * mu) != 0:
+            raise ValueError("checkpoint at global step %d lies inside a generation cycle of %d x %d optimizer steps: resume it with the steps_per_generation "
+                             "it was written with" % (start_step, k, mu))
         epoch = start_step // steps_per_epoch                  # fully trained epochs: the sampler is advanced, nothing is replayed
         loader.skip_epochs(epoch)
         skip_batches = ((start_step // mu) % windows_per_epoch) * ga      # consumed part of the current epoch (skipped before any prefetch work)
@@ -1093,15 +1243,24 @@ class TimeR1_Trainer:
         self._loss_acc, self._tr_loss_last = [], 0.0
         self.control.should_training_stop = False
         while not self.control.should_training_stop and self.state.global_step < self.state.max_steps and epoch < n_epochs:
-            window = []
+            window, cycle = [], []
             for batch in self._prefetching(loader, skip_batches):
                 window.append(batch)
                 if len(window) < ga:
                     continue
-                self.optimizer_window(window, t_start)
+                if k == 1:
+                    self.optimizer_window(window, t_start)
+                else:
+                    cycle.append(window)
+                    if len(cycle) == k:
+                        self.generation_cycle(cycle, t_start)
+                        cycle = []
                 window = []
                 if self.state.global_step >= self.state.max_steps or self.control.should_training_stop:
                     break
+            if cycle and self.dp.rank == 0:
+                print("[time-r1_amd] epoch %d: %d trailing window(s) do not fill a generation cycle of %d and are dropped (steps_per_epoch = "
+                      "len(loader) // GA // %d * %d * num_iterations)" % (epoch, len(cycle), k, k, k), flush=True)
             if window and len(loader) < ga and self.state.global_step < self.state.max_steps and not self.control.should_training_stop:
                 # an epoch shorter than one accumulation window (small dataset / many ranks): HF steps on the last batch of a short epoch
                 # (TF trainer.py do_sync_step at steps_in_epoch) - without this the run would end after zero optimizer steps

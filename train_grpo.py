@@ -47,7 +47,9 @@ def main():
     ap = argparse.ArgumentParser()
     cfg_fields = {f.name: f for f in dataclasses.fields(GRPOConfig)}
     for name, f in cfg_fields.items():
-        if f.type in (bool, "bool") or isinstance(f.default, bool):
+        if name == "steps_per_generation":      # Optional[int]: micro-steps one rollout serves, a multiple of --gradient_accumulation_steps (None = one window)
+            ap.add_argument("--" + name, type=int, default=None)
+        elif f.type in (bool, "bool") or isinstance(f.default, bool):
             ap.add_argument("--" + name, type=str2bool, default=f.default)
         elif isinstance(f.default, (int, float, str)) and f.default is not None:
             ap.add_argument("--" + name, type=type(f.default), default=f.default)
@@ -103,7 +105,8 @@ def main():
     if ckpt and os.path.isdir(ckpt):
         st = json.load(open(os.path.join(ckpt, "trainer_state.json")))
         ga = max(1, args.gradient_accumulation_steps)
-        per_epoch = max(len(trainer.get_train_dataloader()) // ga, 1) * max(1, args.num_iterations)      # optimizer steps: num_iterations per loader window
+        k = (args.steps_per_generation or ga) // ga      # windows per generation cycle: only whole cycles of an epoch are trained
+        per_epoch = max(len(trainer.get_train_dataloader()) // ga, 1) // k * k * max(1, args.num_iterations)      # optimizer steps: num_iterations per loader window
         trainer.state.max_steps = int(st["global_step"]) + math.ceil(args.num_train_epochs * per_epoch)
         trainer.train(resume_from_checkpoint=ckpt)
     else:
